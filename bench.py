@@ -7,9 +7,12 @@
         bench.py --gpus N --steps K --warmup W
 
 One JSON line on rank 0.  `value` = whole-job volumes/s (global batch * K / max-over-ranks time), inputs resident
-in HBM before timing.  `roofline` = the dominant kernel (measured live with HIP events on its own launches, same
-shapes as in the step; the launch with the largest time per step) against the 8 TB/s HBM peak; `cpu_baseline` = the oracle's
-vanilla-torch restatement timed on the host cores (rank 0, N=1 only, bounded sample, 16 and 8 threads).
+in HBM before timing; `ms_per_step` = milliseconds per timed step.  A plain run does only that: set-up, W warm-up steps,
+K timed steps, the result line.  --full adds the legs that take runs of their own: `roofline` = the dominant kernel
+(measured live with HIP events on its own launches, same shapes as in the step; the launch with the largest time per step)
+against the 8 TB/s HBM peak; `cpu_baseline` = the oracle's vanilla-torch restatement timed on the host cores (rank 0, N=1
+only, bounded sample, 16 and 8 threads).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(see dump_outputs), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -230,6 +233,24 @@ def roofline_dominant(size, batch, dtype_code, iters=10, ts=None):
             "flops_per_launch": 2 * 2 * 27 * cin * cout * vox}
 
 
+def dump_outputs(d, ts, metrics, workload):
+    """What a caller of the timed path holds after its last step: the step's metrics and, for the training workloads, the
+    model state the step updated in place -- parameters and their gradients (the flat fp32 arenas, 45 MB for the default
+    net) and the BatchNorm buffers (float64: the batch counters are integers); DANN adds the discriminator's arenas."""
+    import numpy as np
+    arrays = {"metrics": metrics.float()}
+    if workload != "eval":
+        arrays.update(params=ts.arena.p, grads=ts.arena.g,
+                      buffers=torch.cat([b.detach().reshape(-1).double() for b in ts.model.buffers()]))
+        if workload == "dann":
+            arrays.update(disc_params=ts.disc_arena.p, disc_grads=ts.disc_arena.g)
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= 64e6, "outputs over the 64 MB budget: dump a seeded sample instead"
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 class _SclkSampler:
     """Shader clock during the timed region: every 20 ms the current level ('*') of every card's pp_dpm_sclk; the busiest card
     (highest mean) is ours on a shared host.  Host-side file reads only: the step is a graph replay and does not wait on the host."""
@@ -289,8 +310,12 @@ def main():
                     help="keep every weight gradient on the data-gradient chain (default: the decoder / deep-level ones run on a second stream)")
     ap.add_argument("--chain-prio", default=os.environ.get("MI3D_BENCH_CHAIN_PRIO", "normal"), choices=["normal", "high"],
                     help="priority class of the stream the step runs on (the aux stream of the weight gradients has the lowest)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the dominant kernel's roofline and the CPU baseline (each runs work of its own after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (metrics; training workloads: parameters, gradients, buffers) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--sclk", action="store_true",
                     help="sample the shader clock (sysfs pp_dpm_sclk of the busiest card) during the timed steps -> \"sclk_mhz\" in the JSON "
                          "line: boxes and builds differ in clock, an A/B should say so")
@@ -387,6 +412,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     met = out.detach().cpu().tolist()
+    if a.dump_outputs and rank == 0:       # before --full's legs, which run more steps on the same state
+        dump_outputs(a.dump_outputs, ts, out, a.workload)
 
     if rank == 0:
         global_batch = a.batch * world
@@ -408,10 +435,10 @@ def main():
             "step_algorithmic_gb": algo_gb_step,
             **({"sclk_mhz": sclk_mhz} if sclk_mhz else {}),
         }
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             res["roofline"] = roofline_dominant(a.size, a.batch, 1 if a.dtype == "bf16" else 0,
                                                 ts=ts if (a.workload == "train" and a.dropout == 0.0 and not ts.do_comm) else None)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(a.size, a.batch)
         print(json.dumps(res))
     sys.stdout.flush()

@@ -10,12 +10,12 @@ r=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out/final
 rm -rf $o && mkdir -p $o
-python bench.py > $o/bench_stdout.txt 2> $o/bench_stderr.txt
+python bench.py --full > $o/bench_stdout.txt 2> $o/bench_stderr.txt
 tail -1 $o/bench_stdout.txt > $o/${r}_bench.json
-python bench.py --graph --no-cpu-baseline > $o/bench_graph_stdout.txt 2>> $o/bench_stderr.txt
+python bench.py --full --graph --no-cpu-baseline > $o/bench_graph_stdout.txt 2>> $o/bench_stderr.txt
 tail -1 $o/bench_graph_stdout.txt > $o/${r}_bench_graph.json
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -- python bench.py --no-cpu-baseline > $o/stats_stdout.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats -- python bench.py --full --no-cpu-baseline > $o/stats_stdout.txt 2>&1
 cp $(ls $o/stats/*/*_kernel_stats.csv | head -1) $o/${r}_bench_kernel_stats.csv
 echo "stats done"
 rocprofv3 --kernel-trace --output-format csv -d $o/trace -- python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-roofline > /dev/null 2>&1
