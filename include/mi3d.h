@@ -48,11 +48,6 @@ typedef struct mi3d_unet_desc {
     int32_t N, D, H, W;                     /* per-GPU batch and volume; D,H,W divisible by 2^n_levels */
     int32_t dtype;                          /* internal activation dtype */
     float bn_momentum, bn_eps;              /* 0.1, 1e-5 (nn.BatchNorm3d defaults) */
-    int32_t prepacked_from;                 /* 0 (default): a training forward packs every MFMA weight image itself.  k > 0: the images
-                                             * of the DoubleConv blocks with index >= k (order: encoder.0..L-1, bottleneck, decoder.0..L-1)
-                                             * and of all transposed convs in `workspace` are current -- the caller ran
-                                             * mi3d_unet_pack_from(first_block = k) on the same workspace after its last parameter
-                                             * update -- and the forward packs only blocks < k.  Read by mi3d_unet_forward* only. */
 } mi3d_unet_desc;
 
 /* Parameter / buffer pointer tables follow nn.Module.parameters() / .buffers() order of the reference model:
@@ -115,31 +110,12 @@ int mi3d_unet_backward(const mi3d_unet_desc* d, const float* x, const void* cons
  * `stream` wait for it before the call returns (the call is then stream-ordered for the caller), aux_join == 0 leaves that
  * to the caller: whatever consumes the gradients (optimizer, gradient exchange) and the end of a hipGraph capture must wait
  * for events[3] / aux_stream.  Results are bit-identical to the single-stream route. */
-/* Optimizer tail beside the end of the backward (round 4).  With an aux stream the weight gradients of the leading encoder
- * blocks (the full-resolution levels) are the LAST thing the compute stream produces, everything else is complete on the aux
- * stream earlier: the caller can run the optimizer update of the other parameters and re-pack their MFMA weight images THERE,
- * and only the update of the leading blocks behind the join (train_unet.py:226 fixes no order between parameters).
- *   mi3d_unet_chain_tail_blocks: k = number of leading encoder blocks whose gradients come last (0: do not split).  Valid
- *     when mi3d_unet_backward*(seg 0 .. all, aux_stream, aux_join = 0) has returned: aux_stream is then ordered after every
- *     gradient of the blocks >= k, of the transposed convs and of the head (routes as they are NOW: ask before every step).
- *   mi3d_unet_pack_from: the weight packs of blocks >= first_block and of all transposed convs, one launch on `stream`
- *     (what the forward does for all blocks when desc.prepacked_from == 0). */
-int mi3d_unet_chain_tail_blocks(const mi3d_unet_desc* d);
-int mi3d_unet_pack_from(const mi3d_unet_desc* d, const void* const* params, void* workspace, size_t workspace_bytes,
-                        int first_block, void* stream);
 /* Exchange marks (data-parallel step, round 4): events[i] is recorded on the backward's stream as soon as every gradient of the
  * segments <= segs[i] is complete -- set for the NEXT mi3d_unet_backward / _backward_loss call of the calling thread (n <= 4,
  * n = 0 clears).  The backward then stays ONE call over all segments (a call cut at an exchange costs a slab-sum launch and a
  * host round trip); the exchange stream waits for the mark (mi3d_stream_wait_event) and all-reduces the bucket while the
  * remaining segments run.  Marks are consumed by that call. */
 int mi3d_unet_backward_marks(const int* segs, void* const* events, int n);
-/* Utilities: stream-to-stream ordering through a counter in device memory (flag = device int64[2], zero-initialised by the caller).
- * mi3d_flag_set: flag[0] = value once everything enqueued on `stream` so far has finished (one 1-thread kernel).
- * mi3d_flag_wait: `stream` continues when flag[0] >= value (one 1-wave kernel that polls; values must grow monotonically).  After
- * timeout_us without it the waiter gives up and stores `value` in flag[1].  Round 4 measured them as a replacement for the hardware
- * cross-queue join of the data-parallel step: no gain; the step does not use them, tools/queue_probe.py does. */
-int mi3d_flag_set(int64_t* flag, int64_t value, void* stream);
-int mi3d_flag_wait(int64_t* flag, int64_t value, int64_t timeout_us, void* stream);
 int mi3d_stream_wait_event(void* stream, void* event);
 int mi3d_event_create(void** event_out);
 int mi3d_event_destroy(void* event);
@@ -147,11 +123,6 @@ int mi3d_event_destroy(void* event);
  * offers high / normal; the aux stream of the deferred weight gradients wants the LOWEST class, so that the wave dispatcher
  * gives a free workgroup slot to the data-gradient chain first.  The caller owns the stream (mi3d_stream_destroy). */
 int mi3d_stream_create(int priority_class, void** stream_out);
-/* A non-blocking hipStream_t whose kernels may only run on `cus_per_xcd` (1..31) of the 32 compute units of every XCD
- * (hipExtStreamCreateWithCUMask; mask bit i = CU i / 8 of XCD i % 8, measured with tools/micro/cu_mask_probe.hip): from_top = 0
- * takes CUs 0..n-1 of each XCD, 1 the last n.  Round 4: a CU partition for the aux stream of the deferred weight gradients, so
- * that they stop taking workgroup slots from the data-gradient chain on every CU. */
-int mi3d_stream_create_masked(int cus_per_xcd, int from_top, void** stream_out);
 int mi3d_stream_destroy(void* stream);
 /* Route switches: every kernel-selection switch of the library ("no_persist", "no_fused_bwd", "ks_target", ... -- the table
  * in INTEGRATION.md) is read from the environment (MI3D_<NAME>=<int>) ONCE, when the library is first used; afterwards only
@@ -160,7 +131,6 @@ int mi3d_stream_destroy(void* stream);
 int mi3d_debug_set_route(const char* name, int value);
 int mi3d_debug_get_route(const char* name, int* value_out);
 int mi3d_debug_route_count(void);
-int mi3d_debug_experiments(void);      /* 1: built with make EXPERIMENTS=1 (default-off experiment kernels compiled in) */
 const char* mi3d_debug_route_name(int index);
 /* Measurement hook (bench.py `roofline`: HIP events around ONE kernel on the stream it is launched on, also the aux stream).
  * mi3d_time_next_conv3_kernel arms it for the calling thread: the next launch of `kind` for the layer (Cin, Cout as that
@@ -176,12 +146,6 @@ const char* mi3d_debug_route_name(int index);
  * threads x 128 VGPRs hold their CU slots for `microseconds` on `stream` and read through buf[0..n) meanwhile
  * (bench.py --emulate-comm: what a collective beside the encoder backward costs the persistent grids). */
 int mi3d_debug_occupy_cus(int workgroups, int microseconds, float* buf, int64_t n, void* stream);
-/* mi3d_set_cu_budget: CUs (0..128) the persistent conv grids launched from the calling thread leave free for a collective
- * kernel that is resident beside them (TrainStep sets it for the backward segments that overlap a gradient exchange).
- * THREAD-LOCAL: it applies to launches made by the thread that set it (a backward run by another thread, e.g. the autograd engine's,
- * does not see it), and a hipGraph capture freezes the value that was active while it was captured.  The grids are sized from the
- * device's compute-unit count (hipDeviceAttributeMultiprocessorCount, read once per process). */
-int mi3d_set_cu_budget(int cus);
 int mi3d_timing_event_create(void** event_out);
 int mi3d_time_next_conv3_kernel(void* start_event, void* stop_event, int kind, int Cin, int Cout);
 int mi3d_time_hook_fired(void);

@@ -20,8 +20,7 @@ vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 class UNetDesc(C.Structure):
     _fields_ = [("in_channels", C.c_int32), ("out_channels", C.c_int32), ("n_levels", C.c_int32),
                 ("features", C.c_int32 * MAX_LEVELS), ("N", C.c_int32), ("D", C.c_int32), ("H", C.c_int32),
-                ("W", C.c_int32), ("dtype", C.c_int32), ("bn_momentum", C.c_float), ("bn_eps", C.c_float),
-                ("prepacked_from", C.c_int32)]
+                ("W", C.c_int32), ("dtype", C.c_int32), ("bn_momentum", C.c_float), ("bn_eps", C.c_float)]
 
 
 class LossCfg(C.Structure):
@@ -56,24 +55,17 @@ _SIGS = {
     "mi3d_unet_infer": (i32, [_DP, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi3d_unet_bn_apply_deferred": (i32, [_DP, vp, vp, vp]),
     "mi3d_unet_backward": (i32, [_DP, vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, sz, vp, vp, vp, i32]),
-    "mi3d_unet_chain_tail_blocks": (i32, [_DP]),
-    "mi3d_unet_pack_from": (i32, [_DP, C.POINTER(vp), vp, sz, i32, vp]),
     "mi3d_unet_backward_marks": (i32, [C.POINTER(C.c_int), C.POINTER(vp), i32]),
     "mi3d_stream_wait_event": (i32, [vp, vp]),
-    "mi3d_flag_set": (i32, [vp, C.c_int64, vp]),
-    "mi3d_flag_wait": (i32, [vp, C.c_int64, C.c_int64, vp]),
     "mi3d_event_create": (i32, [C.POINTER(vp)]),
     "mi3d_event_destroy": (i32, [vp]),
     "mi3d_stream_create": (i32, [i32, C.POINTER(vp)]),
-    "mi3d_stream_create_masked": (i32, [i32, i32, C.POINTER(vp)]),
     "mi3d_stream_destroy": (i32, [vp]),
     "mi3d_debug_set_route": (i32, [C.c_char_p, i32]),
     "mi3d_debug_get_route": (i32, [C.c_char_p, C.POINTER(C.c_int)]),
     "mi3d_debug_route_count": (i32, []),
-    "mi3d_debug_experiments": (i32, []),
     "mi3d_debug_route_name": (C.c_char_p, [i32]),
     "mi3d_debug_occupy_cus": (i32, [i32, i32, vp, i64, vp]),
-    "mi3d_set_cu_budget": (i32, [i32]),
     "mi3d_timing_event_create": (i32, [C.POINTER(vp)]),
     "mi3d_time_next_conv3_kernel": (i32, [vp, vp, i32, i32, i32]),
     "mi3d_time_hook_fired": (i32, []),

@@ -117,14 +117,6 @@ int mi3d_adamw_apply(float* p, const float* g, float* m, float* v, int64_t n, fl
     MI3D_CHECK_ARG(step_dev && (n == 0 || (p && g && m && v)) && n >= 0, "mi3d_adamw_apply: bad arguments");
     return adamw_step(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step_dev, (hipStream_t)stream, increment);
 }
-int mi3d_flag_set(int64_t* flag, int64_t value, void* stream) {
-    MI3D_CHECK_ARG(flag, "mi3d_flag_set: null flag");
-    return flag_set(flag, value, (hipStream_t)stream);
-}
-int mi3d_flag_wait(int64_t* flag, int64_t value, int64_t timeout_us, void* stream) {
-    MI3D_CHECK_ARG(flag && timeout_us > 0, "mi3d_flag_wait: bad arguments");
-    return flag_wait(flag, value, timeout_us, (hipStream_t)stream);
-}
 int mi3d_debug_occupy_cus(int workgroups, int microseconds, float* buf, int64_t n, void* stream) {
     return occupy_cus(workgroups, microseconds, buf, n, (hipStream_t)stream);
 }
@@ -347,13 +339,6 @@ int mi3d_debug_get_route(const char* name, int* value_out) {
         if (!strcmp(name, ROUTE_TABLE[i].name)) { *value_out = routes_mut().*(ROUTE_TABLE[i].field); return 0; }
     MI3D_CHECK_ARG(false, "mi3d_debug_get_route: unknown route '%s'", name);
 }
-int mi3d_debug_experiments(void) {
-#ifdef MI3D_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
 int mi3d_debug_route_count(void) { return N_ROUTES; }
 const char* mi3d_debug_route_name(int i) { return (i >= 0 && i < N_ROUTES) ? ROUTE_TABLE[i].name : nullptr; }
 
@@ -374,21 +359,6 @@ int mi3d_stream_create(int priority_class, void** stream_out) {
     int prio = priority_class < 0 ? greatest : priority_class > 0 ? least : (least + greatest) / 2;
     hipStream_t s;
     MI3D_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio));
-    *stream_out = (void*)s;
-    return 0;
-}
-int mi3d_stream_create_masked(int cus_per_xcd, int from_top, void** stream_out) {
-    MI3D_CHECK_ARG(stream_out && cus_per_xcd >= 1 && cus_per_xcd <= 31, "mi3d_stream_create_masked: bad arguments");
-    hipDeviceProp_t prop;
-    int dev = 0;
-    MI3D_HIP(hipGetDevice(&dev));
-    MI3D_HIP(hipGetDeviceProperties(&prop, dev));
-    MI3D_CHECK_ARG(prop.multiProcessorCount == 256, "mi3d_stream_create_masked: expects 8 XCDs x 32 CUs, device has %d CUs", prop.multiProcessorCount);
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int lo = from_top ? (32 - cus_per_xcd) * 8 : 0, hi = lo + cus_per_xcd * 8;
-    for (int b = lo; b < hi; b++) mask[b >> 5] |= 1u << (b & 31);
-    hipStream_t s;
-    MI3D_HIP(hipExtStreamCreateWithCUMask(&s, 8, mask));
     *stream_out = (void*)s;
     return 0;
 }

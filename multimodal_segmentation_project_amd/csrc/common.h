@@ -69,18 +69,15 @@ void mi3d_set_error(const char* fmt, ...);
     X(fused_wg_target, 288) /* weight-gradient workgroups of a fused deep-level backward launch */                  \
     X(no_defer_wgrad, 0)    /* round 4: weight gradients stay on the data-gradient chain even with an aux stream */ \
     X(defer_mask, 7)        /* which weight gradients go to the aux stream: 1 decoder level 0, 2 decoder level 1, 4 deep levels */ \
-    X(apply_on_load, 0)     /* MI3D_EXPERIMENTS builds only (round 4, measured slower): deep levels apply BatchNorm in the next conv's staging pass instead of a bn_apply / bn_bwd_apply launch */ \
     X(no_pool_splitk, 0)    /* 1: a split-K gradient of a pooled tensor is finished by its own pass, not inside the MaxPool3d backward */ \
     X(no_wide_store, 4)     /* bit mask of the kernels that keep 8-byte epilogue stores instead of 16-byte ones (v_permlane16_swap): 1 persistent conv, 2 eight-wave conv, 4 four-wave conv body of the fused backward, 8 transposed-conv forward; 15 = all.  In-process A/B of each site (us/step gained by the wide store): 0 / 5 / -3 / 7, so the four-wave body keeps its 8-byte stores */ \
     X(no_pool_pair, 0)      /* 1: MaxPool3d backward with one thread per window (rounds 1-3) instead of two */ \
     X(no_wgrad_xcd, 0)      /* 1: full-resolution weight gradients take tile = slab index (rounds 1-3) instead of XCD-contiguous tiles */ \
     X(no_upbwd_xcd_mix, 0)  /* 1: fused transposed-conv backward with the round-3 block mapping (even blocks weight gradient, odd data gradient: one kind per XCD) */ \
-    X(opt_tail, 0)          /* 1: AdamW + weight re-pack of everything but the leading encoder blocks on the aux stream beside the end of the backward (TrainStep reads it; measured neutral: the aux stream is the long pole there) */ \
     X(wide_bn, 3)           /* round 4: the conv epilogue's BatchNorm partial rows are finished by the apply pass itself, no finalize launch: 1 = layers with <= 128 rows (level 2; every thin workgroup's prologue), 2 = also the layers with up to 1024 rows (levels 0-1) through wide_bn_wgs workgroups of 1024 threads; 0 = a finalize launch per layer (rounds 1-3) */ \
     X(wide_bn_wgs, 256)     /* workgroups of a wide BatchNorm pass */ \
     X(wide_min_rows, 129)   /* partial rows from which the wide kernel (instead of the thin workgroups' prologue) finishes the statistics */ \
-    X(splitk_ticket, 1)     /* round 4: a split-K forward conv of a training step finishes itself (the last of a tile's ks workgroups sums the partials, stores y and the BatchNorm partial row); 0 = the bn_stats_splitk launch does (rounds 2-3) */ \
-    X(conv_dma, 0)          /* MI3D_EXPERIMENTS builds only: LDS-DMA staging in the Cout = 16 persistent forward conv */
+    X(splitk_ticket, 1)     /* round 4: a split-K forward conv of a training step finishes itself (the last of a tile's ks workgroups sums the partials, stores y and the BatchNorm partial row); 0 = the bn_stats_splitk launch does (rounds 2-3) */
 struct Mi3dRoutes {
 #define MI3D_ROUTE_FIELD(name, dflt) int name = dflt;
     MI3D_ROUTE_LIST(MI3D_ROUTE_FIELD)

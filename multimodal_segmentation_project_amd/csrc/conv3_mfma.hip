@@ -21,8 +21,6 @@
 
 #include <hip/hip_ext.h>
 
-#include <utility>
-
 #include "ops.h"
 #include "slab_sum.h"
 
@@ -397,7 +395,6 @@ __global__ __launch_bounds__(BLK) void conv3_mfma_kernel(const bf16* __restrict_
 constexpr size_t conv8_lds(int TY, int TX, int COB) {        // TX == 8 <=> BX == 4 tilings: LDS row pitch 12 voxels (see the kernel)
     return (size_t)6 * (TY + 2) * (TX == 8 ? 12 : TX + 2) * 32 + (size_t)14 * COB * 1024 + (size_t)8 * COB * 16 * 2 * 4;
 }
-constexpr size_t CONV8_XF_LDS = 256 * 6 * sizeof(float);     // XF coefficient table behind the kernel's own LDS block
 // Levels 1-4 run ONE tile per workgroup with <= 2 workgroups per CU (432 tiles at level 1), so the serial chain of one
 // workgroup (tile loads -> LDS -> K loop -> stores) IS the kernel time.  This variant halves that chain per wave: 8 waves,
 // wave w owns z-slice w & 3 and HALF of the slice's M-blocks (w >> 2); staging is spread over 512 threads; the chunk's weight
@@ -405,23 +402,14 @@ constexpr size_t CONV8_XF_LDS = 256 * 6 * sizeof(float);     // XF coefficient t
 // which keeps the kernel under 128 VGPRs = 4 waves per SIMD.  Same arithmetic per output element as conv3_mfma_body (same
 // K order, same fp32 accumulation) -> bit-identical outputs; the statistic partials sum 8 instead of 4 wave rows.
 //
-// XF != 0 ("apply on load", round 4, small-geometry tiling only): the input tensor is a BatchNorm output that was never
-// written -- the staging pass computes it from the raw tensor(s) between the global load and the LDS store, and the launch
-// that used to do that (bn_apply / bn_bwd_apply: one link of the deep-level chain each) disappears:
-//   XF = 1  forward conv1 of a block:  z1 = relu(a*y0 + b) * drop      (x = y0 of conv0; a, b from conv0's statistics)
-//   XF = 2  input gradient:            dy = g*m*dz + A*y + B            (x = dz, xf.y2 = the layer's own raw output y)
-// The per-channel coefficients come from the <= 128 partial rows the statistics / reduction kernel left (summed in the
-// prologue, in double, like the "small BatchNorm" consumers bn_apply_kernel<TRAIN> / bn_bwd_apply_kernel<SMALL> do); the
-// workgroups of tile 0 / output group 0 publish stat[4][C] + running statistics (XF = 1) or dgamma / dbeta (XF = 2) for the
-// channel chunks they own.  Output group 0 also WRITES the transformed tensor for the voxels inside its tile (xf.side): the
-// weight-gradient kernels of the backward read it (z1 resp. dy) exactly as before.  Element for element the arithmetic is
-// bn_apply_kernel's / bn_bwd_apply_kernel's (same fmaf order, same rounding), so both routes give the same bits.
-template <int TZ, int TYB, int TXB, int BX, int COB, bool STATS, bool SPLITK, int XF = 0, bool TK = false>
-__global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const bf16* __restrict__ x, int xcs, int Cin,
-                                                          const bf16* __restrict__ wp, const float* __restrict__ bias,
-                                                          bf16* __restrict__ y, int ycs, int CoutTotal, int D, int H, int W,
-                                                          int tilesZ, int tilesY, int tilesX, float* __restrict__ part, int relu,
-                                                          XfArgs xf) {
+// TK (split-K ticket, conv3_mfma_ticket_ok): tk_count = per (tile, output group) arrival counters (zero before the launch, left
+// zero by it), tk_rows = the BatchNorm partial rows [tiles][2][Cout] the finishing workgroups write
+template <int TZ, int TYB, int TXB, int BX, int COB, bool STATS, bool SPLITK, bool TK = false>
+__global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restrict__ x, int xcs, int Cin,
+                                                            const bf16* __restrict__ wp, const float* __restrict__ bias,
+                                                            bf16* __restrict__ y, int ycs, int CoutTotal, int D, int H, int W,
+                                                            int tilesZ, int tilesY, int tilesX, float* __restrict__ part, int relu,
+                                                            float* tk_rows, int* tk_count) {
     constexpr int NT = 512;
     constexpr int BY = 16 / BX;
     constexpr int TY = TYB * BY, TX = TXB * BX;
@@ -459,7 +447,6 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
         for (int c = 0; c < COB; c++) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr int NIT = (NVOX * 2 + NT - 1) / NT;
     int soff[NIT], sdst[NIT];
-    [[maybe_unused]] int svox[NIT], own = 0;                // XF: voxel index of the piece (second raw tensor, side tensor), "this workgroup writes it" bits
 #pragma unroll
     for (int it = 0; it < NIT; it++) {
         int idx = threadIdx.x + it * NT;
@@ -469,10 +456,6 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
         int gz = z0 - 1 + iz, gy = y0 - 1 + iy, gx = x0 - 1 + ix;
         bool inb = idx < NVOX * 2 && gz >= 0 && gz < D && gy >= 0 && gy < H && gx >= 0 && gx < W;
         soff[it] = inb ? ((gz * H + gy) * W + gx) * xcs + half * 8 : -1;
-        if constexpr (XF != 0) {
-            svox[it] = (gz * H + gy) * W + gx;
-            if (inb && iz >= 1 && iz <= TZ && iy >= 1 && iy <= TY && ix >= 1 && ix <= TX && bid_.y == 0 && xf.side) own |= 1 << it;
-        }
     }
     const bf16* xn = x + (int64_t)n * D * H * W * xcs;
     int nchunk = Cin / 16, chunk0 = 0;
@@ -482,15 +465,6 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
         nchunk = chunk0 + per;
     }
     bf16x8 sv[NIT];
-    [[maybe_unused]] bf16x8 sv2[NIT];
-    [[maybe_unused]] const bf16* x2n = nullptr;
-    [[maybe_unused]] bf16* siden = nullptr;
-    // XF coefficient table [k][256 channels of this workgroup's chunks]: k = a, b, d (Dropout3d scale), and for XF = 2 g, A, B
-    [[maybe_unused]] float* cft = reinterpret_cast<float*>(lds8 + conv8_lds(TY, TX, COB));
-    if constexpr (XF != 0) {
-        x2n = xf.y2 + (int64_t)n * D * H * W * xf.y2cs;
-        siden = xf.side ? xf.side + (int64_t)n * D * H * W * xf.side_cs : nullptr;
-    }
     constexpr int NWI = (14 * COB * 64 + NT - 1) / NT;
     bf16x8 wv[NWI];
     auto load_chunk = [&](int chunk) {
@@ -498,10 +472,6 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
         for (int it = 0; it < NIT; it++) {
             sv[it] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
             if (soff[it] >= 0) sv[it] = *reinterpret_cast<const bf16x8*>(xn + soff[it] + chunk * 16);
-            if constexpr (XF == 2) {
-                sv2[it] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                if (soff[it] >= 0) sv2[it] = *reinterpret_cast<const bf16x8*>(x2n + svox[it] * xf.y2cs + (threadIdx.x & 1) * 8 + chunk * 16);
-            }
         }
 #pragma unroll
         for (int i = 0; i < NWI; i++) {
@@ -512,65 +482,7 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
             }
         }
     };
-    load_chunk(chunk0);                                   // (XF: in flight under the coefficient prologue)
-    if constexpr (XF != 0) {
-        const int C = xf.C, c0 = chunk0 * 16, nloc = (nchunk - chunk0) * 16;      // channels of the input tensor owned here
-        // sum the partial rows [nrows][2][C] for (k, c) in [0,2) x [c0, c0 + nloc): 512 / (2 nloc) row groups, then the groups
-        // in fixed order.  (Sums of <= 128 fp32 values of one sign pattern in double: the order does not change the result.)
-        double* red8 = reinterpret_cast<double*>(lds8);                               // the tile area is free before the first stage
-        const int npair = 2 * nloc, ngrp = NT / npair;
-        {
-            const int pair = threadIdx.x % npair, grp = threadIdx.x / npair;
-            double acc_ = 0.0;
-            if (grp < ngrp) {
-                const int k = pair / nloc, cc = pair - k * nloc;
-                for (int r = grp; r < xf.nrows; r += ngrp) acc_ += (double)xf.rows[((size_t)r * 2 + k) * C + c0 + cc];
-                red8[grp * npair + pair] = acc_;
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < nloc) {
-            const int cc = threadIdx.x, c = c0 + cc;
-            double s0 = 0.0, s1 = 0.0;
-            for (int q = 0; q < ngrp; q++) { s0 += red8[q * npair + cc]; s1 += red8[q * npair + nloc + cc]; }
-            const bool pub = xcd_contig(bid_.x, bid_.gx) == 0 && bid_.y == 0;        // tile 0, output group 0: one publisher per chunk range
-            const float dsc = xf.drop ? xf.drop[(size_t)n * C + c] : 1.f;
-            if constexpr (XF == 1) {
-                double mean = s0 / (double)xf.M;
-                double var = s1 / (double)xf.M - mean * mean;
-                if (var < 0.0) var = 0.0;
-                double inv = 1.0 / sqrt(var + (double)xf.eps);
-                float a = (float)((double)xf.gamma[c] * inv);
-                float b = (float)((double)xf.beta[c] - mean * (double)xf.gamma[c] * inv);
-                cft[cc] = a; cft[256 + cc] = b; cft[512 + cc] = dsc;
-                if (pub) {
-                    xf.stat[c] = (float)mean; xf.stat[C + c] = (float)inv; xf.stat[2 * C + c] = a; xf.stat[3 * C + c] = b;
-                    if (xf.momentum < 0.f) {
-                        double* side = reinterpret_cast<double*>(xf.rmean);
-                        if (side) { side[c] = mean; side[C + c] = xf.M > 1 ? var * (double)xf.M / (double)(xf.M - 1) : var; }
-                    } else {
-                        if (xf.rmean) xf.rmean[c] = (float)((1.0 - xf.momentum) * xf.rmean[c] + xf.momentum * mean);
-                        if (xf.rvar) {
-                            double unb = xf.M > 1 ? var * (double)xf.M / (double)(xf.M - 1) : var;
-                            xf.rvar[c] = (float)((1.0 - xf.momentum) * xf.rvar[c] + xf.momentum * unb);
-                        }
-                        if (xf.nbt && c == 0) *xf.nbt += 1;
-                    }
-                }
-            } else {
-                const float mean = xf.stat[c], inv = xf.stat[C + c], a = xf.stat[2 * C + c], b = xf.stat[3 * C + c];
-                const float cf0 = (float)(s0 / (double)xf.M), cf1 = (float)(s1 / (double)xf.M);
-                const float gg = a, k = gg * cf1 * inv;
-                cft[cc] = a; cft[256 + cc] = b; cft[512 + cc] = dsc;
-                cft[768 + cc] = gg; cft[1024 + cc] = -k; cft[1280 + cc] = k * mean - gg * cf0;
-                if (pub) {
-                    if (xf.dgamma) xf.dgamma[c] = xf.accumulate ? xf.dgamma[c] + (float)s1 : (float)s1;
-                    if (xf.dbeta) xf.dbeta[c] = xf.accumulate ? xf.dbeta[c] + (float)s0 : (float)s0;
-                }
-            }
-        }
-        // (the first chunk's barrier in front of the LDS stores orders the table writes before their first use)
-    }
+    load_chunk(chunk0);
     auto frag_off = [&](int s) {
         int t0 = 2 * s, t1 = (2 * s + 1 < 27) ? 2 * s + 1 : 26;
         int off0 = (((t0 / 9) * IY + ((t0 / 3) % 3)) * IXP + (t0 % 3)) * 32;
@@ -580,44 +492,6 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
     auto row_off = [&](int r) { int rg = hb * MBW + r; return (((rg / TXB) * BY) * IXP + (rg % TXB) * BX) * 32; };
     for (int chunk = chunk0; chunk < nchunk; chunk++) {
         __syncthreads();
-        if constexpr (XF != 0) {
-            // this thread's 8 channels of the chunk: (chunk - chunk0) * 16 + (threadIdx.x & 1) * 8 (NT is even: `half` is fixed);
-            // four channels at a time, so that the coefficient registers stay few (the kernel lives under 128 VGPRs)
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const float* ct = cft + (chunk - chunk0) * 16 + (threadIdx.x & 1) * 8 + q * 4;
-                const f32x4 ca = *reinterpret_cast<const f32x4*>(ct), cb = *reinterpret_cast<const f32x4*>(ct + 256),
-                            cd = *reinterpret_cast<const f32x4*>(ct + 512);
-                [[maybe_unused]] f32x4 cg, cA, cB;
-                if constexpr (XF == 2) {
-                    cg = *reinterpret_cast<const f32x4*>(ct + 768); cA = *reinterpret_cast<const f32x4*>(ct + 1024);
-                    cB = *reinterpret_cast<const f32x4*>(ct + 1280);
-                }
-#pragma unroll
-                for (int it = 0; it < NIT; it++) {
-                    if (soff[it] < 0) continue;                  // outside the volume: the conv's zero padding, not a transformed zero
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        if constexpr (XF == 1) {
-                            float t = fmaf((float)sv[it][q * 4 + i], ca[i], cb[i]);
-                            t = t > 0.f ? t : 0.f;
-                            sv[it][q * 4 + i] = (bf16)(t * cd[i]);
-                        } else {
-                            const float yv = (float)sv2[it][q * 4 + i], gv = (float)sv[it][q * 4 + i];
-                            const float pre = fmaf(yv, ca[i], cb[i]);
-                            const float m = pre > 0.f ? cd[i] : 0.f;
-                            sv[it][q * 4 + i] = (bf16)fmaf(cg[i] * m, gv, fmaf(cA[i], yv, cB[i]));
-                        }
-                    }
-                }
-            }
-            if (own) {
-#pragma unroll
-                for (int it = 0; it < NIT; it++)
-                    if (own & (1 << it))
-                        *reinterpret_cast<bf16x8*>(siden + svox[it] * xf.side_cs + (threadIdx.x & 1) * 8 + chunk * 16) = sv[it];
-            }
-        }
 #pragma unroll
         for (int it = 0; it < NIT; it++) {
             int idx = threadIdx.x + it * NT;
@@ -683,7 +557,7 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the write-through stores above have been acknowledged
             __syncthreads();
             if (threadIdx.x == 0) {
-                int* cnt = xf.tk_count + (tile_id * bid_.gy + bid_.y);
+                int* cnt = tk_count + (tile_id * bid_.gy + bid_.y);
                 const int old = atomicAdd(cnt, 1);
                 const int lastv = old == ks - 1;
                 s_last = lastv;
@@ -753,7 +627,7 @@ __global__ __launch_bounds__(512, XF == 2 ? 2 : 4) void conv3_mfma8_kernel(const
                 float v = 0.f;
 #pragma unroll
                 for (int w_ = 0; w_ < 8; w_++) v += red[w_][ch / 16][ch % 16][k];
-                xf.tk_rows[((int64_t)bid_.x * 2 + k) * CoutTotal + cobBase * 16 + ch] = v;
+                tk_rows[((int64_t)bid_.x * 2 + k) * CoutTotal + cobBase * 16 + ch] = v;
             }
             return;
         }
@@ -1126,239 +1000,7 @@ __global__ __launch_bounds__(BLK, 2) void conv3_mfma_persist_kernel(const bf16* 
                                              nullptr, relu);
 }
 
-#ifdef MI3D_EXPERIMENTS      // default-off experiment routes are compiled only into experiment builds (make EXPERIMENTS=1)
-// ------------------------------------------------------------------------ persistent variant with asynchronous staging
-// Cout = 16 forward layers at full resolution (16 -> 16, 32 -> 16).  Same tile, K-step order and epilogue as the kernel
-// above; what changes is how a workgroup's phases relate.  There, a chunk is  barrier | LDS writes | barrier | issue the next
-// loads | MFMAs | stores  in series (stamps: the MFMA phase is half of a wave's time) and only the partner workgroup on the
-// CU hides any of it.  Here the halo tile goes global -> LDS by DMA (buffer_load ... lds: no staging registers, no ds_write,
-// out-of-bounds pieces arrive as zeros from the buffer bounds check) into the OTHER of two LDS tiles while the MFMAs of the
-// current chunk run, with ONE barrier per chunk; the registers the staging freed hold all weight fragments (no weight reads
-// from LDS), and the fragment reads are a hand-pipelined stream (ring of 7, counted lgkmcnt waits).
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-template <int NCH>
-struct DmaMma {
-    static constexpr int IY = 10, IX = 18, RS = IX * 32, PS = IY * IX * 32;
-    static constexpr int NFRAG = 70, PF = 6, NR = PF + 1;
-    const char *pA, *pB, *pH, *pI;
-    bf16x8 R[NR];
-    template <int I>
-    __device__ __forceinline__ bf16x8 fload() const {
-        if constexpr (I < 54) {
-            constexpr int dz = I / 18, k = I % 18;
-            if constexpr (k < 10) return *reinterpret_cast<const bf16x8*>(pA + (dz * IY + k) * RS);
-            else return *reinterpret_cast<const bf16x8*>(pB + (dz * IY + (k - 10)) * RS);
-        } else if constexpr (I < 62) {
-            return *reinterpret_cast<const bf16x8*>(pH + (I - 54) * RS);
-        } else {
-            return *reinterpret_cast<const bf16x8*>(pI + (I - 62) * RS);
-        }
-    }
-    template <int CH, int I, typename Side>
-    __device__ __forceinline__ void step(f32x4 (&acc)[8], const bf16x8 (&Wr)[NCH][14], Side& side) {
-        // one DMA piece of the next chunk every 7 fragments: spread under the MFMAs instead of a burst in front of them
-        if constexpr (I >= 2 && (I - 2) % 7 == 0 && (I - 2) / 7 < 9) side(std::integral_constant<int, (I - 2) / 7>{});
-        if constexpr (I + PF < NFRAG) R[(I + PF) % NR] = fload<I + PF>();
-        const bf16x8 f = R[I % NR];
-        if constexpr (I < 54) {
-            constexpr int dz = I / 18, k = I % 18;
-            if constexpr (k < 10) {
-                if constexpr (k < 8) acc[k] = mfma16(Wr[CH][dz * 4 + 0], f, acc[k]);
-                if constexpr (k >= 1 && k - 1 < 8) acc[k - 1] = mfma16(Wr[CH][dz * 4 + 1], f, acc[k - 1]);
-                if constexpr (k >= 2 && k - 2 < 8) acc[k - 2] = mfma16(Wr[CH][dz * 4 + 2], f, acc[k - 2]);
-            } else {
-                acc[k - 10] = mfma16(Wr[CH][dz * 4 + 3], f, acc[k - 10]);
-            }
-        } else if constexpr (I < 62) {
-            acc[I - 54] = mfma16(Wr[CH][12], f, acc[I - 54]);
-        } else {
-            acc[I - 62] = mfma16(Wr[CH][13], f, acc[I - 62]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    template <int... Is>
-    __device__ __forceinline__ void prologue(std::integer_sequence<int, Is...>) { ((R[Is] = fload<Is>()), ...); }
-    template <int CH, typename Side, int... Is>
-    __device__ __forceinline__ void run(f32x4 (&acc)[8], const bf16x8 (&Wr)[NCH][14], Side& side, std::integer_sequence<int, Is...>) {
-        (step<CH, Is>(acc, Wr, side), ...);
-    }
-    template <int CH, typename Side>
-    __device__ __forceinline__ void chunk(f32x4 (&acc)[8], const bf16x8 (&Wr)[NCH][14], const char* tile, int laneOff, int g,
-                                          Side& side) {
-        pA = tile + laneOff + (g >> 1) * 32;                                   // dx = 0 | 1
-        pB = tile + laneOff + (g >> 1) * RS + 64;                              // dy = 0 | 1 at dx = 2
-        pH = tile + laneOff + (g >> 1) * PS + (2 * IX + 2) * 32;               // dz = 0 | 1 at (dy, dx) = (2, 2)
-        pI = tile + laneOff + 2 * PS + 2 * RS + 64;                            // (2, 2, 2) | pad
-        prologue(std::make_integer_sequence<int, PF>{});
-        __builtin_amdgcn_sched_barrier(0);
-        run<CH>(acc, Wr, side, std::make_integer_sequence<int, NFRAG>{});
-    }
-};
-
-constexpr int DMA_NIT = 9, DMA_TILE_BYTES = DMA_NIT * BLK * 16;      // 36 864 B per LDS tile (6*10*18 voxels * 32 B = 34 560 used)
-constexpr unsigned DMA_OOB = 0xffffff00u;                             // >= num_records: the bounds check returns zeros
-
-template <int NCH, bool STATS>
-__global__ __launch_bounds__(BLK, 2) void conv3_mfma_persist_dma_kernel(const bf16* __restrict__ x, int xcs,
-                                                                        const bf16* __restrict__ wp, const float* __restrict__ bias,
-                                                                        bf16* __restrict__ y, int ycs, int D, int H, int W,
-                                                                        int tilesZ, int tilesY, int tilesX, int ntiles,
-                                                                        float* __restrict__ part, Halves xh, Halves yh, int relu) {
-    constexpr int TZ = 4, TY = 8, TX = 16, IY = 10, IX = 18, MB = 8, NVOX = 6 * IY * IX;
-    extern __shared__ __attribute__((aligned(16))) char dma_lds[];
-    float (*red)[16][2] = reinterpret_cast<float (*)[16][2]>(dma_lds + 2 * DMA_TILE_BYTES);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int vn = lane & 15, g = lane >> 4;
-    const int laneOff = ((vn * 16 + (g & 1) * 8) * 2) + wave * (IY * IX * 32);
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(x), (short)0, (int)DMA_OOB, 0x00020000);
-
-    // staging map, tile-invariant: byte offset of this thread's pieces relative to halo voxel (0,0,0), and their halo
-    // coordinates packed 12 bits each for the border tiles
-    unsigned relb[DMA_NIT];
-    unsigned pk[(DMA_NIT + 1) / 2];
-#pragma unroll
-    for (int i = 0; i < (DMA_NIT + 1) / 2; i++) pk[i] = 0;
-#pragma unroll
-    for (int it = 0; it < DMA_NIT; it++) {
-        int idx = threadIdx.x + it * BLK;
-        int vox = idx >> 1, half = idx & 1;
-        int ix = vox % IX, t = vox / IX, iy = t % IY, iz = t / IY;
-        relb[it] = idx < NVOX * 2 ? (unsigned)((((iz * H + iy) * W + ix) * xcs + half * 8) * 2) : DMA_OOB;
-        if (iz > 7) iz = 7;
-        pk[it >> 1] |= (unsigned)(ix | (iy << 5) | (iz << 9)) << ((it & 1) * 16);
-    }
-    // all weight fragments stay in registers (ktap mode 1 pack: [chunk][14 K-steps][lane][8])
-    bf16x8 Wr[NCH][14];
-#pragma unroll
-    for (int ch = 0; ch < NCH; ch++)
-#pragma unroll
-        for (int s_ = 0; s_ < 14; s_++) Wr[ch][s_] = *reinterpret_cast<const bf16x8*>(wp + ((int64_t)ch * 14 + s_) * 512 + lane * 8);
-    float bv[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) bv[j] = bias ? bias[g * 4 + j] : 0.f;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-
-    auto tile_origin = [&](int tile, int& n, int& z0, int& y0, int& x0) {
-        int tz_ = tile % tilesZ; tile /= tilesZ;
-        int ty_ = tile % tilesY; tile /= tilesY;
-        int tx_ = tile % tilesX; n = tile / tilesX;
-        z0 = tz_ * TZ; y0 = ty_ * TY; x0 = tx_ * TX;
-    };
-    // DMA of (tile, chunk) into LDS tile `buf`: each wave-instruction lands 64 consecutive 16-byte pieces.  stage_prep
-    // computes the nine byte offsets (out of bounds -> DMA_OOB), stage_piece<it> issues one piece
-    unsigned soff[DMA_NIT];
-    char* sdst = dma_lds;
-    bool s_on = false;
-    auto stage_prep = [&](int tile, int chunk, int buf) {
-        int n, z0, y0, x0;
-        tile_origin(tile, n, z0, y0, x0);
-        const int64_t base = ((((int64_t)n * D + (z0 - 1)) * H + (y0 - 1)) * W + (x0 - 1)) * xcs + chunk * 16 +
-                             (chunk >= xh.split ? xh.delta : 0);
-        const unsigned baseb = (unsigned)(base * 2);         // may wrap below zero for border tiles: only used where in bounds
-        const bool interior = z0 >= 1 && z0 + TZ + 1 <= D && y0 >= 1 && y0 + TY + 1 <= H && x0 >= 1 && x0 + TX + 1 <= W;
-        sdst = dma_lds + buf * DMA_TILE_BYTES + wave * 1024;
-#pragma unroll
-        for (int it = 0; it < DMA_NIT; it++) {
-            unsigned off = relb[it] == DMA_OOB ? DMA_OOB : baseb + relb[it];
-            if (!interior) {
-                unsigned c = pk[it >> 1] >> ((it & 1) * 16);
-                unsigned gz = (unsigned)(z0 - 1) + ((c >> 9) & 7u), gy = (unsigned)(y0 - 1) + ((c >> 5) & 15u),
-                         gx = (unsigned)(x0 - 1) + (c & 31u);
-                bool inb = gz < (unsigned)D && gy < (unsigned)H && gx < (unsigned)W;
-                off = inb ? off : DMA_OOB;
-            }
-            soff[it] = off;
-        }
-        s_on = true;
-    };
-    auto stage_piece = [&](auto itc) {
-        constexpr int it = decltype(itc)::value;
-        if (s_on) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(sdst + it * (BLK * 16)), 16, soff[it], 0, 0, 0);
-    };
-    auto stage_all = [&]() {
-        stage_piece(std::integral_constant<int, 0>{}); stage_piece(std::integral_constant<int, 1>{});
-        stage_piece(std::integral_constant<int, 2>{}); stage_piece(std::integral_constant<int, 3>{});
-        stage_piece(std::integral_constant<int, 4>{}); stage_piece(std::integral_constant<int, 5>{});
-        stage_piece(std::integral_constant<int, 6>{}); stage_piece(std::integral_constant<int, 7>{});
-        stage_piece(std::integral_constant<int, 8>{});
-        static_assert(DMA_NIT == 9, "stage_all issues nine pieces");
-    };
-
-    int tile;
-    {
-        int nwg = gridDim.x, bid = blockIdx.x, q8 = nwg / 8, r8 = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
-    int buf = 0;
-    if (tile < ntiles) { stage_prep(tile, 0, 0); stage_all(); }
-    DmaMma<NCH> mm;
-    for (; tile < ntiles; tile += gridDim.x) {
-        f32x4 acc[MB];
-#pragma unroll
-        for (int r = 0; r < MB; r++) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto one_chunk = [&](auto chc) {
-            constexpr int ch = decltype(chc)::value;
-            // my pieces of the current tile have landed; after the barrier everyone's have, and everyone has finished
-            // reading the other tile (the previous chunk's MFMAs) -> it may be overwritten by the next DMA
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            s_on = false;
-            if (ch + 1 < NCH) stage_prep(tile, ch + 1, buf ^ 1);
-            else if (tile + (int)gridDim.x < ntiles) stage_prep(tile + gridDim.x, 0, buf ^ 1);
-            stage_all();
-            auto no_side = [](auto) {};
-            mm.template chunk<ch>(acc, Wr, dma_lds + buf * DMA_TILE_BYTES, laneOff, g, no_side);
-            buf ^= 1;
-        };
-        one_chunk(std::integral_constant<int, 0>{});
-        if constexpr (NCH > 1) one_chunk(std::integral_constant<int, NCH - 1>{});
-        static_assert(NCH <= 2, "one or two 16-channel chunks");
-        // ---- epilogue of this tile
-        int n, z0, y0, x0;
-        tile_origin(tile, n, z0, y0, x0);
-        int gz = z0 + wave, gx = x0 + vn;
-        bf16* yrow = y + ((((int64_t)n * D + gz) * H + y0) * W + gx) * ycs + g * 4 + (0 >= yh.split ? yh.delta : 0);
-        bool okzx = gz < D && gx < W;
-#pragma unroll
-        for (int r = 0; r < MB; r++) {
-            bool ok = okzx && (y0 + r) < H;
-            bf16x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float v = acc[r][j] + bv[j];
-                if (relu) v = fmaxf(v, 0.f);
-                o[j] = (bf16)v;
-                if (STATS) { float q = ok ? (float)o[j] : 0.f; s1[j] += q; s2[j] = fmaf(q, q, s2[j]); }
-            }
-            if (ok) *reinterpret_cast<bf16x4*>(yrow + (int64_t)r * W * ycs) = o;
-        }
-    }
-    if constexpr (STATS) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float a = s1[j], b = s2[j];
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-            if (vn == 0) { red[wave][g * 4 + j][0] = a; red[wave][g * 4 + j][1] = b; }
-        }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < 32; idx += BLK) {
-            int k = idx & 1, chn = idx >> 1;
-            float v = (red[0][chn][k] + red[1][chn][k]) + (red[2][chn][k] + red[3][chn][k]);
-            part[((int64_t)blockIdx.x * 2 + k) * 16 + chn] = v;
-        }
-    }
-}
-
-#endif  // MI3D_EXPERIMENTS
-
 // eight-wave kernels (route conv8, default on): round 3 A/B level-1 forward convs 112 -> 103 us, deep 153 -> 143 us per step
-// CU budget (mi3d_set_cu_budget): CUs the caller wants left free of persistent workgroups because a collective kernel is
-// resident on them (data-parallel step: the gradient all-reduce runs beside the encoder backward).  A persistent grid sized
-// for all 256 CUs would otherwise run a second, partial round on the CUs it has to share.
-static thread_local int g_cu_budget = 0;
-extern "C" int mi3d_set_cu_budget(int cus) { g_cu_budget = cus < 0 ? 0 : (cus > 128 ? 128 : cus); return 0; }
 // compute units of the device (256 on MI355X), queried once per process; the plan sizes its partial-row buffers with the
 // same number, so it must not change between mi3d_unet_workspace_bytes and the launches
 inline int device_cus() {
@@ -1371,7 +1013,6 @@ inline int device_cus() {
     }();
     return n;
 }
-inline int persist_cus() { return device_cus() - g_cu_budget; }
 // ---- measurement hook (bench.py `roofline`): HIP events tightly around ONE kernel launch, keyed on the LAYER -----------------
 // kind 0 = fused full-resolution backward (input + weight gradient in one launch), 1 = stand-alone weight gradient,
 // 2 = persistent conv with BatchNorm partial sums (training forward), 3 = persistent conv without (input gradient);
@@ -1395,7 +1036,7 @@ inline bool persist_ok(int Cin, int Cout, Geo g) {
 }
 inline int persist_grid(int Cin, int Cout, Geo g) {
     int64_t nt = (int64_t)g.N * cdiv(g.D, 4) * cdiv(g.H, 8) * cdiv(g.W, 16);
-    int want = 2 * persist_cus();      // 2 resident workgroups per CU
+    int want = 2 * device_cus();      // 2 resident workgroups per CU
     return (int)(nt < want ? nt : want);
 }
 
@@ -1431,20 +1072,18 @@ __global__ __launch_bounds__(BLK) void splitk_finish_kernel(const float* __restr
 template <int TZ, int TYB, int TXB, int BX, int COB>
 int launch_cfg(const bf16* x, int xcs, int Cin, const bf16* wp, const float* bias, bf16* y, int ycs, int Cout, Geo g,
                float* part, int ksplit, float* skws, hipStream_t s, bool defer_finish = false, int relu = 0,
-               const XfArgs* xf = nullptr, float* tk_rows = nullptr, int* tk_count = nullptr) {
+               float* tk_rows = nullptr, int* tk_count = nullptr) {
     constexpr int TY = TYB * (16 / BX), TX = TXB * BX;
     int tz = cdiv(g.D, TZ), ty = cdiv(g.H, TY), tx = cdiv(g.W, TX);
     dim3 grid((unsigned)(g.N * tz * ty * tx), (unsigned)(Cout / (16 * COB)), (unsigned)ksplit);
     if (tk_rows) {       // split-K launch that finishes itself (ticket per (tile, output group)); eight-wave kernel only
-        MI3D_CHECK_ARG(ksplit > 1 && tk_count && mi3d_routes().conv8 != 0 && (!xf || xf->mode == 0) &&
+        MI3D_CHECK_ARG(ksplit > 1 && tk_count && mi3d_routes().conv8 != 0 &&
                        (int64_t)grid.x * grid.y <= CONV3_TK_COUNTERS && ycs % 8 == 0 && ((uintptr_t)y % 16) == 0,
                        "conv3_mfma: this launch cannot take the split-K ticket");
-        XfArgs xa;
-        xa.tk_rows = tk_rows; xa.tk_count = tk_count;
         constexpr size_t lds_tk = conv8_lds(TY, TX, COB);
-        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, 0, true>), lds_tk + CONV8_XF_LDS);
-        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, 0, true><<<grid, 512, lds_tk, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W,
-                                                                                                tz, ty, tx, skws, 0, xa);
+        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, true>), lds_tk);
+        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, true><<<grid, 512, lds_tk, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W,
+                                                                                             tz, ty, tx, skws, 0, tk_rows, tk_count);
         MI3D_LAUNCH_CHECK();
         return 0;
     }
@@ -1452,29 +1091,12 @@ int launch_cfg(const bf16* x, int xcs, int Cin, const bf16* wp, const float* bia
     static_assert((TYB * TXB) % 2 == 0, "tile shapes used here have an even number of M-blocks per slice");
     const bool w8 = mi3d_routes().conv8 != 0;
     constexpr size_t lds8 = conv8_lds(TY, TX, COB);
-#define LC8X(ST_, SK_, XF_, PART_, BIAS_, RELU_)                                                                               \
-    do {                                                                                                                       \
-        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST_, SK_, XF_>), lds8 + CONV8_XF_LDS);               \
-        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST_, SK_, XF_><<<grid, 512, lds8 + (XF_ ? CONV8_XF_LDS : 0), s>>>(x, xcs, Cin, wp, BIAS_, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, PART_, RELU_, xf ? *xf : XfArgs()); \
-    } while (0)
-    // apply on load: only the small-geometry tiling with two output blocks carries the transform (TX == 8, COB == 2)
-    constexpr bool XF_CFG = TX == 8 && COB == 2;
-    const int xfm = xf ? xf->mode : 0;
-    MI3D_CHECK_ARG(xfm == 0 || (XF_CFG && w8 && xf->C == Cin && Cin <= 256 && xf->rows && xf->nrows > 0 && xf->stat &&
-                                (xfm == 1 || (xfm == 2 && xf->y2))),
-                   "conv3_mfma: this launch cannot apply BatchNorm on load");
-#ifdef MI3D_EXPERIMENTS      // the apply-on-load kernels are a measured-slower experiment: experiment builds only
 #define LC8(ST_, SK_, PART_, BIAS_, RELU_)                                                                                     \
     do {                                                                                                                       \
-        if constexpr (XF_CFG) {                                                                                                \
-            if (xfm == 1) { LC8X(ST_, SK_, 1, PART_, BIAS_, RELU_); break; }                                                    \
-            if (xfm == 2) { LC8X(ST_, SK_, 2, PART_, BIAS_, RELU_); break; }                                                    \
-        }                                                                                                                      \
-        LC8X(ST_, SK_, 0, PART_, BIAS_, RELU_);                                                                                \
+        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST_, SK_>), lds8);                                   \
+        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST_, SK_><<<grid, 512, lds8, s>>>(x, xcs, Cin, wp, BIAS_, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, PART_, RELU_, \
+                                                                                   nullptr, nullptr);                          \
     } while (0)
-#else
-#define LC8(ST_, SK_, PART_, BIAS_, RELU_) LC8X(ST_, SK_, 0, PART_, BIAS_, RELU_)
-#endif
     if (ksplit > 1) {
         if (w8) LC8(false, true, skws, nullptr, 0);
         else conv3_mfma_kernel<TZ, TYB, TXB, BX, COB, false, true><<<grid, BLK, 0, s>>>(x, xcs, Cin, wp, nullptr, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, skws, 0);
@@ -1490,7 +1112,6 @@ int launch_cfg(const bf16* x, int xcs, int Cin, const bf16* wp, const float* bia
         else conv3_mfma_kernel<TZ, TYB, TXB, BX, COB, false, false><<<grid, BLK, 0, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, nullptr, relu & 1);
     }
 #undef LC8
-#undef LC8X
     MI3D_LAUNCH_CHECK();
     return 0;
 }
@@ -1578,13 +1199,6 @@ int conv3_bwd_ks_target() {
     return kst < 1 ? 1 : kst;
 }
 
-bool conv3_mfma_xform_ok(int Cin, int Cout, Geo g) {
-#ifndef MI3D_EXPERIMENTS
-    return false;
-#endif
-    return !big_geo(g) && !persist_ok(Cin, Cout, g) && Cout % 32 == 0 && Cin % 16 == 0 && Cin <= 256 && mi3d_routes().conv8 != 0;
-}
-
 bool conv3_mfma_ticket_ok(int Cin, int Cout, Geo g) {
     if (!mi3d_routes().splitk_ticket || mi3d_routes().conv8 == 0 || big_geo(g) || persist_ok(Cin, Cout, g)) return false;
     if (pick_ksplit(Cin, Cout, g) <= 1) return false;
@@ -1594,10 +1208,9 @@ bool conv3_mfma_ticket_ok(int Cin, int Cout, Geo g) {
 
 int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float* bias, void* y, int ycs, int Cout, Geo g,
                    float* part, float* skws, hipStream_t s, Halves xh, Halves yh, int* ks_deferred, int relu, int ks_target,
-                   const XfArgs* xf, float* tk_rows, int* tk_count) {
+                   float* tk_rows, int* tk_count) {
     if (ks_deferred) *ks_deferred = 0;
     MI3D_CHECK_ARG(!tk_rows || (conv3_mfma_ticket_ok(Cin, Cout, g) && skws && ks_target == 0), "conv3_mfma_fwd: no split-K ticket for %d->%d here", Cin, Cout);
-    MI3D_CHECK_ARG(!xf || xf->mode == 0 || conv3_mfma_xform_ok(Cin, Cout, g), "conv3_mfma_fwd: no apply-on-load kernel for %d->%d here", Cin, Cout);
     MI3D_CHECK_ARG((!xh.on() && !yh.on()) || persist_ok(Cin, Cout, g), "conv3_mfma_fwd: planar halves need the persistent kernel");
     MI3D_CHECK_ARG(conv3_mfma_supported(Cin, Cout, xcs, ycs), "conv3_mfma_fwd: unsupported channels %d->%d", Cin, Cout);
     MI3D_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0, "conv3_mfma_fwd: misaligned tensors");
@@ -1617,27 +1230,6 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
             else if (part) conv3_mfma_persist_kernel<COB_, NCH_, true><<<grid, BLK, 0, s>>>(xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, part, xh, yh, relu); \
             else conv3_mfma_persist_kernel<COB_, NCH_, false><<<grid, BLK, 0, s>>>(xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, nullptr, xh, yh, relu); \
         } while (0)
-        // Cout = 16: asynchronous-staging variant (the tensor must be addressable with 32-bit byte offsets)
-        // OFF by default: the kernels are 6-9 % faster, but with them in the step the part runs at 2350 instead of
-        // 2392 MHz (rocm-smi during bench.py, at LOWER package power) and the step gets 15-40 us slower
-#ifdef MI3D_EXPERIMENTS
-        const bool dma = Cout == 16 && (Cin == 16 || Cin == 32) && mi3d_routes().conv_dma &&
-                         (size_t)g.M() * (size_t)(xh.on() ? 2 * xcs : xcs) * 2 < (size_t)DMA_OOB;
-        if (dma) {
-            size_t lds = 2 * (size_t)DMA_TILE_BYTES + 4 * 16 * 2 * sizeof(float);
-#define PD(NCH_)                                                                                                              \
-            do {                                                                                                              \
-                if (part) { MI3D_SET_MAX_LDS_ONCE((&conv3_mfma_persist_dma_kernel<NCH_, true>), lds);                         \
-                    conv3_mfma_persist_dma_kernel<NCH_, true><<<grid, BLK, lds, s>>>(xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, part, xh, yh, relu & 1); } \
-                else { MI3D_SET_MAX_LDS_ONCE((&conv3_mfma_persist_dma_kernel<NCH_, false>), lds);                             \
-                    conv3_mfma_persist_dma_kernel<NCH_, false><<<grid, BLK, lds, s>>>(xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, nullptr, xh, yh, relu & 1); } \
-            } while (0)
-            if (Cin == 16) PD(1); else PD(2);
-#undef PD
-            MI3D_LAUNCH_CHECK();
-            return 0;
-        }
-#endif  // MI3D_EXPERIMENTS
         if (Cin == 16 && Cout == 16) PK(1, 1);
         else if (Cin == 32) PK(1, 2);
         else PK(2, 1);
@@ -1656,12 +1248,12 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
         return launch_cfg<4, 8, 1, 16, 1>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, part, 1, nullptr, s, false, relu);
     }
     if (tk_rows) {      // the launch finishes its split-K sums and the BatchNorm partial rows itself (nothing deferred)
-        if (two) return launch_cfg<4, 2, 2, 4, 2>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, nullptr, ks, skws, s, false, 0, nullptr, tk_rows, tk_count);
-        return launch_cfg<4, 2, 2, 4, 1>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, nullptr, ks, skws, s, false, 0, nullptr, tk_rows, tk_count);
+        if (two) return launch_cfg<4, 2, 2, 4, 2>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, nullptr, ks, skws, s, false, 0, tk_rows, tk_count);
+        return launch_cfg<4, 2, 2, 4, 1>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, nullptr, ks, skws, s, false, 0, tk_rows, tk_count);
     }
     bool defer = ks > 1 && ks_deferred;
     if (defer) *ks_deferred = ks;
-    if (two) return launch_cfg<4, 2, 2, 4, 2>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, part, ks, skws, s, defer, relu, xf);
+    if (two) return launch_cfg<4, 2, 2, 4, 2>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, part, ks, skws, s, defer, relu);
     return launch_cfg<4, 2, 2, 4, 1>(xp, xcs, Cin, w, bias, yp, ycs, Cout, g, part, ks, skws, s, defer, relu);
 }
 
@@ -2307,7 +1899,7 @@ inline WgCfg wgrad_cfg(int Cin, int Cout, Geo g, int target = 0) {
     c.nt = 27;
     c.tg = 1;
     // persistent: one round of workgroups, 2 per CU
-    int64_t want = (target > 0 ? target : 2 * persist_cus()) / (int64_t)groups;
+    int64_t want = (target > 0 ? target : 2 * device_cus()) / (int64_t)groups;
     if (want < 1) want = 1;
     int64_t rounds = cdiv(ntiles, want);               // tiles per workgroup; then the fewest slabs that keep it
     c.nsb = (int)cdiv(ntiles, rounds);
@@ -2418,7 +2010,7 @@ int conv3_mfma_bwd_fused_persist(const void* x, int xcs, int Cin, const void* dy
     MI3D_CHECK_ARG(conv3_mfma_bwd_fused_persist_ok(Cin, Cout, xcs, dycs, g) && dx, "conv3_mfma_bwd_fused_persist: unsupported layer");
     int groups = (Cout / 16) * (Cin / 16);
     int64_t ntw = (int64_t)g.N * cdiv(g.D, WTZ) * cdiv(g.H, WTY) * cdiv(g.W, WTX);
-    const int wcap = persist_cus(), pcap = persist_cus();   // one workgroup of each kind per CU (512 + 512 = no co-residency: measured equal to unfused)
+    const int wcap = device_cus(), pcap = device_cus();   // one workgroup of each kind per CU (512 + 512 = no co-residency: measured equal to unfused)
     int64_t want = wcap / groups; if (want < 1) want = 1;
     int64_t rounds = cdiv(ntw, want);
     int nsb = (int)cdiv(ntw, rounds);
@@ -2469,7 +2061,7 @@ bool conv3_mfma_bwd_fused_ok(int Cin, int Cout, int xcs, int dycs, int dxcs, Geo
 }
 
 int conv3_mfma_bwd_wg_target(int Cin, int Cout, int xcs, int dycs, int dxcs, Geo g) {
-    if (conv3_mfma_bwd_fused_persist_ok(Cin, Cout, xcs, dycs, g)) return persist_cus();
+    if (conv3_mfma_bwd_fused_persist_ok(Cin, Cout, xcs, dycs, g)) return device_cus();
     if (conv3_mfma_bwd_fused_ok(Cin, Cout, xcs, dycs, dxcs, g)) return mi3d_routes().fused_wg_target;
     return 0;
 }

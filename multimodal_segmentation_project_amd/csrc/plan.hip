@@ -297,12 +297,10 @@ int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, con
     block_input(c, b, x, xin, xcs, xdt);
     void* zout; int zcs;
     block_output(c, b, zout, zcs);
-    XfArgs xfa;                      // conv0's BatchNorm + ReLU + Dropout3d applied in conv1's staging pass (deep levels)
     for (int h = 0; h < 2; h++) {
         const HalfP& H = B.h[h];
         const void* in = h == 0 ? xin : c.at(B.z1);
         int ics = h == 0 ? xcs : H.Cout, idt = h == 0 ? xdt : p.dt;
-        if (h == 1 && xfa.mode) { in = c.at(B.h[0].y); ics = B.h[0].Cout; }     // the raw conv0 output; z1 is written as a by-product
         float* rm = buffers ? (float*)buffers[H.bidx] : nullptr;
         float* rv = buffers ? (float*)buffers[H.bidx + 1] : nullptr;
         int64_t* nbt = buffers ? (int64_t*)buffers[H.bidx + 2] : nullptr;
@@ -319,12 +317,11 @@ int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, con
             // WITHOUT split-K -- conv with fused partial sums -> apply, two launches instead of three -- measured +0.10 ms in
             // round 2: the 8-16-chunk K loops on 32-216 workgroups cost more than the launch they save; that route is gone.)
             // round 4: a split-K launch of a training forward finishes itself behind a per-tile ticket (y, BatchNorm partial rows)
-            const bool tk = training && c.tk_zeroed && !(h == 1 && xfa.mode) && conv3_mfma_ticket_ok(H.Cin, H.Cout, g);
+            const bool tk = training && c.tk_zeroed && conv3_mfma_ticket_ok(H.Cin, H.Cout, g);
             MI3D_TRY(conv3_mfma_fwd(in, ics, H.Cin, c.at(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
                                     training ? c.at<float>(p.statpart) : nullptr, c.at<float>(p.skws), c.s,
                                     (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), Halves(), training ? &ksd : nullptr, 0, 0,
-                                    (h == 1 && xfa.mode) ? &xfa : nullptr, tk ? c.at<float>(p.statpart) : nullptr,
-                                    tk ? c.at<int>(p.tkcount) : nullptr));
+                                    tk ? c.at<float>(p.statpart) : nullptr, tk ? c.at<int>(p.tkcount) : nullptr));
             fused_stats = training && (tk || conv3_mfma_fuses_stats(H.Cin, H.Cout, g));
         } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0 && !mi3d_routes().force_direct &&
                    !mi3d_routes().no_c1_mfma) {
@@ -363,17 +360,6 @@ int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, con
             MI3D_TRY(bn_eval_stats(H.Cout, c.P(H.pidx + 2), c.P(H.pidx + 3), rm, rv, p.d.bn_eps, c.at<float>(H.stat), c.s));
         }
         BnSmall sm{rows_at, small_rows, c.P(H.pidx + 2), c.P(H.pidx + 3), rm, rv, nbt, mom, p.d.bn_eps};
-        if (h == 0 && training && small_rows > 0 && !fused_stats && p.dt == MI3D_BF16 && B.h[1].mfma && mi3d_routes().apply_on_load &&
-            conv3_mfma_xform_ok(B.h[1].Cin, B.h[1].Cout, g)) {
-            // no apply launch: conv1 finishes the statistics rows in its prologue, applies while staging and writes z1 on the way
-            xfa.mode = 1;
-            xfa.stat = c.at<float>(H.stat); xfa.rows = c.at<float>(p.bnws); xfa.nrows = small_rows; xfa.M = g.M(); xfa.C = H.Cout;
-            xfa.gamma = c.P(H.pidx + 2); xfa.beta = c.P(H.pidx + 3); xfa.rmean = rm; xfa.rvar = rv; xfa.nbt = nbt;
-            xfa.momentum = mom; xfa.eps = p.d.bn_eps;
-            xfa.drop = (drop && training) ? drop + H.drop_off : nullptr;
-            xfa.side = (bf16*)zo; xfa.side_cs = zocs;
-            continue;
-        }
         if (h == 1 && pooled)
             MI3D_TRY(bn_apply_relu_drop_pool(p.dt, c.at(H.y), H.Cout, H.Cout, g, c.at<float>(H.stat),
                                              (drop && training) ? drop + H.drop_off : nullptr, zo, zocs, pooled, pcs, c.s,
@@ -414,18 +400,7 @@ int drain_aux(const Ctx& c, const float* x, void* const* grads, int accumulate, 
 
 // Fork: the queued weight gradients may start once everything the compute stream has enqueued so far is done (their dy
 // buffers are complete).  lazy: only the event is recorded here, the launches are enqueued by later drain_aux calls.
-int flush_deferred(const Ctx& c, const float* x, void* const* grads, int accumulate, bool lazy = false, bool force = false) {
-    if (c.ndq == 0 && force) {
-        MI3D_CHECK_ARG(c.nfork < 3, "flush_deferred: more than three forks in one call");
-        // nothing queued (defer_mask), but the caller relies on the aux stream being ordered after this point of the chain
-        // (mi3d_unet_chain_tail_blocks: its optimizer tail runs there)
-        const int e = c.nfork++;
-        MI3D_HIP(hipEventRecord(c.ev[e % 3], c.s));
-        MI3D_HIP(hipStreamWaitEvent(c.s2, c.ev[e % 3], 0));
-        c.waited_ev = e;
-        c.aux_used = true;
-        return 0;
-    }
+int flush_deferred(const Ctx& c, const float* x, void* const* grads, int accumulate, bool lazy = false) {
     if (c.ndq == 0) return 0;
     MI3D_CHECK_ARG(c.nfork < 3, "flush_deferred: more than three forks in one call");
     const int e = c.nfork++;
@@ -462,15 +437,10 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
         int ics = h == 0 ? xcs : H.Cout, idt = h == 0 ? xdt : p.dt;
         void* dx_f = h == 1 ? c.at(p.sC) : dxin;
         int dxs_f = h == 1 ? H.Cin : dxcs;
-        // apply on load (deep levels, deferred layers): only the reduction is launched; the input-gradient conv computes dy while
-        // staging (dz, y), writes it to the layer's dy buffer for the weight gradient, and publishes dgamma / dbeta
-        int xf_rows = 0;
-        const bool want_xf = dfr && dx_f && p.dt == MI3D_BF16 && mi3d_routes().apply_on_load && dcs % 8 == 0 &&
-                             conv3_mfma_xform_ok(H.Cout, H.Cin, g) && bn_small_route(H.Cout, g.M());
         MI3D_TRY(bn_bwd(p.dt, dz, dcs, c.at(H.y), H.Cout, H.Cout, g.M(), g.V(), c.at<float>(H.stat),
                         drop ? drop + H.drop_off : nullptr, dyb, H.Cout, G(H.pidx + 2), G(H.pidx + 3), accumulate,
                         c.at<float>(p.bnws), c.s, c.has_pend ? &c.pend : (c.has_pend2 ? &c.pend2 : nullptr), h == 0 ? dz_skp : nullptr,
-                        h == 0 ? dz_ks : 0, (c.has_pend && c.has_pend2) ? &c.pend2 : nullptr, want_xf ? &xf_rows : nullptr));
+                        h == 0 ? dz_ks : 0, (c.has_pend && c.has_pend2) ? &c.pend2 : nullptr));
         c.has_pend = false;
         c.has_pend2 = false;
         if (c.mark_pending) { MI3D_HIP(hipEventRecord(c.mark_pending, c.s)); c.mark_pending = nullptr; }      // the slab sums of the marked segment rode in this launch
@@ -480,42 +450,26 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
             // same K order: both routes produce the same bits
             c.dq[c.ndq++] = Ctx::DJob{b, h, conv3_mfma_bwd_wg_target(H.Cin, H.Cout, ics, H.Cout, dx_f ? dxs_f : 8, g)};
         }
-        // fork points: what is queued goes to the aux stream when the chain has finished the last layer of a group -- its
-        // BatchNorm backward, or (apply on load) the input-gradient conv that writes dy -- whether or not that very layer is
-        // deferred under the current defer_mask
-        auto fork_here = [&]() -> int {
-            if (!aux) return 0;
-            // group 1 forks when the GPU is still busy with the full-resolution decoder (the host is far ahead: enqueue at once);
-            // group 2 forks at the end of the launch-bound deep chain: its launches are fed in between the chain's next ones.
-            // (Measured and dropped, profiles/r04_experiments_aux_wgrad.txt / _opt_tail_pool_forks.txt: one fork per layer +26 ... +43 us,
-            // per deep layer only +6 us, the decoder fork one block later -1 us, another workgroup count for the aux kernels +10 ... +40 us)
+        // fork points: what is queued goes to the aux stream when the chain has finished the last layer of a group (its BatchNorm
+        // backward), whether or not that very layer is deferred under the current defer_mask.  Group 1 forks when the GPU is still
+        // busy with the full-resolution decoder (the host is far ahead: enqueue at once); group 2 forks at the end of the
+        // launch-bound deep chain: its launches are fed in between the chain's next ones.
+        // (Measured and dropped, profiles/r04_experiments_aux_wgrad.txt and the fork-placement record beside it: one fork per layer +26 ... +43 us,
+        // per deep layer only +6 us, the decoder fork one block later -1 us, another workgroup count for the aux kernels +10 ... +40 us)
+        if (aux)
             for (int q = 0; q < 2; q++)
-                if (b == p.flush_b[q] && h == p.flush_h[q]) MI3D_TRY(flush_deferred(c, x, grads, accumulate, q == 1, q == 1));
-            return 0;
-        };
-        if (xf_rows == 0) MI3D_TRY(fork_here());
+                if (b == p.flush_b[q] && h == p.flush_h[q]) MI3D_TRY(flush_deferred(c, x, grads, accumulate, q == 1));
         if (dfr) {
             if (dx_f) {
                 const bool to_pool = h == 0 && c.pool_defer && dx_f == dxin;
                 const bool defer = (h == 1 || to_pool) && c.defer_slabs && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
                 int ksd = 0;
-                XfArgs xb;
-                if (xf_rows > 0) {
-                    xb.mode = 2;
-                    xb.y2 = (const bf16*)c.at(H.y); xb.y2cs = H.Cout;
-                    xb.stat = c.at<float>(H.stat); xb.rows = c.at<float>(p.bnws); xb.nrows = xf_rows; xb.M = g.M(); xb.C = H.Cout;
-                    xb.dgamma = G(H.pidx + 2); xb.dbeta = G(H.pidx + 3); xb.accumulate = accumulate;
-                    xb.drop = drop ? drop + H.drop_off : nullptr;
-                    xb.side = (bf16*)dyb; xb.side_cs = H.Cout;
-                }
-                MI3D_TRY(conv3_mfma_fwd(xf_rows > 0 ? dz : dyb, xf_rows > 0 ? dcs : H.Cout, H.Cout, c.at(H.wpd), nullptr, dx_f, dxs_f, H.Cin, g, nullptr,
+                MI3D_TRY(conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx_f, dxs_f, H.Cin, g, nullptr,
                                         (dxs_f % 8 == 0) ? c.at<float>(p.skws) : nullptr, c.s, Halves(),
-                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), defer ? &ksd : nullptr, 0, conv3_bwd_ks_target(),
-                                        xf_rows > 0 ? &xb : nullptr));
+                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), defer ? &ksd : nullptr, 0, conv3_bwd_ks_target()));
                 if (ksd > 0 && h == 1) { dz_skp = c.at<float>(p.skws); dz_ks = ksd; }
                 if (ksd > 0 && h == 0) c.pool_ks = ksd;
             }
-            if (xf_rows > 0) MI3D_TRY(fork_here());        // dy exists only now
             continue;
         }
         if (H.mfma && dx_f && (G(H.pidx) || G(H.pidx + 1)) && conv3_mfma_bwd_fused_persist_ok(H.Cin, H.Cout, ics, H.Cout, g)) {
@@ -609,7 +563,7 @@ int block_infer(const Ctx& c, int b, const float* x) {
 
 extern "C" {
 
-int mi3d_abi_version(void) { return 5; }
+int mi3d_abi_version(void) { return 6; }
 
 int mi3d_unet_num_params(const mi3d_unet_desc* d) { return d ? 8 * (2 * d->n_levels + 1) + 2 * d->n_levels + 2 : -1; }
 int mi3d_unet_num_buffers(const mi3d_unet_desc* d) { return d ? 6 * (2 * d->n_levels + 1) : -1; }
@@ -659,43 +613,23 @@ static LossCfg cfg_of(const mi3d_loss_cfg* c) {
     return k;
 }
 
-// MFMA weight images of the DoubleConv blocks [b0, b1) (+ the transposed convs) of the training forward / backward, one launch
-static int pack_training_weights(const Ctx& c, int b0, int b1, bool upconvs, bool zero_tickets = false) {
+// MFMA weight images of the DoubleConv blocks and the transposed convs of the training forward / backward, one launch
+static int pack_training_weights(const Ctx& c, bool zero_tickets) {
     const Plan& p = c.p;
     PackJobs J;
     J.n = 0; J.nblocks = 0;
     if (zero_tickets) { J.zero = c.at<int>(p.tkcount); J.nzero = CONV3_TK_COUNTERS; }
-    for (int b = b0; b < b1 && b < p.nblk; b++)
+    for (int b = 0; b < p.nblk; b++)
         for (int h = 0; h < 2; h++) {
             const HalfP& H = p.blk[b].h[h];
             if (H.mfma) MI3D_TRY(pack_all_add_conv3(J, c.P(H.pidx), H.Cin, H.Cout, c.at(H.wpf), c.at(H.wpd), p.geo[p.blk[b].level]));
         }
-    if (upconvs)
-        for (int i = 0; i < p.L; i++) {
-            int l = p.L - 1 - i;
-            if (p.up_mfma[i]) MI3D_TRY(pack_all_add_upconv(J, c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], c.at(p.upw[i])));
-        }
+    for (int i = 0; i < p.L; i++) {
+        int l = p.L - 1 - i;
+        if (p.up_mfma[i]) MI3D_TRY(pack_all_add_upconv(J, c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], c.at(p.upw[i])));
+    }
     if (zero_tickets && J.n > 0) c.tk_zeroed = true;      // (pack_all_launch launches nothing for an empty job list)
     return pack_all_launch(J, c.s);
-}
-
-extern "C" int mi3d_unet_pack_from(const mi3d_unet_desc* d, const void* const* params, void* workspace, size_t workspace_bytes,
-                                   int first_block, void* stream) {
-    Plan p;
-    MI3D_TRY(build_plan(d, p));
-    MI3D_CHECK_ARG(params && workspace && workspace_bytes >= p.total && first_block >= 0, "mi3d_unet_pack_from: bad arguments");
-    Ctx c{p, (char*)workspace, params, (hipStream_t)stream};
-    return pack_training_weights(c, first_block, p.nblk, true);
-}
-
-// leading encoder blocks whose weight gradients stay on the data-gradient chain (no deferred layer), i.e. are produced last
-extern "C" int mi3d_unet_chain_tail_blocks(const mi3d_unet_desc* d) {
-    Plan p;
-    if (!d || build_plan(d, p) != 0) return 0;
-    if (mi3d_routes().no_defer_wgrad || p.flush_b[1] < 0) return 0;      // no fork behind the deep levels: the aux stream is not ordered
-    int k = 0;
-    while (k < p.L && p.blk[k].h[0].defer == 0 && p.blk[k].h[1].defer == 0) k++;
-    return (k < p.L) ? k : 0;
 }
 
 static int unet_forward_impl(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
@@ -712,9 +646,8 @@ static int unet_forward_impl(const mi3d_unet_desc* d, const float* x, const void
     int L = p.L;
     if (d->in_channels > 1)
         MI3D_TRY(ncdhw_to_ndhwc(p.dt, x, c.at(p.xcl), d->in_channels, d->in_channels, d->N, p.geo[0].V(), c.s));
-    // every MFMA weight pack of the network in one launch (prepacked_from = k > 0: the caller's mi3d_unet_pack_from already did
-    // the blocks >= k and the transposed convs behind its optimizer update)
-    MI3D_TRY(pack_training_weights(c, 0, d->prepacked_from > 0 ? d->prepacked_from : p.nblk, d->prepacked_from <= 0, training != 0));
+    // every MFMA weight pack of the network in one launch
+    MI3D_TRY(pack_training_weights(c, training != 0));
     c.packed = true;
     for (int l = 0; l < L; l++) {
         // fused apply + pool: even sides (every voxel in exactly one window) and 32-bit element indices

@@ -71,17 +71,7 @@ def _capture_stream(device):
     return _CAPTURE_STREAMS[key]
 
 
-def _masked_stream(device, cus_per_xcd, from_top=1):
-    """torch stream object around a hipStream_t confined to cus_per_xcd CUs of every XCD (mi3d_stream_create_masked)."""
-    h = C.c_void_p()
-    call("mi3d_stream_create_masked", int(cus_per_xcd), int(from_top), C.byref(h))
-    st = torch.cuda.ExternalStream(h.value, device=device)
-    st.mi3d_handle = h
-    st.mi3d_cus_per_xcd = int(cus_per_xcd)
-    return st
-
-
-def concurrent_stream(device, candidates=6, hold_us=300, priority="high", role="aux", cus_per_xcd=0):
+def concurrent_stream(device, candidates=6, hold_us=300, priority="high", role="aux"):
     """A stream whose kernels really run BESIDE those of the current (compute) stream.  HIP multiplexes streams onto a few
     hardware queues, and two streams that share a queue execute strictly one after the other (measured with rocprofv3: the
     default stream and the 8th stream created in a process both sat on queue 4, and a collective kernel on the latter ran
@@ -94,16 +84,14 @@ def concurrent_stream(device, candidates=6, hold_us=300, priority="high", role="
     RuntimeWarning: the step is still correct, only nothing will run beside the compute stream."""
     import warnings
     dev = torch.device(device)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), priority, role, int(cus_per_xcd))
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), priority, role)
     if key in _STREAM_CACHE:
         return _STREAM_CACHE[key]
     main = torch.cuda.current_stream(device)
     buf = torch.zeros(1024, dtype=torch.float32, device=device)
     best = None
     for i in range(candidates):
-        if i == 0 and cus_per_xcd > 0:
-            c = _masked_stream(device, cus_per_xcd)
-        elif i == 0 and priority == "low":
+        if i == 0 and priority == "low":
             c = _priority_stream(device, +1)
         elif i == 0 and priority == "high":
             c = torch.cuda.Stream(device=device, priority=-1)
@@ -190,6 +178,10 @@ class _StepBase:
                                      fine_buckets=os.environ.get("MI3D_FINE_BUCKETS", "0") == "1")
         # the exchange stream must sit on another hardware queue than the compute stream (see concurrent_stream)
         self.comm_stream = concurrent_stream(self.device, role="comm") if self.do_comm else None
+        # MI3D_NO_MARKS=1: exchange points cut the backward into calls instead of marks; MI3D_COMM_SERIAL=1: every bucket behind
+        # the last segment, on the compute stream (TrainStep)
+        self.no_marks = bool(os.environ.get("MI3D_NO_MARKS"))
+        self.comm_serial = bool(os.environ.get("MI3D_COMM_SERIAL"))
         self._mark_handles = []          # exchange-mark events (mi3d_unet_backward_marks)
         self.use_graph = bool(use_graph)
         self._statics = {}
@@ -258,10 +250,6 @@ class _StepBase:
 
     def _join_comm(self):
         torch.cuda.current_stream().wait_stream(self.comm_stream)
-
-    def _param_versions(self):
-        """Sum of the version counters of the model's Parameters (each is a view of the arena with its OWN counter)."""
-        return sum(p._version for p in self.arena.params)
 
     def _adamw(self, arena, ranges, hyper, s):
         lr, b1, b2, eps, wd = hyper
@@ -369,7 +357,7 @@ class TrainStep(_StepBase):
     def __init__(self, model, loss="combined", lr=1e-3, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8,
                  grad_accum=1, kd_teacher=None, kd_alpha=0.7, kd_temperature=2.0, process_group=None,
                  compute_dtype=None, use_graph=False, aux_wgrad=None, reference_zero_grad_quirk=False,
-                 force_comm=False, overlap_teacher=True, keep_logits=False, aux_cus=None):
+                 force_comm=False, overlap_teacher=True, keep_logits=False):
         """aux_wgrad: the backward's critical path is the input-gradient chain alone -- the weight gradients of the decoder's
         full-resolution convs and of all deep-level convs run on a second stream (include/mi3d.h, mi3d_unet_backward: aux_stream),
         forked from the chain at most three times and joined in front of the optimizer; bit-identical results.  None (default):
@@ -406,8 +394,7 @@ class TrainStep(_StepBase):
             # finish ~150 us before the end of the backward, so the big all-reduce bucket (dp.bucket_ranges) would lose the
             # 0.45 ms of encoder backward it hides under; the exchange is worth more than the ~20 us the deferral buys
             aux_wgrad = not use_graph and not self.do_comm
-        self.aux_stream = (concurrent_stream(self.device, priority=os.environ.get("MI3D_AUX_PRIO", "high"),
-                                             cus_per_xcd=int(aux_cus if aux_cus is not None else os.environ.get("MI3D_AUX_CUS", "0")))
+        self.aux_stream = (concurrent_stream(self.device, priority=os.environ.get("MI3D_AUX_PRIO", "high"))
                            if aux_wgrad else None)
         self._events = None
         self._event_handles = []
@@ -512,7 +499,7 @@ class TrainStep(_StepBase):
                 live = any(t and lo <= o < hi for o, t in zip(self.arena.offsets, trainable))
                 if live and last >= 0:
                     sched.setdefault(min(seg, last), []).append(seg)
-            if os.environ.get("MI3D_COMM_SERIAL") and sched and last >= 0:
+            if self.comm_serial and sched and last >= 0:
                 # every bucket behind the last segment, on the compute stream: no second hardware queue in the step at all (any
                 # kernel on another queue costs this step 100-250 us on this runtime, profiles/r04_experiments_second_queue.txt),
                 # at the price of an all-reduce that hides under nothing
@@ -540,14 +527,21 @@ class TrainStep(_StepBase):
     # ---- the kernel sequence of one micro-step (everything on the current stream except the all-reduces)
     def _enqueue(self, st, variant, comm):
         first, boundary = variant
-        desc = st["desc"]
         s = stream_ptr()
-        model = self.model
         # Q2: see reference_zero_grad_quirk in __init__
         if self.quirk:
             accumulate, run_backward = 0, boundary
         else:
             accumulate, run_backward = (0 if first else 1), True
+        drop, t_logits = self._forward_loss(st, s)
+        self._backward_exchange(st, s, comm, drop, t_logits, accumulate, boundary, run_backward)
+        if boundary:
+            self._optimizer(st, s)
+
+    def _forward_loss(self, st, s):
+        """Dropout scales, the teacher's forward, the student's forward with loss and metrics.  Returns (drop, t_logits)."""
+        desc = st["desc"]
+        model = self.model
         drop = None
         p = float(getattr(model, "dropout_rate", 0.0))
         injected = getattr(model, "_mi3d_injected_drop_scales", None)
@@ -569,12 +563,6 @@ class TrainStep(_StepBase):
         n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
         fused = st["fused_head"]
         keep = ptr(st["logits"]) if self.keep_logits else None
-        # weight packs the last optimizer tail already refreshed on the aux stream (valid only while nobody has written the
-        # parameters through torch since: load_state_dict, a torch optimizer, any in-place op on a Parameter bump its version
-        # counter; writes through `.data` or raw pointers do not -- set ts._static["prepacked"] = None after such a write)
-        pre = st.get("prepacked")
-        desc.prepacked_from = (pre[0] if (pre and pre[2] == getattr(self, "_param_epoch", 0) and pre[1] == self._param_versions())
-                               else 0)        # (the epoch: another static state of this object -- another batch shape -- may have stepped since)
         if fused and self.teacher is None:
             # 1x1x1 head + loss + metrics in one pass: the logits are never written (mi3d.h, mi3d_unet_forward_loss)
             call("mi3d_unet_forward_loss", C.byref(desc), ptr(st["x"]), st["ptab"], st["btab"], ptr(drop), 1, ptr(st["y"]), None,
@@ -604,6 +592,13 @@ class TrainStep(_StepBase):
             call("mi3d_seg_loss_metrics_forward", ptr(st["logits"]), ptr(st["y"]), ptr(t_logits), n, c, desc.D, v,
                  C.byref(self.cfg), ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]),
                  ptr(st["met_ws"]), s)
+        return drop, t_logits
+
+    def _backward_exchange(self, st, s, comm, drop, t_logits, accumulate, boundary, run_backward):
+        """The backward in runs of segments, with the gradient exchange (and the metrics' all-reduce) between them."""
+        desc = st["desc"]
+        n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
+        fused = st["fused_head"]
         # SURVEY C4: the four scalar gathers fused into one 4-float all-reduce; it rides on the first gradient exchange
         # point (one fork of the comm stream less) and is in flight under the rest of the backward
         met = st["metrics"]
@@ -618,25 +613,13 @@ class TrainStep(_StepBase):
             do_comm = self.do_comm and boundary
             aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
             aux_open = False        # aux-stream work of an earlier call that nothing on the compute stream has waited for yet
-            # optimizer tail on the aux stream (include/mi3d.h, mi3d_unet_chain_tail_blocks): without a gradient exchange the whole
-            # backward is ONE C call; with aux_join = 0 the aux stream ends up ordered after every gradient except those of the
-            # leading `tail_k` encoder blocks, which the compute stream produces last
-            tail_k = 0
-            if (aux is not None and boundary and not do_comm and not self.use_graph and nseg == 2 * st["L"] + 2
-                    and _lib.get_route("opt_tail")):
-                tail_k = _lib.lib().mi3d_unet_chain_tail_blocks(C.byref(desc))
             # one C call per run of segments between exchange steps: kernels of adjacent segments share launches (a
             # weight-gradient slab sum rides in the next BatchNorm reduction), which a call boundary would cut
             start = 0
-            # MI3D_COMM_CUS=n: the segments launched while a gradient exchange is in flight size their persistent grids for
-            # 256 - n CUs (the collective kernel holds the others: see mi3d_set_cu_budget)
-            budget = int(os.environ.get("MI3D_COMM_CUS", "0")) if do_comm else 0
-            in_flight = False
             # exchange marks (include/mi3d.h, mi3d_unet_backward_marks): an eagerly launched step keeps the backward ONE call;
             # the library records an event when a bucket's gradients are complete and the exchange stream waits for THAT
             mid = [(sg, tuple(st["comm_after"][sg])) for sg in range(nseg - 1) if do_comm and st["comm_after"].get(sg)]
-            use_marks = bool(mid) and not self.use_graph and aux is None and not budget and len(mid) <= 4 and \
-                not os.environ.get("MI3D_NO_MARKS")
+            use_marks = bool(mid) and not self.use_graph and aux is None and len(mid) <= 4 and not self.no_marks
             if use_marks:
                 while len(self._mark_handles) < len(mid):
                     e = C.c_void_p()
@@ -650,14 +633,12 @@ class TrainStep(_StepBase):
                 if use_marks and not last:
                     continue
                 if last or exch:
-                    if budget and in_flight:
-                        call("mi3d_set_cu_budget", budget)
                     # the compute stream joins the aux stream at the end of the LAST call only (in front of the optimizer); a call
                     # that is followed by a gradient exchange leaves the join to the exchange stream (_on_comm_stream), so the
                     # deep-level weight gradients keep running under the next segments.  Segmented graphs end a capture at every
                     # exchange: there every call joins
-                    join = 1 if ((last and not tail_k) or self.use_graph or aux is None) else 0
-                    aux_open = aux_open or (aux is not None and not join and not tail_k)
+                    join = 1 if (last or self.use_graph or aux is None) else 0
+                    aux_open = aux_open or (aux is not None and not join)
                     if fused:
                         call("mi3d_unet_backward_loss", C.byref(desc), ptr(st["x"]), st["ptab"], st["gtab"], ptr(drop),
                              ptr(st["y"]), ptr(t_logits), C.byref(self.cfg), ptr(st["coef"]), ptr(self.inv_accum), None, 1.0,
@@ -666,9 +647,6 @@ class TrainStep(_StepBase):
                         call("mi3d_unet_backward", C.byref(desc), ptr(st["x"]), st["ptab"], st["gtab"], ptr(drop),
                              ptr(st["dlogits"]), None, 1.0, accumulate, start, seg + 1, ptr(st["ws"]), st["ws_bytes"], s, aux,
                              self._events, join)
-                    if budget and in_flight:
-                        call("mi3d_set_cu_budget", 0)
-                    in_flight = in_flight or bool(exch)
                     start = seg + 1
                     if use_marks:
                         cs = self.comm_stream
@@ -699,30 +677,9 @@ class TrainStep(_StepBase):
             comm(lambda: self._on_comm_stream(lambda: self.comm.average_(met)))
         if self.do_comm and not joined:
             comm(join_fn)
-        if boundary and run_backward and self.aux_stream is not None and tail_k > 0:
-            # AdamW over everything but the leading blocks + the re-pack of those weights for the next forward run on the aux
-            # stream, behind the deferred weight gradients and beside the compute stream's last (full-resolution encoder) backward
-            # kernels; the compute stream joins and updates the leading blocks.  Same arithmetic per parameter, same step count.
-            cut = self.arena.offsets[8 * tail_k]
-            r_a = [(max(lo, cut), hi) for lo, hi in st["opt_ranges"] if hi > cut]
-            r_b = [(lo, min(hi, cut)) for lo, hi in st["opt_ranges"] if lo < cut]
-            hyper = self._hyper()
-            with torch.cuda.stream(self.aux_stream):
-                a = self.aux_stream.cuda_stream
-                lr, b1, b2, eps, wd = hyper
-                for lo, hi in r_a:
-                    call("mi3d_adamw_apply", self.arena.p.data_ptr() + 4 * lo, self.arena.g.data_ptr() + 4 * lo,
-                         self.arena.m.data_ptr() + 4 * lo, self.arena.v.data_ptr() + 4 * lo, hi - lo, lr, b1, b2, eps, wd, 1.0,
-                         ptr(self.arena.step), 0, a)
-                call("mi3d_unet_pack_from", C.byref(desc), st["ptab"], ptr(st["ws"]), st["ws_bytes"], tail_k, a)
-            torch.cuda.current_stream().wait_stream(self.aux_stream)
-            self._adamw(self.arena, r_b if r_b else [(0, 0)], hyper, s)
-            self._param_epoch = getattr(self, "_param_epoch", 0) + 1
-            st["prepacked"] = (tail_k, self._param_versions(), self._param_epoch)
-        elif boundary:
-            self._adamw(self.arena, st["opt_ranges"], self._hyper(), s)
-            self._param_epoch = getattr(self, "_param_epoch", 0) + 1
-            st["prepacked"] = None
+
+    def _optimizer(self, st, s):
+        self._adamw(self.arena, st["opt_ranges"], self._hyper(), s)
 
     def step(self, images, labels, last_batch=False):
         """One micro-step on (images (N,Cin,D,H,W) float, labels (N,1,D,H,W) int64).  Returns a device float32[4]

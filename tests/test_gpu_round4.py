@@ -14,7 +14,6 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import multimodal_segmentation_project_amd as mi  # noqa: F401
-from multimodal_segmentation_project_amd import _lib
 from multimodal_segmentation_project_amd.trainer import TrainStep
 from multimodal_segmentation_project_amd.unet import UNet3D
 
@@ -79,99 +78,6 @@ def test_deferred_weight_gradients_are_bitwise_the_chain_route(size, graph):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("size,graph,aux", [(96, False, True), (96, True, False), (32, False, True), (48, False, True), (64, True, False)])
-def test_apply_on_load_is_bitwise_the_launched_apply(routes, size, graph, aux):
-    """Deep levels: conv0's BatchNorm + ReLU + Dropout3d is applied in conv1's staging pass (forward; z1 written as a by-product),
-    and a deferred layer's BatchNorm backward in the staging pass of its input-gradient conv (dy written as a by-product for the
-    weight gradient on the aux stream) -- models/unet.py:12-18 fixes WHAT is computed, not in which launch.  Against the route
-    with the bn_apply / bn_bwd_apply launches (the default; apply_on_load = 0): metrics, every gradient, parameters after AdamW, BatchNorm
-    buffers incl. num_batches_tracked, bit for bit; with Dropout3d masks (per-sample scales enter the staging coefficients)."""
-    if not _lib.lib().mi3d_debug_experiments():
-        pytest.skip("apply on load is compiled into experiment builds only (make EXPERIMENTS=1): measured slower, off the product path")
-    x, y = synth(2, size, 777, blocky=True)
-    res = []
-    for on in (1, 0):
-        routes.set("apply_on_load", on)
-        m = default_model().to(DEV).train()
-        ts = TrainStep(m, loss="combined", lr=1e-3, weight_decay=0.01, compute_dtype=torch.bfloat16, use_graph=graph, aux_wgrad=aux)
-        ts.load_batch(x.to(DEV), y.to(DEV))
-        outs = [ts.step_static().clone() for _ in range(2)]
-        torch.cuda.synchronize()
-        res.append((outs, ts.arena.g.clone(), ts.arena.p.clone(), [b.clone() for b in m.buffers()]))
-        spans = [(k, o, p.numel()) for (k, p), o in zip(m.named_parameters(), ts.arena.offsets)]
-        ts.close()
-    routes.reset("apply_on_load")
-    (o0, g0, p0, b0), (o1, g1, p1, b1) = res
-    for a, b in zip(o0, o1):
-        assert torch.equal(a, b), (a, b)
-    assert torch.isfinite(g0).all() and float(g0.abs().max()) > 0
-    if not torch.equal(g0, g1):
-        bad = [(k, relerr(g0[o:o + n].cpu(), g1[o:o + n].cpu())) for k, o, n in spans if not torch.equal(g0[o:o + n], g1[o:o + n])]
-        raise AssertionError(f"{len(bad)} gradient tensors differ between the routes: {bad[:8]}")
-    assert torch.equal(p0, p1)
-    for (k, _), a, b in zip(m.named_buffers(), b0, b1):
-        assert torch.equal(a, b), k
-
-
-def test_apply_on_load_with_dropout_masks(routes):
-    """The same comparison with Dropout3d(p = 0.3) in train mode: the injected per-(sample, channel) scales must reach the staging
-    coefficients of the right sample (tile -> sample) in both directions."""
-    if not _lib.lib().mi3d_debug_experiments():
-        pytest.skip("apply on load is compiled into experiment builds only (make EXPERIMENTS=1)")
-    x, y = synth(2, 32, 778, blocky=True)
-    res = []
-    for on in (1, 0):
-        routes.set("apply_on_load", on)
-        torch.manual_seed(0)            # also the seed of the model's counter-based dropout stream: the same masks on both routes
-        m = UNet3D(in_channels=1, out_channels=4, dropout_rate=0.3).to(DEV).train()
-        ts = TrainStep(m, loss="combined", lr=1e-3, weight_decay=0.01, compute_dtype=torch.bfloat16, use_graph=False, aux_wgrad=True)
-        ts.load_batch(x.to(DEV), y.to(DEV))
-        outs = [ts.step_static().clone() for _ in range(2)]
-        torch.cuda.synchronize()
-        res.append((outs, ts.arena.g.clone(), ts.arena.p.clone()))
-        ts.close()
-    routes.reset("apply_on_load")
-    (o0, g0, p0), (o1, g1, p1) = res
-    for a, b in zip(o0, o1):
-        assert torch.equal(a, b), (a, b)
-    assert torch.equal(g0, g1) and torch.equal(p0, p1)
-
-
-@pytest.mark.parametrize("size", [96, 32])
-def test_optimizer_tail_on_the_aux_stream_is_bitwise_the_serial_tail(routes, size):
-    """Eager step with aux-stream weight gradients: AdamW over everything but the leading (full-resolution) encoder blocks and
-    the re-pack of those weights run on the aux stream beside the end of the backward, the compute stream updates the leading
-    blocks behind the join, and the next forward packs only them (desc.prepacked_from).  Against the default (opt_tail = 0: whole update and
-    all packs on the compute stream): metrics of every step, parameters, AdamW moments, step count, BatchNorm buffers bit for
-    bit over four steps -- including a step after the parameters were changed THROUGH TORCH between two steps (the arena's
-    version counter must invalidate the pre-packed weights: stale packs would show in the very next loss)."""
-    x, y = synth(2, size, 31, blocky=True)
-    res = []
-    for off in (0, 1):
-        routes.set("opt_tail", 1 - off)
-        m = default_model().to(DEV).train()
-        ts = TrainStep(m, loss="combined", lr=1e-3, weight_decay=0.01, compute_dtype=torch.bfloat16, use_graph=False, aux_wgrad=True)
-        ts.load_batch(x.to(DEV), y.to(DEV))
-        outs = [ts.step_static().clone() for _ in range(2)]
-        if off == 0:
-            assert ts._static.get("prepacked") is not None and ts._static["prepacked"][0] >= 1
-        with torch.no_grad():
-            m.bottleneck.double_conv[0].weight.mul_(1.25)          # a deep-level weight, re-packed by the aux tail route
-            m.decoder[3].double_conv[4].weight.add_(0.01)
-        outs += [ts.step_static().clone() for _ in range(2)]
-        torch.cuda.synchronize()
-        res.append((outs, ts.arena.p.clone(), ts.arena.m.clone(), ts.arena.v.clone(), ts.arena.step.clone(), [b.clone() for b in m.buffers()]))
-        ts.close()
-    routes.reset("opt_tail")
-    (o0, p0, m0, v0, s0, b0), (o1, p1, m1, v1, s1, b1) = res
-    for i, (a, b) in enumerate(zip(o0, o1)):
-        assert torch.equal(a, b), (i, a, b)
-    assert float(o0[2][0]) != float(o0[1][0])
-    assert torch.equal(p0, p1) and torch.equal(m0, m1) and torch.equal(v0, v1) and torch.equal(s0, s1)
-    for a, b in zip(b0, b1):
-        assert torch.equal(a, b)
-
-
 def test_wide_batchnorm_consumers_with_dropout_masks(routes):
     """Round 4: at levels 0-1 the BatchNorm apply (+ pool) passes finish the conv epilogue's partial rows themselves, as <= 256
     workgroups of 1024 threads (bn_apply_wide_kernel / bn_apply_pool_wide_kernel), instead of a finalize launch per layer
@@ -204,31 +110,6 @@ def test_wide_batchnorm_consumers_with_dropout_masks(routes):
         else:
             assert relerr(b0[k], b1[k]) < 5e-3, (k, relerr(b0[k], b1[k]))
     assert relerr(g0, g1) < 5e-2, relerr(g0, g1)
-
-
-def test_cu_masked_aux_stream_is_bitwise_the_unmasked_one():
-    """mi3d_stream_create_masked (hipExtStreamCreateWithCUMask): the aux stream of the deferred weight gradients confined to 16 of
-    the 32 CUs of every XCD.  A masked stream is a BLOCKING stream (it serialises with the null stream), so the step runs on a
-    pool stream here; where the weight gradients run changes nothing in what they compute."""
-    x, y = synth(2, 48, 781, blocky=True)
-    res = []
-    with torch.cuda.stream(torch.cuda.Stream(device=DEV)):
-        for cus in (0, 16):
-            torch.manual_seed(0)
-            m = UNet3D(in_channels=1, out_channels=4, dropout_rate=0.0).to(DEV).train()
-            ts = TrainStep(m, loss="combined", lr=1e-3, weight_decay=0.01, compute_dtype=torch.bfloat16, use_graph=False, aux_cus=cus)
-            assert ts.aux_stream is not None
-            if cus:
-                assert getattr(ts.aux_stream, "mi3d_cus_per_xcd", 0) == cus and ts.aux_stream.mi3d_concurrent
-            ts.load_batch(x.to(DEV), y.to(DEV))
-            outs = [ts.step_static().clone() for _ in range(2)]
-            torch.cuda.synchronize()
-            res.append((outs, ts.arena.g.clone(), ts.arena.p.clone()))
-            ts.close()
-    (o0, g0, p0), (o1, g1, p1) = res
-    for a, b in zip(o0, o1):
-        assert torch.equal(a, b)
-    assert torch.equal(g0, g1) and torch.equal(p0, p1)
 
 
 @pytest.mark.parametrize("size,p_drop", [(96, 0.0), (64, 0.3)])

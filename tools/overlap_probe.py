@@ -32,7 +32,7 @@ def main():
             for _ in range(3):
                 ts.step_static()
             torch.cuda.synchronize()
-            for wgs, usec, budget in ((0, 0, 0), (16, 2000, 0), (32, 2000, 0), (32, 2000, 32), (64, 2000, 0), (64, 2000, 64), (128, 2000, 0)):
+            for wgs, usec in ((0, 0), (16, 2000), (32, 2000), (64, 2000), (128, 2000)):
                 K = 4
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
@@ -40,16 +40,14 @@ def main():
                 if wgs:
                     side.wait_stream(main)
                     call("mi3d_debug_occupy_cus", wgs, usec, buf.data_ptr(), buf.numel(), side.cuda_stream)
-                call("mi3d_set_cu_budget", budget)
                 e0.record(main)
                 for _ in range(K):
                     ts.step_static()
                 e1.record(main)
-                call("mi3d_set_cu_budget", 0)
                 e1.synchronize()
                 torch.cuda.synchronize()
                 wall = (time.perf_counter() - t0) * 1e3
-                print(f"{main_kind:14s} stand-in {wgs:3d} wg x {usec:4d} us, CU budget {budget:3d}: {K} steps {e0.elapsed_time(e1):7.3f} ms "
+                print(f"{main_kind:14s} stand-in {wgs:3d} wg x {usec:4d} us: {K} steps {e0.elapsed_time(e1):7.3f} ms "
                       f"(events on the main stream), wall incl. stand-in {wall:7.3f} ms", flush=True)
 
 
