@@ -124,7 +124,7 @@ int mi3d_event_destroy(void* event);
  * gives a free workgroup slot to the data-gradient chain first.  The caller owns the stream (mi3d_stream_destroy). */
 int mi3d_stream_create(int priority_class, void** stream_out);
 int mi3d_stream_destroy(void* stream);
-/* Route switches: every kernel-selection switch of the library ("no_persist", "no_fused_bwd", "ks_target", ... -- the table
+/* Route switches: every kernel-selection switch of the library ("no_persist", "no_fused_bwd", "conv8", ... -- the table
  * in INTEGRATION.md) is read from the environment (MI3D_<NAME>=<int>) ONCE, when the library is first used; afterwards only
  * these calls change one.  Debug / test interface: do not call it concurrently with launches; a captured hipGraph keeps the
  * routes it was captured with.  Unknown names fail. */

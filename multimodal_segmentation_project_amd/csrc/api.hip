@@ -47,8 +47,7 @@ static inline LossCfg to_cfg(const mi3d_loss_cfg* c) {
 }
 
 static inline bool use_mfma(int in_dtype, int out_dtype, int Cin, int Cout, int xcs, int ycs) {
-    return in_dtype == MI3D_BF16 && out_dtype == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, xcs, ycs) &&
-           !mi3d_routes().force_direct;
+    return in_dtype == MI3D_BF16 && out_dtype == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, xcs, ycs);
 }
 
 extern "C" {
@@ -163,7 +162,7 @@ int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int C
     // the same kernel choice as the whole-network plan (plan.hip block_backward), so the per-operator parity tests pin
     // the kernels the training step runs: both products of a layer in ONE fused launch where that exists
     if (dx && (dW || db) && x_dtype == MI3D_BF16 && use_mfma(dy_dtype, dy_dtype, Cout, Cin, dycs, dxcs) &&
-        use_mfma(x_dtype, dy_dtype, Cin, Cout, xcs, dycs) && !mi3d_routes().api_unfused) {
+        use_mfma(x_dtype, dy_dtype, Cin, Cout, xcs, dycs)) {
         size_t wgf = conv3_mfma_wgrad_ws_floats(Cin, Cout, g);
         if (conv3_direct_wgrad_ws_floats(Cin, Cout, g) > wgf) wgf = conv3_direct_wgrad_ws_floats(Cin, Cout, g);
         float* skws = slabs + ((wgf + 63) & ~(size_t)63);
@@ -184,8 +183,7 @@ int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int C
         if (dx) MI3D_TRY(conv3_direct_fwd(dy_dtype, dy_dtype, dy, dycs, Cout, wpd, nullptr, dx, dxcs, Cin, g, s));
     }
     if (dW || db) {
-        if (x_dtype == MI3D_F32 && dy_dtype == MI3D_BF16 && Cin == 1 && xcs == 1 && Cout % 16 == 0 && dycs % 8 == 0 &&
-            !mi3d_routes().force_direct)
+        if (x_dtype == MI3D_F32 && dy_dtype == MI3D_BF16 && Cin == 1 && xcs == 1 && Cout % 16 == 0 && dycs % 8 == 0)
             MI3D_TRY(conv3_mfma_wgrad_c1((const float*)x, dy, dycs, Cout, g, dW, db, accumulate, slabs,
                                          conv3_mfma_wgrad_ws_floats(Cin, Cout, g), s));
         else if (use_mfma(x_dtype, dy_dtype, Cin, Cout, xcs, dycs) && dycs % 8 == 0)
@@ -293,7 +291,7 @@ int mi3d_upconv2_forward(int dtype, const void* x, int xcs, int Cin, const float
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_upconv2_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_upconv2_forward: workspace too small");
     float* wf = (float*)workspace;
     float* wb = wf + (size_t)cdiv(Cout, 8) * Cin * 64;
-    if (dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, ycs) && !mi3d_routes().force_direct) {
+    if (dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, ycs)) {
         MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, (hipStream_t)stream));
         return upconv2_mfma_fwd(x, xcs, Cin, workspace, bias, y, ycs, Cout, Geo{N, D, H, W}, (hipStream_t)stream);
     }
@@ -309,7 +307,7 @@ int mi3d_upconv2_backward(int dtype, const void* x, int xcs, int Cin, const floa
     float* wf = (float*)workspace;
     float* wb = wf + (size_t)cdiv(Cout, 8) * Cin * 64;
     float* slabs = (float*)workspace + upconv2_pack_floats(Cin, Cout);
-    if (dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, gycs) && (!dx || dxcs % 4 == 0) && !mi3d_routes().force_direct) {
+    if (dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, gycs) && (!dx || dxcs % 4 == 0)) {
         MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, (hipStream_t)stream));
         return upconv2_mfma_bwd(x, xcs, Cin, gy, gycs, Cout, workspace, dx, dxcs, dW, db, accumulate, slabs,
                                 upconv2_mfma_bwd_ws_floats(Cin, Cout, g), g, (hipStream_t)stream);

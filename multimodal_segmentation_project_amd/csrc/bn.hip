@@ -778,18 +778,21 @@ inline bool bn_small(int C, int64_t M) {
 inline int bn_small_rows(int nblk, int C) { return nblk > SMALL_ROWS ? SMALL_ROWS : nblk; }
 bool bn_small_ok(int C, int64_t M, int rows) { return bn_small(C, M) && rows >= 1 && rows <= SMALL_ROWS; }
 // round 4: `rows` partial rows written by a conv epilogue ([rows][2][C]) can be finished by the consumer (thin workgroups up to
-// SMALL_ROWS rows, the wide kernels above that): no finalize launch between the conv and the apply pass
+// SMALL_ROWS rows, the wide kernels above that; the wide kernels for every row count measured no gain, 2.1518 vs 2.1510 ms/step in
+// profiles/r04_experiments_wide_bn.txt): no finalize launch between the conv and the apply pass
 inline bool wide_shape_ok(int C) { return C >= 8 && C <= MAXC_BN && (C & (C - 1)) == 0; }
 bool bn_rows_route_ok(int C, int64_t M, int rows) {
     const int mode = mi3d_routes().wide_bn;
     if (!(mode & 1) || rows < 1 || M * C >= (1ll << 31)) return false;
-    if (rows <= SMALL_ROWS && rows < mi3d_routes().wide_min_rows) return C >= 4 && C <= MAXC_BN && (C & (C - 1)) == 0;
+    if (rows <= SMALL_ROWS) return C >= 4 && C <= MAXC_BN && (C & (C - 1)) == 0;
     return (mode & 2) && rows <= WIDE_ROWS && wide_shape_ok(C) && (int64_t)rows * C <= (int64_t)WIDE_J * WNT * 2;
 }
+// workgroups of a wide pass: every one pulls all partial rows through its XCD's L2, so the cost grows with their number
+// (profiles/r04_experiments_wide_bn.txt, ms/step: 256 2.0575, 512 2.0679, 1024 2.0992 on one box; 256 2.1510, 384 2.1632 on another)
+constexpr int WIDE_WGS = 256;
 inline int wide_grid(int64_t total_threads) {
-    int want = (int)((total_threads + WNT - 1) / WNT), cap = mi3d_routes().wide_bn_wgs;
-    if (cap < 1) cap = 1;
-    return want < 1 ? 1 : (want > cap ? cap : want);
+    int want = (int)((total_threads + WNT - 1) / WNT);
+    return want < 1 ? 1 : (want > WIDE_WGS ? WIDE_WGS : want);
 }
 
 int bn_train_stats(int dtype, const void* y, int ycs, int C, int64_t M, const float* gamma, const float* beta,
@@ -845,7 +848,7 @@ int bn_apply_relu_drop(int dtype, const void* y, int ycs, int C, int64_t M, int6
     }
     DISPATCH_T(dtype, T, {
         bool v8 = vec8_ok(C, ycs, zcs, y, z, sizeof(T));
-        if (small && (small->nrows > SMALL_ROWS || small->nrows >= mi3d_routes().wide_min_rows)) {
+        if (small && small->nrows > SMALL_ROWS) {
             if (v8 && dtype == MI3D_BF16 && wide_shape_ok(C) && (int64_t)small->nrows * C <= (int64_t)WIDE_J * WNT * 2) {
                 bn_apply_wide_kernel<<<wide_grid(M * (C / 8)), WNT, 0, s>>>((const bf16*)y, ycs, C, M, V, stat, t, drop, (bf16*)z, zcs);
                 MI3D_LAUNCH_CHECK();
@@ -882,7 +885,7 @@ int bn_apply_relu_drop_pool(int dtype, const void* y, int ycs, int C, Geo g, flo
         const int G8 = C / 8;
         const bool pair = v8 && (G8 & (G8 - 1)) == 0 && G8 <= 32 && !mi3d_routes().no_pool_pair;
         if (pair) grid = stream_grid(M / 8 * G8 * 2, G8 * 2);
-        if (small && (small->nrows > SMALL_ROWS || small->nrows >= mi3d_routes().wide_min_rows)) {
+        if (small && small->nrows > SMALL_ROWS) {
             if (pair && dtype == MI3D_BF16 && wide_shape_ok(C) && (int64_t)small->nrows * C <= (int64_t)WIDE_J * WNT * 2) {
                 bn_apply_pool_wide_kernel<<<wide_grid(M / 8 * G8 * 2), WNT, 0, s>>>((const bf16*)y, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, (bf16*)z, zcs, (bf16*)pooled, pcs);
                 MI3D_LAUNCH_CHECK();

@@ -46,37 +46,21 @@ void mi3d_set_error(const char* fmt, ...);
 // captured hipGraph and later eager launches cannot disagree and no launch path calls getenv().  Tests and tools change a
 // route through the ABI (mi3d_debug_set_route), not through setenv.  X(name, default)
 #define MI3D_ROUTE_LIST(X)                                                                                          \
-    X(force_direct, 0)      /* fp32-FMA kernels everywhere (no MFMA path) */                                        \
     X(no_planar, 0)         /* interleaved instead of planar skip/up halves at C = 16 */                            \
     X(no_persist, 0)        /* generic instead of persistent full-resolution conv kernels */                        \
-    X(no_c1_mfma, 0)        /* first layer (Cin = 1) forward on the fp32 kernel */                                  \
-    X(no_conv1_mfma, 0)     /* 1x1x1 head backward without the matrix cores */                                      \
     X(no_head_loss, 0)      /* head and loss as separate passes (logits / dlogits through memory) */                \
     X(no_pool_fuse, 0)      /* BatchNorm apply and MaxPool3d as two launches */                                     \
     X(no_small_bn, 0)       /* deep levels: statistics finished by a finalize launch, not the consumer's prologue */\
     X(no_defer_tail, 0)     /* split-K input gradients finished by their own pass */                                \
-    X(no_pend_slabs, 0)     /* weight-gradient slab sums launched on their own */                                   \
     X(no_upbwd_carry, 0)    /* the decoder conv's slab sum is not carried across the transposed conv's backward */  \
-    X(no_bwd_tail, 0)       /* split-K finish and slab sum of a fused backward as two launches */                   \
     X(no_fused_bwd, 0)      /* weight gradient and input gradient of a conv layer in two launches, every level */   \
     X(no_fused_bwd_p, 0)    /* ... full-resolution (persistent) layers only */                                      \
     X(no_fused_bwd_big, 0)  /* ... level-1 (16-wide tile) layers only */                                            \
     X(no_fused_upbwd, 0)    /* transposed conv: weight gradient and input gradient in two launches */               \
-    X(api_unfused, 0)       /* mi3d_conv3_backward: stand-alone kernels instead of the step's fused launches */     \
     X(conv8, 1)             /* eight-wave forward conv for levels 1-4 (0: four-wave kernels) */                     \
-    X(ks_target, 128)       /* split-K workgroup target, forward */                                                 \
-    X(ks_target_bwd, 128)   /* split-K workgroup target, input gradient */                                          \
-    X(fused_wg_target, 288) /* weight-gradient workgroups of a fused deep-level backward launch */                  \
-    X(no_defer_wgrad, 0)    /* round 4: weight gradients stay on the data-gradient chain even with an aux stream */ \
-    X(defer_mask, 7)        /* which weight gradients go to the aux stream: 1 decoder level 0, 2 decoder level 1, 4 deep levels */ \
     X(no_pool_splitk, 0)    /* 1: a split-K gradient of a pooled tensor is finished by its own pass, not inside the MaxPool3d backward */ \
-    X(no_wide_store, 4)     /* bit mask of the kernels that keep 8-byte epilogue stores instead of 16-byte ones (v_permlane16_swap): 1 persistent conv, 2 eight-wave conv, 4 four-wave conv body of the fused backward, 8 transposed-conv forward; 15 = all.  In-process A/B of each site (us/step gained by the wide store): 0 / 5 / -3 / 7, so the four-wave body keeps its 8-byte stores */ \
     X(no_pool_pair, 0)      /* 1: MaxPool3d backward with one thread per window (rounds 1-3) instead of two */ \
-    X(no_wgrad_xcd, 0)      /* 1: full-resolution weight gradients take tile = slab index (rounds 1-3) instead of XCD-contiguous tiles */ \
-    X(no_upbwd_xcd_mix, 0)  /* 1: fused transposed-conv backward with the round-3 block mapping (even blocks weight gradient, odd data gradient: one kind per XCD) */ \
-    X(wide_bn, 3)           /* round 4: the conv epilogue's BatchNorm partial rows are finished by the apply pass itself, no finalize launch: 1 = layers with <= 128 rows (level 2; every thin workgroup's prologue), 2 = also the layers with up to 1024 rows (levels 0-1) through wide_bn_wgs workgroups of 1024 threads; 0 = a finalize launch per layer (rounds 1-3) */ \
-    X(wide_bn_wgs, 256)     /* workgroups of a wide BatchNorm pass */ \
-    X(wide_min_rows, 129)   /* partial rows from which the wide kernel (instead of the thin workgroups' prologue) finishes the statistics */ \
+    X(wide_bn, 3)           /* round 4: the conv epilogue's BatchNorm partial rows are finished by the apply pass itself, no finalize launch: 1 = layers with <= 128 rows (level 2; every thin workgroup's prologue), 2 = also the layers with up to 1024 rows (levels 0-1) through at most 256 workgroups of 1024 threads; 0 = a finalize launch per layer (rounds 1-3) */ \
     X(splitk_ticket, 1)     /* round 4: a split-K forward conv of a training step finishes itself (the last of a tile's ks workgroups sums the partials, stores y and the BatchNorm partial row); 0 = the bn_stats_splitk launch does (rounds 2-3) */
 struct Mi3dRoutes {
 #define MI3D_ROUTE_FIELD(name, dflt) int name = dflt;

@@ -1127,8 +1127,8 @@ inline int pick_ksplit(int Cin, int Cout, Geo g, int target_override = 0) {
     // split-K workgroup target.  Round 2 (four-wave kernels): 128 / 256 / 512 / 1024 -> 2.375 / 2.350 / 2.395 / 2.421 ms.  Round 3
     // (eight-wave kernels: a workgroup's chain is half as long, fewer and fatter workgroups win; more layers keep their BatchNorm
     // partial sums in the conv epilogue): 64 / 96 / 128 / 192 / 256 / 384 / 512 -> 2.252 / 2.229 / 2.219 / 2.221 / 2.263 / 2.265 / 2.286 ms
-    const int target = mi3d_routes().ks_target;
-    const int tgt = target_override > 0 ? (target_override < target ? target_override : target) : target;
+    constexpr int SPLITK_TARGET = 128;
+    const int tgt = target_override > 0 && target_override < SPLITK_TARGET ? target_override : SPLITK_TARGET;
     while (wgs * k < tgt && k * 2 <= nchunk && nchunk % (k * 2) == 0 && k < 16) k *= 2;
     return k;
 }
@@ -1194,11 +1194,6 @@ bool conv3_mfma_fuses_stats(int Cin, int Cout, Geo g) { return pick_ksplit(Cin, 
 // (only when conv3_mfma_fuses_stats); skws = K-split scratch (conv3_mfma_splitk_floats) or NULL to force single pass
 bool conv3_mfma_halves_ok(int Cin, int Cout, Geo g) { return persist_ok(Cin, Cout, g); }
 
-int conv3_bwd_ks_target() {
-    int kst = mi3d_routes().ks_target_bwd;    // pick_ksplit clamps it to the forward target (the planned split-K scratch)
-    return kst < 1 ? 1 : kst;
-}
-
 bool conv3_mfma_ticket_ok(int Cin, int Cout, Geo g) {
     if (!mi3d_routes().splitk_ticket || mi3d_routes().conv8 == 0 || big_geo(g) || persist_ok(Cin, Cout, g)) return false;
     if (pick_ksplit(Cin, Cout, g) <= 1) return false;
@@ -1207,10 +1202,10 @@ bool conv3_mfma_ticket_ok(int Cin, int Cout, Geo g) {
 }
 
 int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float* bias, void* y, int ycs, int Cout, Geo g,
-                   float* part, float* skws, hipStream_t s, Halves xh, Halves yh, int* ks_deferred, int relu, int ks_target,
+                   float* part, float* skws, hipStream_t s, Halves xh, Halves yh, int* ks_deferred, int relu, int split_target,
                    float* tk_rows, int* tk_count) {
     if (ks_deferred) *ks_deferred = 0;
-    MI3D_CHECK_ARG(!tk_rows || (conv3_mfma_ticket_ok(Cin, Cout, g) && skws && ks_target == 0), "conv3_mfma_fwd: no split-K ticket for %d->%d here", Cin, Cout);
+    MI3D_CHECK_ARG(!tk_rows || (conv3_mfma_ticket_ok(Cin, Cout, g) && skws && split_target == 0), "conv3_mfma_fwd: no split-K ticket for %d->%d here", Cin, Cout);
     MI3D_CHECK_ARG((!xh.on() && !yh.on()) || persist_ok(Cin, Cout, g), "conv3_mfma_fwd: planar halves need the persistent kernel");
     MI3D_CHECK_ARG(conv3_mfma_supported(Cin, Cout, xcs, ycs), "conv3_mfma_fwd: unsupported channels %d->%d", Cin, Cout);
     MI3D_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0, "conv3_mfma_fwd: misaligned tensors");
@@ -1219,7 +1214,7 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
     if (persist_ok(Cin, Cout, g)) {
         int tz = cdiv(g.D, 4), ty = cdiv(g.H, 8), tx = cdiv(g.W, 16), nt = g.N * tz * ty * tx, grid = persist_grid(Cin, Cout, g);
         // bit 1 of the relu word: 16-byte epilogue stores (two M-block rows trade halves through v_permlane16_swap)
-        if (!(mi3d_routes().no_wide_store & 1) && ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && yh.delta % 8 == 0) relu |= 2;
+        if (ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && yh.delta % 8 == 0) relu |= 2;
 #define PK(COB_, NCH_)                                                                                                         \
         do {                                                                                                                   \
             hipEvent_t tev0 = nullptr, tev1 = nullptr;                                                                          \
@@ -1237,9 +1232,9 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
         MI3D_LAUNCH_CHECK();
         return 0;
     }
-    int ks = skws ? pick_ksplit(Cin, Cout, g, ks_target) : 1;
+    int ks = skws ? pick_ksplit(Cin, Cout, g, split_target) : 1;
     // bit 1 of the relu word: 16-byte epilogue stores in the eight-wave kernels (two output blocks per workgroup)
-    if (!(mi3d_routes().no_wide_store & 2) && ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && Cout % 32 == 0) relu |= 2;
+    if (ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && Cout % 32 == 0) relu |= 2;
     if (ks > 1) MI3D_CHECK_ARG(ycs % 8 == 0 && ((uintptr_t)y % 16) == 0, "conv3_mfma_fwd: split-K needs 16-B aligned output rows");
     if (big_geo(g)) {
         // (round 4: ONE 16-channel output block per workgroup at the 16-wide levels -- twice the workgroups, half the chain each, the
@@ -1516,7 +1511,7 @@ struct FusedArgs {
     const bf16* dxin; int dxcs_in, dCin; const bf16* dwp; bf16* dyout; int dycs_out, dCout; int dtZ, dtY, dtX; float* dpart;
     int dgx, dgy, dgz;
     int N, D, H, W;
-    int flags;                // bit 1: 16-byte epilogue stores in the input-gradient half
+    int flags;                // bit 1: 16-byte epilogue stores in the input-gradient half (never set, see conv3_mfma_bwd_fused)
 };
 // Full-resolution variant: the input-gradient conv is the persistent kernel body.  Both halves are persistent with ONE
 // workgroup per CU each, so every CU runs one MFMA-heavy dgrad workgroup beside one staging/LDS-heavy wgrad workgroup
@@ -1916,10 +1911,10 @@ int launch_wgrad(const bf16* x, int xcs, int Cin, const bf16* dy, int dycs, int 
     // full-resolution layers: the XCD-aware tile assignment of the fused launch (the stand-alone kernel must sum the same tiles into
     // the same slabs: both routes produce the same bits)
     const bool full = persist_ok(Cout, Cin, g);
-    const int xcd_tiles = (full && !mi3d_routes().no_wgrad_xcd) ? 1 : 0;
+    const int xcd_tiles = full ? 1 : 0;
     // every other layer: flat, placed grid (see the kernel); same slabs, same tiles per slab, same bits
     int pgx = 0, pgy = 0, pgz = 0;
-    if (!full && c.tg == 1 && !mi3d_routes().no_wgrad_xcd) {
+    if (!full && c.tg == 1) {
         pgx = (int)grid.x; pgy = (int)grid.y; pgz = (int)grid.z;
         grid = dim3((unsigned)(pgx * pgy * pgz));
     }
@@ -2024,8 +2019,8 @@ int conv3_mfma_bwd_fused_persist(const void* x, int xcs, int Cin, const void* dy
     a.ptZ = cdiv(g.D, 4); a.ptY = cdiv(g.H, 8); a.ptX = cdiv(g.W, 16); a.pnt = g.N * a.ptZ * a.ptY * a.ptX;
     a.pgrid = a.pnt < pcap ? a.pnt : pcap; a.dyh = dxh;
     a.N = g.N; a.D = g.D; a.H = g.H; a.W = g.W;
-    a.xcd_tiles = mi3d_routes().no_wgrad_xcd ? 0 : 1;
-    a.flags = (!(mi3d_routes().no_wide_store & 1) && dxcs % 8 == 0 && ((uintptr_t)dx % 16) == 0 && dxh.delta % 8 == 0) ? 2 : 0;
+    a.xcd_tiles = 1;      // the tile mapping of the stand-alone weight gradient at full resolution (launch_wgrad)
+    a.flags = (dxcs % 8 == 0 && ((uintptr_t)dx % 16) == 0 && dxh.delta % 8 == 0) ? 2 : 0;
     int nw = a.wgx * a.wgy * a.wgz;
     int half = nw > a.pgrid ? nw : a.pgrid;
     unsigned nblk = (unsigned)(2 * half);
@@ -2060,9 +2055,15 @@ bool conv3_mfma_bwd_fused_ok(int Cin, int Cout, int xcs, int dycs, int dxcs, Geo
            !mi3d_routes().no_fused_bwd;
 }
 
+// the weight-gradient half of a fused launch shares the launch (and the CUs' two workgroup slots) with the input-gradient half:
+// sized for ~288 workgroups instead of the stand-alone kernel's 512 it leaves fewer, fatter slabs (less slab traffic to sum) and
+// lets the input-gradient workgroups start earlier.  Scan at 96^3 (tools/abenv.py, ms/step): 64: 2.71, 128: 2.42, 192: 2.33,
+// 256: 2.32, 288: 2.286, 320: 2.288, 352: 2.296, 384: 2.303, 448: 2.309, 512: 2.313
+constexpr int FUSED_WGRAD_TARGET = 288;
+
 int conv3_mfma_bwd_wg_target(int Cin, int Cout, int xcs, int dycs, int dxcs, Geo g) {
     if (conv3_mfma_bwd_fused_persist_ok(Cin, Cout, xcs, dycs, g)) return device_cus();
-    if (conv3_mfma_bwd_fused_ok(Cin, Cout, xcs, dycs, dxcs, g)) return mi3d_routes().fused_wg_target;
+    if (conv3_mfma_bwd_fused_ok(Cin, Cout, xcs, dycs, dxcs, g)) return FUSED_WGRAD_TARGET;
     return 0;
 }
 
@@ -2072,18 +2073,14 @@ int conv3_mfma_bwd_fused(const void* x, int xcs, int Cin, const void* dy, int dy
     if (ks_deferred) *ks_deferred = 0;
     MI3D_CHECK_ARG(conv3_mfma_bwd_fused_ok(Cin, Cout, xcs, dycs, dxcs, g) && dx && ((uintptr_t)dx % 16) == 0 && skws,
                    "conv3_mfma_bwd_fused: unsupported layer %d->%d", Cin, Cout);
-    // the weight-gradient half shares the launch (and the CUs' two workgroup slots) with the input-gradient half: sized for
-    // ~288 workgroups instead of the stand-alone kernel's 512 it leaves fewer, fatter slabs (less slab traffic to sum) and lets
-    // the input-gradient workgroups start earlier.  Scan at 96^3 (tools/abenv.py, ms/step): 64: 2.71, 128: 2.42, 192: 2.33,
-    // 256: 2.32, 288: 2.286, 320: 2.288, 352: 2.296, 384: 2.303, 448: 2.309, 512: 2.313.  MI3D_FUSED_WG_TARGET overrides
-    WgCfg c = wgrad_cfg(Cin, Cout, g, mi3d_routes().fused_wg_target);
+    WgCfg c = wgrad_cfg(Cin, Cout, g, FUSED_WGRAD_TARGET);
     int64_t nW = (int64_t)Cout * Cin * 27, slab_sz = nW + Cout;
     MI3D_CHECK_ARG(wgws_floats >= (size_t)c.nsb * slab_sz, "conv3_mfma_bwd_fused: workspace too small");
     bool big = big_geo(g);
     // split-K target of the input-gradient half: 128 workgroups instead of the stand-alone conv's 256 -- it runs beside the
     // weight-gradient workgroups of the same launch (scan at 96^3, ms/step: 32: 2.33, 64: 2.294, 96: 2.282, 128: 2.259,
-    // 192: 2.260, 256: 2.284).  MI3D_KS_TARGET_BWD overrides (values above 256 would outgrow the planned split-K scratch)
-    int ks = pick_ksplit(Cout, Cin, g, conv3_bwd_ks_target());   // dgrad: input channels = Cout, output channels = Cin (1 if big)
+    // 192: 2.260, 256: 2.284)
+    int ks = pick_ksplit(Cout, Cin, g, CONV3_BWD_SPLITK_TARGET);   // dgrad: input channels = Cout, output channels = Cin (1 if big)
     FusedArgs a;
     a.wx = (const bf16*)x; a.wxcs = xcs; a.wCin = Cin; a.wdy = (const bf16*)dy; a.wdycs = dycs; a.wCout = Cout;
     a.tZ = cdiv(g.D, WTZ); a.tY = cdiv(g.H, WTY); a.tX = cdiv(g.W, WTX); a.slabs = wgws;
@@ -2092,7 +2089,9 @@ int conv3_mfma_bwd_fused(const void* x, int xcs, int Cin, const void* dy, int dy
     a.dCout = Cin; a.dtZ = cdiv(g.D, 4); a.dtY = cdiv(g.H, 8); a.dtX = cdiv(g.W, big ? 16 : 8); a.dpart = ks > 1 ? skws : nullptr;
     a.dgx = g.N * a.dtZ * a.dtY * a.dtX; a.dgy = Cin / 32; a.dgz = ks;
     a.N = g.N; a.D = g.D; a.H = g.H; a.W = g.W;
-    a.flags = (!(mi3d_routes().no_wide_store & 4) && dxcs % 8 == 0 && ((uintptr_t)dx % 16) == 0) ? 2 : 0;
+    // 8-byte epilogue stores: in-process A/B of the 16-byte ones (v_permlane16_swap), us/step gained: persistent conv 0,
+    // eight-wave conv 5, transposed-conv forward 7, this four-wave body -3
+    a.flags = 0;
     size_t lds = (size_t)(WNV + WNH) * 32;
     if (lds < 16 * 1024 + 256) lds = 16 * 1024 + 256;
     MI3D_SET_MAX_LDS_ONCE((&conv3_bwd_fused_kernel<false, true>), lds);
@@ -2108,7 +2107,7 @@ int conv3_mfma_bwd_fused(const void* x, int xcs, int Cin, const void* dy, int dy
         *ks_deferred = ks;
         return wgrad_slab_sum(wgws, c.nsb, Cin, Cout, dW, db, accumulate, s, pend);
     }
-    if (ks > 1 && !mi3d_routes().no_bwd_tail) {
+    if (ks > 1) {
         int64_t tot = g.M() * (Cin / 8);
         TailArgs t;
         t.part = skws; t.ks = ks; t.M = g.M(); t.C = Cin; t.y = (bf16*)dx; t.ycs = dxcs;
@@ -2121,11 +2120,6 @@ int conv3_mfma_bwd_fused(const void* x, int xcs, int Cin, const void* dy, int dy
         bwd_tail_kernel<<<t.nfin + nsl, BLK, 0, s>>>(t);
         MI3D_LAUNCH_CHECK();
         return 0;
-    }
-    if (ks > 1) {
-        int64_t tot = g.M() * (Cin / 8);
-        splitk_finish_kernel<<<cdiv(tot, BLK) > 2048 ? 2048 : cdiv(tot, BLK), BLK, 0, s>>>(skws, ks, g.M(), Cin, nullptr, (bf16*)dx, dxcs, 0);
-        MI3D_LAUNCH_CHECK();
     }
     return wgrad_slab_sum(wgws, c.nsb, Cin, Cout, dW, db, accumulate, s, pend);
 }

@@ -107,7 +107,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
 
     for (int l = 0; l < p.L; l++)
         p.planar[l] = p.dt == MI3D_BF16 && p.C[l] % 16 == 0 && conv3_mfma_halves_ok(2 * p.C[l], p.C[l], p.geo[l]) &&
-                      conv3_mfma_halves_ok(p.C[l], 2 * p.C[l], p.geo[l]) && !mi3d_routes().force_direct && !mi3d_routes().no_planar;
+                      conv3_mfma_halves_ok(p.C[l], 2 * p.C[l], p.geo[l]) && !mi3d_routes().no_planar;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
     int64_t drop_off = 0;
@@ -128,7 +128,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             H.Cout = cout;
             H.y = take((size_t)g.M() * cout * p.esz);
             H.stat = take((size_t)4 * cout * sizeof(float));
-            H.mfma = p.dt == MI3D_BF16 && conv3_mfma_supported(H.Cin, H.Cout, 16, 16) && !mi3d_routes().force_direct;
+            H.mfma = p.dt == MI3D_BF16 && conv3_mfma_supported(H.Cin, H.Cout, 16, 16);
             if (H.mfma) {
                 H.wpf = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
                 H.wpd = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
@@ -145,7 +145,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             H.bidx = 6 * b + 3 * h;
             H.drop_off = drop_off;
             drop_off += (int64_t)d->N * cout;
-            bool c1 = p.dt == MI3D_BF16 && H.Cin == 1 && H.Cout % 16 == 0 && !mi3d_routes().force_direct;
+            bool c1 = p.dt == MI3D_BF16 && H.Cin == 1 && H.Cout % 16 == 0;
             if (c1) {
                 size_t sp = (size_t)conv3_c1_fwd_stat_blocks(g) * 2 * cout;
                 if (sp > statpart_floats) statpart_floats = sp;
@@ -173,8 +173,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
     for (int i = 0; i < p.L; i++) {
         int l = p.L - 1 - i;
         p.zd[i] = take((size_t)p.geo[l].M() * p.C[l] * p.esz);
-        p.up_mfma[i] = p.dt == MI3D_BF16 && upconv2_mfma_supported(2 * p.C[l], p.C[l], 2 * p.C[l], 2 * p.C[l]) &&
-                       !mi3d_routes().force_direct;
+        p.up_mfma[i] = p.dt == MI3D_BF16 && upconv2_mfma_supported(2 * p.C[l], p.C[l], 2 * p.C[l], 2 * p.C[l]);
         p.upw[i] = take(p.up_mfma[i] ? upconv2_mfma_pack_elems(2 * p.C[l], p.C[l]) * 2
                                      : upconv2_pack_floats(2 * p.C[l], p.C[l]) * sizeof(float));
         size_t wf = p.up_mfma[i] ? upconv2_mfma_bwd_ws_floats(2 * p.C[l], p.C[l], p.geo[l + 1])
@@ -243,22 +242,20 @@ struct Ctx {
     // conv's backward launch, and the next BatchNorm-backward reduction carries both
     mutable SlabJob pend2;
     mutable bool has_pend2 = false;
-    bool defer_slabs = false;
     // the input gradient of a block's first conv (= the gradient of the pooled tensor one level up) left as split-K partials for
     // the MaxPool3d backward of the next segment to finish (no splitk_finish launch); pool_defer: the caller allows it
     mutable int pool_ks = 0;
     mutable bool pool_defer = false;
     mutable hipEvent_t mark_pending = nullptr;      // exchange mark waiting for the launch that completes its segment's gradients
     // called before ANY launch that writes the (single) slab workspace: an older pending sum must read it first.
-    // Returns where the launcher may leave its own slab sum instead of launching it (NULL: launch immediately)
+    // Returns where the launcher leaves its own slab sum instead of launching it
     SlabJob* pend_slot() const {
         if (has_pend) { slab_job_launch(pend, s); has_pend = false; }
         if (has_pend2) { slab_job_launch(pend2, s); has_pend2 = false; }
-        if (!defer_slabs) return nullptr;
         pend = SlabJob();
         return &pend;
     }
-    void pend_filled() const { has_pend = defer_slabs && pend.nblocks > 0; }
+    void pend_filled() const { has_pend = pend.nblocks > 0; }
     int flush_pend() const {
         int rc = 0;
         if (has_pend) { rc = slab_job_launch(pend, s); has_pend = false; }
@@ -323,8 +320,7 @@ int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, con
                                     (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), Halves(), training ? &ksd : nullptr, 0, 0,
                                     tk ? c.at<float>(p.statpart) : nullptr, tk ? c.at<int>(p.tkcount) : nullptr));
             fused_stats = training && (tk || conv3_mfma_fuses_stats(H.Cin, H.Cout, g));
-        } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0 && !mi3d_routes().force_direct &&
-                   !mi3d_routes().no_c1_mfma) {
+        } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0) {
             // first layer on the matrix cores (taps are the K dimension), BN partial sums fused like the other convs
             MI3D_TRY(conv3_c1_fwd_mfma((const float*)in, c.P(H.pidx), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
                                        training ? c.at<float>(p.statpart) : nullptr, c.s));
@@ -420,7 +416,7 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
     const void* xin; int xcs, xdt;
     block_input(c, b, x, xin, xcs, xdt);
     auto G = [&](int i) { return grads ? (float*)grads[i] : nullptr; };
-    const bool aux = c.s2 != nullptr && c.ev != nullptr && !mi3d_routes().no_defer_wgrad;
+    const bool aux = c.s2 != nullptr && c.ev != nullptr;
     const float* dz_skp = nullptr;      // dz of half 0 left as split-K partials by half 1's fused backward launch
     int dz_ks = 0;
     for (int h = 1; h >= 0; h--) {
@@ -428,8 +424,7 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
         int k = c.seq++;
         if (aux && c.nhq) MI3D_TRY(drain_aux(c, x, grads, accumulate, 3));      // feed the aux stream between the chain's launches
         // deferred weight gradient: dy goes to the layer's own buffer, which nobody overwrites before the aux stream has read it
-        const int dbit = H.defer == 2 ? 4 : (B.level == 0 ? 1 : 2);
-        const bool dfr = aux && H.defer && (mi3d_routes().defer_mask & dbit) && (G(H.pidx) || G(H.pidx + 1));
+        const bool dfr = aux && H.defer && (G(H.pidx) || G(H.pidx + 1));
         void* dyb = dfr ? c.at(H.dyk) : c.at((k & 1) ? p.sB2 : p.sB);
         const void* dz = h == 1 ? dz2 : c.at(p.sC);
         int dcs = h == 1 ? dzcs : H.Cout;
@@ -451,22 +446,22 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
             c.dq[c.ndq++] = Ctx::DJob{b, h, conv3_mfma_bwd_wg_target(H.Cin, H.Cout, ics, H.Cout, dx_f ? dxs_f : 8, g)};
         }
         // fork points: what is queued goes to the aux stream when the chain has finished the last layer of a group (its BatchNorm
-        // backward), whether or not that very layer is deferred under the current defer_mask.  Group 1 forks when the GPU is still
-        // busy with the full-resolution decoder (the host is far ahead: enqueue at once); group 2 forks at the end of the
-        // launch-bound deep chain: its launches are fed in between the chain's next ones.
+        // backward).  Group 1 forks when the GPU is still busy with the full-resolution decoder (the host is far ahead: enqueue at
+        // once); group 2 forks at the end of the launch-bound deep chain: its launches are fed in between the chain's next ones.
         // (Measured and dropped, profiles/r04_experiments_aux_wgrad.txt and the fork-placement record beside it: one fork per layer +26 ... +43 us,
-        // per deep layer only +6 us, the decoder fork one block later -1 us, another workgroup count for the aux kernels +10 ... +40 us)
+        // per deep layer only +6 us, the decoder fork one block later -1 us, another workgroup count for the aux kernels +10 ... +40 us,
+        // deferring only some of the three groups 13 ... 102 us)
         if (aux)
             for (int q = 0; q < 2; q++)
                 if (b == p.flush_b[q] && h == p.flush_h[q]) MI3D_TRY(flush_deferred(c, x, grads, accumulate, q == 1));
         if (dfr) {
             if (dx_f) {
                 const bool to_pool = h == 0 && c.pool_defer && dx_f == dxin;
-                const bool defer = (h == 1 || to_pool) && c.defer_slabs && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
+                const bool defer = (h == 1 || to_pool) && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
                 int ksd = 0;
                 MI3D_TRY(conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx_f, dxs_f, H.Cin, g, nullptr,
                                         (dxs_f % 8 == 0) ? c.at<float>(p.skws) : nullptr, c.s, Halves(),
-                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), defer ? &ksd : nullptr, 0, conv3_bwd_ks_target()));
+                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), defer ? &ksd : nullptr, 0, CONV3_BWD_SPLITK_TARGET));
                 if (ksd > 0 && h == 1) { dz_skp = c.at<float>(p.skws); dz_ks = ksd; }
                 if (ksd > 0 && h == 0) c.pool_ks = ksd;
             }
@@ -486,7 +481,7 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
             // half 1's input gradient feeds straight into half 0's BatchNorm-backward reduction: leave a split-K result as
             // partials and let that reduction finish it (one launch less on the chain)
             const bool to_pool = h == 0 && c.pool_defer && dx_f == dxin;
-            bool defer = (h == 1 || to_pool) && ps && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
+            bool defer = (h == 1 || to_pool) && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
             int ksd = 0;
             MI3D_TRY(conv3_mfma_bwd_fused(in, ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx_f, dxs_f, g, G(H.pidx), G(H.pidx + 1),
                                           accumulate, c.at<float>(p.wgws), p.wgws_floats, c.at<float>(p.skws), c.s, ps,
@@ -503,7 +498,7 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
             if (H.mfma)
                 MI3D_TRY(conv3_mfma_wgrad(in, ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
                                           wgws, p.wgws_floats, ws_, (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), ps));
-            else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0 && !mi3d_routes().force_direct)
+            else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0)
                 MI3D_TRY(conv3_mfma_wgrad_c1((const float*)in, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
                                              wgws, p.wgws_floats, ws_, ps));
             else
@@ -517,7 +512,7 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
             if (H.mfma)
                 MI3D_TRY(conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx, dxs, H.Cin, g, nullptr,
                                         (dxs % 8 == 0) ? c.at<float>(p.skws) : nullptr, c.s, Halves(),
-                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), nullptr, 0, conv3_bwd_ks_target()));
+                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), nullptr, 0, CONV3_BWD_SPLITK_TARGET));
             else
                 MI3D_TRY(conv3_direct_fwd(p.dt, p.dt, dyb, H.Cout, H.Cout, c.at<float>(H.wpd), nullptr, dx, dxs, H.Cin, g, c.s));
         }
@@ -548,8 +543,7 @@ int block_infer(const Ctx& c, int b, const float* x) {
             MI3D_TRY(conv3_mfma_fwd(in, ics, H.Cin, c.at(H.wpf), fbias, zo, zocs, H.Cout, g, nullptr,
                                     (zocs % 8 == 0 && ((uintptr_t)zo % 16) == 0) ? c.at<float>(p.skws) : nullptr, c.s,
                                     (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), Halves(), nullptr, 1));
-        } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0 && !mi3d_routes().force_direct &&
-                   !mi3d_routes().no_c1_mfma) {
+        } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0) {
             MI3D_TRY(conv3_c1_fwd_mfma((const float*)in, c.P(H.pidx), fbias, zo, zocs, H.Cout, g, nullptr, c.s, scale, 1));
         } else {
             MI3D_TRY(conv3_direct_pack(c.P(H.pidx), H.Cin, H.Cout, c.at<float>(H.wpf), nullptr, c.s, scale));
@@ -850,7 +844,6 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
     Ctx c{p, (char*)workspace, params, (hipStream_t)stream};
     if (aux_stream && events) { c.s2 = (hipStream_t)aux_stream; c.ev = (hipEvent_t*)events; }
     float* wgws = c.at<float>(p.wgws);
-    c.defer_slabs = !mi3d_routes().no_pend_slabs;
     auto G = [&](int i) { return (float*)grads[i]; };
     BwdMarks marks = g_marks;
     g_marks.n = 0;
@@ -894,7 +887,7 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
             // the decoder conv's pending slab sum (it reads wgws) stays pending across the transposed conv's backward, which
             // therefore writes its slabs to the second workspace; the next BatchNorm-backward reduction carries both sums: one
             // chain link less per level (not with the two-stream weight gradients, which own that workspace)
-            const bool keep = p.up_mfma[i] && c.has_pend && !c.has_pend2 && c.defer_slabs && !mi3d_routes().no_upbwd_carry;
+            const bool keep = p.up_mfma[i] && c.has_pend && !c.has_pend2 && !mi3d_routes().no_upbwd_carry;
             if (p.up_mfma[i] && keep) {
                 c.pend2 = SlabJob();
                 MI3D_TRY(upconv2_mfma_bwd(uin, 2 * p.C[l], 2 * p.C[l], gup, gupcs, p.C[l],

@@ -360,7 +360,6 @@ __global__ __launch_bounds__(BLK) void upconv_mfma_bwd_weight_kernel(const bf16*
 struct UFusedArgs {
     const bf16* x; int xcs, Cin; const bf16* g; int gcs, Cout; const bf16* wb; bf16* dx; int dxcs; float* slabs;
     int N, D, H, W; int wgx, wgy, wgz, dgx, dgy;
-    int map;
 };
 template <int S, bool KSPLIT>
 __global__ __launch_bounds__(BLK) void upconv_mfma_bwd_fused_kernel(UFusedArgs a) {
@@ -370,7 +369,7 @@ __global__ __launch_bounds__(BLK) void upconv_mfma_bwd_fused_kernel(UFusedArgs a
     int b = blockIdx.x, m = nw < nd ? nw : nd;
     bool is_w; int idx;
     const int m16 = (2 * m) & ~15;          // whole groups of 16 blocks: 8 XCDs x (one weight-gradient + one data-gradient block)
-    if (a.map && b < m16) {
+    if (b < m16) {
         // round 4: workgroup b runs on XCD b % 8, so "even = weight gradient, odd = data gradient" gave each XCD ONE kind; now the
         // kinds alternate inside an XCD (its k-th block, k = b / 8, is a weight-gradient block iff k is even)
         int xcd = b & 7, k = b >> 3;
@@ -456,7 +455,7 @@ int upconv2_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const floa
     while (gx * gy < 512 && gy < Cout / 16) gy *= 2;      // few voxels (deep levels): parallelise over channel blocks
     int gz = (gx * gy < 512 && !(Cin == 32 && Cout == 16)) ? 8 : 1;     // ... and over the 8 taps
     dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)gz);
-    const int wide = (gz == 1 && ycs % 8 == 0 && ((uintptr_t)yp % 16) == 0 && !(mi3d_routes().no_wide_store & 8)) ? 1 : 0;
+    const int wide = (gz == 1 && ycs % 8 == 0 && ((uintptr_t)yp % 16) == 0) ? 1 : 0;
 #define UF(K) upconv_mfma_fwd_kernel<K><<<grid, BLK, 0, s>>>(xp, xcs, wf, bias, yp, ycs, Cout, g.N, g.D, g.H, g.W, wide)
     switch (Cin / 32) { case 1: UF(1); break; case 2: UF(2); break; case 4: UF(4); break; default: UF(8); break; }
 #undef UF
@@ -493,8 +492,7 @@ int upconv2_mfma_bwd(const void* x, int xcs, int Cin, const void* gy, int gycs, 
         MI3D_CHECK_ARG(ws_floats >= (size_t)nsb * slab_sz, "upconv2_mfma_bwd: workspace too small");
         if (!ksp && gx * gy > dcap) gx = dcap / gy < 1 ? 1 : dcap / gy;          // persistent data-gradient workgroups
         UFusedArgs a{xp, xcs, Cin, gp, gycs, Cout, wb, (bf16*)dx, dxcs, ws, g.N, g.D, g.H, g.W,
-                     nsb, Cin / 32, (int)cdiv(Cout, 32), ksp ? (int)gkx : gx, ksp ? Cin / 16 : gy,
-                     mi3d_routes().no_upbwd_xcd_mix ? 0 : 1};
+                     nsb, Cin / 32, (int)cdiv(Cout, 32), ksp ? (int)gkx : gx, ksp ? Cin / 16 : gy};
         size_t lds = (size_t)(2 * UV + 16 * UV) * 32;
         unsigned nblk = (unsigned)(a.wgx * a.wgy * a.wgz + a.dgx * a.dgy);
 #define UFL(SS, KS_)                                                                                                          \

@@ -14,8 +14,8 @@ Design (MI355X-first, not a DDP translation):
     on contiguous arena ranges (no bucket copy-in/copy-out).
   * backward runs as runs of segments with TWO exchanges by default (dp.bucket_ranges): after encoder.L-1's segment the
     arena range [encoder.L-1 .. final_conv] (97 % of the gradient bytes) is all-reduced on a side stream (RCCL over xGMI)
-    while the bandwidth-heavy encoder.L-2..0 backward runs; [encoder.0..L-2] follows at the end (MI3D_FINE_BUCKETS=1: four
-    readiness-ordered buckets, measured slower).  The four scalar gathers of the reference (C4) are one 4-float all-reduce
+    while the bandwidth-heavy encoder.L-2..0 backward runs; [encoder.0..L-2] follows at the end (dp.bucket_ranges(fine=True):
+    four readiness-ordered buckets, measured slower).  The four scalar gathers of the reference (C4) are one 4-float all-reduce
     that rides on the first exchange.
   * a step is captured into hipGraphs: ONE graph at world 1; at world > 1 the step is launched eagerly (or, on request, as
     one graph per comm-free run of kernels with the all-reduces between them: RCCL calls stay outside the graphs).
@@ -59,7 +59,7 @@ def _priority_stream(device, cls):
     return st
 
 
-_STREAM_CACHE = {}      # (device index, priority, role) -> stream chosen by concurrent_stream
+_STREAM_CACHE = {}      # (device index, role) -> stream chosen by concurrent_stream
 _CAPTURE_STREAMS = {}   # device index -> the stream hipGraph captures run on (nothing else ever does)
 
 
@@ -71,32 +71,27 @@ def _capture_stream(device):
     return _CAPTURE_STREAMS[key]
 
 
-def concurrent_stream(device, candidates=6, hold_us=300, priority="high", role="aux"):
+def concurrent_stream(device, candidates=6, hold_us=300, role="aux"):
     """A stream whose kernels really run BESIDE those of the current (compute) stream.  HIP multiplexes streams onto a few
     hardware queues, and two streams that share a queue execute strictly one after the other (measured with rocprofv3: the
     default stream and the 8th stream created in a process both sat on queue 4, and a collective kernel on the latter ran
     between, not beside, the backward kernels -- profiles/r03_dp_streams.txt).  So the stream is CHOSEN by a measurement: a
     stand-in kernel that holds a few workgroups for `hold_us` is launched on the candidate and on the compute stream; if the
     pair takes about one hold time they overlap (minimum of three timed repetitions: a busy GPU only ever makes a pair look
-    slower).  The first candidate has the requested priority class ("high": its own queue on this runtime; "low": the lowest
-    class, mi3d_stream_create).  The choice is cached per (device, priority, role): every step object of a process shares it
-    and the probe runs once.  When no candidate overlaps, the last one is returned with mi3d_concurrent = False and a
-    RuntimeWarning: the step is still correct, only nothing will run beside the compute stream."""
+    slower).  The first candidate is a high-priority stream (its own queue on this runtime).  The choice is cached per
+    (device, role): every step object of a process shares it and the probe runs once.  When no candidate overlaps, the last
+    one is returned with mi3d_concurrent = False and a RuntimeWarning: the step is still correct, only nothing will run
+    beside the compute stream."""
     import warnings
     dev = torch.device(device)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), priority, role)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), role)
     if key in _STREAM_CACHE:
         return _STREAM_CACHE[key]
     main = torch.cuda.current_stream(device)
     buf = torch.zeros(1024, dtype=torch.float32, device=device)
     best = None
     for i in range(candidates):
-        if i == 0 and priority == "low":
-            c = _priority_stream(device, +1)
-        elif i == 0 and priority == "high":
-            c = torch.cuda.Stream(device=device, priority=-1)
-        else:
-            c = torch.cuda.Stream(device=device)
+        c = torch.cuda.Stream(device=device, priority=-1 if i == 0 else 0)
         times = []
         for rep in range(4):                       # first pass loads the code object
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -174,8 +169,7 @@ class _StepBase:
         # at world 1 -- a 1-rank RCCL group on the 1-GPU box exercises the real code path
         self.force_comm = bool(force_comm) or os.environ.get("MI3D_FORCE_COMM", "0") == "1"
         self.do_comm = self.world > 1 or (self.force_comm and dist.is_available() and dist.is_initialized())
-        self.comm = DataParallelComm(self.arena, n_levels, process_group, force=self.do_comm,
-                                     fine_buckets=os.environ.get("MI3D_FINE_BUCKETS", "0") == "1")
+        self.comm = DataParallelComm(self.arena, n_levels, process_group, force=self.do_comm)
         # the exchange stream must sit on another hardware queue than the compute stream (see concurrent_stream)
         self.comm_stream = concurrent_stream(self.device, role="comm") if self.do_comm else None
         # MI3D_NO_MARKS=1: exchange points cut the backward into calls instead of marks; MI3D_COMM_SERIAL=1: every bucket behind
@@ -394,8 +388,7 @@ class TrainStep(_StepBase):
             # finish ~150 us before the end of the backward, so the big all-reduce bucket (dp.bucket_ranges) would lose the
             # 0.45 ms of encoder backward it hides under; the exchange is worth more than the ~20 us the deferral buys
             aux_wgrad = not use_graph and not self.do_comm
-        self.aux_stream = (concurrent_stream(self.device, priority=os.environ.get("MI3D_AUX_PRIO", "high"))
-                           if aux_wgrad else None)
+        self.aux_stream = concurrent_stream(self.device) if aux_wgrad else None
         self._events = None
         self._event_handles = []
         if aux_wgrad:

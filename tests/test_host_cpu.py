@@ -257,20 +257,30 @@ def test_bench_roofline_candidates_have_committed_traffic_records():
     assert bench._kernel_traffic("no_such_kernel", 0.1) is None
 
 
-def test_route_switches_are_read_once_and_set_through_the_abi():
+def test_route_table_is_read_once_and_set_through_the_abi():
     """Every kernel-selection switch lives in one struct (csrc/common.h MI3D_ROUTE_LIST): the environment is read at first use
     only, later changes go through mi3d_debug_set_route; unknown names fail loudly."""
     import os
     names = _lib.route_names()
-    assert "no_defer_wgrad" in names and "ks_target" in names and len(names) == len(set(names))
-    assert _lib.get_route("ks_target") == 128 and _lib.get_route("conv8") == 1
+    assert "no_defer_tail" in names and "wide_bn" in names and len(names) == len(set(names))
+    assert _lib.get_route("wide_bn") == 3 and _lib.get_route("conv8") == 1
     os.environ["MI3D_NO_PERSIST"] = "1"          # after the first use: ignored
     try:
         assert _lib.get_route("no_persist") == 0
     finally:
         del os.environ["MI3D_NO_PERSIST"]
-    with _lib.routes(no_persist=1, ks_target=64):
-        assert _lib.get_route("no_persist") == 1 and _lib.get_route("ks_target") == 64
-    assert _lib.get_route("no_persist") == 0 and _lib.get_route("ks_target") == 128
+    with _lib.routes(no_persist=1, wide_bn=1):
+        assert _lib.get_route("no_persist") == 1 and _lib.get_route("wide_bn") == 1
+    assert _lib.get_route("no_persist") == 0 and _lib.get_route("wide_bn") == 3
     with pytest.raises(_lib.Mi3dError):
         _lib.set_route("no_such_route", 1)
+
+
+def test_every_route_switch_is_exercised_by_a_gpu_test():
+    """The route table keeps exactly the switches whose non-default route some GPU test compares with the default: a switch
+    that no tests/test_gpu_*.py names would be unverified code, so its default belongs in the code instead."""
+    import glob
+    names = _lib.route_names()
+    assert len(names) == 16
+    gpu_tests = "\n".join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py"))))
+    assert [n for n in names if not re.search(rf"\b{n}\b", gpu_tests)] == []

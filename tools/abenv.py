@@ -2,7 +2,7 @@
 """A/B of route switches on ONE box: wall-clock ms/step (bench.py, hipGraph) and per-kernel time per step (rocprofv3
 --kernel-trace --stats) for several environment settings.
 
-    python tools/abenv.py base= wring=MI3D_CONV_WRING=1 nobn=MI3D_NO_BN_ONEPASS=1 [--steps 40] [--rounds 2] [--noprof]
+    python tools/abenv.py base= nopair=MI3D_NO_POOL_PAIR=1 conv4=MI3D_CONV8=0 [--steps 40] [--rounds 2] [--noprof]
 Each argument is name=ENV=VAL[,ENV=VAL...] (empty = default build).  The first setting is the reference of the kernel diff."""
 import csv
 import glob

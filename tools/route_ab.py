@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of ROUTES in ONE process (round 4: +-3 us resolution; separate processes on one box differ by +-10 us, boxes by +-50 us).
 Each argument is name=route:value[,route:value...] (empty = defaults); the routes are switched through mi3d_debug_set_route between
-timed blocks of eager steps of bench.py's step object.  python tools/route_ab.py base= old=no_wide_store:1 [--rounds 4] [--steps 40]"""
+timed blocks of eager steps of bench.py's step object.  python tools/route_ab.py base= old=no_pool_pair:1 [--rounds 4] [--steps 40]"""
 import os
 import sys
 import time

@@ -14,3 +14,10 @@ run --steps 20 --workload distill
 run --steps 20 --workload dann
 run --steps 40 --workload eval
 run --steps 40 --workload eval --size 128
+run --steps 40 --graph
+run --steps 20 --batch 4 --graph
+run --steps 20 --batch 8 --graph
+run --steps 20 --size 128 --graph
+run --steps 10 --size 192 --batch 1 --graph
+run --steps 40 --dropout 0.1 --graph
+run --steps 10 --dtype fp32
