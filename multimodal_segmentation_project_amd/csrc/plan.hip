@@ -24,6 +24,10 @@ struct HalfP {
     int pidx, bidx;
     int64_t drop_off;
     bool mfma;                    // bf16 implicit-GEMM path (conv3_mfma.hip) vs direct fp32-FMA path
+    // first layer on the matrix cores (conv3_c1_fwd_mfma / conv3_mfma_wgrad_c1, taps are the K dimension).  Cin == 1 with
+    // Cout % 16 == 0 can only be block 0, half 0 of a one-channel network (every other layer reads >= 2 channels or writes as
+    // many as it reads), which is exactly where the input is the caller's fp32 tensor; never together with mfma (Cin % 16)
+    bool c1;
     // Deferred weight gradient (round 4): with an aux stream the layer's dy gets its OWN buffer (dyk) that stays alive, the
     // data-gradient chain runs the input-gradient conv alone, and the weight gradient is launched later on the aux stream.
     //   1 = decoder layer at a 16-wide-tile level (levels 0-1 at 96^3): runs under the latency-bound deep-level chain
@@ -129,6 +133,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             H.y = take((size_t)g.M() * cout * p.esz);
             H.stat = take((size_t)4 * cout * sizeof(float));
             H.mfma = p.dt == MI3D_BF16 && conv3_mfma_supported(H.Cin, H.Cout, 16, 16);
+            H.c1 = p.dt == MI3D_BF16 && H.Cin == 1 && H.Cout % 16 == 0;
             if (H.mfma) {
                 H.wpf = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
                 H.wpd = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
@@ -145,12 +150,11 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             H.bidx = 6 * b + 3 * h;
             H.drop_off = drop_off;
             drop_off += (int64_t)d->N * cout;
-            bool c1 = p.dt == MI3D_BF16 && H.Cin == 1 && H.Cout % 16 == 0;
-            if (c1) {
+            if (H.c1) {
                 size_t sp = (size_t)conv3_c1_fwd_stat_blocks(g) * 2 * cout;
                 if (sp > statpart_floats) statpart_floats = sp;
             }
-            size_t wf = (H.mfma || c1) ? conv3_mfma_wgrad_ws_floats(H.Cin, H.Cout, g) : conv3_direct_wgrad_ws_floats(H.Cin, H.Cout, g);
+            size_t wf = (H.mfma || H.c1) ? conv3_mfma_wgrad_ws_floats(H.Cin, H.Cout, g) : conv3_direct_wgrad_ws_floats(H.Cin, H.Cout, g);
             if (wf > wg_floats) wg_floats = wf;
             // the dy buffers are part of the layout whatever the route says (a route changed between the workspace query and a
             // launch must not move anything)
@@ -208,96 +212,139 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
     return 0;
 }
 
+// The weight-gradient slab sums that wait for a launch to ride in.  A launcher that is handed a slot leaves its final slab sum
+// there instead of launching it (nblocks > 0: a sum waits).  The rule, once:
+//   * a launch that writes the first slab workspace (wgws) takes `first`: older sums read their workspaces before it, with
+//     launches of their own;
+//   * the transposed conv's backward may take `carry` instead while the decoder conv's sum waits: it writes the SECOND
+//     workspace (wgws2) and both sums stay;
+//   * the next BatchNorm-backward reduction carries up to two (`riders`, then `rode` behind that launch);
+//   * an exchange mark is recorded behind the launch that carried its segment's sums (`rode`), or behind a flush when the
+//     segment launched no BatchNorm backward / the call ends (`finish`).
+struct Pending {
+    SlabJob pend, pend2;
+    hipEvent_t mark = nullptr;      // exchange mark waiting for the launch that completes its segment's gradients
+    static bool waits(const SlabJob& j) { return j.nblocks > 0; }
+    int flush(hipStream_t s) {
+        int rc = 0;
+        if (waits(pend)) { rc = slab_job_launch(pend, s); pend.nblocks = 0; }
+        if (waits(pend2)) { int r2 = slab_job_launch(pend2, s); pend2.nblocks = 0; if (!rc) rc = r2; }
+        return rc;
+    }
+    SlabJob* first(hipStream_t s) {      // where the launcher leaves its own slab sum instead of launching it
+        flush(s);
+        pend = SlabJob();
+        return &pend;
+    }
+    SlabJob* carry() {      // NULL: nothing to carry across, or the second slot is taken
+        if (!waits(pend) || waits(pend2)) return nullptr;
+        pend2 = SlabJob();
+        return &pend2;
+    }
+    void riders(const SlabJob*& extra, const SlabJob*& extra2) const {
+        extra = waits(pend) ? &pend : (waits(pend2) ? &pend2 : nullptr);
+        extra2 = (waits(pend) && waits(pend2)) ? &pend2 : nullptr;
+    }
+    int rode(hipStream_t s) {            // the sums `riders` handed out are in a launch on s
+        pend.nblocks = pend2.nblocks = 0;
+        if (mark) { MI3D_HIP(hipEventRecord(mark, s)); mark = nullptr; }
+        return 0;
+    }
+    int finish(hipStream_t s) {
+        MI3D_TRY(flush(s));
+        return rode(s);
+    }
+    // two marks on one launch cannot happen (one event per segment); an older mark still waiting means the segment in
+    // between launched no BatchNorm backward: complete it now
+    int set_mark(hipEvent_t ev, hipStream_t s) {
+        if (mark) MI3D_TRY(finish(s));
+        mark = ev;
+        return 0;
+    }
+};
+
+// the state of one C call
 struct Ctx {
     const Plan& p;
-    char* ws;
-    const void* const* params;
-    hipStream_t s;
+    char* ws = nullptr;
+    const void* const* params = nullptr;
+    hipStream_t s = nullptr;
     // optional second stream: the DEFERRED weight gradients (HalfP::defer) run there, off the data-gradient chain, behind
     // at most three forks per call (events 0..2) and one join (event 3); works eagerly and inside a hipGraph capture
     hipStream_t s2 = nullptr;
     hipEvent_t* ev = nullptr;
-    mutable int seq = 0;
+    int seq = 0;
     struct DJob { int b, h, wg_target; };
-    mutable DJob dq[4 * MAXL + 2];             // weight gradients whose dy is ready and that have not been forked yet
+    DJob dq[4 * MAXL + 2];             // weight gradients whose dy is ready and that have not been forked yet
     // forked (their event is recorded on the chain) but not yet ENQUEUED on the aux stream: the host enqueues them a few at a
     // time between the chain's next launches (drain_aux).  A step is launched by ONE host thread, and at the end of the
     // launch-bound deep-level chain it is barely ahead of the GPU: enqueueing the ten deep-level weight gradients and their slab
     // sums in one go left the chain's queue empty for ~125 us (profiles/r04_defer_eager_streams_before.txt)
     struct HJob { int b, h, wg_target, ev; };
-    mutable HJob hq[4 * MAXL + 2];
-    mutable int nhq = 0, hq_head = 0, waited_ev = -1;
-    mutable int ndq = 0, nfork = 0;
-    mutable bool aux_used = false;
-    mutable bool packed = false;      // weight packs already done by the one-launch pack_all
-    mutable bool tk_zeroed = false;   // this call's pack launch cleared the split-K ticket counters
+    HJob hq[4 * MAXL + 2];
+    int nhq = 0, hq_head = 0, waited_ev = -1;
+    int ndq = 0, nfork = 0;
+    bool aux_used = false;
+    bool tk_zeroed = false;   // this call's pack launch cleared the split-K ticket counters
     // training & 4: another forward runs beside this one on a second stream (DANN source || target): the wide BatchNorm consumers
     // (whole-CU 1024-thread workgroups) get in each other's way there (+45 us/step measured); thin consumers + finalize launches
-    mutable bool beside = false;
-    // one pending weight-gradient slab sum: it rides in the next BatchNorm-backward reduction launch (or is flushed
-    // with its own launch when another one arrives first / at the end of the call)
-    mutable SlabJob pend;
-    mutable bool has_pend = false;
-    // a second pending sum (reading the SECOND slab workspace): the decoder conv's sum stays pending across the transposed
-    // conv's backward launch, and the next BatchNorm-backward reduction carries both
-    mutable SlabJob pend2;
-    mutable bool has_pend2 = false;
+    bool beside = false;
+    Pending pending;
     // the input gradient of a block's first conv (= the gradient of the pooled tensor one level up) left as split-K partials for
     // the MaxPool3d backward of the next segment to finish (no splitk_finish launch); pool_defer: the caller allows it
-    mutable int pool_ks = 0;
-    mutable bool pool_defer = false;
-    mutable hipEvent_t mark_pending = nullptr;      // exchange mark waiting for the launch that completes its segment's gradients
-    // called before ANY launch that writes the (single) slab workspace: an older pending sum must read it first.
-    // Returns where the launcher leaves its own slab sum instead of launching it
-    SlabJob* pend_slot() const {
-        if (has_pend) { slab_job_launch(pend, s); has_pend = false; }
-        if (has_pend2) { slab_job_launch(pend2, s); has_pend2 = false; }
-        pend = SlabJob();
-        return &pend;
-    }
-    void pend_filled() const { has_pend = pend.nblocks > 0; }
-    int flush_pend() const {
-        int rc = 0;
-        if (has_pend) { rc = slab_job_launch(pend, s); has_pend = false; }
-        if (has_pend2) { int r2 = slab_job_launch(pend2, s); has_pend2 = false; if (!rc) rc = r2; }
-        return rc;
-    }
+    int pool_ks = 0;
+    bool pool_defer = false;
     template <typename T = void> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
     const float* P(int i) const { return reinterpret_cast<const float*>(params[i]); }
 };
 
-// input tensor of block b: pointer, channel stride, dtype
-void block_input(const Ctx& c, int b, const float* x, const void*& ptr, int& cs, int& dt) {
-    const Plan& p = c.p;
-    dt = p.dt;
-    if (b == 0) {
-        if (p.d.in_channels == 1) { ptr = x; cs = 1; dt = MI3D_F32; }
-        else { ptr = c.at(p.xcl); cs = p.d.in_channels; }
-    } else if (b <= p.L) { ptr = c.at(p.pool[b - 1]); cs = p.C[b - 1]; }
-    else { int l = p.blk[b].level; ptr = c.at(p.cat[l]); cs = p.catcs(l); }
+// The one way into a call that launches: plan, pointers, workspace size and alignment.  `fn` is the public function the
+// caller used, `ptrs` whether the pointers only that function takes are all there.
+int enter(Ctx& c, Plan& p, const mi3d_unet_desc* d, const char* fn, bool ptrs, const void* const* params, void* workspace,
+          size_t workspace_bytes, void* stream) {
+    MI3D_TRY(build_plan(d, p));
+    MI3D_CHECK_ARG(ptrs && params && workspace, "%s: null pointer", fn);
+    MI3D_CHECK_ARG(workspace_bytes >= p.total, "workspace too small: %zu < %zu", workspace_bytes, p.total);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    c.ws = (char*)workspace;
+    c.params = params;
+    c.s = (hipStream_t)stream;
+    return 0;
 }
-// output tensor (z2) of block b
-void block_output(const Ctx& c, int b, void*& ptr, int& cs) {
+
+// What one conv layer (block b, half h) reads and writes; its route class is H.mfma / H.c1.  x = the network's input.
+struct LayerIO {
+    const HalfP& H;
+    Geo g;
+    const void* in; int ics, idt;     // input tensor: pointer, channel stride, dtype
+    void* out; int ocs;               // activated output (z1 of the block for half 0, the block's output for half 1)
+    Halves ih;                        // planes of the input: on() only for half 0 of a decoder block at a planar level
+};
+LayerIO layer_io(const Ctx& c, int b, int h, const float* x) {
     const Plan& p = c.p;
-    if (b < p.L) { ptr = c.at(p.cat[b]); cs = p.catcs(b); }
-    else if (b == p.L) { ptr = c.at(p.zb); cs = p.C[p.L]; }
-    else { ptr = c.at(p.zd[b - p.L - 1]); cs = p.C[p.blk[b].level]; }
+    const BlockP& B = p.blk[b];
+    const HalfP& H = B.h[h];
+    const int l = B.level;
+    LayerIO v{H, p.geo[l], c.at(B.z1), H.Cout, p.dt, c.at(B.z1), H.Cout, Halves()};
+    if (h == 1) {
+        if (b < p.L) { v.out = c.at(p.cat[b]); v.ocs = p.catcs(b); }
+        else v.out = c.at(b == p.L ? p.zb : p.zd[b - p.L - 1]);
+    } else if (b == 0) {
+        if (p.d.in_channels == 1) { v.in = x; v.ics = 1; v.idt = MI3D_F32; }
+        else { v.in = c.at(p.xcl); v.ics = p.d.in_channels; }
+    } else if (b <= p.L) { v.in = c.at(p.pool[b - 1]); v.ics = p.C[b - 1]; }
+    else { v.in = c.at(p.cat[l]); v.ics = p.catcs(l); v.ih = p.halves(l); }
+    return v;
 }
 
 // pooled != NULL (encoder blocks on even volumes): the second apply pass also writes MaxPool3d(2,2) of the block output
-int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, const float* drop, int training,
+int block_forward(Ctx& c, int b, const float* x, void* const* buffers, const float* drop, int training,
                   void* pooled = nullptr, int pcs = 0) {
     const Plan& p = c.p;
-    const BlockP& B = p.blk[b];
-    Geo g = p.geo[B.level];
-    const void* xin; int xcs, xdt;
-    block_input(c, b, x, xin, xcs, xdt);
-    void* zout; int zcs;
-    block_output(c, b, zout, zcs);
     for (int h = 0; h < 2; h++) {
-        const HalfP& H = B.h[h];
-        const void* in = h == 0 ? xin : c.at(B.z1);
-        int ics = h == 0 ? xcs : H.Cout, idt = h == 0 ? xdt : p.dt;
+        const LayerIO v = layer_io(c, b, h, x);
+        const HalfP& H = v.H;
+        const Geo g = v.g;
         float* rm = buffers ? (float*)buffers[H.bidx] : nullptr;
         float* rv = buffers ? (float*)buffers[H.bidx + 1] : nullptr;
         int64_t* nbt = buffers ? (int64_t*)buffers[H.bidx + 2] : nullptr;
@@ -305,29 +352,26 @@ int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, con
         const float mom = training == 2 ? -1.f : p.d.bn_momentum;
         if (training == 2) { rv = nullptr; nbt = nullptr; }
         bool fused_stats = false;
-        void* zo = h == 0 ? c.at(B.z1) : zout;
-        int zocs = h == 0 ? H.Cout : zcs;
         int ksd = 0, c1_blocks = 0;
         if (H.mfma) {
-            if (!c.packed) MI3D_TRY(conv3_mfma_pack(c.P(H.pidx), H.Cin, H.Cout, c.at(H.wpf), c.at(H.wpd), g, c.s));
             // training: a split-K launch leaves its finishing pass to the statistics kernel (ksd = split factor).  (Deep levels
             // WITHOUT split-K -- conv with fused partial sums -> apply, two launches instead of three -- measured +0.10 ms in
             // round 2: the 8-16-chunk K loops on 32-216 workgroups cost more than the launch they save; that route is gone.)
             // round 4: a split-K launch of a training forward finishes itself behind a per-tile ticket (y, BatchNorm partial rows)
             const bool tk = training && c.tk_zeroed && conv3_mfma_ticket_ok(H.Cin, H.Cout, g);
-            MI3D_TRY(conv3_mfma_fwd(in, ics, H.Cin, c.at(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
-                                    training ? c.at<float>(p.statpart) : nullptr, c.at<float>(p.skws), c.s,
-                                    (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), Halves(), training ? &ksd : nullptr, 0, 0,
-                                    tk ? c.at<float>(p.statpart) : nullptr, tk ? c.at<int>(p.tkcount) : nullptr));
+            MI3D_TRY(conv3_mfma_fwd(v.in, v.ics, H.Cin, c.at(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
+                                    training ? c.at<float>(p.statpart) : nullptr, c.at<float>(p.skws), c.s, v.ih, Halves(),
+                                    training ? &ksd : nullptr, 0, 0, tk ? c.at<float>(p.statpart) : nullptr,
+                                    tk ? c.at<int>(p.tkcount) : nullptr));
             fused_stats = training && (tk || conv3_mfma_fuses_stats(H.Cin, H.Cout, g));
-        } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0) {
-            // first layer on the matrix cores (taps are the K dimension), BN partial sums fused like the other convs
-            MI3D_TRY(conv3_c1_fwd_mfma((const float*)in, c.P(H.pidx), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
+        } else if (H.c1) {
+            // BN partial sums fused like the other convs
+            MI3D_TRY(conv3_c1_fwd_mfma((const float*)v.in, c.P(H.pidx), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
                                        training ? c.at<float>(p.statpart) : nullptr, c.s));
             if (training) { fused_stats = true; c1_blocks = conv3_c1_fwd_stat_blocks(g); }
         } else {
             MI3D_TRY(conv3_direct_pack(c.P(H.pidx), H.Cin, H.Cout, c.at<float>(H.wpf), c.at<float>(H.wpd), c.s));
-            MI3D_TRY(conv3_direct_fwd(idt, p.dt, in, ics, H.Cin, c.at<float>(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout,
+            MI3D_TRY(conv3_direct_fwd(v.idt, p.dt, v.in, v.ics, H.Cin, c.at<float>(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout,
                                       H.Cout, g, c.s));
         }
         int small_rows = 0;      // deep levels: the statistics' few partial rows are finished by the apply kernel (no finalize launch)
@@ -358,36 +402,27 @@ int block_forward(const Ctx& c, int b, const float* x, void* const* buffers, con
         BnSmall sm{rows_at, small_rows, c.P(H.pidx + 2), c.P(H.pidx + 3), rm, rv, nbt, mom, p.d.bn_eps};
         if (h == 1 && pooled)
             MI3D_TRY(bn_apply_relu_drop_pool(p.dt, c.at(H.y), H.Cout, H.Cout, g, c.at<float>(H.stat),
-                                             (drop && training) ? drop + H.drop_off : nullptr, zo, zocs, pooled, pcs, c.s,
+                                             (drop && training) ? drop + H.drop_off : nullptr, v.out, v.ocs, pooled, pcs, c.s,
                                              small_rows > 0 ? &sm : nullptr));
         else
             MI3D_TRY(bn_apply_relu_drop(p.dt, c.at(H.y), H.Cout, H.Cout, g.M(), g.V(), c.at<float>(H.stat),
-                                        (drop && training) ? drop + H.drop_off : nullptr, zo, zocs, c.s, small_rows > 0 ? &sm : nullptr));
+                                        (drop && training) ? drop + H.drop_off : nullptr, v.out, v.ocs, c.s, small_rows > 0 ? &sm : nullptr));
     }
     return 0;
 }
 
-// Launch the queued weight gradients on the aux stream, ordered after everything the compute stream has enqueued so far
-// (their dy buffers are complete).  They run one after the other there, each followed by its slab sum, sharing the third
-// slab workspace; nothing on the compute stream waits for them before the end of the step (unet_backward_impl joins).
 // enqueue up to `n` forked weight gradients on the aux stream (n < 0: all).  Each runs after the fork event of its group, one
 // after the other there, followed by its slab sum, sharing the third slab workspace; nothing on the compute stream waits for
 // them before the end of the step (unet_backward_impl joins).
-int drain_aux(const Ctx& c, const float* x, void* const* grads, int accumulate, int n) {
+int drain_aux(Ctx& c, const float* x, void* const* grads, int accumulate, int n) {
     const Plan& p = c.p;
     for (; c.hq_head < c.nhq && n != 0; c.hq_head++, n--) {
         const Ctx::HJob& j = c.hq[c.hq_head];
         if (j.ev != c.waited_ev) { MI3D_HIP(hipStreamWaitEvent(c.s2, c.ev[j.ev % 3], 0)); c.waited_ev = j.ev; }
-        const BlockP& B = p.blk[j.b];
-        const HalfP& H = B.h[j.h];
-        Geo g = p.geo[B.level];
-        const void* xin; int xcs, xdt;
-        block_input(c, j.b, x, xin, xcs, xdt);
-        const void* in = j.h == 0 ? xin : c.at(B.z1);
-        int ics = j.h == 0 ? xcs : H.Cout;
-        MI3D_TRY(conv3_mfma_wgrad(in, ics, H.Cin, c.at(H.dyk), H.Cout, H.Cout, g, (float*)grads[H.pidx], (float*)grads[H.pidx + 1], accumulate,
-                                  c.at<float>(p.wgws3), p.wgws_floats, c.s2, (j.h == 0 && j.b > p.L) ? p.halves(B.level) : Halves(), nullptr,
-                                  j.wg_target));
+        const LayerIO v = layer_io(c, j.b, j.h, x);
+        const HalfP& H = v.H;
+        MI3D_TRY(conv3_mfma_wgrad(v.in, v.ics, H.Cin, c.at(H.dyk), H.Cout, H.Cout, v.g, (float*)grads[H.pidx], (float*)grads[H.pidx + 1],
+                                  accumulate, c.at<float>(p.wgws3), p.wgws_floats, c.s2, v.ih, nullptr, j.wg_target));
         c.aux_used = true;
     }
     if (c.hq_head == c.nhq) c.hq_head = c.nhq = 0;
@@ -396,7 +431,7 @@ int drain_aux(const Ctx& c, const float* x, void* const* grads, int accumulate, 
 
 // Fork: the queued weight gradients may start once everything the compute stream has enqueued so far is done (their dy
 // buffers are complete).  lazy: only the event is recorded here, the launches are enqueued by later drain_aux calls.
-int flush_deferred(const Ctx& c, const float* x, void* const* grads, int accumulate, bool lazy = false) {
+int flush_deferred(Ctx& c, const float* x, void* const* grads, int accumulate, bool lazy = false) {
     if (c.ndq == 0) return 0;
     MI3D_CHECK_ARG(c.nfork < 3, "flush_deferred: more than three forks in one call");
     const int e = c.nfork++;
@@ -408,42 +443,54 @@ int flush_deferred(const Ctx& c, const float* x, void* const* grads, int accumul
 }
 
 // backward of block b given dz2 (dtype T, stride dzcs); writes dxin (may be NULL) with stride dxcs
-int block_backward(const Ctx& c, int b, const float* x, void* const* grads, const float* drop, const void* dz2,
+int block_backward(Ctx& c, int b, const float* x, void* const* grads, const float* drop, const void* dz2,
                    int dzcs, void* dxin, int dxcs, int accumulate) {
     const Plan& p = c.p;
-    const BlockP& B = p.blk[b];
-    Geo g = p.geo[B.level];
-    const void* xin; int xcs, xdt;
-    block_input(c, b, x, xin, xcs, xdt);
     auto G = [&](int i) { return grads ? (float*)grads[i] : nullptr; };
     const bool aux = c.s2 != nullptr && c.ev != nullptr;
-    const float* dz_skp = nullptr;      // dz of half 0 left as split-K partials by half 1's fused backward launch
+    float* const skws = c.at<float>(p.skws);
+    const float* dz_skp = nullptr;      // dz of half 0 left as split-K partials by half 1's input gradient
     int dz_ks = 0;
     for (int h = 1; h >= 0; h--) {
-        const HalfP& H = B.h[h];
+        const LayerIO v = layer_io(c, b, h, x);
+        const HalfP& H = v.H;
+        const Geo g = v.g;
         int k = c.seq++;
         if (aux && c.nhq) MI3D_TRY(drain_aux(c, x, grads, accumulate, 3));      // feed the aux stream between the chain's launches
+        const bool wg = G(H.pidx) || G(H.pidx + 1);
         // deferred weight gradient: dy goes to the layer's own buffer, which nobody overwrites before the aux stream has read it
-        const bool dfr = aux && H.defer && (G(H.pidx) || G(H.pidx + 1));
+        const bool dfr = aux && H.defer && wg;
         void* dyb = dfr ? c.at(H.dyk) : c.at((k & 1) ? p.sB2 : p.sB);
         const void* dz = h == 1 ? dz2 : c.at(p.sC);
         int dcs = h == 1 ? dzcs : H.Cout;
-        const void* in = h == 0 ? xin : c.at(B.z1);
-        int ics = h == 0 ? xcs : H.Cout, idt = h == 0 ? xdt : p.dt;
-        void* dx_f = h == 1 ? c.at(p.sC) : dxin;
-        int dxs_f = h == 1 ? H.Cin : dxcs;
+        void* dx = h == 1 ? c.at(p.sC) : dxin;
+        int dxs = h == 1 ? H.Cin : dxcs;
+        // the layer's input gradient as a launch of its own.  ksd != NULL: a split-K result may stay as partials (see below)
+        auto dgrad = [&](int* ksd) {
+            if (!H.mfma) return conv3_direct_fwd(p.dt, p.dt, dyb, H.Cout, H.Cout, c.at<float>(H.wpd), nullptr, dx, dxs, H.Cin, g, c.s);
+            return conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx, dxs, H.Cin, g, nullptr, (dxs % 8 == 0) ? skws : nullptr,
+                                  c.s, Halves(), v.ih, ksd, 0, CONV3_BWD_SPLITK_TARGET);
+        };
+        // half 1's input gradient feeds straight into half 0's BatchNorm-backward reduction, half 0's into the MaxPool3d backward of
+        // the next segment (pool_defer): a split-K result stays as partials and that launch finishes it (one launch less on the
+        // chain).  The launch reports its split factor in ksd (0 = dx was written as usual), filed for whoever reads the partials
+        int ksd = 0;
+        int* const ksp = (h == 1 || c.pool_defer) && dxs % 8 == 0 && !mi3d_routes().no_defer_tail ? &ksd : nullptr;
+        auto file_partials = [&] {
+            if (ksd > 0 && h == 1) { dz_skp = skws; dz_ks = ksd; }
+            if (ksd > 0 && h == 0) c.pool_ks = ksd;
+        };
+        const SlabJob *extra, *extra2;
+        c.pending.riders(extra, extra2);
         MI3D_TRY(bn_bwd(p.dt, dz, dcs, c.at(H.y), H.Cout, H.Cout, g.M(), g.V(), c.at<float>(H.stat),
                         drop ? drop + H.drop_off : nullptr, dyb, H.Cout, G(H.pidx + 2), G(H.pidx + 3), accumulate,
-                        c.at<float>(p.bnws), c.s, c.has_pend ? &c.pend : (c.has_pend2 ? &c.pend2 : nullptr), h == 0 ? dz_skp : nullptr,
-                        h == 0 ? dz_ks : 0, (c.has_pend && c.has_pend2) ? &c.pend2 : nullptr));
-        c.has_pend = false;
-        c.has_pend2 = false;
-        if (c.mark_pending) { MI3D_HIP(hipEventRecord(c.mark_pending, c.s)); c.mark_pending = nullptr; }      // the slab sums of the marked segment rode in this launch
+                        c.at<float>(p.bnws), c.s, extra, h == 0 ? dz_skp : nullptr, h == 0 ? dz_ks : 0, extra2));
+        MI3D_TRY(c.pending.rode(c.s));
         if (dfr) {
             // the chain runs the input-gradient conv alone; the weight gradient is queued for the aux stream.  Its slab partition
             // is the fused launch's (conv3_mfma_bwd_wg_target), the input gradient uses the fused launch's split-K factor and the
             // same K order: both routes produce the same bits
-            c.dq[c.ndq++] = Ctx::DJob{b, h, conv3_mfma_bwd_wg_target(H.Cin, H.Cout, ics, H.Cout, dx_f ? dxs_f : 8, g)};
+            c.dq[c.ndq++] = Ctx::DJob{b, h, conv3_mfma_bwd_wg_target(H.Cin, H.Cout, v.ics, H.Cout, dx ? dxs : 8, g)};
         }
         // fork points: what is queued goes to the aux stream when the chain has finished the last layer of a group (its BatchNorm
         // backward).  Group 1 forks when the GPU is still busy with the full-resolution decoder (the host is far ahead: enqueue at
@@ -455,67 +502,35 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
             for (int q = 0; q < 2; q++)
                 if (b == p.flush_b[q] && h == p.flush_h[q]) MI3D_TRY(flush_deferred(c, x, grads, accumulate, q == 1));
         if (dfr) {
-            if (dx_f) {
-                const bool to_pool = h == 0 && c.pool_defer && dx_f == dxin;
-                const bool defer = (h == 1 || to_pool) && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
-                int ksd = 0;
-                MI3D_TRY(conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx_f, dxs_f, H.Cin, g, nullptr,
-                                        (dxs_f % 8 == 0) ? c.at<float>(p.skws) : nullptr, c.s, Halves(),
-                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), defer ? &ksd : nullptr, 0, CONV3_BWD_SPLITK_TARGET));
-                if (ksd > 0 && h == 1) { dz_skp = c.at<float>(p.skws); dz_ks = ksd; }
-                if (ksd > 0 && h == 0) c.pool_ks = ksd;
-            }
+            if (dx) { MI3D_TRY(dgrad(ksp)); file_partials(); }
             continue;
         }
-        if (H.mfma && dx_f && (G(H.pidx) || G(H.pidx + 1)) && conv3_mfma_bwd_fused_persist_ok(H.Cin, H.Cout, ics, H.Cout, g)) {
-            Halves hv = (h == 0 && b > p.L) ? p.halves(B.level) : Halves();
-            SlabJob* ps = c.pend_slot();
-            MI3D_TRY(conv3_mfma_bwd_fused_persist(in, ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx_f, dxs_f, g, G(H.pidx),
-                                                  G(H.pidx + 1), accumulate, c.at<float>(p.wgws), p.wgws_floats, c.s, hv, hv, ps));
-            c.pend_filled();
+        if (H.mfma && dx && wg && conv3_mfma_bwd_fused_persist_ok(H.Cin, H.Cout, v.ics, H.Cout, g)) {
+            MI3D_TRY(conv3_mfma_bwd_fused_persist(v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx, dxs, g, G(H.pidx),
+                                                  G(H.pidx + 1), accumulate, c.at<float>(p.wgws), p.wgws_floats, c.s, v.ih, v.ih,
+                                                  c.pending.first(c.s)));
             continue;
         }
-        if (H.mfma && dx_f && (G(H.pidx) || G(H.pidx + 1)) && !(h == 0 && b > p.L && p.planar[B.level]) &&
-            conv3_mfma_bwd_fused_ok(H.Cin, H.Cout, ics, H.Cout, dxs_f, g)) {
-            SlabJob* ps = c.pend_slot();
-            // half 1's input gradient feeds straight into half 0's BatchNorm-backward reduction: leave a split-K result as
-            // partials and let that reduction finish it (one launch less on the chain)
-            const bool to_pool = h == 0 && c.pool_defer && dx_f == dxin;
-            bool defer = (h == 1 || to_pool) && dxs_f % 8 == 0 && !mi3d_routes().no_defer_tail;
-            int ksd = 0;
-            MI3D_TRY(conv3_mfma_bwd_fused(in, ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx_f, dxs_f, g, G(H.pidx), G(H.pidx + 1),
-                                          accumulate, c.at<float>(p.wgws), p.wgws_floats, c.at<float>(p.skws), c.s, ps,
-                                          defer ? &ksd : nullptr));
-            if (ksd > 0 && h == 0) { c.pool_ks = ksd; ksd = 0; }
-            c.pend_filled();
-            if (ksd > 0) { dz_skp = c.at<float>(p.skws); dz_ks = ksd; }
+        if (H.mfma && dx && wg && !v.ih.on() && conv3_mfma_bwd_fused_ok(H.Cin, H.Cout, v.ics, H.Cout, dxs, g)) {
+            MI3D_TRY(conv3_mfma_bwd_fused(v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx, dxs, g, G(H.pidx), G(H.pidx + 1),
+                                          accumulate, c.at<float>(p.wgws), p.wgws_floats, skws, c.s, c.pending.first(c.s), ksp));
+            file_partials();
             continue;
         }
-        if (G(H.pidx) || G(H.pidx + 1)) {
-            hipStream_t ws_ = c.s;
+        if (wg) {
             float* wgws = c.at<float>(p.wgws);
-            SlabJob* ps = c.pend_slot();
+            SlabJob* ps = c.pending.first(c.s);
             if (H.mfma)
-                MI3D_TRY(conv3_mfma_wgrad(in, ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
-                                          wgws, p.wgws_floats, ws_, (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), ps));
-            else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0)
-                MI3D_TRY(conv3_mfma_wgrad_c1((const float*)in, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
-                                             wgws, p.wgws_floats, ws_, ps));
+                MI3D_TRY(conv3_mfma_wgrad(v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
+                                          wgws, p.wgws_floats, c.s, v.ih, ps));
+            else if (H.c1)
+                MI3D_TRY(conv3_mfma_wgrad_c1((const float*)v.in, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
+                                             wgws, p.wgws_floats, c.s, ps));
             else
-                MI3D_TRY(conv3_direct_wgrad(idt, p.dt, in, ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1),
-                                            accumulate, wgws, p.wgws_floats, ws_));
-            c.pend_filled();
+                MI3D_TRY(conv3_direct_wgrad(v.idt, p.dt, v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1),
+                                            accumulate, wgws, p.wgws_floats, c.s));
         }
-        void* dx = h == 1 ? c.at(p.sC) : dxin;
-        int dxs = h == 1 ? H.Cin : dxcs;
-        if (dx) {
-            if (H.mfma)
-                MI3D_TRY(conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx, dxs, H.Cin, g, nullptr,
-                                        (dxs % 8 == 0) ? c.at<float>(p.skws) : nullptr, c.s, Halves(),
-                                        (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), nullptr, 0, CONV3_BWD_SPLITK_TARGET));
-            else
-                MI3D_TRY(conv3_direct_fwd(p.dt, p.dt, dyb, H.Cout, H.Cout, c.at<float>(H.wpd), nullptr, dx, dxs, H.Cin, g, c.s));
-        }
+        if (dx) MI3D_TRY(dgrad(nullptr));
     }
     return 0;
 }
@@ -523,33 +538,76 @@ int block_backward(const Ctx& c, int b, const float* x, void* const* grads, cons
 // inference forward of block b: BatchNorm (running statistics) folded into the conv (scale in the packed filter, bias
 // replaced), ReLU in the conv epilogue, output written straight to where the activated tensor lives -- no raw conv
 // output, no statistics, no separate normalisation pass.  stat[0..C) = scale, stat[C..2C) = folded bias (bn_fold_all).
-int block_infer(const Ctx& c, int b, const float* x) {
+int block_infer(Ctx& c, int b, const float* x) {
     const Plan& p = c.p;
-    const BlockP& B = p.blk[b];
-    Geo g = p.geo[B.level];
-    const void* xin; int xcs, xdt;
-    block_input(c, b, x, xin, xcs, xdt);
-    void* zout; int zcs;
-    block_output(c, b, zout, zcs);
     for (int h = 0; h < 2; h++) {
-        const HalfP& H = B.h[h];
-        const void* in = h == 0 ? xin : c.at(B.z1);
-        int ics = h == 0 ? xcs : H.Cout, idt = h == 0 ? xdt : p.dt;
-        void* zo = h == 0 ? c.at(B.z1) : zout;
-        int zocs = h == 0 ? H.Cout : zcs;
+        const LayerIO v = layer_io(c, b, h, x);
+        const HalfP& H = v.H;
         const float* scale = c.at<float>(H.stat);
         const float* fbias = scale + H.Cout;
         if (H.mfma) {
-            MI3D_TRY(conv3_mfma_fwd(in, ics, H.Cin, c.at(H.wpf), fbias, zo, zocs, H.Cout, g, nullptr,
-                                    (zocs % 8 == 0 && ((uintptr_t)zo % 16) == 0) ? c.at<float>(p.skws) : nullptr, c.s,
-                                    (h == 0 && b > p.L) ? p.halves(B.level) : Halves(), Halves(), nullptr, 1));
-        } else if (p.dt == MI3D_BF16 && idt == MI3D_F32 && H.Cin == 1 && H.Cout % 16 == 0) {
-            MI3D_TRY(conv3_c1_fwd_mfma((const float*)in, c.P(H.pidx), fbias, zo, zocs, H.Cout, g, nullptr, c.s, scale, 1));
+            MI3D_TRY(conv3_mfma_fwd(v.in, v.ics, H.Cin, c.at(H.wpf), fbias, v.out, v.ocs, H.Cout, v.g, nullptr,
+                                    (v.ocs % 8 == 0 && ((uintptr_t)v.out % 16) == 0) ? c.at<float>(p.skws) : nullptr, c.s,
+                                    v.ih, Halves(), nullptr, 1));
+        } else if (H.c1) {
+            MI3D_TRY(conv3_c1_fwd_mfma((const float*)v.in, c.P(H.pidx), fbias, v.out, v.ocs, H.Cout, v.g, nullptr, c.s, scale, 1));
         } else {
             MI3D_TRY(conv3_direct_pack(c.P(H.pidx), H.Cin, H.Cout, c.at<float>(H.wpf), nullptr, c.s, scale));
-            MI3D_TRY(conv3_direct_fwd(idt, p.dt, in, ics, H.Cin, c.at<float>(H.wpf), fbias, zo, zocs, H.Cout, g, c.s, 1));
+            MI3D_TRY(conv3_direct_fwd(v.idt, p.dt, v.in, v.ics, H.Cin, c.at<float>(H.wpf), fbias, v.out, v.ocs, H.Cout, v.g, c.s, 1));
         }
     }
+    return 0;
+}
+
+// Every MFMA weight image of the network (DoubleConv blocks, transposed convs) as jobs of ONE launch.  fold_scale (inference):
+// the BatchNorm scale bn_fold_all leaves in stat[0..C) is multiplied into the forward images
+int add_pack_jobs(const Ctx& c, PackJobs& J, bool fold_scale) {
+    const Plan& p = c.p;
+    for (int b = 0; b < p.nblk; b++)
+        for (int h = 0; h < 2; h++) {
+            const HalfP& H = p.blk[b].h[h];
+            if (H.mfma)
+                MI3D_TRY(pack_all_add_conv3(J, c.P(H.pidx), H.Cin, H.Cout, c.at(H.wpf), c.at(H.wpd), p.geo[p.blk[b].level],
+                                            fold_scale ? c.at<float>(H.stat) : nullptr));
+        }
+    for (int i = 0; i < p.L; i++) {
+        int l = p.L - 1 - i;
+        if (p.up_mfma[i]) MI3D_TRY(pack_all_add_upconv(J, c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], c.at(p.upw[i])));
+    }
+    return 0;
+}
+
+// Decoder step i (level l = L-1-i): the transposed conv takes the block below (2C channels at level l + 1) to the up half of
+// cat[l]; its backward takes the up half of gcat[l] back
+struct UpIO {
+    int l, Cin, Cout;
+    Geo g;                       // INPUT geometry
+    const void* in;
+    float* w; float* wb;         // packed weights: the MFMA image or the direct forward image / the direct backward image
+    size_t half; int cs;         // bytes to the up half of cat[l] and gcat[l] / their channel stride
+};
+UpIO up_io(const Ctx& c, int i) {
+    const Plan& p = c.p;
+    const int l = p.L - 1 - i, C = p.C[l];
+    float* w = c.at<float>(p.upw[i]);
+    return UpIO{l, 2 * C, C, p.geo[l + 1], c.at(i == 0 ? p.zb : p.zd[i - 1]), w, w + (size_t)cdiv(C, 8) * (2 * C) * 64,
+                p.half_off(l), p.catcs(l)};
+}
+// forward of decoder step i, with the nearest resize where resize[l] (training and inference)
+int up_forward(Ctx& c, int i) {
+    const Plan& p = c.p;
+    const UpIO u = up_io(c, i);
+    char* up = c.at<char>(p.cat[u.l]) + u.half;
+    const bool rs = p.resize[u.l];
+    void* dst = rs ? c.at(p.uptmp) : (void*)up;
+    int dcs = rs ? u.Cout : u.cs;
+    if (p.up_mfma[i]) {
+        MI3D_TRY(upconv2_mfma_fwd(u.in, u.Cin, u.Cin, u.w, c.P(p.up_pidx(i) + 1), dst, dcs, u.Cout, u.g, c.s));
+    } else {
+        MI3D_TRY(upconv2_pack(c.P(p.up_pidx(i)), u.Cin, u.Cout, u.w, u.wb, c.s));
+        MI3D_TRY(upconv2_fwd(p.dt, u.in, u.Cin, u.Cin, u.w, c.P(p.up_pidx(i) + 1), dst, dcs, u.Cout, u.g, c.s));
+    }
+    if (rs) MI3D_TRY(nearest_resize_fwd(p.dt, dst, dcs, u.Cout, p.up_geo(u.l), up, u.cs, p.geo[u.l], c.s));
     return 0;
 }
 
@@ -607,42 +665,25 @@ static LossCfg cfg_of(const mi3d_loss_cfg* c) {
     return k;
 }
 
-// MFMA weight images of the DoubleConv blocks and the transposed convs of the training forward / backward, one launch
-static int pack_training_weights(const Ctx& c, bool zero_tickets) {
-    const Plan& p = c.p;
-    PackJobs J;
-    J.n = 0; J.nblocks = 0;
-    if (zero_tickets) { J.zero = c.at<int>(p.tkcount); J.nzero = CONV3_TK_COUNTERS; }
-    for (int b = 0; b < p.nblk; b++)
-        for (int h = 0; h < 2; h++) {
-            const HalfP& H = p.blk[b].h[h];
-            if (H.mfma) MI3D_TRY(pack_all_add_conv3(J, c.P(H.pidx), H.Cin, H.Cout, c.at(H.wpf), c.at(H.wpd), p.geo[p.blk[b].level]));
-        }
-    for (int i = 0; i < p.L; i++) {
-        int l = p.L - 1 - i;
-        if (p.up_mfma[i]) MI3D_TRY(pack_all_add_upconv(J, c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], c.at(p.upw[i])));
-    }
-    if (zero_tickets && J.n > 0) c.tk_zeroed = true;      // (pack_all_launch launches nothing for an empty job list)
-    return pack_all_launch(J, c.s);
-}
-
 static int unet_forward_impl(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
                       const float* drop_scales, int training, float* logits, float* gap_out, void* workspace,
                       size_t workspace_bytes, void* stream, const HeadLoss* hl) {
     Plan p;
-    MI3D_TRY(build_plan(d, p));
-    MI3D_CHECK_ARG(x && params && workspace, "mi3d_unet_forward: null pointer");
-    MI3D_CHECK_ARG(workspace_bytes >= p.total, "workspace too small: %zu < %zu", workspace_bytes, p.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    Ctx c{p, (char*)workspace, params, (hipStream_t)stream};
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_forward", x != nullptr, params, workspace, workspace_bytes, stream));
     c.beside = (training & 4) != 0;
     training &= 3;
     int L = p.L;
     if (d->in_channels > 1)
         MI3D_TRY(ncdhw_to_ndhwc(p.dt, x, c.at(p.xcl), d->in_channels, d->in_channels, d->N, p.geo[0].V(), c.s));
-    // every MFMA weight pack of the network in one launch
-    MI3D_TRY(pack_training_weights(c, training != 0));
-    c.packed = true;
+    {   // every MFMA weight pack of the network in one launch, which also clears the split-K ticket counters of a training forward
+        PackJobs J;
+        J.n = 0; J.nblocks = 0;
+        if (training) { J.zero = c.at<int>(p.tkcount); J.nzero = CONV3_TK_COUNTERS; }
+        MI3D_TRY(add_pack_jobs(c, J, false));
+        if (training && J.n > 0) c.tk_zeroed = true;      // (pack_all_launch launches nothing for an empty job list)
+        MI3D_TRY(pack_all_launch(J, c.s));
+    }
     for (int l = 0; l < L; l++) {
         // fused apply + pool: even sides (every voxel in exactly one window) and 32-bit element indices
         const bool even = p.geo[l].D % 2 == 0 && p.geo[l].H % 2 == 0 && p.geo[l].W % 2 == 0 &&
@@ -653,23 +694,7 @@ static int unet_forward_impl(const mi3d_unet_desc* d, const float* x, const void
     MI3D_TRY(block_forward(c, L, x, buffers, drop_scales, training));
     if (gap_out) MI3D_TRY(gap_fwd(p.dt, c.at(p.zb), p.C[L], p.C[L], d->N, p.geo[L].V(), gap_out, c.s));
     for (int i = 0; i < L; i++) {
-        int l = L - 1 - i;
-        float* wf = c.at<float>(p.upw[i]);
-        float* wb = wf + (size_t)cdiv(p.C[l], 8) * (2 * p.C[l]) * 64;
-        const void* uin = i == 0 ? c.at(p.zb) : c.at(p.zd[i - 1]);
-        char* catl = c.at<char>(p.cat[l]);
-        void* udst = p.resize[l] ? c.at(p.uptmp) : (void*)(catl + p.half_off(l));
-        int udcs = p.resize[l] ? p.C[l] : p.catcs(l);
-        if (p.up_mfma[i]) {
-            if (!c.packed) MI3D_TRY(upconv2_mfma_pack(c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], c.at(p.upw[i]), c.s));
-            MI3D_TRY(upconv2_mfma_fwd(uin, 2 * p.C[l], 2 * p.C[l], c.at(p.upw[i]), c.P(p.up_pidx(i) + 1),
-                                      udst, udcs, p.C[l], p.geo[l + 1], c.s));
-        } else {
-            MI3D_TRY(upconv2_pack(c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], wf, wb, c.s));
-            MI3D_TRY(upconv2_fwd(p.dt, uin, 2 * p.C[l], 2 * p.C[l], wf, c.P(p.up_pidx(i) + 1), udst, udcs, p.C[l], p.geo[l + 1], c.s));
-        }
-        if (p.resize[l])
-            MI3D_TRY(nearest_resize_fwd(p.dt, udst, udcs, p.C[l], p.up_geo(l), catl + p.half_off(l), p.catcs(l), p.geo[l], c.s));
+        MI3D_TRY(up_forward(c, i));
         MI3D_TRY(block_forward(c, L + 1 + i, x, buffers, drop_scales, training));
     }
     if (hl) {
@@ -692,10 +717,9 @@ int mi3d_unet_head_loss_forward(const mi3d_unet_desc* d, const void* const* para
                                 const mi3d_loss_cfg* cfg, float* loss_out, float* coef, float* metrics_out, void* loss_workspace,
                                 void* metrics_workspace, float* logits_opt, void* workspace, size_t workspace_bytes, void* stream) {
     Plan p;
-    MI3D_TRY(build_plan(d, p));
-    MI3D_CHECK_ARG(params && labels && cfg && loss_out && coef && loss_workspace && workspace, "mi3d_unet_head_loss_forward: null pointer");
-    MI3D_CHECK_ARG(workspace_bytes >= p.total, "workspace too small: %zu < %zu", workspace_bytes, p.total);
-    Ctx c{p, (char*)workspace, params, (hipStream_t)stream};
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_head_loss_forward", labels && cfg && loss_out && coef && loss_workspace, params, workspace,
+                   workspace_bytes, stream));
     LossCfg k = cfg_of(cfg);
     MI3D_CHECK_ARG(head_loss_ok(p.dt, c.at(p.zd[p.L - 1]), p.C[0], p.C[0], d->out_channels, k),
                    "mi3d_unet_head_loss_forward: no fused head + loss for this configuration (see mi3d_unet_head_loss_supported)");
@@ -747,19 +771,14 @@ int mi3d_unet_bn_apply_deferred(const mi3d_unet_desc* d, void* const* buffers, c
 int mi3d_unet_infer(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
                     float* logits, float* gap_out, void* workspace, size_t workspace_bytes, void* stream) {
     Plan p;
-    MI3D_TRY(build_plan(d, p));
-    MI3D_CHECK_ARG(x && params && buffers && workspace, "mi3d_unet_infer: null pointer");
-    MI3D_CHECK_ARG(workspace_bytes >= p.total, "workspace too small: %zu < %zu", workspace_bytes, p.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    Ctx c{p, (char*)workspace, params, (hipStream_t)stream};
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_infer", x && buffers, params, workspace, workspace_bytes, stream));
     int L = p.L;
     if (d->in_channels > 1)
         MI3D_TRY(ncdhw_to_ndhwc(p.dt, x, c.at(p.xcl), d->in_channels, d->in_channels, d->N, p.geo[0].V(), c.s));
     {   // launch 1: every BatchNorm folded; launch 2: every MFMA weight pack, BatchNorm scale multiplied in
         BnFoldJobs F;
         F.n = 0; F.eps = d->bn_eps;
-        PackJobs J;
-        J.n = 0; J.nblocks = 0;
         for (int b = 0; b < p.nblk; b++)
             for (int h = 0; h < 2; h++) {
                 const HalfP& H = p.blk[b].h[h];
@@ -767,15 +786,12 @@ int mi3d_unet_infer(const mi3d_unet_desc* d, const float* x, const void* const* 
                 float* scale = c.at<float>(H.stat);
                 F.j[F.n++] = BnFoldJob{c.P(H.pidx + 2), c.P(H.pidx + 3), (const float*)buffers[H.bidx], (const float*)buffers[H.bidx + 1],
                                        c.P(H.pidx + 1), scale, scale + H.Cout, H.Cout};
-                if (H.mfma) MI3D_TRY(pack_all_add_conv3(J, c.P(H.pidx), H.Cin, H.Cout, c.at(H.wpf), c.at(H.wpd), p.geo[p.blk[b].level], scale));
             }
-        for (int i = 0; i < L; i++) {
-            int l = L - 1 - i;
-            if (p.up_mfma[i]) MI3D_TRY(pack_all_add_upconv(J, c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], c.at(p.upw[i])));
-        }
+        PackJobs J;
+        J.n = 0; J.nblocks = 0;
+        MI3D_TRY(add_pack_jobs(c, J, true));
         MI3D_TRY(bn_fold_all(F, c.s));
         MI3D_TRY(pack_all_launch(J, c.s));
-        c.packed = true;
     }
     for (int l = 0; l < L; l++) {
         MI3D_TRY(block_infer(c, l, x));
@@ -784,22 +800,7 @@ int mi3d_unet_infer(const mi3d_unet_desc* d, const float* x, const void* const* 
     MI3D_TRY(block_infer(c, L, x));
     if (gap_out) MI3D_TRY(gap_fwd(p.dt, c.at(p.zb), p.C[L], p.C[L], d->N, p.geo[L].V(), gap_out, c.s));
     for (int i = 0; i < L; i++) {
-        int l = L - 1 - i;
-        float* wf = c.at<float>(p.upw[i]);
-        float* wb = wf + (size_t)cdiv(p.C[l], 8) * (2 * p.C[l]) * 64;
-        const void* uin = i == 0 ? c.at(p.zb) : c.at(p.zd[i - 1]);
-        char* catl = c.at<char>(p.cat[l]);
-        void* udst = p.resize[l] ? c.at(p.uptmp) : (void*)(catl + p.half_off(l));
-        int udcs = p.resize[l] ? p.C[l] : p.catcs(l);
-        if (p.up_mfma[i]) {
-            MI3D_TRY(upconv2_mfma_fwd(uin, 2 * p.C[l], 2 * p.C[l], c.at(p.upw[i]), c.P(p.up_pidx(i) + 1),
-                                      udst, udcs, p.C[l], p.geo[l + 1], c.s));
-        } else {
-            MI3D_TRY(upconv2_pack(c.P(p.up_pidx(i)), 2 * p.C[l], p.C[l], wf, wb, c.s));
-            MI3D_TRY(upconv2_fwd(p.dt, uin, 2 * p.C[l], 2 * p.C[l], wf, c.P(p.up_pidx(i) + 1), udst, udcs, p.C[l], p.geo[l + 1], c.s));
-        }
-        if (p.resize[l])
-            MI3D_TRY(nearest_resize_fwd(p.dt, udst, udcs, p.C[l], p.up_geo(l), catl + p.half_off(l), p.catcs(l), p.geo[l], c.s));
+        MI3D_TRY(up_forward(c, i));
         MI3D_TRY(block_infer(c, L + 1 + i, x));
     }
     if (logits)
@@ -833,15 +834,13 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
                        int seg_begin, int seg_end, void* workspace, size_t workspace_bytes, void* stream, void* aux_stream,
                        void* const* events, int aux_join, const HeadLoss* hl) {
     Plan p;
-    MI3D_TRY(build_plan(d, p));
-    MI3D_CHECK_ARG(x && params && grads && workspace, "mi3d_unet_backward: null pointer");
-    MI3D_CHECK_ARG(workspace_bytes >= p.total, "workspace too small: %zu < %zu", workspace_bytes, p.total);
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_backward", x && grads, params, workspace, workspace_bytes, stream));
     // `dlogits` below only says "the segmentation branch has a gradient": with the fused head it is never dereferenced
     const float* dlogits = hl ? reinterpret_cast<const float*>(hl->coef) : dlogits_in;
     MI3D_CHECK_ARG(dlogits || dgap, "mi3d_unet_backward: neither dlogits nor dgap given");
     int L = p.L, nseg = 2 * L + 2;
     MI3D_CHECK_ARG(seg_begin >= 0 && seg_end <= nseg && seg_begin <= seg_end, "bad segment range [%d,%d)", seg_begin, seg_end);
-    Ctx c{p, (char*)workspace, params, (hipStream_t)stream};
     if (aux_stream && events) { c.s2 = (hipStream_t)aux_stream; c.ev = (hipEvent_t*)events; }
     float* wgws = c.at<float>(p.wgws);
     auto G = [&](int i) { return (float*)grads[i]; };
@@ -850,15 +849,10 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
     for (int seg = seg_begin; seg < seg_end; seg++) {
         if (seg > seg_begin)
             for (int i = 0; i < marks.n; i++)
-                if (marks.seg[i] == seg - 1) {
-                    // two marks on one launch cannot happen (one event per segment); an older mark still pending means the
-                    // segment in between launched no BatchNorm backward: complete it now
-                    if (c.mark_pending) { MI3D_TRY(c.flush_pend()); MI3D_HIP(hipEventRecord(c.mark_pending, c.s)); }
-                    c.mark_pending = marks.ev[i];
-                }
+                if (marks.seg[i] == seg - 1) MI3D_TRY(c.pending.set_mark(marks.ev[i], c.s));
         if (seg == 0) {
             if (!dlogits) continue;
-            SlabJob* ps = c.pend_slot();
+            SlabJob* ps = c.pending.first(c.s);
             if (hl) {
                 MI3D_CHECK_ARG(head_loss_bwd_ok(p.dt, c.at(p.zd[L - 1]), p.C[0], p.C[0], d->out_channels, hl->cfg, c.at(p.gz[0]), p.C[0]),
                                "mi3d_unet_backward_loss: no fused head + loss for this configuration (see mi3d_unet_head_loss_supported)");
@@ -869,43 +863,31 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
                 MI3D_TRY(conv1_bwd(p.dt, c.at(p.zd[L - 1]), p.C[0], p.C[0], c.P(p.final_pidx()), dlogits, d->out_channels,
                                    c.at(p.gz[0]), p.C[0], G(p.final_pidx()), G(p.final_pidx() + 1), accumulate, wgws, d->N,
                                    p.geo[0].V(), c.s, ps));
-            c.pend_filled();
         } else if (seg <= L) {
             if (!dlogits) continue;
             int l = seg - 1, i = L - 1 - l;       // decoder.i works at level l
             MI3D_TRY(block_backward(c, L + 1 + i, x, grads, drop_scales, c.at(p.gz[l]), p.C[l], c.at(p.gcat[l]), p.catcs(l), accumulate));
-            const void* uin = i == 0 ? c.at(p.zb) : c.at(p.zd[i - 1]);
-            float* wf = c.at<float>(p.upw[i]);
-            float* wb = wf + (size_t)cdiv(p.C[l], 8) * (2 * p.C[l]) * 64;
-            char* gcatl = c.at<char>(p.gcat[l]);
-            const void* gup = gcatl + p.half_off(l);
-            int gupcs = p.catcs(l);
+            const UpIO u = up_io(c, i);
+            const void* gup = c.at<char>(p.gcat[l]) + u.half;
+            int gupcs = u.cs;
             if (p.resize[l]) {       // adjoint of the nearest resize in front of the concat (models/unet.py:81-83)
-                MI3D_TRY(nearest_resize_bwd(p.dt, gup, gupcs, p.C[l], p.geo[l], c.at(p.uptmp), p.C[l], p.up_geo(l), c.s));
-                gup = c.at(p.uptmp); gupcs = p.C[l];
+                MI3D_TRY(nearest_resize_bwd(p.dt, gup, gupcs, u.Cout, p.geo[l], c.at(p.uptmp), u.Cout, p.up_geo(l), c.s));
+                gup = c.at(p.uptmp); gupcs = u.Cout;
             }
-            // the decoder conv's pending slab sum (it reads wgws) stays pending across the transposed conv's backward, which
-            // therefore writes its slabs to the second workspace; the next BatchNorm-backward reduction carries both sums: one
-            // chain link less per level (not with the two-stream weight gradients, which own that workspace)
-            const bool keep = p.up_mfma[i] && c.has_pend && !c.has_pend2 && !mi3d_routes().no_upbwd_carry;
-            if (p.up_mfma[i] && keep) {
-                c.pend2 = SlabJob();
-                MI3D_TRY(upconv2_mfma_bwd(uin, 2 * p.C[l], 2 * p.C[l], gup, gupcs, p.C[l],
-                                          c.at(p.upw[i]), c.at(p.gz[l + 1]), 2 * p.C[l], G(p.up_pidx(i)), G(p.up_pidx(i) + 1),
-                                          accumulate, c.at<float>(p.wgws2), p.wgws_floats, p.geo[l + 1], c.s, &c.pend2));
-                c.has_pend2 = c.pend2.nblocks > 0;
-                continue;
-            }
-            SlabJob* ps = c.pend_slot();
             if (p.up_mfma[i]) {
-                MI3D_TRY(upconv2_mfma_bwd(uin, 2 * p.C[l], 2 * p.C[l], gup, gupcs, p.C[l],
-                                          c.at(p.upw[i]), c.at(p.gz[l + 1]), 2 * p.C[l], G(p.up_pidx(i)), G(p.up_pidx(i) + 1),
-                                          accumulate, wgws, p.wgws_floats, p.geo[l + 1], c.s, ps));
-                c.pend_filled();
-            } else
-                MI3D_TRY(upconv2_bwd(p.dt, uin, 2 * p.C[l], 2 * p.C[l], gup, gupcs, p.C[l], wb,
-                                     c.at(p.gz[l + 1]), 2 * p.C[l], G(p.up_pidx(i)), G(p.up_pidx(i) + 1), accumulate, wgws,
-                                     p.wgws_floats, p.geo[l + 1], c.s));
+                // the decoder conv's pending slab sum (it reads wgws) stays pending across the transposed conv's backward, which
+                // therefore writes its slabs to the second workspace; the next BatchNorm-backward reduction carries both sums: one
+                // chain link less per level (not with the two-stream weight gradients, which own that workspace)
+                SlabJob* ps = mi3d_routes().no_upbwd_carry ? nullptr : c.pending.carry();
+                float* slabs = ps ? c.at<float>(p.wgws2) : wgws;
+                if (!ps) ps = c.pending.first(c.s);
+                MI3D_TRY(upconv2_mfma_bwd(u.in, u.Cin, u.Cin, gup, gupcs, u.Cout, u.w, c.at(p.gz[l + 1]), u.Cin, G(p.up_pidx(i)),
+                                          G(p.up_pidx(i) + 1), accumulate, slabs, p.wgws_floats, u.g, c.s, ps));
+            } else {
+                c.pending.first(c.s);
+                MI3D_TRY(upconv2_bwd(p.dt, u.in, u.Cin, u.Cin, gup, gupcs, u.Cout, u.wb, c.at(p.gz[l + 1]), u.Cin, G(p.up_pidx(i)),
+                                     G(p.up_pidx(i) + 1), accumulate, wgws, p.wgws_floats, u.g, c.s));
+            }
         } else if (seg == L + 1) {
             if (dgap)
                 MI3D_TRY(gap_bwd(p.dt, dgap, gap_scale, c.at(p.gz[L]), p.C[L], p.C[L], d->N, p.geo[L].V(), dlogits ? 1 : 0, c.s));
@@ -926,8 +908,7 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
             c.pool_defer = false;
         }
     }
-    MI3D_TRY(c.flush_pend());
-    if (c.mark_pending) { MI3D_HIP(hipEventRecord(c.mark_pending, c.s)); c.mark_pending = nullptr; }
+    MI3D_TRY(c.pending.finish(c.s));
     for (int i = 0; i < marks.n; i++)
         if (marks.seg[i] == seg_end - 1) MI3D_HIP(hipEventRecord(marks.ev[i], c.s));
     // weight gradients still queued (a call that ends before the group's own fork point): they go out now, so that every
