@@ -276,6 +276,26 @@ int mi3d_preprocess_mri(const float* in, float* out, int64_t n, float p_low, flo
  * 2: CHAOS ranges {[55,70]:2, [110,135]:3, [175,200]:3, [240,255]:1, else 0} */
 int mi3d_remap_labels(const int64_t* in, int64_t* out, int64_t n, int kind, void* stream);
 
+/* Resampling of ONE decoded scan to the training grid: scipy.ndimage.zoom(..., mode='nearest', prefilter=False) as the
+ * reference's offline scripts call it (scripts/resampling/amos_ct_resample.py:56-70,93-97; the same four calls in
+ * chaos_resample.py:53,63,83,87 and resample_totalseg_ras_mri.py:57,65,92,94).  in: (D, H, W), out: (Do, Ho, Wo), both
+ * contiguous, in != out.  The per-axis tables are built by the caller on the host in float64 (resample.py axis_table)
+ * and passed as device pointers, one row per OUTPUT index of the axis; rows_* must equal the output sides. */
+/* bytes of the float (D, H, W) stage-1 volume of a two-stage chain (amos_ct_resample.py:60 -> :70), rounded up to 256 */
+size_t mi3d_zoom3_workspace_bytes(int D, int H, int W);
+/* order=3 (amos_ct_resample.py:60,70).  Table row, 48 bytes, tables 16-byte aligned:
+ *   { int32_t idx[4]; double w[4]; }   input indices of the taps floor(c)-1 .. floor(c)+2, each clamped to [0, n_in-1]
+ *                                      (mode='nearest'), and their cubic B-spline weights (no prefilter).
+ * out = float32(sum over the 4x4x4 taps of in * w_d * w_h * w_w), summed in float64.  ct_window != 0 also applies
+ * mi3d_preprocess_ct(window_min, window_max) to the rounded value (the step the script leaves commented out at :74). */
+int mi3d_zoom3_cubic(const float* in, float* out, int D, int H, int W, int Do, int Ho, int Wo, const void* table_d, int rows_d,
+                     const void* table_h, int rows_h, const void* table_w, int rows_w, int ct_window, float window_min,
+                     float window_max, void* stream);
+/* order=0 (amos_ct_resample.py:93,97): out[d][h][w] = in[index_d[d]][index_h[h]][index_w[w]].  Two order-0 zooms compose
+ * into one call with index = index1[index2] per axis, so the intermediate label volume need not exist. */
+int mi3d_zoom3_nearest_i64(const int64_t* in, int64_t* out, int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d,
+                           int rows_d, const int32_t* index_h, int rows_h, const int32_t* index_w, int rows_w, void* stream);
+
 /* Training-set augmentation, combined_transform() (utils/dataloader.py:223-262, used at train_unet.py:361): the
  * arithmetic of MONAI's RandBiasField -> RandGaussianNoise -> RandAdjustContrast -> RandHistogramShift ->
  * RandCoarseDropout on one (C, D, H, W) float volume, with the random parameters already drawn by the host

@@ -95,6 +95,9 @@ _SIGS = {
     "mi3d_preprocess_mri_workspace_bytes": (sz, []),
     "mi3d_preprocess_mri": (i32, [vp, vp, i64, f32, f32, vp, vp]),
     "mi3d_remap_labels": (i32, [vp, vp, i64, i32, vp]),
+    "mi3d_zoom3_workspace_bytes": (sz, [i32, i32, i32]),
+    "mi3d_zoom3_cubic": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
+    "mi3d_zoom3_nearest_i64": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_augment_workspace_bytes": (sz, []),
     "mi3d_augment": (i32, [vp, vp, vp, i32, i32, i32, i32, _AP, vp, sz, vp]),
     "mi3d_fill_boxes_i64": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64, vp]),

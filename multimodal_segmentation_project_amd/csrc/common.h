@@ -138,6 +138,12 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// preprocess_ct, utils/dataloader.py:111-117: ONE definition for ct_window_kernel (preproc.hip) and the epilogue of the cubic
+// zoom (resample.hip), so that both round the same way
+__device__ __forceinline__ float ct_window_f32(float v, float lo, float hi) {
+    v = v < lo ? lo : (v > hi ? hi : v);
+    return (v - lo) / (hi - lo);
+}
 #endif  // __HIPCC__
 
 // dtype dispatch for launchers: DISPATCH_T(dtype, T, { ... uses T ... })

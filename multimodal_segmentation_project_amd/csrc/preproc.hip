@@ -32,12 +32,8 @@ __device__ __forceinline__ float ikey(unsigned k) {
 }
 
 __global__ __launch_bounds__(BLK) void ct_window_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t n, float lo, float hi) {
-    float inv = hi - lo;
-    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK) {
-        float v = in[i];
-        v = v < lo ? lo : (v > hi ? hi : v);
-        out[i] = (v - lo) / inv;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK)
+        out[i] = ct_window_f32(in[i], lo, hi);
 }
 
 // pass 0: sum(x); pass 1: sum((x - mean)^2)   -> part[blockIdx.x]

@@ -572,6 +572,67 @@ def gen_preproc(out):
     np.savez_compressed(os.path.join(out, "preproc.npz"), **d)
 
 
+def gen_resample(out):
+    """The resampling scripts' zoom calls (scripts/resampling/amos_ct_resample.py:60,70,93,97; same calls in
+    chaos_resample.py:53,63,83,87 and resample_totalseg_ras_mri.py:57,65,92,94) on seeded in-memory volumes.  The scripts
+    cannot be imported (top-level code, hard-coded paths, nibabel), so the CALL FORM is restated here:
+    scipy.ndimage.zoom(x, factors, order=3|0, mode='nearest', prefilter=False) on the float64 array get_fdata() returns,
+    stage-2 factors = target_shape[i] / stage-1 shape[i] (:64-66).  All inputs are float32-representable.
+    Several files, because one float64 stage output is several hundred KB and no committed file may pass 1 MiB:
+      resample.npz      plain zooms: zoomA (23,31,17) x (1.7,0.83,2.9); zoomB (5,7,3) x 0.5; zoomC (1,6,5) x (1,2,0.2)
+      resample_ct.npz   chain (40,36,12) at (0.7,0.8,5.0) mm -> (32,32,32), HU-like values, labels 0..15
+      resample_mri.npz  chain (36,36,10) at (1.6,1.6,7.7) mm -> (24,24,24); its float64 stage-1 image (58,58,77) is 2 MB,
+                        so it is stored whole as slabs along axis 0 in resample_mri_image1_<k>.npz (image1_parts says
+                        how many)."""
+    import scipy
+    from scipy.ndimage import zoom
+    rng = np.random.default_rng(11)
+    d = {}
+    for name, shape, fac in (("zoomA", (23, 31, 17), (1.7, 0.83, 2.9)), ("zoomB", (5, 7, 3), 0.5), ("zoomC", (1, 6, 5), (1, 2, 0.2))):
+        img = (rng.standard_normal(shape) * 300.0).astype(np.float32)
+        lab = rng.integers(0, 16, shape)
+        d[f"{name}/image_in"], d[f"{name}/label_in"] = img, lab.astype(np.uint8)
+        d[f"{name}/factors"] = np.broadcast_to(np.asarray(fac, dtype=np.float64), (3,)).copy()
+        d[f"{name}/image_out"] = zoom(img.astype(np.float64), fac, order=3, mode='nearest', prefilter=False)
+        d[f"{name}/label_out"] = zoom(lab.astype(np.float64), fac, order=0, mode='nearest', prefilter=False).astype(np.uint8)
+    np.savez_compressed(os.path.join(out, "resample.npz"), **d)
+    for name, shape, spacing, target in (("ct", (40, 36, 12), (0.7, 0.8, 5.0), (32, 32, 32)),
+                                         ("mri", (36, 36, 10), (1.6, 1.6, 7.7), (24, 24, 24))):
+        if name == "ct":
+            img = rng.uniform(-1000.0, 1500.0, shape).astype(np.float32)
+        else:
+            img = (rng.gamma(2.0, 120.0, shape) + 30.0 * rng.standard_normal(shape)).astype(np.float32)
+        lab = rng.integers(0, 16, shape)
+        voxel_spacing, target_spacing = np.asarray(spacing, dtype=np.float64), np.array([1.0, 1.0, 1.0])
+        scale_factors = voxel_spacing / target_spacing                                                     # :56
+        img1 = zoom(img.astype(np.float64), scale_factors, order=3, mode='nearest', prefilter=False)      # :60
+        resize_factors = [target[i] / img1.shape[i] for i in range(3)]                                    # :64-66
+        img2 = zoom(img1, resize_factors, order=3, mode='nearest', prefilter=False)                       # :70
+        lab1 = zoom(lab.astype(np.float64), scale_factors, order=0, mode='nearest', prefilter=False)      # :93
+        lab2 = zoom(lab1, resize_factors, order=0, mode='nearest', prefilter=False)                       # :97
+        assert img2.shape == target and lab2.shape == target
+        c = {"image_in": img, "label_in": lab.astype(np.uint8), "spacing": voxel_spacing, "target_shape": np.array(target),
+             "scale_factors": scale_factors, "resize_factors": np.array(resize_factors), "shape1": np.array(img1.shape),
+             "image2": img2, "label1": lab1.astype(np.uint8), "label2": lab2.astype(np.uint8)}            # :101 astype(uint8)
+        if img1.nbytes < 900_000:
+            c["image1"] = img1
+        else:                                     # whole, as slabs along axis 0 in files of their own
+            parts = np.array_split(img1, -(-img1.nbytes // 700_000), axis=0)
+            for k, part in enumerate(parts):
+                np.savez_compressed(os.path.join(out, f"resample_{name}_image1_{k}.npz"), image1_part=part)
+            c["image1_parts"] = np.array(len(parts))
+        np.savez_compressed(os.path.join(out, f"resample_{name}.npz"), **c)
+    with open(os.path.join(out, "PROVENANCE_resample.txt"), "w") as f:
+        f.write("resample.npz, resample_ct.npz, resample_mri.npz, resample_mri_image1_*.npz: generated by tools/gen_golden.py --only resample\n")
+        f.write("outputs are scipy.ndimage.zoom(x, factors, order=3|0, mode='nearest', prefilter=False) on seeded float64 arrays.\n")
+        f.write("The reference's resampling scripts (scripts/resampling/amos_ct_resample.py:56-70,93-97, chaos_resample.py,\n")
+        f.write("resample_totalseg_ras_mri.py) cannot be imported (top-level code, hard-coded paths, nibabel), so their call form\n")
+        f.write("is restated in the tool; nothing of the scripts is executed or copied.\n")
+        f.write("The MRI chain's float64 stage-1 image (2 MB, over the 1 MiB file limit) is stored whole, as slabs along axis 0,\n")
+        f.write("in resample_mri_image1_<k>.npz; np.concatenate(parts, axis=0) restores it.\n")
+        f.write(f"scipy {scipy.__version__}, numpy {np.__version__}\n")
+
+
 def _autocast_yardstick(d, pre, ref_unet, ref_metrics, x, y, fp32_logits, fp32_grads, seed=0):
     """The reference's own bf16 autocast run (accelerate mixed_precision='bf16') vs its fp32 run on the same inputs."""
     torch.manual_seed(seed)
@@ -931,6 +992,9 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     torch.set_num_threads(8)
     torch.use_deterministic_algorithms(False)
+    if want("resample"): gen_resample(a.out)              # needs scipy only, not the reference tree
+    if only == {"resample"}:
+        return
     ref_unet, ref_unet_dann, ref_metrics, ref_train_unet, ref_train_dann = _import_reference()
     if want("small_unet"): gen_small_unet(ref_unet, ref_metrics, a.out)
     if want("doubleconv"): gen_doubleconv(ref_unet, a.out)
