@@ -93,11 +93,13 @@ int mi3d_linear_backward(const float* x, const float* w, const float* y, const f
                          int relu, const float* drop, float* gx, float* gw, float* gb, int accumulate, float gx_scale,
                          float* workspace, void* stream) {
     MI3D_CHECK_ARG(x && w && y && gy && workspace, "mi3d_linear_backward: null pointer");
+    MI3D_CHECK_ARG(M > 0 && K > 0 && Nout > 0, "mi3d_linear_backward: M=%d K=%d Nout=%d must be positive", M, K, Nout);
     return linear_bwd(x, w, y, gy, M, K, Nout, relu, drop, gx, gw, gb, accumulate, gx_scale, workspace, (hipStream_t)stream);
 }
 int mi3d_softmax_ce_rows(const float* logits, const int64_t* labels, int M, int C, float* loss, float* dlogits,
                          float scale, void* stream) {
     MI3D_CHECK_ARG(logits && labels, "mi3d_softmax_ce_rows: null pointer");
+    MI3D_CHECK_ARG(M > 0 && C > 0, "mi3d_softmax_ce_rows: M=%d C=%d must be positive", M, C);
     return softmax_ce_rows(logits, labels, M, C, loss, dlogits, scale, (hipStream_t)stream);
 }
 

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(BLK) void linear_bwd_w_kernel(const float* __restri
                                                            float* __restrict__ gw, float* __restrict__ gb, int M, int K,
                                                            int Nout, int accumulate) {
     int i = blockIdx.x * BLK + threadIdx.x;
-    if (i < Nout * K) {
+    if (gw && i < Nout * K) {
         int o = i / K, k = i - o * K;
         float s = 0.f;
         for (int m = 0; m < M; m++) s = fmaf(gpre[(int64_t)m * Nout + o], x[(int64_t)m * K + k], s);
@@ -169,14 +169,16 @@ __global__ void softmax_ce_rows_kernel(const float* __restrict__ logits, const i
 // 16-byte accesses, the next iteration's four loads in flight under the current update, and the first loads issued BEFORE the
 // double-precision bias corrections (two pow + sqrt, ~1 us of dependent arithmetic that every wave repeats): round 3, 32.5 -> see
 // DESIGN.  Per element the arithmetic is unchanged (bit-identical parameters).
-__device__ __forceinline__ void adamw_one(float& pi, float gi, float& mi, float& vi, float lr, float b1, float b2, float eps, float wd,
+// The 16-byte route and the scalar route (tails, ranges off 16-byte alignment) must round identically, or an element's last bits
+// depend on where its range starts: every multiply-add is an explicit fma and contraction is off.  decay = fma(-lr, wd, 1).
+__device__ __forceinline__ void adamw_one(float& pi, float gi, float& mi, float& vi, float decay, float b1, float b2, float eps,
                                           float grad_scale, float bc2s, float step_size) {
+#pragma clang fp contract(off)
     gi = gi * grad_scale;
-    pi = pi * (1.f - lr * wd);
-    mi = b1 * mi + (1.f - b1) * gi;       // torch: exp_avg.lerp_(grad, 1-b1)
-    vi = b2 * vi + (1.f - b2) * gi * gi;
+    mi = __builtin_fmaf(b1, mi, (1.f - b1) * gi);       // torch: exp_avg.lerp_(grad, 1-b1)
+    vi = __builtin_fmaf(b2, vi, ((1.f - b2) * gi) * gi);
     float denom = sqrtf(vi) / bc2s + eps;
-    pi = pi - step_size * (mi / denom);
+    pi = __builtin_fmaf(decay, pi, -(step_size * (mi / denom)));      // p * (1 - lr * wd) - step_size * m / denom
 }
 __global__ __launch_bounds__(BLK) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
@@ -195,6 +197,7 @@ __global__ __launch_bounds__(BLK) void adamw_kernel(float* __restrict__ p, const
     float bc1 = (float)(1.0 - pow((double)b1, step));
     float bc2s = (float)sqrt(1.0 - pow((double)b2, step));
     float step_size = lr / bc1;
+    const float decay = __builtin_fmaf(-lr, wd, 1.f);
     while (have) {
         int64_t j = i + stride;
         bool have2 = j < n4;
@@ -203,10 +206,10 @@ __global__ __launch_bounds__(BLK) void adamw_kernel(float* __restrict__ p, const
             g5 = reinterpret_cast<const float4*>(g)[j]; p5 = reinterpret_cast<const float4*>(p)[j];
             m5 = reinterpret_cast<const float4*>(m)[j]; v5 = reinterpret_cast<const float4*>(v)[j];
         }
-        adamw_one(p4.x, g4.x, m4.x, v4.x, lr, b1, b2, eps, wd, grad_scale, bc2s, step_size);
-        adamw_one(p4.y, g4.y, m4.y, v4.y, lr, b1, b2, eps, wd, grad_scale, bc2s, step_size);
-        adamw_one(p4.z, g4.z, m4.z, v4.z, lr, b1, b2, eps, wd, grad_scale, bc2s, step_size);
-        adamw_one(p4.w, g4.w, m4.w, v4.w, lr, b1, b2, eps, wd, grad_scale, bc2s, step_size);
+        adamw_one(p4.x, g4.x, m4.x, v4.x, decay, b1, b2, eps, grad_scale, bc2s, step_size);
+        adamw_one(p4.y, g4.y, m4.y, v4.y, decay, b1, b2, eps, grad_scale, bc2s, step_size);
+        adamw_one(p4.z, g4.z, m4.z, v4.z, decay, b1, b2, eps, grad_scale, bc2s, step_size);
+        adamw_one(p4.w, g4.w, m4.w, v4.w, decay, b1, b2, eps, grad_scale, bc2s, step_size);
         reinterpret_cast<float4*>(m)[i] = m4;
         reinterpret_cast<float4*>(v)[i] = v4;
         reinterpret_cast<float4*>(p)[i] = p4;
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(BLK) void adamw_kernel(float* __restrict__ p, const
     // scalar tail (and the whole range when a pointer is not 16-byte aligned)
     for (int64_t k = n4 * 4 + (int64_t)blockIdx.x * BLK + threadIdx.x; k < n; k += stride) {
         float pi = p[k], mi = m[k], vi = v[k];
-        adamw_one(pi, g[k], mi, vi, lr, b1, b2, eps, wd, grad_scale, bc2s, step_size);
+        adamw_one(pi, g[k], mi, vi, decay, b1, b2, eps, grad_scale, bc2s, step_size);
         m[k] = mi; v[k] = vi; p[k] = pi;
     }
 }
@@ -307,8 +310,8 @@ int linear_bwd(const float* x, const float* w, const float* y, const float* gy, 
         linear_bwd_x_kernel<<<cdiv((int64_t)M * K, BLK), BLK, 0, s>>>(ws, w, gx, M, K, Nout, gx_scale);
         MI3D_LAUNCH_CHECK();
     }
-    if (gw) {
-        linear_bwd_w_kernel<<<cdiv((int64_t)Nout * K, BLK), BLK, 0, s>>>(ws, x, gw, gb, M, K, Nout, accumulate);
+    if (gw || gb) {                                      // gb does not depend on gw: either may be NULL
+        linear_bwd_w_kernel<<<cdiv(gw ? (int64_t)Nout * K : Nout, BLK), BLK, 0, s>>>(ws, x, gw, gb, M, K, Nout, accumulate);
         MI3D_LAUNCH_CHECK();
     }
     return 0;
