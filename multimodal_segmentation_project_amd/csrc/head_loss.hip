@@ -514,6 +514,17 @@ __global__ __launch_bounds__(1024) void seg_loss_finalize_kernel(const double* _
     seg_loss_finalize_body(part, nblk, N, C, V, cfg, loss_out, coef);
 }
 
+// distillation term of dL/dz: kd_s (ps - pt).  ps and pt are products (softmax_c: exp * 1/sum), so under implicit contraction
+// the difference becomes fma(e, r, -pt), fma(-et, rt, ps) or a plain subtraction depending on the kernel this is inlined into
+// (measured: one ulp between the VV = 4 and VV = 1 instantiations of seg_loss_bwd_kernel at C = 3 with a teacher); as in
+// dlogits_voxel the operations are taken as written
+template <int NC>
+__device__ __forceinline__ void kd_voxel(const float (&ps)[NC], const float (&pt)[NC], float kd_s, float (&kd)[NC]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < NC; c++) kd[c] = kd_s * (ps[c] - pt[c]);
+}
+
 // dL/dz of one voxel (header of this file); shared by the plain backward pass and the head-fused one so that both
 // produce the same bits from the same logits
 template <int NC>
@@ -571,8 +582,7 @@ __global__ __launch_bounds__(BLK) void seg_loss_bwd_kernel(const float* __restri
                 float ps[NC], pt[NC], ls, lt;
                 softmax_c<NC>(z[k], C, inv_t, ps, ls);
                 softmax_c<NC>(zt_[k], C, inv_t, pt, lt);
-#pragma unroll
-                for (int c = 0; c < NC; c++) kd[c] = kd_s * (ps[c] - pt[c]);
+                kd_voxel<NC>(ps, pt, kd_s, kd);
             }
             dlogits_voxel<NC>(z[k], t[k], C, A, B, ce_s, go, kd, o[k]);
         }
@@ -825,8 +835,7 @@ __global__ __launch_bounds__(C1W * 64) void head_loss_bwd_mfma_kernel(const bf16
                 for (int c = 0; c < NC; c++) ztv[c] = (c < Cout && vl < V) ? tg[(int64_t)c * V + vl] : 0.f;
                 softmax_c<NC>(zl, Cout, inv_t, ps, ls);
                 softmax_c<NC>(ztv, Cout, inv_t, pt, lt);
-#pragma unroll
-                for (int c = 0; c < NC; c++) kd0[c] = kd_s * (ps[c] - pt[c]);
+                kd_voxel<NC>(ps, pt, kd_s, kd0);
             }
             dlogits_voxel<NC>(zl, tl, Cout, A, B, ce_s, go, kd0, o);
 #pragma unroll
@@ -1156,6 +1165,7 @@ int seg_loss_fwd(const float* logits, const int64_t* labels, const float* teache
 int seg_loss_bwd(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int64_t V, LossCfg cfg,
                  const float* coef, const float* grad_out, float* dlogits, hipStream_t s) {
     MI3D_CHECK_ARG(C >= 1 && C <= MAXC, "seg_loss_bwd: %d classes unsupported", C);
+    MI3D_CHECK_ARG(cfg.w_kd == 0.f || teacher, "seg_loss_bwd: distillation weight without teacher logits");
     const float* tch = cfg.w_kd != 0.f ? teacher : nullptr;
     bool v4 = vv4(V, logits, labels, tch) && al16(dlogits);
     dim3 grid((unsigned)per_sample_blocks(V, v4 ? 4 : 1, N, 4096), (unsigned)N);
