@@ -19,18 +19,17 @@
 // (stride 32 B, the two channel halves interleaved) -> conflict-free without padding.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include <hip/hip_ext.h>
 
+#include "mfma_tile.h"
 #include "ops.h"
 #include "slab_sum.h"
 
 namespace {
 
 constexpr int BLK = 256;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // K-step -> tap assignment.  mode 0 (natural): K-step s holds taps (2s, 2s+1).  mode 1 ("row reuse", persistent
 // full-resolution kernel): taps are paired so that consecutive K-steps read the SAME LDS rows shifted by dy, which
@@ -154,29 +153,207 @@ __device__ __forceinline__ int xcd_contig(int b, int n) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
 }
 
+// ------------------------------------------------------------------------------------------------ tile geometry
+// One description per tiling: output tile = TZ x (TYB*BY) x (TXB*BX) voxels cut into 16-voxel M-blocks (BY x BX), input = the
+// (tile + 2)^3 halo.  Kernels and launchers read every size from here.
+template <int TZ_, int TYB_, int TXB_, int BX_>
+struct ConvTile {
+    static constexpr int TZ = TZ_, TYB = TYB_, TXB = TXB_, BX = BX_;
+    static constexpr int BY = 16 / BX;
+    static constexpr int TY = TYB * BY, TX = TXB * BX;
+    static constexpr int IZ = TZ + 2, IY = TY + 2, IX = TX + 2;
+    // LDS row pitch in voxels.  With 4 x 4-voxel M-blocks (BX = 4) a 10-voxel pitch puts rows 0 and 3 of a block on the same
+    // banks of a ds_read_b128 lane group (SQ_LDS_BANK_CONFLICT 24-29 % of the LDS-active cycles of these kernels); 12 voxels
+    // (384 B = 128 mod 256) makes the 16 pieces of every lane group tile the 256-byte bank row exactly
+    static constexpr int IXP = BX == 4 ? 12 : IX;
+    static constexpr int MB = TYB * TXB;                       // M-blocks per z-slice
+    static constexpr int NVT = TZ * TY * TX;                   // output voxels
+    static constexpr int NVOX = IZ * IY * IX, NVOXP = IZ * IY * IXP;     // halo voxels, and with the padded pitch
+    static constexpr int pieces(int nthr) { return (NVOX * 2 + nthr - 1) / nthr; }   // 16-byte staging pieces per thread
+};
+using FullTile = ConvTile<4, 8, 1, 16>;      // 4 x 8 x 16: the persistent forward, the weight gradients and the first layer
+
+// LDS layouts (byte offsets and the total), one per body: the kernel carves its pointers from it, the launcher sizes the launch
+// with it.  The BatchNorm rows red[waves][COB][16][2] come last in each.
+template <class T, int COB>
+struct Lds4 {            // four-wave body: halo tile (32 B per voxel) | red[4]
+    static constexpr int xs = 0, red = T::NVOXP * 32, bytes = red + 4 * COB * 16 * 2 * 4;
+};
+template <class T, int COB>
+struct Lds8 {            // eight-wave kernel: halo tile | the chunk's weight fragments [14][COB][64 lanes][8] | red[8]
+    static constexpr int xs = 0, wl = T::NVOXP * 32, red = wl + 14 * COB * 1024, bytes = red + 8 * COB * 16 * 2 * 4;
+};
+template <int COB, int NCH>
+struct LdsP {            // persistent body: halo tile | all weight fragments [NCH][14][COB][64 lanes][8] | red[4]
+    static constexpr int xs = 0, wl = FullTile::NVOX * 32, red = wl + NCH * 14 * COB * 1024, bytes = red + 4 * COB * 16 * 2 * 4;
+};
+
+// staging map of the four- and eight-wave kernels: each of the NTHR threads moves NIT 16-byte pieces (voxel, channel half) per
+// chunk; the voxel -> global offset map is chunk-invariant, so it is computed once.  soff = -1: outside the volume -> zero fill;
+// sdst = element offset of the piece in the padded LDS tile (unused where the pitch is not padded)
+template <class T, int NTHR, int NIT>
+__device__ __forceinline__ void staging_map(int z0, int y0, int x0, int D, int H, int W, int xcs, int (&soff)[NIT], int (&sdst)[NIT]) {
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+        int idx = threadIdx.x + it * NTHR;
+        int vox = idx >> 1, half = idx & 1;
+        int ix = vox % T::IX, t = vox / T::IX, iy = t % T::IY, iz = t / T::IY;
+        sdst[it] = T::IXP == T::IX ? 0 : (t * T::IXP + ix) * 16 + half * 8;
+        int gz = z0 - 1 + iz, gy = y0 - 1 + iy, gx = x0 - 1 + ix;
+        bool inb = idx < T::NVOX * 2 && gz >= 0 && gz < D && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        soff[it] = inb ? ((gz * H + gy) * W + gx) * xcs + half * 8 : -1;
+    }
+}
+template <class T, int NTHR, int NIT>
+__device__ __forceinline__ void staging_store(bf16* xs, const int (&sdst)[NIT], const bf16x8 (&sv)[NIT]) {
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+        int idx = threadIdx.x + it * NTHR;
+        if (idx < T::NVOX * 2) *reinterpret_cast<bf16x8*>(xs + (T::IXP == T::IX ? idx * 8 : sdst[it])) = sv[it];
+    }
+}
+// K-step s (taps 2s, 2s + 1; ktap mode 0) -> LDS byte offset of the lane's fragment in M-block 0, and M-block rg -> its offset
+template <class T>
+__device__ __forceinline__ int frag_off(int s, int laneOff, int g) {
+    int t0 = 2 * s, t1 = (2 * s + 1 < 27) ? 2 * s + 1 : 26;
+    int off0 = (((t0 / 9) * T::IY + ((t0 / 3) % 3)) * T::IXP + (t0 % 3)) * 32;
+    int off1 = (((t1 / 9) * T::IY + ((t1 / 3) % 3)) * T::IXP + (t1 % 3)) * 32;
+    return laneOff + ((g >> 1) ? off1 : off0);
+}
+template <class T>
+__device__ __forceinline__ int row_off(int rg) { return (((rg / T::TXB) * T::BY) * T::IXP + (rg % T::TXB) * T::BX) * 32; }
+
+// One M-block of a wave: block rg of z-slice gz of the tile at (y0, x0); lane (vn, g) = voxel vn of the block, output channels
+// g*4 .. g*4 + 3 of each of the COB 16-channel blocks.  The callers keep the loop over their blocks: (wave, r) in the four-wave
+// body, (zs, hb * MBW + r) in the eight-wave kernel.  (Per block and with the index written out at the call: a helper that loops
+// over the blocks itself, or a hoisted hb * MBW, costs these kernels VGPRs and scratch -- profiles/conv_tile_refactor_resources.txt)
+// split-K: fp32 partial tile pk[voxel][CoutTotal], 4 channels (16 B) per lane
+template <class T, int COB, bool TK>
+__device__ __forceinline__ void splitk_store(const f32x4 (&acc)[COB], float* __restrict__ pk, int n, int gz, int y0, int x0, int rg, int vn,
+                                             int g, int D, int H, int W, int CoutTotal, int cobBase) {
+    int byb = rg / T::TXB, bxb = rg % T::TXB;
+    int gy = y0 + byb * T::BY + vn / T::BX, gx = x0 + bxb * T::BX + vn % T::BX;
+    if (gz < D && gy < H && gx < W) {
+        float* pp = pk + ((((int64_t)n * D + gz) * H + gy) * W + gx) * CoutTotal + cobBase * 16 + g * 4;
+#pragma unroll
+        for (int c = 0; c < COB; c++) {
+            if constexpr (TK) {          // write-through (agent-coherent) store: the finishing workgroup sits on another XCD
+                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(pp + c * 16), "v"(acc[c]) : "memory");
+            } else
+                *reinterpret_cast<f32x4*>(pp + c * 16) = acc[c];
+        }
+    }
+}
+// epilogue of the four- and eight-wave kernels: bias, ReLU (inference: BatchNorm folded into weights and bias), bf16 rounding,
+// BatchNorm sums (s1, s2) of the ROUNDED in-volume values, 8-byte store per lane and output block -- or, WIDE and relu bit 1,
+// one 16-byte store
+template <class T, int COB, bool STATS, bool WIDE>
+__device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[COB], const float* __restrict__ bias, bf16* __restrict__ y, int ycs, int relu,
+                                              int n, int gz, int y0, int x0, int rg, int vn, int g, int D, int H, int W, int cobBase,
+                                              float (&s1)[COB][4], float (&s2)[COB][4]) {
+    int byb = rg / T::TXB, bxb = rg % T::TXB;
+    int gy = y0 + byb * T::BY + vn / T::BX, gx = x0 + bxb * T::BX + vn % T::BX;
+    bool ok = gz < D && gy < H && gx < W;
+    bf16* yp = y + ((((int64_t)n * D + gz) * H + gy) * W + gx) * ycs + cobBase * 16 + g * 4;
+    bf16x4 oc[COB];
+#pragma unroll
+    for (int c = 0; c < COB; c++) {
+        bf16x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            float v = acc[c][j] + (bias ? bias[(cobBase + c) * 16 + g * 4 + j] : 0.f);
+            if (relu & 1) v = fmaxf(v, 0.f);
+            o[j] = (bf16)v;
+            if (STATS && ok) { float q = (float)o[j]; s1[c][j] += q; s2[c][j] += q * q; }
+        }
+        oc[c] = o;
+    }
+    if constexpr (WIDE && COB == 2) {
+        if (relu & 2) {
+            // wide store (round 4): the lane's two 4-channel pieces (output blocks 0 and 1 of ONE voxel) trade halves with the
+            // neighbouring 16-lane rows; lane (vn, g) then holds channels (g & 1) * 16 + (g >> 1) * 8 .. + 7:
+            // one 16-B store per lane, the voxel's 64 B written by four lanes
+            u32x4 wv = swap_halves16(oc[0], oc[1]);
+            if (ok) *reinterpret_cast<u32x4*>(yp - g * 4 + (g & 1) * 16 + (g >> 1) * 8) = wv;
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < COB; c++)
+        if (ok) *reinterpret_cast<bf16x4*>(yp + c * 16) = oc[c];
+}
+// the same for the kernels whose lane holds one voxel per M-block row (persistent, first layer): bias in registers, out-of-volume
+// voxels enter the sums as zeros, the squares through fmaf
+template <bool STATS>
+__device__ __forceinline__ bf16x4 round4_masked(f32x4 a, const float (&bv)[4], bool relu, bool ok, float (&s1)[4], float (&s2)[4]) {
+    bf16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        float v = a[j] + bv[j];
+        if (relu) v = fmaxf(v, 0.f);
+        o[j] = (bf16)v;
+        if (STATS) { float q = ok ? (float)o[j] : 0.f; s1[j] += q; s2[j] = fmaf(q, q, s2[j]); }
+    }
+    return o;
+}
+
+// BatchNorm partial row of a workgroup: part[(blk*2 + k)*CoutTotal + ch0 + ch], k = 0 sum, 1 sum of squares (the layout
+// bn_stats_finalize consumes), from the per-wave rows in red.  The order of the cross-wave sum is part of each kernel's bits:
+// PAIRWISE (r0 + r1) + (r2 + r3), otherwise row by row (the eight-wave kernels start from 0.f)
+template <int COB, int NW, bool PAIRWISE>
+__device__ __forceinline__ void bn_row_write(float (*red)[COB][16][2], float* __restrict__ part, int64_t blk, int CoutTotal, int ch0) {
+    static_assert(NW == 8 || NW == 4, "waves per workgroup");
+    for (int idx = threadIdx.x; idx < COB * 16 * 2; idx += NW * 64) {
+        int k = idx & 1, ch = idx >> 1;
+        int c = ch / 16, cc = ch % 16;
+        float v;
+        if constexpr (NW == 8) {
+            v = 0.f;
+#pragma unroll
+            for (int w = 0; w < 8; w++) v += red[w][c][cc][k];
+        } else if constexpr (PAIRWISE) v = (red[0][c][cc][k] + red[1][c][cc][k]) + (red[2][c][cc][k] + red[3][c][cc][k]);
+        else v = red[0][c][cc][k] + red[1][c][cc][k] + red[2][c][cc][k] + red[3][c][cc][k];
+        part[(blk * 2 + k) * CoutTotal + ch0 + ch] = v;
+    }
+}
+// lane sums (s1, s2) -> wave rows (16 voxel lanes per channel, xor shuffles) -> LDS -> the workgroup's partial row
+template <int COB, int NW, bool PAIRWISE>
+__device__ __forceinline__ void bn_rows_reduce(const float (&s1)[COB][4], const float (&s2)[COB][4], float (*red)[COB][16][2], int wave,
+                                               int vn, int g, float* __restrict__ part, int64_t blk, int CoutTotal, int ch0) {
+#pragma unroll
+    for (int c = 0; c < COB; c++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            float a = s1[c][j], b = s2[c][j];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+            if (vn == 0) { red[wave][c][g * 4 + j][0] = a; red[wave][c][g * 4 + j][1] = b; }
+        }
+    __syncthreads();
+    bn_row_write<COB, NW, PAIRWISE>(red, part, blk, CoutTotal, ch0);
+}
+
+// ------------------------------------------------------------------------------------------------ four-wave body
 template <int TZ, int TYB, int TXB, int BX, int COB, bool STATS, bool SPLITK, bool EXT_LDS = false>
 __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict__ x, int xcs, int Cin,
                                                 const bf16* __restrict__ wp, const float* __restrict__ bias,
                                                 bf16* __restrict__ y, int ycs, int CoutTotal, int D, int H, int W,
                                                 int tilesZ, int tilesY, int tilesX, float* __restrict__ part,
                                                 char* ext_lds = nullptr, int relu = 0) {
-    constexpr int BY = 16 / BX;
-    constexpr int TY = TYB * BY, TX = TXB * BX;
-    constexpr int IZ = TZ + 2, IY = TY + 2, IX = TX + 2;
+    using T = ConvTile<TZ, TYB, TXB, BX>;
+    using L = Lds4<T, COB>;
     static_assert(TZ == 4, "one z-slice of the tile per wave");
-    constexpr int MB = TYB * TXB;                  // M-blocks per wave (wave w owns z-slice w of the tile)
-    // LDS row pitch: 12 voxels instead of 10 for the 4 x 4-voxel M-blocks (bank conflicts, see conv3_mfma8_kernel)
-    constexpr int IXP = BX == 4 ? 12 : IX;
-    constexpr int NVOX = IZ * IY * IX, NVOXP = IZ * IY * IXP;
+    constexpr int MB = T::MB;                      // M-blocks per wave (wave w owns z-slice w of the tile)
     // EXT_LDS: the tile lives in the caller's (dynamic) LDS block -- a fused launch shares one block between the bodies
     bf16* xs;
     float (*red)[COB][16][2];
     if constexpr (EXT_LDS) {
-        xs = reinterpret_cast<bf16*>(ext_lds);
-        red = reinterpret_cast<float (*)[COB][16][2]>(ext_lds + NVOXP * 32);
+        xs = reinterpret_cast<bf16*>(ext_lds + L::xs);
+        red = reinterpret_cast<float (*)[COB][16][2]>(ext_lds + L::red);
     } else {
-        __shared__ __attribute__((aligned(16))) bf16 xs_s[NVOXP * 16];
+        __shared__ __attribute__((aligned(16))) bf16 xs_s[(L::red - L::xs) / 2];
         __shared__ float red_s[4][COB][16][2];
+        static_assert(sizeof(xs_s) + sizeof(red_s) == L::bytes, "the two arrays are the layout");
         xs = xs_s;
         red = red_s;
     }
@@ -187,14 +364,14 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
     int tx_ = tile % tilesX; tile /= tilesX;
     int ty_ = tile % tilesY; tile /= tilesY;
     int tz_ = tile % tilesZ; int n = tile / tilesZ;
-    int z0 = tz_ * TZ, y0 = ty_ * TY, x0 = tx_ * TX;
+    int z0 = tz_ * TZ, y0 = ty_ * T::TY, x0 = tx_ * T::TX;
     int cobBase = bid_.y * COB;
     int nCobTotal = CoutTotal / 16;
 
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int vn = lane & 15, g = lane >> 4;
     // per-lane LDS byte offset of its voxel inside an M-block + channel half
-    int laneOff = (((vn / BX) * IXP + (vn % BX)) * 16 + (g & 1) * 8) * 2 + wave * (IY * IXP * 32);
+    int laneOff = (((vn / BX) * T::IXP + (vn % BX)) * 16 + (g & 1) * 8) * 2 + wave * (T::IY * T::IXP * 32);
     const char* xsb = reinterpret_cast<const char*>(xs);
 
     f32x4 acc[MB][COB];
@@ -203,20 +380,9 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
 #pragma unroll
         for (int c = 0; c < COB; c++) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // staging map: each thread moves NIT 16-byte pieces (voxel, channel half) per chunk; the voxel -> global offset map
-    // is chunk-invariant, so it is computed once (-1 = outside the volume -> zero fill)
-    constexpr int NIT = (NVOX * 2 + BLK - 1) / BLK;
+    constexpr int NIT = T::pieces(BLK);
     int soff[NIT], sdst[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        int idx = threadIdx.x + it * BLK;
-        int vox = idx >> 1, half = idx & 1;
-        int ix = vox % IX, t = vox / IX, iy = t % IY, iz = t / IY;
-        sdst[it] = IXP == IX ? 0 : (t * IXP + ix) * 16 + half * 8;                 // element offset of the piece in the (padded) LDS tile
-        int gz = z0 - 1 + iz, gy = y0 - 1 + iy, gx = x0 - 1 + ix;
-        bool inb = idx < NVOX * 2 && gz >= 0 && gz < D && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        soff[it] = inb ? ((gz * H + gy) * W + gx) * xcs + half * 8 : -1;
-    }
+    staging_map<T, BLK>(z0, y0, x0, D, H, W, xcs, soff, sdst);
     const bf16* xn = x + (int64_t)n * D * H * W * xcs;
     int nchunk = Cin / 16, chunk0 = 0;
     if (SPLITK) {
@@ -244,11 +410,7 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
         for (int c = 0; c < COB; c++) wf[s][c] = *wptr(chunk0, s, c);
     for (int chunk = chunk0; chunk < nchunk; chunk++) {
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < NIT; it++) {
-            int idx = threadIdx.x + it * BLK;
-            if (idx < NVOX * 2) *reinterpret_cast<bf16x8*>(xs + (IXP == IX ? idx * 8 : sdst[it])) = sv[it];
-        }
+        staging_store<T, BLK>(xs, sdst, sv);
         __syncthreads();
         // async-stage split: the next chunk's global loads are in flight while this chunk's MFMAs run
         if (chunk + 1 < nchunk) {
@@ -260,18 +422,11 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
         // (one sub-step) ahead of the MFMAs that consume them
         constexpr int FG = MB < 4 ? MB : 4;
         constexpr int SUBS = MB / FG, NSUB = 14 * SUBS;
-        auto frag_off = [&](int s) {
-            int t0 = 2 * s, t1 = (2 * s + 1 < 27) ? 2 * s + 1 : 26;
-            int off0 = (((t0 / 9) * IY + ((t0 / 3) % 3)) * IXP + (t0 % 3)) * 32;
-            int off1 = (((t1 / 9) * IY + ((t1 / 3) % 3)) * IXP + (t1 % 3)) * 32;
-            return laneOff + ((g >> 1) ? off1 : off0);
-        };
-        auto row_off = [&](int r) { return (((r / TXB) * BY) * IXP + (r % TXB) * BX) * 32; };
         bf16x8 xf[2][FG];
         {
-            int toff = frag_off(0);
+            int toff = frag_off<T>(0, laneOff, g);
 #pragma unroll
-            for (int r = 0; r < FG; r++) xf[0][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off(r));
+            for (int r = 0; r < FG; r++) xf[0][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(r));
         }
         bf16x8 wcur[COB];
 #pragma unroll
@@ -291,10 +446,10 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
             }
             if (u + 1 < NSUB) {
                 int s1 = (u + 1) / SUBS, h1 = (u + 1) % SUBS;
-                int toff = frag_off(s1);
+                int toff = frag_off<T>(s1, laneOff, g);
 #pragma unroll
                 for (int r = 0; r < FG; r++)
-                    xf[(u + 1) & 1][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off(h1 * FG + r));
+                    xf[(u + 1) & 1][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(h1 * FG + r));
             }
 #pragma unroll
             for (int r = 0; r < FG; r++)
@@ -304,81 +459,23 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
     }
 
     if constexpr (SPLITK) {
-        // fp32 partial tile: part[kz][voxel][CoutTotal], 4 channels (16 B) per lane
+        // part[kz][voxel][CoutTotal]
         int64_t Mtot = (int64_t)(bid_.gx / (tilesZ * tilesY * tilesX)) * D * H * W;
         float* pk = part + (int64_t)bid_.z * Mtot * CoutTotal;
 #pragma unroll
-        for (int r = 0; r < MB; r++) {
-            int bz = wave, byb = r / TXB, bxb = r % TXB;
-            int gz = z0 + bz, gy = y0 + byb * BY + vn / BX, gx = x0 + bxb * BX + vn % BX;
-            if (gz < D && gy < H && gx < W) {
-                float* pp = pk + ((((int64_t)n * D + gz) * H + gy) * W + gx) * CoutTotal + cobBase * 16 + g * 4;
-#pragma unroll
-                for (int c = 0; c < COB; c++) *reinterpret_cast<f32x4*>(pp + c * 16) = acc[r][c];
-            }
-        }
+        for (int r = 0; r < MB; r++) splitk_store<T, COB, false>(acc[r], pk, n, z0 + wave, y0, x0, r, vn, g, D, H, W, CoutTotal, cobBase);
         return;
     }
-    // ---- epilogue: bias, bf16 store (4 channels = 8 B per lane), BN partial statistics of the rounded values
+    // 8-byte stores only: the 16-byte ones measured slower in this body (see conv3_mfma_bwd_fused)
     float s1[COB][4], s2[COB][4];
 #pragma unroll
     for (int c = 0; c < COB; c++)
 #pragma unroll
         for (int j = 0; j < 4; j++) s1[c][j] = s2[c][j] = 0.f;
 #pragma unroll
-    for (int r = 0; r < MB; r++) {
-        int bz = wave, byb = r / TXB, bxb = r % TXB;
-        int gz = z0 + bz, gy = y0 + byb * BY + vn / BX, gx = x0 + bxb * BX + vn % BX;
-        bool ok = gz < D && gy < H && gx < W;
-        bf16* yp = y + ((((int64_t)n * D + gz) * H + gy) * W + gx) * ycs + cobBase * 16 + g * 4;
-        bf16x4 oc[COB];
-#pragma unroll
-        for (int c = 0; c < COB; c++) {
-            bf16x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float v = acc[r][c][j] + (bias ? bias[(cobBase + c) * 16 + g * 4 + j] : 0.f);
-                if (relu & 1) v = fmaxf(v, 0.f);       // inference: BatchNorm folded into (weights, bias), ReLU here
-                o[j] = (bf16)v;
-                if (STATS && ok) { float q = (float)o[j]; s1[c][j] += q; s2[c][j] += q * q; }
-            }
-            oc[c] = o;
-        }
-        if constexpr (COB == 2) {
-            if (relu & 2) {          // wide store: see conv3_mfma8_kernel
-                typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
-                typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-                u32x2 u0 = __builtin_bit_cast(u32x2, oc[0]), u1 = __builtin_bit_cast(u32x2, oc[1]);
-                u32x2 p0 = __builtin_amdgcn_permlane16_swap(u0[0], u1[0], false, false);
-                u32x2 p1 = __builtin_amdgcn_permlane16_swap(u0[1], u1[1], false, false);
-                u32x4 wv = {p0[0], p1[0], p0[1], p1[1]};
-                if (ok) *reinterpret_cast<u32x4*>(yp - g * 4 + (g & 1) * 16 + (g >> 1) * 8) = wv;
-                continue;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < COB; c++)
-            if (ok) *reinterpret_cast<bf16x4*>(yp + c * 16) = oc[c];
-    }
-    if constexpr (STATS) {
-#pragma unroll
-        for (int c = 0; c < COB; c++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float a = s1[c][j], b = s2[c][j];
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-                if (vn == 0) { red[wave][c][g * 4 + j][0] = a; red[wave][c][g * 4 + j][1] = b; }
-            }
-        __syncthreads();
-        // part[((blk*2 + k)*C + ch]  (same layout bn_stats_finalize consumes); blk = blockIdx.x, channels of this group
-        for (int idx = threadIdx.x; idx < COB * 16 * 2; idx += BLK) {
-            int k = idx & 1, ch = idx >> 1;
-            int c = ch / 16, cc = ch % 16;
-            float v = red[0][c][cc][k] + red[1][c][cc][k] + red[2][c][cc][k] + red[3][c][cc][k];
-            part[((int64_t)bid_.x * 2 + k) * CoutTotal + cobBase * 16 + ch] = v;
-        }
-    }
+    for (int r = 0; r < MB; r++)
+        conv_epilogue<T, COB, STATS, false>(acc[r], bias, y, ycs, relu, n, z0 + wave, y0, x0, r, vn, g, D, H, W, cobBase, s1, s2);
+    if constexpr (STATS) bn_rows_reduce<COB, 4, false>(s1, s2, red, wave, vn, g, part, bid_.x, CoutTotal, cobBase * 16);
 }
 
 template <int TZ, int TYB, int TXB, int BX, int COB, bool STATS, bool SPLITK>
@@ -392,9 +489,6 @@ __global__ __launch_bounds__(BLK) void conv3_mfma_kernel(const bf16* __restrict_
 
 
 // ------------------------------------------------------------------------------------------ eight-wave forward variant
-constexpr size_t conv8_lds(int TY, int TX, int COB) {        // TX == 8 <=> BX == 4 tilings: LDS row pitch 12 voxels (see the kernel)
-    return (size_t)6 * (TY + 2) * (TX == 8 ? 12 : TX + 2) * 32 + (size_t)14 * COB * 1024 + (size_t)8 * COB * 16 * 2 * 4;
-}
 // Levels 1-4 run ONE tile per workgroup with <= 2 workgroups per CU (432 tiles at level 1), so the serial chain of one
 // workgroup (tile loads -> LDS -> K loop -> stores) IS the kernel time.  This variant halves that chain per wave: 8 waves,
 // wave w owns z-slice w & 3 and HALF of the slice's M-blocks (w >> 2); staging is spread over 512 threads; the chunk's weight
@@ -410,22 +504,17 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
                                                             bf16* __restrict__ y, int ycs, int CoutTotal, int D, int H, int W,
                                                             int tilesZ, int tilesY, int tilesX, float* __restrict__ part, int relu,
                                                             float* tk_rows, int* tk_count) {
+    using T = ConvTile<TZ, TYB, TXB, BX>;
+    using L = Lds8<T, COB>;
     constexpr int NT = 512;
-    constexpr int BY = 16 / BX;
-    constexpr int TY = TYB * BY, TX = TXB * BX;
-    constexpr int IZ = TZ + 2, IY = TY + 2, IX = TX + 2;
-    // LDS row pitch in voxels.  With 4 x 4-voxel M-blocks (BX = 4) a 10-voxel pitch puts rows 0 and 3 of a block on the same
-    // banks of a ds_read_b128 lane group (SQ_LDS_BANK_CONFLICT 24-29 % of the LDS-active cycles of these kernels); 12 voxels
-    // (384 B = 128 mod 256) makes the 16 pieces of every lane group tile the 256-byte bank row exactly
-    constexpr int IXP = BX == 4 ? 12 : IX;
+    constexpr int TY = T::TY, TX = T::TX;
     static_assert(TZ == 4, "one z-slice of the tile per wave pair");
-    constexpr int MB = TYB * TXB, MBW = MB / 2;          // M-blocks per slice / per wave
+    constexpr int MB = T::MB, MBW = MB / 2;          // M-blocks per slice / per wave
     static_assert(MB % 2 == 0 && MBW <= 4, "two waves share a slice");
-    constexpr int NVOX = IZ * IY * IX, NVOXP = IZ * IY * IXP;
     extern __shared__ __attribute__((aligned(16))) char lds8[];
-    bf16* xs = reinterpret_cast<bf16*>(lds8);
-    bf16* wl = xs + NVOXP * 16;                                   // [14][COB][64 lanes][8] of the current chunk
-    float (*red)[COB][16][2] = reinterpret_cast<float (*)[COB][16][2]>(lds8 + (NVOXP * 16 + 14 * COB * 512) * 2);
+    bf16* xs = reinterpret_cast<bf16*>(lds8 + L::xs);
+    bf16* wl = reinterpret_cast<bf16*>(lds8 + L::wl);            // [14][COB][64 lanes][8] of the current chunk
+    float (*red)[COB][16][2] = reinterpret_cast<float (*)[COB][16][2]>(lds8 + L::red);
     Bid bid_ = real_bid();
     int tile = xcd_contig(bid_.x, bid_.gx);
     [[maybe_unused]] const int tile_id = tile;
@@ -438,25 +527,16 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int zs = wave & 3, hb = wave >> 2;
     int vn = lane & 15, g = lane >> 4;
-    int laneOff = (((vn / BX) * IXP + (vn % BX)) * 16 + (g & 1) * 8) * 2 + zs * (IY * IXP * 32);
+    int laneOff = (((vn / BX) * T::IXP + (vn % BX)) * 16 + (g & 1) * 8) * 2 + zs * (T::IY * T::IXP * 32);
     const char* xsb = reinterpret_cast<const char*>(xs);
     f32x4 acc[MBW][COB];
 #pragma unroll
     for (int r = 0; r < MBW; r++)
 #pragma unroll
         for (int c = 0; c < COB; c++) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr int NIT = (NVOX * 2 + NT - 1) / NT;
+    constexpr int NIT = T::pieces(NT);
     int soff[NIT], sdst[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        int idx = threadIdx.x + it * NT;
-        int vox = idx >> 1, half = idx & 1;
-        int ix = vox % IX, t = vox / IX, iy = t % IY, iz = t / IY;
-        sdst[it] = IXP == IX ? 0 : (t * IXP + ix) * 16 + half * 8;              // element offset of the piece in the (padded) LDS tile
-        int gz = z0 - 1 + iz, gy = y0 - 1 + iy, gx = x0 - 1 + ix;
-        bool inb = idx < NVOX * 2 && gz >= 0 && gz < D && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        soff[it] = inb ? ((gz * H + gy) * W + gx) * xcs + half * 8 : -1;
-    }
+    staging_map<T, NT>(z0, y0, x0, D, H, W, xcs, soff, sdst);
     const bf16* xn = x + (int64_t)n * D * H * W * xcs;
     int nchunk = Cin / 16, chunk0 = 0;
     if (SPLITK) {
@@ -483,20 +563,9 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
         }
     };
     load_chunk(chunk0);
-    auto frag_off = [&](int s) {
-        int t0 = 2 * s, t1 = (2 * s + 1 < 27) ? 2 * s + 1 : 26;
-        int off0 = (((t0 / 9) * IY + ((t0 / 3) % 3)) * IXP + (t0 % 3)) * 32;
-        int off1 = (((t1 / 9) * IY + ((t1 / 3) % 3)) * IXP + (t1 % 3)) * 32;
-        return laneOff + ((g >> 1) ? off1 : off0);
-    };
-    auto row_off = [&](int r) { int rg = hb * MBW + r; return (((rg / TXB) * BY) * IXP + (rg % TXB) * BX) * 32; };
     for (int chunk = chunk0; chunk < nchunk; chunk++) {
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < NIT; it++) {
-            int idx = threadIdx.x + it * NT;
-            if (idx < NVOX * 2) *reinterpret_cast<bf16x8*>(xs + (IXP == IX ? idx * 8 : sdst[it])) = sv[it];
-        }
+        staging_store<T, NT>(xs, sdst, sv);
 #pragma unroll
         for (int i = 0; i < NWI; i++) {
             int q = threadIdx.x + i * NT;
@@ -506,9 +575,9 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
         if (chunk + 1 < nchunk) load_chunk(chunk + 1);        // in flight under this chunk's K loop
         bf16x8 xq[2][MBW];
         {
-            int toff = frag_off(0);
+            int toff = frag_off<T>(0, laneOff, g);
 #pragma unroll
-            for (int r = 0; r < MBW; r++) xq[0][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off(r));
+            for (int r = 0; r < MBW; r++) xq[0][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(hb * MBW + r));
         }
 #pragma unroll
         for (int s = 0; s < 14; s++) {
@@ -516,9 +585,9 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
 #pragma unroll
             for (int c = 0; c < COB; c++) wcur[c] = *reinterpret_cast<const bf16x8*>(wl + ((s * COB + c) * 64 + lane) * 8);
             if (s + 1 < 14) {
-                int toff = frag_off(s + 1);
+                int toff = frag_off<T>(s + 1, laneOff, g);
 #pragma unroll
-                for (int r = 0; r < MBW; r++) xq[(s + 1) & 1][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off(r));
+                for (int r = 0; r < MBW; r++) xq[(s + 1) & 1][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(hb * MBW + r));
             }
 #pragma unroll
             for (int r = 0; r < MBW; r++)
@@ -530,21 +599,8 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
         int64_t Mtot = (int64_t)(bid_.gx / (tilesZ * tilesY * tilesX)) * D * H * W;
         float* pk = part + (int64_t)bid_.z * Mtot * CoutTotal;
 #pragma unroll
-        for (int r = 0; r < MBW; r++) {
-            int rg = hb * MBW + r;
-            int byb = rg / TXB, bxb = rg % TXB;
-            int gz = z0 + zs, gy = y0 + byb * BY + vn / BX, gx = x0 + bxb * BX + vn % BX;
-            if (gz < D && gy < H && gx < W) {
-                float* pp = pk + ((((int64_t)n * D + gz) * H + gy) * W + gx) * CoutTotal + cobBase * 16 + g * 4;
-#pragma unroll
-                for (int c = 0; c < COB; c++) {
-                    if constexpr (TK) {          // write-through (agent-coherent) store: the finishing workgroup sits on another XCD
-                        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(pp + c * 16), "v"(acc[r][c]) : "memory");
-                    } else
-                        *reinterpret_cast<f32x4*>(pp + c * 16) = acc[r][c];
-                }
-            }
-        }
+        for (int r = 0; r < MBW; r++)
+            splitk_store<T, COB, TK>(acc[r], pk, n, z0 + zs, y0, x0, hb * MBW + r, vn, g, D, H, W, CoutTotal, cobBase);
         if constexpr (!TK) return;
         else {
             // ---- split-K ticket: the last of this (tile, output group)'s ks workgroups finishes the tile.  Release the partials
@@ -567,7 +623,7 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
             const bool last = s_last != 0;
             __syncthreads();                                           // (red is reused below)
             if (!last) return;
-            constexpr int NVT = TZ * TY * TX, G8 = COB * 2;          // voxels of the tile, 8-channel groups of this workgroup
+            constexpr int NVT = T::NVT, G8 = COB * 2;                 // voxels of the tile, 8-channel groups of this workgroup
             static_assert(NT % G8 == 0, "a thread keeps its channel group");
             const int grp = threadIdx.x % G8, ch0 = cobBase * 16 + grp * 8;
             float bv8[8], s1[8], s2[8];
@@ -622,13 +678,7 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
                 }
             }
             __syncthreads();
-            for (int idx = threadIdx.x; idx < COB * 16 * 2; idx += NT) {
-                const int k = idx & 1, ch = idx >> 1;
-                float v = 0.f;
-#pragma unroll
-                for (int w_ = 0; w_ < 8; w_++) v += red[w_][ch / 16][ch % 16][k];
-                tk_rows[((int64_t)bid_.x * 2 + k) * CoutTotal + cobBase * 16 + ch] = v;
-            }
+            bn_row_write<COB, 8, false>(red, tk_rows, bid_.x, CoutTotal, cobBase * 16);
             return;
         }
     }
@@ -638,72 +688,17 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
 #pragma unroll
         for (int j = 0; j < 4; j++) s1[c][j] = s2[c][j] = 0.f;
 #pragma unroll
-    for (int r = 0; r < MBW; r++) {
-        int rg = hb * MBW + r;
-        int byb = rg / TXB, bxb = rg % TXB;
-        int gz = z0 + zs, gy = y0 + byb * BY + vn / BX, gx = x0 + bxb * BX + vn % BX;
-        bool ok = gz < D && gy < H && gx < W;
-        bf16* yp = y + ((((int64_t)n * D + gz) * H + gy) * W + gx) * ycs + cobBase * 16 + g * 4;
-        bf16x4 oc[COB];
-#pragma unroll
-        for (int c = 0; c < COB; c++) {
-            bf16x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float v = acc[r][c][j] + (bias ? bias[(cobBase + c) * 16 + g * 4 + j] : 0.f);
-                if (relu & 1) v = fmaxf(v, 0.f);
-                o[j] = (bf16)v;
-                if (STATS && ok) { float q = (float)o[j]; s1[c][j] += q; s2[c][j] += q * q; }
-            }
-            oc[c] = o;
-        }
-        if constexpr (COB == 2) {
-            if (relu & 2) {
-                // wide store (round 4): the lane's two 4-channel pieces (output blocks 0 and 1 of ONE voxel) trade halves with the
-                // neighbouring 16-lane rows (v_permlane16_swap); lane (vn, g) then holds channels (g & 1) * 16 + (g >> 1) * 8 .. + 7:
-                // one 16-B store per lane, the voxel's 64 B written by four lanes
-                typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
-                typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-                u32x2 u0 = __builtin_bit_cast(u32x2, oc[0]), u1 = __builtin_bit_cast(u32x2, oc[1]);
-                u32x2 p0 = __builtin_amdgcn_permlane16_swap(u0[0], u1[0], false, false);
-                u32x2 p1 = __builtin_amdgcn_permlane16_swap(u0[1], u1[1], false, false);
-                u32x4 wv = {p0[0], p1[0], p0[1], p1[1]};
-                if (ok) *reinterpret_cast<u32x4*>(yp - g * 4 + (g & 1) * 16 + (g >> 1) * 8) = wv;
-                continue;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < COB; c++)
-            if (ok) *reinterpret_cast<bf16x4*>(yp + c * 16) = oc[c];
-    }
-    if constexpr (STATS) {
-#pragma unroll
-        for (int c = 0; c < COB; c++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float a = s1[c][j], b = s2[c][j];
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-                if (vn == 0) { red[wave][c][g * 4 + j][0] = a; red[wave][c][g * 4 + j][1] = b; }
-            }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < COB * 16 * 2; idx += NT) {
-            int k = idx & 1, ch = idx >> 1;
-            int c = ch / 16, cc = ch % 16;
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; w++) v += red[w][c][cc][k];
-            part[((int64_t)bid_.x * 2 + k) * CoutTotal + cobBase * 16 + ch] = v;
-        }
-    }
+    for (int r = 0; r < MBW; r++)
+        conv_epilogue<T, COB, STATS, true>(acc[r], bias, y, ycs, relu, n, z0 + zs, y0, x0, hb * MBW + r, vn, g, D, H, W, cobBase, s1, s2);
+    if constexpr (STATS) bn_rows_reduce<COB, 8, false>(s1, s2, red, wave, vn, g, part, bid_.x, CoutTotal, cobBase * 16);
 }
 
 // ------------------------------------------------------------------------------------------ persistent variant
 // Full-resolution layers (16->16, 32->16, 16->32: 60 % of all conv FLOPs and most of the bytes).  Same math and tile
 // (4 x 8 x 16 voxels) as conv3_mfma_kernel, restructured around what the profile showed (instruction-issue bound,
 // ~1100 instructions per 112 MFMAs, most of it per-workgroup setup):
-//   * a workgroup is PERSISTENT and strides over tiles: the staging map (piece -> relative offset) and ALL weight
-//     fragments (NCH*14*COB x 16 B per lane, <= 112 VGPRs) are set up once and stay in registers;
+//   * a workgroup is PERSISTENT and strides over tiles: the staging map (piece -> relative offset, in registers) and ALL
+//     weight fragments (NCH*14*COB x 1 KB, in LDS) are set up once;
 //   * interior tiles take a check-free staging path (one add per 16-B piece); only border tiles test coordinates;
 //   * the next tile's (or chunk's) global loads are issued before the MFMA loop of the current one (T14 split);
 //   * BatchNorm partial sums accumulate in registers across tiles -> ONE partial row per workgroup.
@@ -714,23 +709,26 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
                                                         int tilesZ, int tilesY, int tilesX, int ntiles,
                                                         float* __restrict__ part, Halves xh, Halves yh, char* ext_lds = nullptr,
                                                         int relu = 0) {
-    constexpr int TZ = 4, TY = 8, TX = 16, IZ = 6, IY = 10, IX = 18, MB = 8;
-    constexpr int NVOX = IZ * IY * IX, NIT = (NVOX * 2 + BLK - 1) / BLK;
+    using T = FullTile;
+    using L = LdsP<COB, NCH>;
+    constexpr int TZ = T::TZ, TY = T::TY, TX = T::TX, IY = T::IY, IX = T::IX, MB = T::MB;
+    static_assert(T::BX == 16 && T::IXP == IX && MB == 8, "a lane's voxel is x position vn of M-block row r; rows are not padded");
+    constexpr int NVOX = T::NVOX, NIT = T::pieces(BLK);
     constexpr int CoutTotal = COB * 16;
-    // weights: resident in registers when they are 56 VGPRs (16->16), otherwise resident in LDS (28 KB) so that two
-    // workgroups still fit per CU (registers AND LDS)
-    constexpr bool WLDS = true;      // registers go to the F/G row fragments; weights (14-28 KB) live in LDS
+    // weights (14-28 KB) are resident in LDS: the registers go to the F/G row fragments, and two workgroups still fit per CU
+    // (registers AND LDS)
     constexpr int NWF = NCH * 14 * COB;
     bf16* xs; bf16* wl;
     float (*red)[COB][16][2];
     if constexpr (EXT_LDS) {              // fused launch: one dynamic LDS block shared with the other body
-        xs = reinterpret_cast<bf16*>(ext_lds);
-        wl = xs + NVOX * 16;
-        red = reinterpret_cast<float (*)[COB][16][2]>(ext_lds + (NVOX * 16 + NWF * 512) * 2);
+        xs = reinterpret_cast<bf16*>(ext_lds + L::xs);
+        wl = reinterpret_cast<bf16*>(ext_lds + L::wl);
+        red = reinterpret_cast<float (*)[COB][16][2]>(ext_lds + L::red);
     } else {
-        __shared__ __attribute__((aligned(16))) bf16 xs_s[NVOX * 16];
-        __shared__ __attribute__((aligned(16))) bf16 wl_s[WLDS ? NWF * 512 : 8];
+        __shared__ __attribute__((aligned(16))) bf16 xs_s[(L::wl - L::xs) / 2];
+        __shared__ __attribute__((aligned(16))) bf16 wl_s[(L::red - L::wl) / 2];
         __shared__ float red_s[4][COB][16][2];
+        static_assert(sizeof(xs_s) + sizeof(wl_s) + sizeof(red_s) == L::bytes, "the three arrays are the layout");
         xs = xs_s; wl = wl_s; red = red_s;
     }
     int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -759,16 +757,6 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
         int ix = vox % IX, t = vox / IX, iy = t % IY, iz = t / IY;
         if (iz > 7) iz = 7;                                    // only the invalid tail pieces of the last iteration
         pk[it >> 1] |= (unsigned)(ix | (iy << 5) | (iz << 9)) << ((it & 1) * 16);
-    }
-    bf16x8 wf[WLDS ? 1 : NCH][WLDS ? 1 : 14][COB];
-    if constexpr (!WLDS) {
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++)
-#pragma unroll
-            for (int s = 0; s < 14; s++)
-#pragma unroll
-                for (int c = 0; c < COB; c++)
-                    wf[ch][s][c] = *reinterpret_cast<const bf16x8*>(wp + (((int64_t)ch * 14 + s) * COB + c) * 512 + lane * 8);
     }
     float bv[COB][4];
 #pragma unroll
@@ -818,18 +806,12 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
 
     // XCD-aware start: workgroups b, b+8, b+16.. share an XCD (round-robin dispatch) -> give them ADJACENT tiles so
     // the halo voxels neighbouring tiles share are served by that XCD's L2 instead of the fabric (bijective remap)
-    int tile;
-    {
-        int nwg = bid_.gx, bid = bid_.x, q8 = nwg / 8, r8 = nwg % 8, xcd = bid % 8, idx = bid / 8;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-    }
+    int tile = xcd_contig(bid_.x, bid_.gx);
     if (tile < ntiles) load_pieces(tile, 0);
     // weights -> LDS AFTER the first tile's loads are in flight (both are cold fetches; the tile loop's first barrier orders
     // these LDS writes before any fragment read)
-    if constexpr (WLDS) {
-        for (int i = threadIdx.x; i < NWF * 64; i += BLK)
-            *reinterpret_cast<bf16x8*>(wl + i * 8) = *reinterpret_cast<const bf16x8*>(wp + (int64_t)i * 8);
-    }
+    for (int i = threadIdx.x; i < NWF * 64; i += BLK)
+        *reinterpret_cast<bf16x8*>(wl + i * 8) = *reinterpret_cast<const bf16x8*>(wp + (int64_t)i * 8);
     for (; tile < ntiles; tile += bid_.gx) {
         f32x4 acc[MB][COB];
 #pragma unroll
@@ -851,8 +833,7 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
             // M-block row y read halo row y+dy: 10 row fragments F[0..9] feed 24 MFMAs (2.4x fewer ds_read_b128); the
             // dx = 2 taps pair up over dy (G), the last two K-steps over dz.  70 instead of 112 LDS reads per chunk.
             auto W_ = [&](int s, int c) -> bf16x8 {
-                if constexpr (WLDS) return *reinterpret_cast<const bf16x8*>(wl + ((ch * 14 + s) * COB + c) * 512 + lane * 8);
-                else return wf[ch][s][c];
+                return *reinterpret_cast<const bf16x8*>(wl + ((ch * 14 + s) * COB + c) * 512 + lane * 8);
             };
             const int hx = (g >> 1) * 32;                       // lane half -> dx = 0 | 1
             const int hy = (g >> 1) * (IX * 32) + 64;           // lane half -> dy = 0 | 1 at dx = 2
@@ -921,15 +902,16 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
         bf16* yrow = y + ((((int64_t)n * D + gz) * H + y0) * W + gx) * ycs + g * 4;
         bool okzx = gz < D && gx < W;
         if (relu & 2) {
-            // wide stores (round 4): a lane holds 4 channels (8 B) of one voxel per M-block row; rows r and r + 1 trade halves through
-            // v_permlane16_swap (odd 16-lane rows of the first operand <-> even rows of the second), after which lane (vn, g) holds 8
-            // consecutive channels (g >> 1) * 8 .. + 7 of voxel vn in row r + (g & 1): ONE 16-B store instead of two 8-B ones
+            // wide stores (round 4): a lane holds 4 channels (8 B) of one voxel per M-block row; rows r and r + 1 trade halves
+            // between 16-lane rows, after which lane (vn, g) holds 8 consecutive channels (g >> 1) * 8 .. + 7 of voxel vn in
+            // row r + (g & 1): ONE 16-B store instead of two 8-B ones
             bf16* ywide = y + ((((int64_t)n * D + gz) * H + y0 + (g & 1)) * W + gx) * ycs + (g >> 1) * 8;
 #pragma unroll
             for (int r = 0; r < MB; r += 2) {
                 const bool okw = okzx && (y0 + r + (g & 1)) < H;
 #pragma unroll
                 for (int c = 0; c < COB; c++) {
+                    // the two rows interleaved per channel, not two round4_masked calls: those cost <1,1,true> four VGPRs
                     bf16x4 oa, ob;
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
@@ -942,12 +924,7 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
                             s1[c][j] += qb; s2[c][j] = fmaf(qb, qb, s2[c][j]);
                         }
                     }
-                    typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
-                    typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-                    u32x2 ua = __builtin_bit_cast(u32x2, oa), ub = __builtin_bit_cast(u32x2, ob);
-                    u32x2 s0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
-                    u32x2 s1_ = __builtin_amdgcn_permlane16_swap(ua[1], ub[1], false, false);
-                    u32x4 w = {s0[0], s1_[0], s0[1], s1_[1]};
+                    u32x4 w = swap_halves16(oa, ob);
                     if (okw) *reinterpret_cast<u32x4*>(ywide + (int64_t)r * W * ycs + c * 16 + (c >= yh.split ? yh.delta : 0)) = w;
                 }
             }
@@ -958,36 +935,12 @@ __device__ __forceinline__ void conv3_mfma_persist_body(Bid bid_, const bf16* __
             bool ok = okzx && (y0 + r) < H;
 #pragma unroll
             for (int c = 0; c < COB; c++) {
-                bf16x4 o;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float v = acc[r][c][j] + bv[c][j];
-                    if (relu) v = fmaxf(v, 0.f);
-                    o[j] = (bf16)v;
-                    if (STATS) { float q = ok ? (float)o[j] : 0.f; s1[c][j] += q; s2[c][j] = fmaf(q, q, s2[c][j]); }
-                }
+                bf16x4 o = round4_masked<STATS>(acc[r][c], bv[c], relu, ok, s1[c], s2[c]);
                 if (ok) *reinterpret_cast<bf16x4*>(yrow + (int64_t)r * W * ycs + c * 16 + (c >= yh.split ? yh.delta : 0)) = o;
             }
         }
     }
-    if constexpr (STATS) {
-#pragma unroll
-        for (int c = 0; c < COB; c++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float a = s1[c][j], b = s2[c][j];
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-                if (vn == 0) { red[wave][c][g * 4 + j][0] = a; red[wave][c][g * 4 + j][1] = b; }
-            }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < COB * 16 * 2; idx += BLK) {
-            int k = idx & 1, chn = idx >> 1;
-            int c = chn / 16, cc = chn % 16;
-            float v = (red[0][c][cc][k] + red[1][c][cc][k]) + (red[2][c][cc][k] + red[3][c][cc][k]);
-            part[((int64_t)bid_.x * 2 + k) * CoutTotal + chn] = v;
-        }
-    }
+    if constexpr (STATS) bn_rows_reduce<COB, 4, true>(s1, s2, red, wave, vn, g, part, bid_.x, CoutTotal, 0);
 }
 
 template <int COB, int NCH, bool STATS>
@@ -1020,10 +973,20 @@ inline int device_cus() {
 struct TimeHook { hipEvent_t e0 = nullptr, e1 = nullptr; int kind = -1, cin = 0, cout = 0; bool armed = false, fired = false; };
 static thread_local TimeHook g_hook;
 inline bool time_hook_take(int kind, int cin, int cout, hipEvent_t& e0, hipEvent_t& e1) {
-    if (!g_hook.armed || g_hook.kind != kind || g_hook.cin != cin || g_hook.cout != cout) return false;
+    if (kind < 0 || !g_hook.armed || g_hook.kind != kind || g_hook.cin != cin || g_hook.cout != cout) return false;
     e0 = g_hook.e0; e1 = g_hook.e1;
     g_hook.armed = false; g_hook.fired = true;
     return true;
+}
+// one launch of Kernel, bracketed by the hook's events when this launch is the one it waits for (kind < 0: never)
+template <auto Kernel, typename... Args>
+int launch_hooked(dim3 grid, dim3 block, size_t lds, hipStream_t s, int kind, int cin, int cout, Args... args) {
+    if (lds) MI3D_SET_MAX_LDS_ONCE(Kernel, lds);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (time_hook_take(kind, cin, cout, e0, e1)) hipExtLaunchKernelGGL(Kernel, grid, block, lds, s, e0, e1, 0, args...);
+    else Kernel<<<grid, block, lds, s>>>(args...);
+    MI3D_LAUNCH_CHECK();
+    return 0;
 }
 
 inline bool persist_ok(int Cin, int Cout, Geo g) {
@@ -1073,47 +1036,45 @@ template <int TZ, int TYB, int TXB, int BX, int COB>
 int launch_cfg(const bf16* x, int xcs, int Cin, const bf16* wp, const float* bias, bf16* y, int ycs, int Cout, Geo g,
                float* part, int ksplit, float* skws, hipStream_t s, bool defer_finish = false, int relu = 0,
                float* tk_rows = nullptr, int* tk_count = nullptr) {
-    constexpr int TY = TYB * (16 / BX), TX = TXB * BX;
-    int tz = cdiv(g.D, TZ), ty = cdiv(g.H, TY), tx = cdiv(g.W, TX);
+    using T = ConvTile<TZ, TYB, TXB, BX>;
+    int tz = cdiv(g.D, TZ), ty = cdiv(g.H, T::TY), tx = cdiv(g.W, T::TX);
     dim3 grid((unsigned)(g.N * tz * ty * tx), (unsigned)(Cout / (16 * COB)), (unsigned)ksplit);
+    constexpr size_t lds8 = Lds8<T, COB>::bytes;
     if (tk_rows) {       // split-K launch that finishes itself (ticket per (tile, output group)); eight-wave kernel only
         MI3D_CHECK_ARG(ksplit > 1 && tk_count && mi3d_routes().conv8 != 0 &&
                        (int64_t)grid.x * grid.y <= CONV3_TK_COUNTERS && ycs % 8 == 0 && ((uintptr_t)y % 16) == 0,
                        "conv3_mfma: this launch cannot take the split-K ticket");
-        constexpr size_t lds_tk = conv8_lds(TY, TX, COB);
-        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, true>), lds_tk);
-        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, true><<<grid, 512, lds_tk, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W,
-                                                                                             tz, ty, tx, skws, 0, tk_rows, tk_count);
+        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, true>), lds8);
+        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, false, true, true><<<grid, 512, lds8, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W,
+                                                                                           tz, ty, tx, skws, 0, tk_rows, tk_count);
         MI3D_LAUNCH_CHECK();
         return 0;
     }
-    // eight-wave variant (see conv3_mfma8_kernel); MI3D_CONV8=0 selects the four-wave kernels
-    static_assert((TYB * TXB) % 2 == 0, "tile shapes used here have an even number of M-blocks per slice");
-    const bool w8 = mi3d_routes().conv8 != 0;
-    constexpr size_t lds8 = conv8_lds(TY, TX, COB);
-#define LC8(ST_, SK_, PART_, BIAS_, RELU_)                                                                                     \
-    do {                                                                                                                       \
-        MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST_, SK_>), lds8);                                   \
-        conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST_, SK_><<<grid, 512, lds8, s>>>(x, xcs, Cin, wp, BIAS_, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, PART_, RELU_, \
-                                                                                   nullptr, nullptr);                          \
-    } while (0)
-    if (ksplit > 1) {
-        if (w8) LC8(false, true, skws, nullptr, 0);
-        else conv3_mfma_kernel<TZ, TYB, TXB, BX, COB, false, true><<<grid, BLK, 0, s>>>(x, xcs, Cin, wp, nullptr, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, skws, 0);
+    // eight-wave kernel (route conv8, default on; MI3D_CONV8=0 selects the four-wave kernels, which store 8 bytes only)
+    static_assert(T::MB % 2 == 0, "tile shapes used here have an even number of M-blocks per slice");
+    auto launch = [&](auto stats, auto splitk, const float* b, float* p, int rl) -> int {
+        constexpr bool ST = decltype(stats)::value, SK = decltype(splitk)::value;
+        if (mi3d_routes().conv8 != 0) {
+            MI3D_SET_MAX_LDS_ONCE((&conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST, SK>), lds8);
+            conv3_mfma8_kernel<TZ, TYB, TXB, BX, COB, ST, SK><<<grid, 512, lds8, s>>>(x, xcs, Cin, wp, b, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, p,
+                                                                                    rl, nullptr, nullptr);
+        } else
+            conv3_mfma_kernel<TZ, TYB, TXB, BX, COB, ST, SK><<<grid, BLK, 0, s>>>(x, xcs, Cin, wp, b, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, p,
+                                                                                rl & 1);
         MI3D_LAUNCH_CHECK();
+        return 0;
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (ksplit > 1) {
+        MI3D_TRY(launch(no, yes, nullptr, skws, 0));
         if (defer_finish) return 0;
         int64_t tot = g.M() * (Cout / 8);
         splitk_finish_kernel<<<cdiv(tot, BLK) > 2048 ? 2048 : cdiv(tot, BLK), BLK, 0, s>>>(skws, ksplit, g.M(), Cout, bias, y, ycs, relu & 1);
-    } else if (part) {
-        if (w8) LC8(true, false, part, bias, relu);
-        else conv3_mfma_kernel<TZ, TYB, TXB, BX, COB, true, false><<<grid, BLK, 0, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, part, relu & 1);
-    } else {
-        if (w8) LC8(false, false, nullptr, bias, relu);
-        else conv3_mfma_kernel<TZ, TYB, TXB, BX, COB, false, false><<<grid, BLK, 0, s>>>(x, xcs, Cin, wp, bias, y, ycs, Cout, g.D, g.H, g.W, tz, ty, tx, nullptr, relu & 1);
+        MI3D_LAUNCH_CHECK();
+        return 0;
     }
-#undef LC8
-    MI3D_LAUNCH_CHECK();
-    return 0;
+    return part ? launch(yes, no, bias, part, relu) : launch(no, no, bias, nullptr, relu);
 }
 
 inline bool big_geo(Geo g) { return g.W >= 32 && g.H >= 16; }
@@ -1215,22 +1176,18 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
         int tz = cdiv(g.D, 4), ty = cdiv(g.H, 8), tx = cdiv(g.W, 16), nt = g.N * tz * ty * tx, grid = persist_grid(Cin, Cout, g);
         // bit 1 of the relu word: 16-byte epilogue stores (two M-block rows trade halves through v_permlane16_swap)
         if (ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && yh.delta % 8 == 0) relu |= 2;
-#define PK(COB_, NCH_)                                                                                                         \
-        do {                                                                                                                   \
-            hipEvent_t tev0 = nullptr, tev1 = nullptr;                                                                          \
-            if (time_hook_take(part ? 2 : 3, Cin, Cout, tev0, tev1)) {                                                          \
-                if (part) hipExtLaunchKernelGGL((conv3_mfma_persist_kernel<COB_, NCH_, true>), dim3(grid), dim3(BLK), 0, s, tev0, tev1, 0, xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, part, xh, yh, relu); \
-                else hipExtLaunchKernelGGL((conv3_mfma_persist_kernel<COB_, NCH_, false>), dim3(grid), dim3(BLK), 0, s, tev0, tev1, 0, xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, (float*)nullptr, xh, yh, relu); \
-            }                                                                                                                   \
-            else if (part) conv3_mfma_persist_kernel<COB_, NCH_, true><<<grid, BLK, 0, s>>>(xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, part, xh, yh, relu); \
-            else conv3_mfma_persist_kernel<COB_, NCH_, false><<<grid, BLK, 0, s>>>(xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W, tz, ty, tx, nt, nullptr, xh, yh, relu); \
-        } while (0)
-        if (Cin == 16 && Cout == 16) PK(1, 1);
-        else if (Cin == 32) PK(1, 2);
-        else PK(2, 1);
-#undef PK
-        MI3D_LAUNCH_CHECK();
-        return 0;
+        // hook kind 2 = with BatchNorm partial sums (training forward), 3 = without (input gradient)
+        auto launch = [&](auto cob, auto nch) -> int {
+            constexpr int COB = decltype(cob)::value, NCH = decltype(nch)::value;
+            if (part)
+                return launch_hooked<conv3_mfma_persist_kernel<COB, NCH, true>>(grid, BLK, 0, s, 2, Cin, Cout, xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W,
+                                                                                tz, ty, tx, nt, part, xh, yh, relu);
+            return launch_hooked<conv3_mfma_persist_kernel<COB, NCH, false>>(grid, BLK, 0, s, 3, Cin, Cout, xp, xcs, w, bias, yp, ycs, g.D, g.H, g.W,
+                                                                             tz, ty, tx, nt, (float*)nullptr, xh, yh, relu);
+        };
+        constexpr std::integral_constant<int, 1> one{};
+        constexpr std::integral_constant<int, 2> two{};
+        return Cin == 16 && Cout == 16 ? launch(one, one) : Cin == 32 ? launch(one, two) : launch(two, one);
     }
     int ks = skws ? pick_ksplit(Cin, Cout, g, split_target) : 1;
     // bit 1 of the relu word: 16-byte epilogue stores in the eight-wave kernels (two output blocks per workgroup)
@@ -1265,19 +1222,16 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
 // more tap/channel groups for the weight-heavy deep layers.  Zero-filled staging makes ragged volumes exact.
 namespace {
 
-constexpr int WTZ = 4, WTY = 8, WTX = 16, WIZ = 6, WIY = 10, WIX = 18;
-constexpr int WNV = WTZ * WTY * WTX, WNH = WIZ * WIY * WIX;
-
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-__device__ __forceinline__ bf16x8 tr_frag(const char* base, int byteoff) {
-    // two transposed reads: voxels +0..3 and +4..7 (128 B further) of this lane group's 8-voxel run
-    auto* p0 = (lds_bf16x4*)(base + byteoff);
-    auto* p1 = (lds_bf16x4*)(base + byteoff + 128);
-    bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p0);
-    bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p1);
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
+// the weight gradients and the first-layer kernels work on the 4 x 8 x 16 tile and its 6 x 10 x 18 halo
+constexpr int WTZ = FullTile::TZ, WTY = FullTile::TY, WTX = FullTile::TX, WIZ = FullTile::IZ, WIY = FullTile::IY, WIX = FullTile::IX;
+constexpr int WNV = FullTile::NVT, WNH = FullTile::NVOX;
+// LDS of conv3_wgrad_body: dy tiles [CO_B][WNV][16] | x halo tiles [CI_B][WNH][16]; the block is reused for the cross-wave
+// reduction (reduce_waves: 16 tiles x 64 lanes x 16 B) and the bias-gradient rows
+template <int CO_B, int CI_B>
+struct LdsWg {
+    static constexpr int dys = 0, xs = CO_B * WNV * 32, bytes = xs + CI_B * WNH * 32;
+    static_assert(bytes >= 16 * 64 * 16, "reduce_waves reuses the block");
+};
 
 // reduce NTILE per-wave accumulator tiles across the 4 waves through LDS; `emit(idx, f32x4 sum)` is called by
 // wave (idx % 4) for tile idx
@@ -1312,8 +1266,9 @@ __device__ __forceinline__ void conv3_wgrad_body(Bid bid_, const bf16* __restric
     // ADJACENT tiles (xcd_contig), so that the x-halo voxels neighbouring tiles share are served by that XCD's L2.  Before, tile =
     // slab index put neighbouring tiles on neighbouring XCDs and every halo was fetched twice (decoder.3.conv0: 261 MB for 170 MB)
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    bf16* dys = reinterpret_cast<bf16*>(lds_raw);                 // [CO_B][WNV][16]
-    bf16* xs = dys + CO_B * WNV * 16;                             // [CI_B][WNH][16]
+    using L = LdsWg<CO_B, CI_B>;
+    bf16* dys = reinterpret_cast<bf16*>(lds_raw + L::dys);        // [CO_B][WNV][16]
+    bf16* xs = reinterpret_cast<bf16*>(lds_raw + L::xs);          // [CI_B][WNH][16]
     const char* dysb = reinterpret_cast<const char*>(dys);
     const char* xsb = reinterpret_cast<const char*>(xs);
     int sb = bid_.x / TG, tg = bid_.x - sb * TG, nsb = bid_.gx / TG;
@@ -1511,7 +1466,6 @@ struct FusedArgs {
     const bf16* dxin; int dxcs_in, dCin; const bf16* dwp; bf16* dyout; int dycs_out, dCout; int dtZ, dtY, dtX; float* dpart;
     int dgx, dgy, dgz;
     int N, D, H, W;
-    int flags;                // bit 1: 16-byte epilogue stores in the input-gradient half (never set, see conv3_mfma_bwd_fused)
 };
 // Full-resolution variant: the input-gradient conv is the persistent kernel body.  Both halves are persistent with ONE
 // workgroup per CU each, so every CU runs one MFMA-heavy dgrad workgroup beside one staging/LDS-heavy wgrad workgroup
@@ -1569,14 +1523,12 @@ __global__ __launch_bounds__(BLK, 2) void conv3_bwd_fused_kernel(FusedArgs a) {
             int f = xcd_contig(b, a.dgx * a.dgy);
             Bid v{f / a.dgy, f % a.dgy, 0, a.dgx, a.dgy, 1, true};
             conv3_mfma_body<4, 8, 1, 16, 2, false, false, true>(v, a.dxin, a.dxcs_in, a.dCin, a.dwp, nullptr, a.dyout, a.dycs_out, a.dCout,
-                                                                a.D, a.H, a.W, a.dtZ, a.dtY, a.dtX, nullptr, fused_lds, a.flags);
-            return;
-        }
-        Bid v{b % a.dgx, (b / a.dgx) % a.dgy, b / (a.dgx * a.dgy), a.dgx, a.dgy, a.dgz};
-        if constexpr (BIG) {}
-        else
+                                                                a.D, a.H, a.W, a.dtZ, a.dtY, a.dtX, nullptr, fused_lds);
+        } else {
+            Bid v{b % a.dgx, (b / a.dgx) % a.dgy, b / (a.dgx * a.dgy), a.dgx, a.dgy, a.dgz};
             conv3_mfma_body<4, 2, 2, 4, 2, false, SPLITK, true>(v, a.dxin, a.dxcs_in, a.dCin, a.dwp, nullptr, a.dyout, a.dycs_out, a.dCout,
-                                                                a.D, a.H, a.W, a.dtZ, a.dtY, a.dtX, a.dpart, fused_lds, a.flags);
+                                                                a.D, a.H, a.W, a.dtZ, a.dtY, a.dtX, a.dpart, fused_lds);
+        }
     }
 }
 
@@ -1719,7 +1671,7 @@ __global__ __launch_bounds__(BLK) void conv3_c1_fwd_mfma_kernel(const float* __r
                                                                 const float* __restrict__ wscale, int relu) {
     constexpr int ROWS = WIZ * WIY;                 // 60 halo rows
     __shared__ __attribute__((aligned(16))) bf16 xsh[4 * ROWS * C1F_LD];
-    __shared__ float red[4][16][2];
+    __shared__ float red[4][1][16][2];
     int co0 = blockIdx.y * 16;
     int lane = threadIdx.x & 63;
     int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1739,7 +1691,7 @@ __global__ __launch_bounds__(BLK) void conv3_c1_fwd_mfma_kernel(const float* __r
     float bv[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) bv[j] = bias ? bias[co0 + kg * 4 + j] : 0.f;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    float s1[1][4] = {{0.f, 0.f, 0.f, 0.f}}, s2[1][4] = {{0.f, 0.f, 0.f, 0.f}};
     // B fragment addressing: copy (vn & 3), element 4*(vn >> 2) of the row; rows of the two (dz,dy) pairs of this lane
     int cpy = vn & 3, e0 = (vn >> 2) * 4;
     int rowA0 = ((2 * kg) / 3) * WIY + (2 * kg) % 3, rowA1 = ((2 * kg + 1) / 3) * WIY + (2 * kg + 1) % 3;
@@ -1817,35 +1769,13 @@ __global__ __launch_bounds__(BLK) void conv3_c1_fwd_mfma_kernel(const float* __r
             acc = mfma16(wa, fa, acc);
             acc = mfma16(wb, fb, acc);
             bool ok = okzx && (y0 + r) < H;
-            bf16x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float v = acc[j] + bv[j];
-                if (relu) v = fmaxf(v, 0.f);
-                o[j] = (bf16)v;
-                float q = ok ? (float)o[j] : 0.f;
-                s1[j] += q; s2[j] = fmaf(q, q, s2[j]);
-            }
+            bf16x4 o = round4_masked<true>(acc, bv, relu, ok, s1[0], s2[0]);
             // (round 4: 16-byte stores through row pairs, as in the persistent conv, measured slower here -- 23.5 -> 28.0 us: the kernel is
             // one MFMA pair per row and the pairing serialises two rows)
             if (ok) *reinterpret_cast<bf16x4*>(yrow + (int64_t)r * W * ycs) = o;
         }
     }
-    if (part) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float a = s1[j], b = s2[j];
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-            if (vn == 0) { red[wave][kg * 4 + j][0] = a; red[wave][kg * 4 + j][1] = b; }
-        }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < 32; idx += BLK) {
-            int k = idx & 1, chn = idx >> 1;
-            float v = (red[0][chn][k] + red[1][chn][k]) + (red[2][chn][k] + red[3][chn][k]);
-            part[((int64_t)blockIdx.x * 2 + k) * Cout + co0 + chn] = v;
-        }
-    }
+    if (part) bn_rows_reduce<1, 4, true>(s1, s2, red, wave, vn, kg, part, blockIdx.x, Cout, co0);
 }
 
 // fixed-order parallel slab sum: block = EW elements x 256/EW slab groups (EW = 8 when the slab is small and the
@@ -1904,9 +1834,7 @@ inline WgCfg wgrad_cfg(int Cin, int Cout, Geo g, int target = 0) {
 template <int CO_B, int CI_B, int NT>
 int launch_wgrad(const bf16* x, int xcs, int Cin, const bf16* dy, int dycs, int Cout, Geo g, float* slabs, WgCfg c,
                  hipStream_t s, Halves xh) {
-    size_t lds = (size_t)(CO_B * WNV + CI_B * WNH) * 32;
-    if (lds < 16 * 1024 + 256) lds = 16 * 1024 + 256;
-    MI3D_SET_MAX_LDS_ONCE((&conv3_wgrad_mfma_kernel<CO_B, CI_B, NT>), lds);
+    constexpr size_t lds = LdsWg<CO_B, CI_B>::bytes;
     dim3 grid((unsigned)(c.nsb * c.tg), (unsigned)(Cout / (16 * CO_B)), (unsigned)(Cin / (16 * CI_B)));
     // full-resolution layers: the XCD-aware tile assignment of the fused launch (the stand-alone kernel must sum the same tiles into
     // the same slabs: both routes produce the same bits)
@@ -1918,16 +1846,9 @@ int launch_wgrad(const bf16* x, int xcs, int Cin, const bf16* dy, int dycs, int 
         pgx = (int)grid.x; pgy = (int)grid.y; pgz = (int)grid.z;
         grid = dim3((unsigned)(pgx * pgy * pgz));
     }
-    hipEvent_t tev0 = nullptr, tev1 = nullptr;
-    if (time_hook_take(1, Cin, Cout, tev0, tev1))
-        hipExtLaunchKernelGGL((conv3_wgrad_mfma_kernel<CO_B, CI_B, NT>), grid, dim3(BLK), lds, s, tev0, tev1, 0, x, xcs, Cin, dy, dycs, Cout,
-                              g.N, g.D, g.H, g.W, cdiv(g.D, WTZ), cdiv(g.H, WTY), cdiv(g.W, WTX), c.tg, slabs, xh, xcd_tiles, pgx, pgy, pgz);
-    else
-        conv3_wgrad_mfma_kernel<CO_B, CI_B, NT><<<grid, BLK, lds, s>>>(x, xcs, Cin, dy, dycs, Cout, g.N, g.D, g.H, g.W,
-                                                                      cdiv(g.D, WTZ), cdiv(g.H, WTY), cdiv(g.W, WTX), c.tg, slabs, xh, xcd_tiles,
-                                                                      pgx, pgy, pgz);
-    MI3D_LAUNCH_CHECK();
-    return 0;
+    return launch_hooked<conv3_wgrad_mfma_kernel<CO_B, CI_B, NT>>(grid, BLK, lds, s, 1, Cin, Cout, x, xcs, Cin, dy, dycs, Cout, g.N, g.D, g.H, g.W,
+                                                                  cdiv(g.D, WTZ), cdiv(g.H, WTY), cdiv(g.W, WTX), c.tg, slabs, xh, xcd_tiles,
+                                                                  pgx, pgy, pgz);
 }
 
 inline int c1_nsb(Geo g) {
@@ -2024,26 +1945,17 @@ int conv3_mfma_bwd_fused_persist(const void* x, int xcs, int Cin, const void* dy
     int nw = a.wgx * a.wgy * a.wgz;
     int half = nw > a.pgrid ? nw : a.pgrid;
     unsigned nblk = (unsigned)(2 * half);
-    // dgrad conv Cout -> Cin: persistent shapes (16,16): <1,1>, (32->16): <1,2>, (16->32): <2,1>
-    size_t ldsw = (size_t)(WNV + WNH) * 32;
-    // measurement hook (mi3d_time_next_conv3_bwd_kernel): one-shot HIP events tightly around this kernel
-    hipEvent_t tev0 = nullptr, tev1 = nullptr;
-    time_hook_take(0, Cin, Cout, tev0, tev1);
-#define FP(COB_, NCH_)                                                                                                        \
-    do {                                                                                                                      \
-        size_t ldsp = (size_t)(6 * 10 * 18 * 16 + NCH_ * 14 * COB_ * 512) * 2 + 4 * COB_ * 16 * 2 * 4;                        \
-        size_t lds = ldsp > ldsw ? ldsp : ldsw;                                                                               \
-        MI3D_SET_MAX_LDS_ONCE((&conv3_bwd_fused_persist_kernel<COB_, NCH_>), lds);                                            \
-        if (tev0 && tev1)                                                                                                     \
-            hipExtLaunchKernelGGL((conv3_bwd_fused_persist_kernel<COB_, NCH_>), dim3(nblk), dim3(BLK), lds, s, tev0, tev1, 0, a); \
-        else                                                                                                                  \
-            conv3_bwd_fused_persist_kernel<COB_, NCH_><<<nblk, BLK, lds, s>>>(a);                                               \
-    } while (0)
-    if (Cout == 16 && Cin == 16) FP(1, 1);
-    else if (Cout == 32) FP(1, 2);
-    else FP(2, 1);
-#undef FP
-    MI3D_LAUNCH_CHECK();
+    // dgrad conv Cout -> Cin: persistent shapes (16,16): <1,1>, (32->16): <1,2>, (16->32): <2,1>; one LDS block for either body.
+    // Hook kind 0 (mi3d_time_next_conv3_kernel): one-shot HIP events tightly around this kernel
+    auto launch = [&](auto cob, auto nch) -> int {
+        constexpr int COB = decltype(cob)::value, NCH = decltype(nch)::value;
+        constexpr size_t lds = LdsP<COB, NCH>::bytes > LdsWg<1, 1>::bytes ? LdsP<COB, NCH>::bytes : LdsWg<1, 1>::bytes;
+        static_assert(lds >= LdsP<COB, NCH>::bytes && lds >= LdsWg<1, 1>::bytes, "one LDS block for either body");
+        return launch_hooked<conv3_bwd_fused_persist_kernel<COB, NCH>>(nblk, BLK, lds, s, 0, Cin, Cout, a);
+    };
+    constexpr std::integral_constant<int, 1> one{};
+    constexpr std::integral_constant<int, 2> two{};
+    MI3D_TRY(Cout == 16 && Cin == 16 ? launch(one, one) : Cout == 32 ? launch(one, two) : launch(two, one));
     return wgrad_slab_sum(wgws, nsb, Cin, Cout, dW, db, accumulate, s, pend);
 }
 
@@ -2089,19 +2001,15 @@ int conv3_mfma_bwd_fused(const void* x, int xcs, int Cin, const void* dy, int dy
     a.dCout = Cin; a.dtZ = cdiv(g.D, 4); a.dtY = cdiv(g.H, 8); a.dtX = cdiv(g.W, big ? 16 : 8); a.dpart = ks > 1 ? skws : nullptr;
     a.dgx = g.N * a.dtZ * a.dtY * a.dtX; a.dgy = Cin / 32; a.dgz = ks;
     a.N = g.N; a.D = g.D; a.H = g.H; a.W = g.W;
-    // 8-byte epilogue stores: in-process A/B of the 16-byte ones (v_permlane16_swap), us/step gained: persistent conv 0,
-    // eight-wave conv 5, transposed-conv forward 7, this four-wave body -3
-    a.flags = 0;
-    size_t lds = (size_t)(WNV + WNH) * 32;
-    if (lds < 16 * 1024 + 256) lds = 16 * 1024 + 256;
-    MI3D_SET_MAX_LDS_ONCE((&conv3_bwd_fused_kernel<false, true>), lds);
-    MI3D_SET_MAX_LDS_ONCE((&conv3_bwd_fused_kernel<false, false>), lds);
-    MI3D_SET_MAX_LDS_ONCE((&conv3_bwd_fused_kernel<true, false>), lds);
+    // the input-gradient half stores 8 bytes per lane: in-process A/B of the 16-byte stores (v_permlane16_swap), us/step gained:
+    // persistent conv 0, eight-wave conv 5, transposed-conv forward 7, this four-wave body -3
+    constexpr size_t lds = LdsWg<1, 1>::bytes;
+    static_assert(lds >= Lds4<ConvTile<4, 8, 1, 16>, 2>::bytes && lds >= Lds4<ConvTile<4, 2, 2, 4>, 2>::bytes,
+                  "one LDS block for the weight-gradient body and either input-gradient body");
     unsigned nblk = (unsigned)(((a.wgx * a.wgy * a.wgz + 7) & ~7) + a.dgx * a.dgy * a.dgz);
-    if (big) conv3_bwd_fused_kernel<true, false><<<nblk, BLK, lds, s>>>(a);
-    else if (ks > 1) conv3_bwd_fused_kernel<false, true><<<nblk, BLK, lds, s>>>(a);
-    else conv3_bwd_fused_kernel<false, false><<<nblk, BLK, lds, s>>>(a);
-    MI3D_LAUNCH_CHECK();
+    if (big) MI3D_TRY((launch_hooked<conv3_bwd_fused_kernel<true, false>>(nblk, BLK, lds, s, -1, 0, 0, a)));
+    else if (ks > 1) MI3D_TRY((launch_hooked<conv3_bwd_fused_kernel<false, true>>(nblk, BLK, lds, s, -1, 0, 0, a)));
+    else MI3D_TRY((launch_hooked<conv3_bwd_fused_kernel<false, false>>(nblk, BLK, lds, s, -1, 0, 0, a)));
     if (ks > 1 && ks_deferred) {
         // the consumer of dx (the BatchNorm-backward reduction of the layer below) sums the split-K partials itself
         *ks_deferred = ks;

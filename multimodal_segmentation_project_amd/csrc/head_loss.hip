@@ -10,6 +10,7 @@
 //   L = w_ce*CE + w_reg*mean_{c>=1} R_c + w_kd*T^2*mean_{n,c,v} KL(p_t^T || p_s^T)
 //   dL/dz_k = w_ce/M (p_k - [t=k]) + p_k (g_k - sum_c g_c p_c) + w_kd*T/(M*C) (ps_k - pt_k),
 //   g_c = w_reg/(C-1) * (A_c [t=c] + B_c),  A_c, B_c = dR_c/dI_c-ish coefficients computed once from the sums.
+#include "mfma_tile.h"
 #include "ops.h"
 
 int slab_reduce(const float* slabs, int nslab, int64_t slab_sz, int64_t nW, float* dW, float* db, int accumulate,
@@ -182,14 +183,6 @@ __global__ __launch_bounds__(BLK) void conv1_bwd_kernel(const T* __restrict__ z,
 //                                               32 x 16 tile, B = dl: lane (co = n, kg) supplies 8 consecutive voxels
 //                                               of class n (two float4 loads); result rows = ci, columns = co
 // A wave owns 32 consecutive voxels per iteration; workgroup = 4 waves; slab layout as the scalar kernel.
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_h;
-__device__ __forceinline__ bf16x8 tr_frag_h(const char* base, int byteoff) {
-    auto* p0 = (lds_bf16x4_h*)(base + byteoff);
-    auto* p1 = (lds_bf16x4_h*)(base + byteoff + 128);
-    bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p0);
-    bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p1);
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 constexpr int C1W = 8;          // waves per workgroup: one slab per workgroup, so more waves = same parallelism with fewer slabs
 __global__ __launch_bounds__(C1W * 64) void conv1_bwd_mfma_kernel(const bf16* __restrict__ z, int zcs, int Cin, const float* __restrict__ w,
                                                              const float* __restrict__ dl, int Cout, bf16* __restrict__ dz, int dzcs,
@@ -255,7 +248,7 @@ __global__ __launch_bounds__(C1W * 64) void conv1_bwd_mfma_kernel(const bf16* __
         // the tile is private to this wave: LDS writes above are complete for the wave before the transposing read
         __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0)
         __builtin_amdgcn_wave_barrier();
-        bf16x8 az = tr_frag_h(ztb, laneK);
+        bf16x8 az = tr_frag(ztb, laneK);
         accW = __builtin_amdgcn_mfma_f32_16x16x32_bf16(az, bd, accW, 0, 0, 0);
         __builtin_amdgcn_wave_barrier();
     }
@@ -868,16 +861,11 @@ __global__ __launch_bounds__(C1W * 64) void head_loss_bwd_mfma_kernel(const bf16
             if (wide_dz) {
                 // 16-byte stores (round 4): the two 16-voxel groups trade halves (v_permlane16_swap); lane (vn, kg) then holds channels
                 // (kg >> 1) * 8 .. + 7 of voxel vc + (kg & 1) * 16 + vn
-                typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
-                typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
-                u32x2 u0 = __builtin_bit_cast(u32x2, obn[0]), u1 = __builtin_bit_cast(u32x2, obn[1]);
-                u32x2 p0 = __builtin_amdgcn_permlane16_swap(u0[0], u1[0], false, false);
-                u32x2 p1 = __builtin_amdgcn_permlane16_swap(u0[1], u1[1], false, false);
-                u32x4 wv = {p0[0], p1[0], p0[1], p1[1]};
+                u32x4 wv = swap_halves16(obn[0], obn[1]);
                 const int64_t vw = vc + (kg & 1) * 16 + vn;
                 if (vw < V) *reinterpret_cast<u32x4*>(dzn + vw * dzcs + (kg >> 1) * 8) = wv;
             }
-            bf16x8 az = tr_frag_h(reinterpret_cast<const char*>(zt[wave][hh]), laneK);
+            bf16x8 az = tr_frag(reinterpret_cast<const char*>(zt[wave][hh]), laneK);
             accW = __builtin_amdgcn_mfma_f32_16x16x32_bf16(az, bd, accW, 0, 0, 0);
         }
         __builtin_amdgcn_wave_barrier();

@@ -8,22 +8,11 @@
 //   bwd data : D[ci][voxel] = A(W: 16 ci x 32 (tap,co)) * B(g gathered: 32 (tap,co) x 16 voxels), same structure.
 //   bwd wgt  : K = voxels is the strided index -> x and g tiles in LDS, fragments via ds_read_b64_tr_b16,
 //              persistent workgroups, cross-wave LDS reduce, deterministic slabs (same scheme as conv3 wgrad).
+#include "mfma_tile.h"
 #include "ops.h"
 
 namespace {
 constexpr int BLK = 256;
-
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-__device__ __forceinline__ bf16x8 tr_frag(const char* base, int byteoff) {
-    auto* p0 = (lds_bf16x4*)(base + byteoff);
-    auto* p1 = (lds_bf16x4*)(base + byteoff + 128);
-    bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p0);
-    bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p1);
-    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 
 // wf[(((tap*COBN + cob)*KS + ks)*64 + lane)*8 + j] = W[32ks + 8G + j][cob*16 + (lane&15)][tap]
 // wb[((cib*S + s)*64 + lane)*8 + j]                = W[cib*16 + (lane&15)][co0 + j][tap],  (tap,co0) from kk0 = 32s + 8G
@@ -79,8 +68,6 @@ __global__ __launch_bounds__(BLK) void upconv_mfma_fwd_kernel(const bf16* __rest
             // x-neighbours 2w and 2w + 1 of the output.  Their two results trade halves through v_permlane16_swap; afterwards lane
             // (vn, G) holds channels (G >> 1) * 8 .. + 7 of voxel 2w + (G & 1): one 16-B store per lane, 64 contiguous bytes per input
             // voxel and 1 KB per wave instead of 8-B pieces with a 64-B stride
-            typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
-            typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
 #pragma unroll
             for (int ab = 0; ab < 4; ab++) {
                 int a = ab >> 1, b = ab & 1;
@@ -100,10 +87,7 @@ __global__ __launch_bounds__(BLK) void upconv_mfma_fwd_kernel(const bf16* __rest
                         const float bj = bias ? bias[cob * 16 + 4 * G + j] : 0.f;
                         o0[j] = (bf16)(acc0[j] + bj); o1[j] = (bf16)(acc1[j] + bj);
                     }
-                    u32x2 u0 = __builtin_bit_cast(u32x2, o0), u1 = __builtin_bit_cast(u32x2, o1);
-                    u32x2 p0 = __builtin_amdgcn_permlane16_swap(u0[0], u1[0], false, false);
-                    u32x2 p1 = __builtin_amdgcn_permlane16_swap(u0[1], u1[1], false, false);
-                    u32x4 wv = {p0[0], p1[0], p0[1], p1[1]};
+                    u32x4 wv = swap_halves16(o0, o1);
                     if (ok) *reinterpret_cast<u32x4*>(yq + cob * 16) = wv;
                 }
             }
