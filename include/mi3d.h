@@ -296,6 +296,24 @@ int mi3d_zoom3_cubic(const float* in, float* out, int D, int H, int W, int Do, i
 int mi3d_zoom3_nearest_i64(const int64_t* in, int64_t* out, int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d,
                            int rows_d, const int32_t* index_h, int rows_h, const int32_t* index_w, int rows_w, void* stream);
 
+/* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
+ * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)
+ * with the random decisions already drawn by the host (spatial.py), as one gather pass.  img: float32, lab: int64, both
+ * contiguous (C, D, H, W); either pair may be NULL; in != out.  (ax0, ax1), 1 <= ax0 < ax1 <= 3, is the plane; matrix (2x2,
+ * row-major) and offset (2) are HOST doubles, read before the call returns.  Per output voxel with plane indices (o0, o1) and
+ * plane sides (n0, n1), in IEEE double, every operation rounded on its own (no FMA):
+ *   cc_i = (o0*M[i][0] + o1*M[i][1]) + off[i], clamped to [0, n_i - 1]
+ *   label  source index floor(cc_i + 0.5) per plane axis, value copied
+ *   image  f_i = floor(cc_i), t_i = cc_i - f_i, upper neighbour min(f_i + 1, n_i - 1); weights (1-t0)(1-t1), (1-t0)t1, t0(1-t1),
+ *          t0 t1; sum of weight * value in the order (f0,f1), (f0,f1+1), (f0+1,f1), (f0+1,f1+1); one rounding to float32
+ * Every plane parallel to the two axes and every channel uses the same coordinates.  flip_mask bit k reverses the SOURCE index
+ * on axis k+1 (n - 1 - i) after the mapping, so the call equals rotate(flip(x)) bit for bit.  matrix = identity and offset = 0
+ * is a pure flip: a copy with reversed indices whose output is bitwise the gather's for finite values (the gather turns -0.0
+ * into +0.0 and 0 * Inf into NaN; the copy keeps both).  Allocates nothing, does not synchronise.  Negative return: bad axes,
+ * null or aliased in/out, non-positive sizes, more than 2^31 - 1 voxels, flip_mask outside 0..7. */
+int mi3d_plane_affine(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W,
+                      int ax0, int ax1, const double* matrix, const double* offset, int flip_mask, void* stream);
+
 /* Training-set augmentation, combined_transform() (utils/dataloader.py:223-262, used at train_unet.py:361): the
  * arithmetic of MONAI's RandBiasField -> RandGaussianNoise -> RandAdjustContrast -> RandHistogramShift ->
  * RandCoarseDropout on one (C, D, H, W) float volume, with the random parameters already drawn by the host

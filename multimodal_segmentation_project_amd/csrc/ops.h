@@ -237,6 +237,11 @@ size_t seg_metrics_ws_bytes(int C);
 int seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out, void* ws,
                 hipStream_t s, int64_t* counts_out = nullptr);
 
+// ---- spatial augmentation: flip + in-plane rotation of one (C, D, H, W) sample ------------- spatial.hip
+// Reference: random_flip / random_rotate, utils/dataloader.py:207-221.  Contract and arithmetic: include/mi3d.h mi3d_plane_affine.
+int plane_affine(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int ax0,
+                 int ax1, const double* matrix, const double* offset, int flip_mask, hipStream_t s);
+
 // ---- misc ---------------------------------------------------------------------------------- misc.hip
 int ncdhw_to_ndhwc(int dtype, const float* src, void* dst, int dcs, int C, int N, int64_t V, hipStream_t s);
 int ndhwc_to_ncdhw(int dtype, const void* src, int scs, float* dst, int C, int N, int64_t V, hipStream_t s);

@@ -633,6 +633,92 @@ def gen_resample(out):
         f.write(f"scipy {scipy.__version__}, numpy {np.__version__}\n")
 
 
+def gen_spatial(out):
+    """The reference's spatial helpers (utils/dataloader.py:207-221) and the scipy call they make, on seeded in-memory volumes.
+      spatial_random.npz            (a) random_flip / random_rotate of the reference itself, EXECUTED through the import stubs, for
+                                    12 seeds: random.seed(k) then one call; `both` = random_flip then random_rotate after one
+                                    random.seed(k).  The drawn flips / angle / axes are recorded by replaying the draws.
+      spatial_rotate_<input>.npz    (b) scipy.ndimage.rotate(x, angle, axes=plane, reshape=False, order=1 | 0, mode='nearest') for
+                                    4 shapes x 3 planes x 7 angles, with the matrix and offset rotate() builds (restated from its
+                                    source: cosdg / sindg, [[c, s], [-s, c]], centre - matrix @ centre).  Inputs: plain (standard
+                                    normal), wide (uniform in +-1000), cancel (checkerboard of +-(1000 + 1e-3 noise): neighbours
+                                    nearly cancel).  Labels (uint8, in the plain file only) are the same for all three.
+    One file per input keeps every file under 1 MiB.  Case keys and lists: tests/spatial_ref.py."""
+    import random
+    import scipy
+    from scipy import ndimage, special
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import spatial_ref as S
+    _import_reference()
+    import utils.dataloader as ref_dl
+    rng = np.random.default_rng(23)
+    d = {}
+    shapes = [(1, 12, 10, 14), (1, 16, 16, 16), (2, 6, 9, 8), (1, 9, 11, 7)]
+    for k in range(12):
+        shape = shapes[k % len(shapes)]
+        img = rng.standard_normal(shape).astype(np.float32)
+        lab = rng.integers(0, 5, shape)
+        random.seed(k)
+        flips = [random.random() > 0.5 for _ in range(3)]
+        random.seed(k)
+        angle = random.uniform(-15, 15)
+        axes = random.choice([(1, 2), (1, 3), (2, 3)])
+        random.seed(k)
+        f_img, f_lab = ref_dl.random_flip(img, lab)
+        random.seed(k)
+        r_img, r_lab = ref_dl.random_rotate(img, lab)
+        random.seed(k)
+        b_img, b_lab = ref_dl.random_rotate(*ref_dl.random_flip(img, lab))
+        replay = random.Random(k)                 # `both`: the rotation's draws come after the three flip draws
+        for _ in range(3):
+            replay.random()
+        d[f"seed{k}/image_in"], d[f"seed{k}/label_in"] = img, lab.astype(np.uint8)
+        d[f"seed{k}/flips"], d[f"seed{k}/angle"], d[f"seed{k}/axes"] = np.array(flips), np.float64(angle), np.array(axes)
+        d[f"seed{k}/both_angle"] = np.float64(replay.uniform(-15, 15))
+        d[f"seed{k}/both_axes"] = np.array(replay.choice([(1, 2), (1, 3), (2, 3)]))
+        for name, a in (("flip_image", f_img), ("rotate_image", r_img), ("both_image", b_img)):
+            assert a.dtype == np.float32
+            d[f"seed{k}/{name}"] = a
+        for name, a in (("flip_label", f_lab), ("rotate_label", r_lab), ("both_label", b_lab)):
+            d[f"seed{k}/{name}"] = a.astype(np.uint8)
+    d["seeds"] = np.arange(12)
+    np.savez_compressed(os.path.join(out, "spatial_random.npz"), **d)
+    files = {name: {} for name in S.INPUTS}
+    for shape in S.SHAPES:
+        sk = "s" + "x".join(str(n) for n in shape)
+        zz = np.indices(shape).sum(axis=0)
+        x = {"plain": rng.standard_normal(shape), "wide": rng.uniform(-1000.0, 1000.0, shape),
+             "cancel": np.where(zz % 2 == 0, 1.0, -1.0) * (1000.0 + 1e-3 * rng.standard_normal(shape))}
+        lab = rng.integers(0, 16, shape)
+        files["plain"][f"{sk}/label_in"] = lab.astype(np.uint8)
+        for name in S.INPUTS:
+            files[name][f"{sk}/image_in"] = x[name].astype(np.float32)
+        for plane in S.PLANES:
+            for ai, angle in enumerate(S.ANGLES):
+                key = S.case_key(shape, plane, ai)
+                c, s = special.cosdg(angle), special.sindg(angle)
+                matrix = np.array([[c, s], [-s, c]])
+                centre = (np.asarray(shape)[list(plane)] - 1) / 2
+                for name in S.INPUTS:
+                    files[name][f"{key}/matrix"], files[name][f"{key}/offset"] = matrix, centre - matrix @ centre
+                    o = ndimage.rotate(files[name][f"{sk}/image_in"], angle, axes=plane, reshape=False, order=1, mode='nearest')
+                    assert o.dtype == np.float32
+                    files[name][f"{key}/image_out"] = o
+                files["plain"][f"{key}/label_out"] = ndimage.rotate(lab, angle, axes=plane, reshape=False, order=0,
+                                                                    mode='nearest').astype(np.uint8)
+    for name in S.INPUTS:
+        np.savez_compressed(os.path.join(out, f"spatial_rotate_{name}.npz"), **files[name])
+    with open(os.path.join(out, "PROVENANCE_spatial.txt"), "w") as f:
+        f.write("spatial_random.npz, spatial_rotate_plain.npz, spatial_rotate_wide.npz, spatial_rotate_cancel.npz: generated by\n")
+        f.write("tools/gen_golden.py --only spatial\n")
+        f.write("spatial_random.npz: outputs of the reference's own random_flip / random_rotate (utils/dataloader.py:207-221,\n")
+        f.write("fransiskusbudi/multimodal_segmentation_project @ 2025-08-24), executed on seeded arrays after random.seed(k);\n")
+        f.write("nothing of the reference is copied.\n")
+        f.write("spatial_rotate_*.npz: outputs of scipy.ndimage.rotate(x, angle, axes=plane, reshape=False, order=1|0, mode='nearest');\n")
+        f.write("matrix / offset are restated from rotate()'s source (scipy.special.cosdg / sindg).\n")
+        f.write(f"scipy {scipy.__version__}, numpy {np.__version__}\n")
+
+
 def _autocast_yardstick(d, pre, ref_unet, ref_metrics, x, y, fp32_logits, fp32_grads, seed=0):
     """The reference's own bf16 autocast run (accelerate mixed_precision='bf16') vs its fp32 run on the same inputs."""
     torch.manual_seed(seed)
@@ -993,7 +1079,8 @@ def main():
     torch.set_num_threads(8)
     torch.use_deterministic_algorithms(False)
     if want("resample"): gen_resample(a.out)              # needs scipy only, not the reference tree
-    if only == {"resample"}:
+    if want("spatial"): gen_spatial(a.out)                # scipy + the reference's utils/dataloader.py
+    if only <= {"resample", "spatial"} and only:
         return
     ref_unet, ref_unet_dann, ref_metrics, ref_train_unet, ref_train_dann = _import_reference()
     if want("small_unet"): gen_small_unet(ref_unet, ref_metrics, a.out)
