@@ -7,8 +7,16 @@
 //   bwd red.: R dz, R y                -> (sum dyh, sum dyh*xhat) partials -> finalize
 //   bwd app.: R dz, R y, W dy          dy = g*(dyh - c1 - xhat*c2)
 // Per-channel reductions: lane-private fp32 accumulation -> LDS across the rows of a block -> one partial
-// per block -> a finalize kernel that sums the partials in double in a fixed order (bitwise reproducible,
-// no float atomics).
+// row per block -> summed in double in a fixed order (bitwise reproducible, no float atomics), by a finalize
+// kernel or in the consumer's prologue.
+// Every formula has ONE definition here, shared by the kernels that need it:
+//   bn_coef / bn_publish   (sum, sumsq) -> mean, var, invstd, a, b;  stat[4][C] and the running statistics
+//   part_channel_sum       a channel's double sum over the partial rows (finalize kernels; the three orders: see rows_sum)
+//   bn_act / bn_mask       the element op  s * relu(a*v + b)  and its mask  a*v + b > 0 ? s : 0
+//   load_ab                a thread's (a, b): consumer prologue (TRAIN) or stat[2C..]
+//   bwd_coef / bwd_param_grads   backward coefficients (A, B);  dgamma, dbeta (+)=
+//   PoolWin / tap_off      2x2x2 pooling window decode and the voxel offset of a tap
+//   DropCache              Dropout3d scales of a thread's channel group, by row or by sample
 #include "ops.h"
 
 namespace {
@@ -17,11 +25,7 @@ constexpr int BLK = 256;
 constexpr int MAXBLK = 1024;
 constexpr int FIN_T = 256;          // threads per channel in the finalize kernels
 
-struct RowMap {
-    int G;   // channel groups per row (C / VEC)
-    int R;   // rows handled per block iteration (BLK / G)
-};
-
+// G = C / VEC channel groups per row, R = BLK / G rows per block iteration: thread -> (row r, group g)
 template <int VEC> __device__ __forceinline__ bool row_map(int C, int& r, int& g, int& R) {
     int G = C / VEC;
     R = BLK / G;
@@ -31,10 +35,8 @@ template <int VEC> __device__ __forceinline__ bool row_map(int C, int& r, int& g
 }
 
 // reduce K lane-private quantities per channel over the block; result to part[blockIdx.x][k][c]
-template <int VEC, int K> __device__ __forceinline__ void block_colreduce(const float (&acc)[K][VEC], int C, bool active,
-                                                                           float* lds, float* part) {
-    int G = C / VEC, R = BLK / G;
-    int r = threadIdx.x / G, g = threadIdx.x - r * G;
+template <int VEC, int K> __device__ __forceinline__ void block_colreduce(const float (&acc)[K][VEC], int C, int r, int g, int R,
+                                                                           bool active, float* lds, float* part) {
     if (active) {
 #pragma unroll
         for (int k = 0; k < K; k++)
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(BLK) void bn_stats_kernel(const T* __restrict__ y, 
             for (int i = 0; i < VEC; i++) { acc[0][i] += v[i]; acc[1][i] += v[i] * v[i]; }
         }
     }
-    block_colreduce<VEC, 2>(acc, C, active, lds, part);
+    block_colreduce<VEC, 2>(acc, C, r, g, R, active, lds, part);
 }
 
 // split-K convolutions (deep levels): the finishing pass y = bf16(bias + sum_k part[k]) runs HERE, fused with the
@@ -99,18 +101,47 @@ __global__ __launch_bounds__(BLK) void bn_stats_splitk_kernel(const float* __res
             for (int i = 0; i < 8; i++) { float q = (float)(bf16)v[i]; acc[0][i] += q; acc[1][i] += q * q; }
         }
     }
-    block_colreduce<8, 2>(acc, C, active, lds, part);
+    block_colreduce<8, 2>(acc, C, r, g, R, active, lds, part);
 }
 
-// one 64-lane block per channel: double sums of the partials in a fixed order
-__global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int nblk, int C, int64_t M,
-                                         const float* gamma, const float* beta, float* running_mean,
-                                         float* running_var, int64_t* nbt, float momentum, float eps,
-                                         float* stat) {
-    // FIN_T threads per channel: lane-strided double sums, wave tree, then the waves in fixed order
+// (sum, sumsq) of a channel over M elements -> BatchNorm coefficients.  Everything in double; a, b are rounded once.
+struct BnCoef { double mean, var, inv; float a, b; };
+__device__ __forceinline__ BnCoef bn_coef(double s, double q, int64_t M, float gamma, float beta, float eps) {
+    BnCoef k;
+    k.mean = s / (double)M;
+    k.var = q / (double)M - k.mean * k.mean;
+    if (k.var < 0.0) k.var = 0.0;
+    k.inv = 1.0 / sqrt(k.var + (double)eps);
+    k.a = (float)((double)gamma * k.inv);
+    k.b = (float)((double)beta - k.mean * (double)gamma * k.inv);
+    return k;
+}
+// channel c: stat[4][C] for the backward pass, then the running statistics (or, momentum < 0, the deferred publish)
+__device__ __forceinline__ void bn_publish(const BnCoef& k, int c, int C, int64_t M, float* stat, float* running_mean,
+                                           float* running_var, int64_t* nbt, float momentum) {
+    stat[c] = (float)k.mean;
+    stat[C + c] = (float)k.inv;
+    stat[2 * C + c] = k.a;
+    stat[3 * C + c] = k.b;
+    if (momentum < 0.f) {          // deferred running-statistics update (ops.h bn_deferred_apply): publish the doubles
+        double* side = reinterpret_cast<double*>(running_mean);
+        if (side) { side[c] = k.mean; side[C + c] = M > 1 ? k.var * (double)M / (double)(M - 1) : k.var; }
+    } else {
+        if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * k.mean);
+        if (running_var) {
+            double unb = M > 1 ? k.var * (double)M / (double)(M - 1) : k.var;
+            running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
+        }
+        if (nbt && c == 0) *nbt += 1;
+    }
+}
+
+// channel c = blockIdx.x of part[nblk][2][C], FIN_T threads: lane-strided double sums, wave tree, then the waves in fixed
+// order.  True in the one thread that holds the result.
+__device__ __forceinline__ bool part_channel_sum(const float* __restrict__ part, int nblk, int C, double& s, double& q) {
     __shared__ double ws_[FIN_T / 64][2];
     int c = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0, q = 0.0;
+    s = 0.0; q = 0.0;
     for (int b = lane; b < nblk; b += FIN_T) {
         s += (double)part[((size_t)b * 2 + 0) * C + c];
         q += (double)part[((size_t)b * 2 + 1) * C + c];
@@ -119,30 +150,22 @@ __global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int nbl
     q = wave_sum_d(q);
     if ((lane & 63) == 0) { ws_[lane >> 6][0] = s; ws_[lane >> 6][1] = q; }
     __syncthreads();
-    if (lane == 0) {
-        s = 0.0; q = 0.0;
+    if (lane != 0) return false;
+    s = 0.0; q = 0.0;
 #pragma unroll
-        for (int w = 0; w < FIN_T / 64; w++) { s += ws_[w][0]; q += ws_[w][1]; }
-        double mean = s / (double)M;
-        double var = q / (double)M - mean * mean;
-        if (var < 0.0) var = 0.0;
-        double inv = 1.0 / sqrt(var + (double)eps);
-        float a = (float)((double)gamma[c] * inv);
-        stat[c] = (float)mean;
-        stat[C + c] = (float)inv;
-        stat[2 * C + c] = a;
-        stat[3 * C + c] = (float)((double)beta[c] - mean * (double)gamma[c] * inv);
-        if (momentum < 0.f) {          // deferred running-statistics update (ops.h bn_deferred_apply): publish the doubles
-            double* side = reinterpret_cast<double*>(running_mean);
-            if (side) { side[c] = mean; side[C + c] = M > 1 ? var * (double)M / (double)(M - 1) : var; }
-        } else {
-            if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-            if (running_var) {
-                double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-                running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-            }
-            if (nbt && c == 0) *nbt += 1;
-        }
+    for (int w = 0; w < FIN_T / 64; w++) { s += ws_[w][0]; q += ws_[w][1]; }
+    return true;
+}
+
+// one FIN_T-thread block per channel
+__global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int nblk, int C, int64_t M,
+                                         const float* gamma, const float* beta, float* running_mean,
+                                         float* running_var, int64_t* nbt, float momentum, float eps,
+                                         float* stat) {
+    double s, q;
+    if (part_channel_sum(part, nblk, C, s, q)) {
+        int c = blockIdx.x;
+        bn_publish(bn_coef(s, q, M, gamma[c], beta[c], eps), c, C, M, stat, running_mean, running_var, nbt, momentum);
     }
 }
 
@@ -153,12 +176,13 @@ __global__ void bn_stats_finalize_kernel(const float* __restrict__ part, int nbl
 // backward pass and updates the running statistics.
 constexpr int SMALL_ROWS = 128;        // round 3 scan (ms/step): 64: 2.330, 128: 2.283, 256: 2.288, 512: 2.307
 constexpr int MAXC_BN = 256;
-struct BnPart {
-    const float* part; int nrows; int64_t M;
-    const float* gamma; const float* beta; float* running_mean; float* running_var; int64_t* nbt;
-    float momentum, eps;
-};
-// sum the nrows partial rows [nrows][2][C] per (k, channel): out[k] for threads < C.  Requirement: C in {4..256} a power
+// The partial rows are summed in THREE orders, one per route, and a route's order is part of its bits:
+//   part_channel_sum  finalize launch (any C, any row count): one block per channel, lane-strided
+//   rows_sum          consumer prologue of a 256-thread workgroup, <= SMALL_ROWS rows: float4 pieces of the flat array
+//   rows_sum_wide     consumer prologue of a 1024-thread workgroup, <= WIDE_ROWS rows: all pieces in flight, two LDS stages
+// Each is shaped by its workgroup and row count (measurements at the definitions); merging them would change the bits of a route.
+//
+// rows_sum: the nrows partial rows [nrows][2][C] per (k, channel): out[k] for threads < C.  Requirement: C in {4..256} a power
 // of two.  The flat array is read as float4, thread t taking elements 4t + 1024 j: its (k, channel quad) is the same for
 // every j, the loads are independent (a scalar `acc += part[r]` loop pays an L2 round trip per row: measured 0.3 us each;
 // only the last, partial 1024-element block is guarded), the per-thread sums are combined through LDS in a fixed order.
@@ -239,41 +263,40 @@ __device__ __forceinline__ void rows_sum_wide(const float* __restrict__ part, in
     }
 }
 
-template <int NT = BLK>
-__device__ __forceinline__ void bn_train_coeffs(const BnPart& t, int C, float* stat, float* ab /* [2][MAXC_BN] */, double* red) {
-    double sq[2];
-    if constexpr (NT == BLK) rows_sum(t.part, t.nrows, C, red, sq);
-    else rows_sum_wide<NT>(t.part, t.nrows, C, red, sq);
-    int c = threadIdx.x;
-    if (c < C) {
-        double mean = sq[0] / (double)t.M;
-        double var = sq[1] / (double)t.M - mean * mean;
-        if (var < 0.0) var = 0.0;
-        double inv = 1.0 / sqrt(var + (double)t.eps);
-        float a = (float)((double)t.gamma[c] * inv);
-        float b = (float)((double)t.beta[c] - mean * (double)t.gamma[c] * inv);
-        ab[c] = a;
-        ab[MAXC_BN + c] = b;
-        if (blockIdx.x == 0) {
-            stat[c] = (float)mean;
-            stat[C + c] = (float)inv;
-            stat[2 * C + c] = a;
-            stat[3 * C + c] = b;
-            if (t.momentum < 0.f) {      // deferred running-statistics update: publish the doubles
-                double* side = reinterpret_cast<double*>(t.running_mean);
-                if (side) { side[c] = mean; side[C + c] = t.M > 1 ? var * (double)t.M / (double)(t.M - 1) : var; }
-            } else {
-                if (t.running_mean) t.running_mean[c] = (float)((1.0 - t.momentum) * t.running_mean[c] + t.momentum * mean);
-                if (t.running_var) {
-                    double unb = t.M > 1 ? var * (double)t.M / (double)(t.M - 1) : var;
-                    t.running_var[c] = (float)((1.0 - t.momentum) * t.running_var[c] + t.momentum * unb);
-                }
-                if (t.nbt && c == 0) *t.nbt += 1;
-            }
+// a[VEC], b[VEC] of the thread's channel group g.  TRAIN: the workgroup (NT threads) first finishes the partial rows
+// (rows_sum / rows_sum_wide), workgroup 0 publishes; otherwise stat[2C..] is final already
+template <int VEC, bool TRAIN, int NT = BLK>
+__device__ __forceinline__ void load_ab(const BnSmall& t, int C, float* stat, int g, float (&a)[VEC], float (&b)[VEC]) {
+    if constexpr (TRAIN) {
+        __shared__ double red[NT * 4];
+        __shared__ float ab[2 * MAXC_BN];
+        double sq[2];
+        if constexpr (NT == BLK) rows_sum(t.part, t.nrows, C, red, sq);
+        else rows_sum_wide<NT>(t.part, t.nrows, C, red, sq);
+        int c = threadIdx.x;
+        if (c < C) {
+            BnCoef k = bn_coef(sq[0], sq[1], t.M, t.gamma[c], t.beta[c], t.eps);
+            ab[c] = k.a;
+            ab[MAXC_BN + c] = k.b;
+            if (blockIdx.x == 0)
+                bn_publish(k, c, C, t.M, stat, t.running_mean, t.running_var, t.num_batches_tracked, t.momentum);
         }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < VEC; i++) { a[i] = ab[g * VEC + i]; b[i] = ab[MAXC_BN + g * VEC + i]; }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VEC; i++) { a[i] = stat[2 * C + g * VEC + i]; b[i] = stat[3 * C + g * VEC + i]; }
     }
-    __syncthreads();
 }
+
+// the element op of the forward pass and its mask in the backward pass (s = Dropout3d scale of the sample and channel)
+__device__ __forceinline__ float bn_act(float v, float a, float b, float s) {
+    float t = fmaf(v, a, b);
+    t = t > 0.f ? t : 0.f;
+    return t * s;
+}
+__device__ __forceinline__ float bn_mask(float v, float a, float b, float s) { return fmaf(v, a, b) > 0.f ? s : 0.f; }
 
 __global__ void bn_eval_stats_kernel(int C, const float* gamma, const float* beta, const float* rm,
                                      const float* rv, float eps, float* stat) {
@@ -288,11 +311,13 @@ __global__ void bn_eval_stats_kernel(int C, const float* gamma, const float* bet
 
 // Dropout3d scale of this thread's channel group for the sample `row` lies in: rows are visited in increasing order, so the
 // VEC scales are (re)loaded only when a sample boundary is crossed (a per-row `drop[(row / V) * C + c]` costs a 32-bit
-// division and VEC global loads per element: +0.14 ms/step at p = 0.1)
+// division and VEC global loads per element: +0.14 ms/step at p = 0.1).  at_sample: the pooled passes know the sample from
+// their window decode.
 template <int VEC>
 struct DropCache {
     float s[VEC];
     int64_t bound = 0;
+    int smp = -1;
     __device__ __forceinline__ DropCache() {
 #pragma unroll
         for (int i = 0; i < VEC; i++) s[i] = 1.f;
@@ -305,40 +330,34 @@ struct DropCache {
             for (int i = 0; i < VEC; i++) s[i] = drop[n * C + c0 + i];
         }
     }
+    __device__ __forceinline__ void at_sample(const float* __restrict__ drop, int n, int C, int c0) {
+        if (drop && n != smp) {
+            smp = n;
+#pragma unroll
+            for (int i = 0; i < VEC; i++) s[i] = drop[(int64_t)n * C + c0 + i];
+        }
+    }
 };
 
 // grid stride (gridDim*BLK) is a multiple of G = C/VEC (launcher guarantees it), so a thread's channel group is
 // fixed: per-channel coefficients are loaded into registers ONCE instead of per element
 template <typename T, int VEC, bool TRAIN>
 __global__ __launch_bounds__(BLK) void bn_apply_kernel(const T* __restrict__ y, int ycs, int C, int64_t M, int64_t V,
-                                                       float* __restrict__ stat, BnPart tr, const float* __restrict__ drop,
+                                                       float* __restrict__ stat, BnSmall tr, const float* __restrict__ drop,
                                                        T* __restrict__ z, int zcs) {
     int G = C / VEC;
     int64_t gtid = (int64_t)blockIdx.x * BLK + threadIdx.x;
     int g = (int)(gtid % G);
     int64_t row = gtid / G, rstep = ((int64_t)gridDim.x * BLK) / G;
     float a[VEC], b[VEC];
-    if constexpr (TRAIN) {
-        __shared__ double red[BLK * 4];
-        __shared__ float ab[2 * MAXC_BN];
-        bn_train_coeffs(tr, C, stat, ab, red);
-#pragma unroll
-        for (int i = 0; i < VEC; i++) { a[i] = ab[g * VEC + i]; b[i] = ab[MAXC_BN + g * VEC + i]; }
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) { a[i] = stat[2 * C + g * VEC + i]; b[i] = stat[3 * C + g * VEC + i]; }
-    }
+    load_ab<VEC, TRAIN>(tr, C, stat, g, a, b);
     DropCache<VEC> dc;
     for (; row < M; row += rstep) {
         float v[VEC], o[VEC];
         ldv<T, VEC>(y + row * ycs + g * VEC, v);
         dc.at(drop, row, V, C, g * VEC);
 #pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            float t = fmaf(v[i], a[i], b[i]);
-            t = t > 0.f ? t : 0.f;
-            o[i] = t * dc.s[i];
-        }
+        for (int i = 0; i < VEC; i++) o[i] = bn_act(v[i], a[i], b[i], dc.s[i]);
         stv<T, VEC>(z + row * zcs + g * VEC, o);
     }
 }
@@ -355,7 +374,7 @@ constexpr int WIDE_ROWS = 1024;
 // while the first loads are in flight, and the main loop keeps WPRE loads per thread in flight.
 constexpr int WPRE = 8;
 __global__ __launch_bounds__(WNT) void bn_apply_wide_kernel(const bf16* __restrict__ y, int ycs, int C, int64_t M, int64_t V,
-                                                            float* __restrict__ stat, BnPart tr, const float* __restrict__ drop,
+                                                            float* __restrict__ stat, BnSmall tr, const float* __restrict__ drop,
                                                             bf16* __restrict__ z, int zcs) {
     constexpr int VEC = 8;
     const int G = C / VEC;
@@ -367,12 +386,8 @@ __global__ __launch_bounds__(WNT) void bn_apply_wide_kernel(const bf16* __restri
 #pragma unroll
     for (int u = 0; u < WPRE; u++)
         if (row + u * rstep < M) raw[u] = *reinterpret_cast<const bf16x8*>(y + (row + u * rstep) * ycs + g * VEC);
-    __shared__ double red[WNT * 4];
-    __shared__ float ab[2 * MAXC_BN];
-    bn_train_coeffs<WNT>(tr, C, stat, ab, red);
     float a[VEC], b[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) { a[i] = ab[g * VEC + i]; b[i] = ab[MAXC_BN + g * VEC + i]; }
+    load_ab<VEC, true, WNT>(tr, C, stat, g, a, b);          // after the loads above: they are in flight during the prologue
     DropCache<VEC> dc;
     while (row < M) {
 #pragma unroll
@@ -382,11 +397,7 @@ __global__ __launch_bounds__(WNT) void bn_apply_wide_kernel(const bf16* __restri
                 dc.at(drop, r, V, C, g * VEC);
                 bf16x8 o;
 #pragma unroll
-                for (int i = 0; i < VEC; i++) {
-                    float t = fmaf((float)raw[u][i], a[i], b[i]);
-                    t = t > 0.f ? t : 0.f;
-                    o[i] = (bf16)(t * dc.s[i]);
-                }
+                for (int i = 0; i < VEC; i++) o[i] = (bf16)bn_act((float)raw[u][i], a[i], b[i], dc.s[i]);
                 *reinterpret_cast<bf16x8*>(z + r * zcs + g * VEC) = o;
             }
         }
@@ -400,12 +411,26 @@ __global__ __launch_bounds__(WNT) void bn_apply_wide_kernel(const bf16* __restri
 // Second half of an encoder block: the same apply pass, one thread per 2x2x2 pooling window and channel group — writes the
 // eight activated voxels (the skip tensor) AND their maximum (MaxPool3d(2,2), models/unet.py:40,71), so the pooling launch and
 // its re-read of the skip tensor disappear.  Even D, H, W only (every voxel lies in exactly one window).
+// Window `win` of the pooled [N][Do][Ho][Wo] grid -> its sample and the voxel index of its corner; tap k = (dz, dy, dx) bits.
+// 32-bit: the launcher checks M * C < 2^31.
+struct PoolWin {
+    int n, d_o, ho, wo;
+    __device__ __forceinline__ PoolWin(unsigned win, int Do, int Ho, int Wo) {
+        wo = (int)(win % (unsigned)Wo); win /= (unsigned)Wo;
+        ho = (int)(win % (unsigned)Ho); win /= (unsigned)Ho;
+        d_o = (int)(win % (unsigned)Do);
+        n = (int)(win / (unsigned)Do);
+    }
+    __device__ __forceinline__ int corner(int D, int H, int W) const { return ((n * D + 2 * d_o) * H + 2 * ho) * W + 2 * wo; }
+};
+__device__ __forceinline__ int tap_off(int k, int H, int W) { return ((k >> 2) * H + ((k >> 1) & 1)) * W + (k & 1); }
+
 // PAIR (round 4, VEC = 8, C / 8 a power of two <= 32): two threads per window -- thread (window, c, g) owns the four voxels (a, b, c),
 // so the lanes of a wave touch one contiguous run per (a, b) instead of every other 32-B half; the halves exchange their maxima with
 // one lane swap (the maximum of the same eight stored values: bit-identical)
 template <typename T, int VEC, bool TRAIN, bool PAIR = false>
 __global__ __launch_bounds__(BLK) void bn_apply_pool_kernel(const T* __restrict__ y, int ycs, int C, int N, int D, int H, int W,
-                                                            float* __restrict__ stat, BnPart tr, const float* __restrict__ drop,
+                                                            float* __restrict__ stat, BnSmall tr, const float* __restrict__ drop,
                                                             T* __restrict__ z, int zcs, T* __restrict__ pl, int pcs) {
     const int G = C / VEC, Do = D / 2, Ho = H / 2, Wo = W / 2;
     const unsigned gtid = blockIdx.x * BLK + threadIdx.x;
@@ -413,62 +438,40 @@ __global__ __launch_bounds__(BLK) void bn_apply_pool_kernel(const T* __restrict_
     [[maybe_unused]] const int pc = PAIR ? (int)((gtid / (unsigned)G) & 1u) : 0;
     constexpr int NK = PAIR ? 4 : 8;
     float a[VEC], b[VEC];
-    if constexpr (TRAIN) {
-        __shared__ double red[BLK * 4];
-        __shared__ float ab[2 * MAXC_BN];
-        bn_train_coeffs(tr, C, stat, ab, red);
-#pragma unroll
-        for (int i = 0; i < VEC; i++) { a[i] = ab[g * VEC + i]; b[i] = ab[MAXC_BN + g * VEC + i]; }
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) { a[i] = stat[2 * C + g * VEC + i]; b[i] = stat[3 * C + g * VEC + i]; }
-    }
+    load_ab<VEC, TRAIN>(tr, C, stat, g, a, b);
     const unsigned TPW = (unsigned)G * (PAIR ? 2u : 1u);          // threads per window
     const unsigned windows = (unsigned)N * Do * Ho * Wo, wstep = (gridDim.x * BLK) / TPW;
-    float ds[VEC];
-    int dn = -1;
-#pragma unroll
-    for (int i = 0; i < VEC; i++) ds[i] = 1.f;
+    DropCache<VEC> dc;
     for (unsigned win = gtid / TPW; win < windows; win += wstep) {
-        unsigned r = win;
-        const int wo = (int)(r % (unsigned)Wo); r /= (unsigned)Wo;
-        const int ho = (int)(r % (unsigned)Ho); r /= (unsigned)Ho;
-        const int d_o = (int)(r % (unsigned)Do);
-        const int n = (int)(r / (unsigned)Do);
-        if (drop && n != dn) {
-            dn = n;
-#pragma unroll
-            for (int i = 0; i < VEC; i++) ds[i] = drop[(int64_t)n * C + g * VEC + i];
-        }
+        const PoolWin pw(win, Do, Ho, Wo);
+        dc.at_sample(drop, pw.n, C, g * VEC);
+        const int corner = pw.corner(D, H, W);
+        int off[NK];
         float v[NK][VEC], m[VEC];
 #pragma unroll
         for (int q = 0; q < NK; q++) {
-            const int k = PAIR ? 2 * q + pc : q;
-            const int64_t off = (((int64_t)n * D + 2 * d_o + (k >> 2)) * H + 2 * ho + ((k >> 1) & 1)) * W + 2 * wo + (k & 1);
-            ldv<T, VEC>(y + off * ycs + g * VEC, v[q]);
+            off[q] = corner + tap_off(PAIR ? 2 * q + pc : q, H, W);
+            ldv<T, VEC>(y + (int64_t)off[q] * ycs + g * VEC, v[q]);
         }
 #pragma unroll
         for (int i = 0; i < VEC; i++) m[i] = -INFINITY;
 #pragma unroll
         for (int q = 0; q < NK; q++) {
-            const int k = PAIR ? 2 * q + pc : q;
-            const int64_t off = (((int64_t)n * D + 2 * d_o + (k >> 2)) * H + 2 * ho + ((k >> 1) & 1)) * W + 2 * wo + (k & 1);
             float o[VEC];
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
-                float t = fmaf(v[q][i], a[i], b[i]);
-                t = t > 0.f ? t : 0.f;
-                o[i] = (float)(T)(t * ds[i]);             // the pooled value is the maximum of the STORED (rounded) values
+                o[i] = (float)(T)bn_act(v[q][i], a[i], b[i], dc.s[i]);      // the pooled value is the maximum of the STORED (rounded) values
                 m[i] = o[i] > m[i] ? o[i] : m[i];
             }
-            stv<T, VEC>(z + off * zcs + g * VEC, o);
+            stv<T, VEC>(z + (int64_t)off[q] * zcs + g * VEC, o);
         }
         if constexpr (PAIR) {
 #pragma unroll
             for (int i = 0; i < VEC; i++) { float om = __shfl_xor(m[i], G, 64); m[i] = om > m[i] ? om : m[i]; }
             if (pc != 0) continue;
         }
-        stv<T, VEC>(pl + ((((int64_t)n * Do + d_o) * Ho + ho) * Wo + wo) * pcs + g * VEC, m);
+        // pooled voxel index (= win) from the decode: written as `win` it costs <float, 8, *, true> a VGPR (83 -> 84)
+        stv<T, VEC>(pl + ((((int64_t)pw.n * Do + pw.d_o) * Ho + pw.ho) * Wo + pw.wo) * pcs + g * VEC, m);
     }
 }
 
@@ -476,7 +479,7 @@ __global__ __launch_bounds__(BLK) void bn_apply_pool_kernel(const T* __restrict_
 // prologue finishes the statistics; same arithmetic per element as the kernel above.
 constexpr int WPW = 2;
 __global__ __launch_bounds__(WNT) void bn_apply_pool_wide_kernel(const bf16* __restrict__ y, int ycs, int C, int N, int D, int H, int W,
-                                                                 float* __restrict__ stat, BnPart tr, const float* __restrict__ drop,
+                                                                 float* __restrict__ stat, BnSmall tr, const float* __restrict__ drop,
                                                                  bf16* __restrict__ z, int zcs, bf16* __restrict__ pl, int pcs) {
     constexpr int VEC = 8;
     const int G = C / VEC, Do = D / 2, Ho = H / 2, Wo = W / 2;
@@ -487,44 +490,30 @@ __global__ __launch_bounds__(WNT) void bn_apply_pool_wide_kernel(const bf16* __r
     const unsigned windows = (unsigned)N * Do * Ho * Wo, wstep = (gridDim.x * WNT) / TPW;
     unsigned win = gtid / TPW;
     bf16x8 raw[WPW][4];
-    int base[WPW], smp[WPW];          // voxel index of the window's corner (+ this thread's x offset), its sample
+    int base[WPW], smp[WPW];          // voxel index of the window's corner + this thread's x offset (taps k = 2q + pc), its sample
     auto issue = [&]() {
 #pragma unroll
         for (int u = 0; u < WPW; u++) {
-            unsigned r = win + u * wstep;
-            if (r < windows) {
-                const int wo = (int)(r % (unsigned)Wo); r /= (unsigned)Wo;
-                const int ho = (int)(r % (unsigned)Ho); r /= (unsigned)Ho;
-                const int d_o = (int)(r % (unsigned)Do);
-                smp[u] = (int)(r / (unsigned)Do);
-                base[u] = ((smp[u] * D + 2 * d_o) * H + 2 * ho) * W + 2 * wo + pc;
+            if (win + u * wstep < windows) {
+                const PoolWin pw(win + u * wstep, Do, Ho, Wo);
+                smp[u] = pw.n;
+                base[u] = pw.corner(D, H, W) + pc;
 #pragma unroll
-                for (int q = 0; q < 4; q++)       // k = 2q + pc: (dz, dy) = (q >> 1, q & 1), dx = pc
-                    raw[u][q] = *reinterpret_cast<const bf16x8*>(y + (int64_t)(base[u] + ((q >> 1) * H + (q & 1)) * W) * ycs + g * VEC);
+                for (int q = 0; q < 4; q++)
+                    raw[u][q] = *reinterpret_cast<const bf16x8*>(y + (int64_t)(base[u] + tap_off(2 * q, H, W)) * ycs + g * VEC);
             }
         }
     };
     issue();
-    __shared__ double red[WNT * 4];
-    __shared__ float ab[2 * MAXC_BN];
-    bn_train_coeffs<WNT>(tr, C, stat, ab, red);
     float a[VEC], b[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; i++) { a[i] = ab[g * VEC + i]; b[i] = ab[MAXC_BN + g * VEC + i]; }
-    float ds[VEC];
-    int dn = -1;
-#pragma unroll
-    for (int i = 0; i < VEC; i++) ds[i] = 1.f;
+    load_ab<VEC, true, WNT>(tr, C, stat, g, a, b);          // after issue(): the loads are in flight during the prologue
+    DropCache<VEC> dc;
     while (win < windows) {
 #pragma unroll
         for (int u = 0; u < WPW; u++) {
             const unsigned w_ = win + u * wstep;
             if (w_ < windows) {                                   // uniform over a window's thread pair (the lane swap below)
-                if (drop && smp[u] != dn) {
-                    dn = smp[u];
-#pragma unroll
-                    for (int i = 0; i < VEC; i++) ds[i] = drop[(int64_t)dn * C + g * VEC + i];
-                }
+                dc.at_sample(drop, smp[u], C, g * VEC);
                 float m[VEC];
 #pragma unroll
                 for (int i = 0; i < VEC; i++) m[i] = -INFINITY;
@@ -533,13 +522,11 @@ __global__ __launch_bounds__(WNT) void bn_apply_pool_wide_kernel(const bf16* __r
                     bf16x8 o;
 #pragma unroll
                     for (int i = 0; i < VEC; i++) {
-                        float t = fmaf((float)raw[u][q][i], a[i], b[i]);
-                        t = t > 0.f ? t : 0.f;
-                        o[i] = (bf16)(t * ds[i]);
+                        o[i] = (bf16)bn_act((float)raw[u][q][i], a[i], b[i], dc.s[i]);
                         const float of = (float)o[i];              // the pooled value is the maximum of the STORED values
                         m[i] = of > m[i] ? of : m[i];
                     }
-                    *reinterpret_cast<bf16x8*>(z + (int64_t)(base[u] + ((q >> 1) * H + (q & 1)) * W) * zcs + g * VEC) = o;
+                    *reinterpret_cast<bf16x8*>(z + (int64_t)(base[u] + tap_off(2 * q, H, W)) * zcs + g * VEC) = o;
                 }
                 bf16x8 mo;
 #pragma unroll
@@ -594,15 +581,13 @@ __device__ __forceinline__ void bn_bwd_reduce_body(int nred, const T* __restrict
             dc.at(drop, row, V, C, g * VEC);
 #pragma unroll
             for (int i = 0; i < VEC; i++) {
-                float pre = fmaf(yv[i], a[i], b[i]);
-                float m = pre > 0.f ? dc.s[i] : 0.f;
-                float dyh = gv[i] * m;
+                float dyh = gv[i] * bn_mask(yv[i], a[i], b[i], dc.s[i]);
                 acc[0][i] += dyh;
                 acc[1][i] += dyh * (yv[i] - mean[i]) * inv[i];
             }
         }
     }
-    block_colreduce<VEC, 2>(acc, C, active, lds, part);
+    block_colreduce<VEC, 2>(acc, C, r, g, R, active, lds, part);
 }
 
 template <typename T, int VEC>
@@ -628,34 +613,33 @@ __global__ __launch_bounds__(BLK) void bn_bwd_reduce_slab_kernel(int nred, const
     }
 }
 
-// coef[3][C] = {c1 = sum_dyh / M, c2 = sum_dyh_xhat / M, g = gamma*invstd(=a)}; dgamma, dbeta (+)=
+// dgamma = sum dyh*xhat, dbeta = sum dyh over the whole tensor, (+)=
+__device__ __forceinline__ void bwd_param_grads(float* dgamma, float* dbeta, int c, int accumulate, double s, double q) {
+    if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
+    if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
+}
+// dy = g*(dyh - c1 - xhat*c2) rewritten per channel as  dy = g*dyh + A*y + B  with
+//   A = -g*c2*invstd,  B = g*(c2*invstd*mean - c1)       (c1 = sum_dyh / M, c2 = sum_dyh_xhat / M, g = gamma*invstd = a)
+__device__ __forceinline__ void bwd_coef(float c1, float c2, float g, float mean, float inv, float& A, float& B) {
+    float k = g * c2 * inv;
+    A = -k;
+    B = k * mean - g * c1;
+}
+
+// coef[3][C] = {c1, c2, g}; dgamma, dbeta (+)=.  One FIN_T-thread block per channel
 __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int nblk, int C, int64_t M,
                                        const float* stat, float* dgamma, float* dbeta, int accumulate, float* coef) {
-    __shared__ double ws_[FIN_T / 64][2];
-    int c = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int b = lane; b < nblk; b += FIN_T) {
-        s += (double)part[((size_t)b * 2 + 0) * C + c];
-        q += (double)part[((size_t)b * 2 + 1) * C + c];
-    }
-    s = wave_sum_d(s);
-    q = wave_sum_d(q);
-    if ((lane & 63) == 0) { ws_[lane >> 6][0] = s; ws_[lane >> 6][1] = q; }
-    __syncthreads();
-    if (lane == 0) {
-        s = 0.0; q = 0.0;
-#pragma unroll
-        for (int w = 0; w < FIN_T / 64; w++) { s += ws_[w][0]; q += ws_[w][1]; }
+    double s, q;
+    if (part_channel_sum(part, nblk, C, s, q)) {
+        int c = blockIdx.x;
         coef[c] = (float)(s / (double)M);
         coef[C + c] = (float)(q / (double)M);
         coef[2 * C + c] = stat[2 * C + c];
-        if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)q : (float)q;
-        if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s : (float)s;
+        bwd_param_grads(dgamma, dbeta, c, accumulate, s, q);
     }
 }
 
-// dy = g*(dyh - c1 - xhat*c2) rewritten per channel as  dy = g*dyh + A*y + B  with
-//   A = -g*c2*invstd,  B = g*(c2*invstd*mean - c1);  coefficients live in registers (fixed channel group per thread)
+// The coefficients live in registers (fixed channel group per thread).
 // SMALL: no finalize launch ran -- `coef` is the reduction's partial rows [nrows][2][C]; the prologue sums them (every
 // workgroup, fixed order, double) and workgroup 0 writes dgamma / dbeta (+)=
 template <typename T, int VEC, bool SMALL>
@@ -669,6 +653,8 @@ __global__ __launch_bounds__(BLK) void bn_bwd_apply_kernel(const T* __restrict__
     int g = (int)(gtid % G);
     int64_t row = gtid / G, rstep = ((int64_t)gridDim.x * BLK) / G;
     float a[VEC], b[VEC], gg[VEC], A[VEC], B[VEC];
+    const float* c12 = coef;          // c1 = c12[c], c2 = c12[c2o + c]: the finalize kernel's coef, or this workgroup's own in LDS
+    int c2o = C;
     if constexpr (SMALL) {
         __shared__ double red[BLK * 4];
         __shared__ float cf[2 * MAXC_BN];
@@ -678,33 +664,19 @@ __global__ __launch_bounds__(BLK) void bn_bwd_apply_kernel(const T* __restrict__
             int c = threadIdx.x;
             cf[c] = (float)(sq[0] / (double)M);
             cf[MAXC_BN + c] = (float)(sq[1] / (double)M);
-            if (blockIdx.x == 0) {
-                if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)sq[1] : (float)sq[1];
-                if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)sq[0] : (float)sq[0];
-            }
+            if (blockIdx.x == 0) bwd_param_grads(dgamma, dbeta, c, accumulate, sq[0], sq[1]);
         }
         __syncthreads();
+        c12 = cf;
+        c2o = MAXC_BN;
+    }
 #pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            int c = g * VEC + i;
-            float mean = stat[c], inv = stat[C + c];
-            a[i] = stat[2 * C + c]; b[i] = stat[3 * C + c];
-            gg[i] = a[i];
-            float k = gg[i] * cf[MAXC_BN + c] * inv;
-            A[i] = -k;
-            B[i] = k * mean - gg[i] * cf[c];
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            int c = g * VEC + i;
-            float mean = stat[c], inv = stat[C + c];
-            a[i] = stat[2 * C + c]; b[i] = stat[3 * C + c];
-            gg[i] = coef[2 * C + c];
-            float k = gg[i] * coef[C + c] * inv;
-            A[i] = -k;
-            B[i] = k * mean - gg[i] * coef[c];
-        }
+    for (int i = 0; i < VEC; i++) {
+        int c = g * VEC + i;
+        float mean = stat[c], inv = stat[C + c];
+        a[i] = stat[2 * C + c]; b[i] = stat[3 * C + c];
+        gg[i] = SMALL ? a[i] : coef[2 * C + c];
+        bwd_coef(c12[c], c12[c2o + c], gg[i], mean, inv, A[i], B[i]);
     }
     DropCache<VEC> dc;
     for (; row < M; row += rstep) {
@@ -713,11 +685,8 @@ __global__ __launch_bounds__(BLK) void bn_bwd_apply_kernel(const T* __restrict__
         ldv<T, VEC>(dz + row * dzcs + g * VEC, gv);
         dc.at(drop, row, V, C, g * VEC);
 #pragma unroll
-        for (int i = 0; i < VEC; i++) {
-            float pre = fmaf(yv[i], a[i], b[i]);
-            float m = pre > 0.f ? dc.s[i] : 0.f;
-            o[i] = fmaf(gg[i] * m, gv[i], fmaf(A[i], yv[i], B[i]));
-        }
+        for (int i = 0; i < VEC; i++)
+            o[i] = fmaf(gg[i] * bn_mask(yv[i], a[i], b[i], dc.s[i]), gv[i], fmaf(A[i], yv[i], B[i]));
         stv<T, VEC>(dy + row * dycs + g * VEC, o);
     }
 }
@@ -775,17 +744,20 @@ inline bool bn_small(int C, int64_t M) {
     return C >= 4 && C <= MAXC_BN && (C & (C - 1)) == 0 && M * C <= SMALL_ELEMS && !mi3d_routes().no_small_bn;
 }
 // number of partial rows for a small tensor
-inline int bn_small_rows(int nblk, int C) { return nblk > SMALL_ROWS ? SMALL_ROWS : nblk; }
+inline int bn_small_rows(int nblk) { return nblk > SMALL_ROWS ? SMALL_ROWS : nblk; }
 bool bn_small_ok(int C, int64_t M, int rows) { return bn_small(C, M) && rows >= 1 && rows <= SMALL_ROWS; }
+// the wide kernels' shape: 16-byte channel groups, and at most WIDE_J pieces of the rows per thread (rows_sum_wide)
+inline bool wide_rows_ok(int C, int rows) {
+    return C >= 8 && C <= MAXC_BN && (C & (C - 1)) == 0 && (int64_t)rows * C <= (int64_t)WIDE_J * WNT * 2;
+}
 // round 4: `rows` partial rows written by a conv epilogue ([rows][2][C]) can be finished by the consumer (thin workgroups up to
 // SMALL_ROWS rows, the wide kernels above that; the wide kernels for every row count measured no gain, 2.1518 vs 2.1510 ms/step in
 // profiles/r04_experiments_wide_bn.txt): no finalize launch between the conv and the apply pass
-inline bool wide_shape_ok(int C) { return C >= 8 && C <= MAXC_BN && (C & (C - 1)) == 0; }
 bool bn_rows_route_ok(int C, int64_t M, int rows) {
     const int mode = mi3d_routes().wide_bn;
     if (!(mode & 1) || rows < 1 || M * C >= (1ll << 31)) return false;
     if (rows <= SMALL_ROWS) return C >= 4 && C <= MAXC_BN && (C & (C - 1)) == 0;
-    return (mode & 2) && rows <= WIDE_ROWS && wide_shape_ok(C) && (int64_t)rows * C <= (int64_t)WIDE_J * WNT * 2;
+    return (mode & 2) && rows <= WIDE_ROWS && wide_rows_ok(C, rows);
 }
 // workgroups of a wide pass: every one pulls all partial rows through its XCD's L2, so the cost grows with their number
 // (profiles/r04_experiments_wide_bn.txt, ms/step: 256 2.0575, 512 2.0679, 1024 2.0992 on one box; 256 2.1510, 384 2.1632 on another)
@@ -794,6 +766,27 @@ inline int wide_grid(int64_t total_threads) {
     int want = (int)((total_threads + WNT - 1) / WNT);
     return want < 1 ? 1 : (want > WIDE_WGS ? WIDE_WGS : want);
 }
+// the kernels' copy of the caller's partial statistics: checked, M filled in.  No statistics: all zero, never read
+inline int bn_small_arg(const char* who, const BnSmall* small, int C, int64_t M, BnSmall& t) {
+    t = BnSmall{};
+    if (!small) return 0;
+    MI3D_CHECK_ARG(small->part && small->nrows >= 1 && small->nrows <= WIDE_ROWS && C <= MAXC_BN && small->gamma && small->beta,
+                   "%s: bad partial statistics", who);
+    t = *small;
+    t.M = M;
+    return 0;
+}
+// compile-time copies of a launcher's run-time choices, in the style of DISPATCH_T: each launcher names its kernel once
+#define DISPATCH_VEC(v8, VEC, ...)                               \
+    do {                                                         \
+        if (v8) { constexpr int VEC = 8; __VA_ARGS__ }           \
+        else { constexpr int VEC = 1; __VA_ARGS__ }              \
+    } while (0)
+#define DISPATCH_FLAG(flag, F, ...)                              \
+    do {                                                         \
+        if (flag) { constexpr bool F = true; __VA_ARGS__ }       \
+        else { constexpr bool F = false; __VA_ARGS__ }           \
+    } while (0)
 
 int bn_train_stats(int dtype, const void* y, int ycs, int C, int64_t M, const float* gamma, const float* beta,
                    float* running_mean, float* running_var, int64_t* nbt, float momentum, float eps, float* stat,
@@ -805,17 +798,12 @@ int bn_train_stats(int dtype, const void* y, int ycs, int C, int64_t M, const fl
         bool v8 = vec8_ok(C, ycs, ycs, y, y, sizeof(T));
         int G = v8 ? C / 8 : C, R = BLK / G;
         int nblk = reduce_grid(M, R);
-        if (small) nblk = bn_small_rows(nblk, C);
+        if (small) nblk = bn_small_rows(nblk);
         size_t lds = (size_t)2 * R * C * sizeof(float);
-        if (v8) bn_stats_kernel<T, 8><<<nblk, BLK, lds, s>>>((const T*)y, ycs, C, M, ws);
-        else bn_stats_kernel<T, 1><<<nblk, BLK, lds, s>>>((const T*)y, ycs, C, M, ws);
+        DISPATCH_VEC(v8, VEC, { bn_stats_kernel<T, VEC><<<nblk, BLK, lds, s>>>((const T*)y, ycs, C, M, ws); });
         MI3D_LAUNCH_CHECK();
         if (small) *small_rows = nblk;
-        else {
-            bn_stats_finalize_kernel<<<C, FIN_T, 0, s>>>(ws, nblk, C, M, gamma, beta, running_mean, running_var, nbt,
-                                                     momentum, eps, stat);
-            MI3D_LAUNCH_CHECK();
-        }
+        else MI3D_TRY(bn_train_finalize(ws, nblk, C, M, gamma, beta, running_mean, running_var, nbt, momentum, eps, stat, s));
     });
     return 0;
 }
@@ -839,17 +827,12 @@ int bn_apply_relu_drop(int dtype, const void* y, int ycs, int C, int64_t M, int6
                        const float* drop, void* z, int zcs, hipStream_t s, const BnSmall* small) {
     MI3D_CHECK_ARG(C >= 1 && M >= 1, "bn_apply: bad shape");
     MI3D_CHECK_ARG(!drop || M < (1ll << 32), "bn_apply: dropout path needs M < 2^32 (32-bit sample index)");
-    BnPart t{};
-    if (small) {
-        MI3D_CHECK_ARG(small->part && small->nrows >= 1 && small->nrows <= WIDE_ROWS && C <= MAXC_BN && small->gamma && small->beta,
-                       "bn_apply: bad partial statistics");
-        t = BnPart{small->part, small->nrows, M, small->gamma, small->beta, small->running_mean, small->running_var,
-                   small->num_batches_tracked, small->momentum, small->eps};
-    }
+    BnSmall t;
+    MI3D_TRY(bn_small_arg("bn_apply", small, C, M, t));
     DISPATCH_T(dtype, T, {
         bool v8 = vec8_ok(C, ycs, zcs, y, z, sizeof(T));
         if (small && small->nrows > SMALL_ROWS) {
-            if (v8 && dtype == MI3D_BF16 && wide_shape_ok(C) && (int64_t)small->nrows * C <= (int64_t)WIDE_J * WNT * 2) {
+            if (v8 && dtype == MI3D_BF16 && wide_rows_ok(C, small->nrows)) {
                 bn_apply_wide_kernel<<<wide_grid(M * (C / 8)), WNT, 0, s>>>((const bf16*)y, ycs, C, M, V, stat, t, drop, (bf16*)z, zcs);
                 MI3D_LAUNCH_CHECK();
                 return 0;
@@ -857,10 +840,9 @@ int bn_apply_relu_drop(int dtype, const void* y, int ycs, int C, int64_t M, int6
             MI3D_CHECK_ARG(small->nrows <= SMALL_ROWS, "bn_apply: %d partial rows need the wide kernel (C = %d, 16-byte rows)", small->nrows, C);
         }
         int grid = v8 ? stream_grid(M * (C / 8), C / 8) : stream_grid(M * C, C);
-        if (v8 && small) bn_apply_kernel<T, 8, true><<<grid, BLK, 0, s>>>((const T*)y, ycs, C, M, V, stat, t, drop, (T*)z, zcs);
-        else if (v8) bn_apply_kernel<T, 8, false><<<grid, BLK, 0, s>>>((const T*)y, ycs, C, M, V, stat, t, drop, (T*)z, zcs);
-        else if (small) bn_apply_kernel<T, 1, true><<<grid, BLK, 0, s>>>((const T*)y, ycs, C, M, V, stat, t, drop, (T*)z, zcs);
-        else bn_apply_kernel<T, 1, false><<<grid, BLK, 0, s>>>((const T*)y, ycs, C, M, V, stat, t, drop, (T*)z, zcs);
+        DISPATCH_VEC(v8, VEC, DISPATCH_FLAG(small != nullptr, TRAIN, {
+            bn_apply_kernel<T, VEC, TRAIN><<<grid, BLK, 0, s>>>((const T*)y, ycs, C, M, V, stat, t, drop, (T*)z, zcs);
+        }););
         MI3D_LAUNCH_CHECK();
     });
     return 0;
@@ -871,13 +853,8 @@ int bn_apply_relu_drop_pool(int dtype, const void* y, int ycs, int C, Geo g, flo
     const int64_t M = g.M();
     MI3D_CHECK_ARG(C >= 1 && M >= 1 && g.D % 2 == 0 && g.H % 2 == 0 && g.W % 2 == 0 && M * C < (1ll << 31),
                    "bn_apply_pool: needs even sides and fewer than 2^31 elements");
-    BnPart t{};
-    if (small) {
-        MI3D_CHECK_ARG(small->part && small->nrows >= 1 && small->nrows <= WIDE_ROWS && C <= MAXC_BN && small->gamma && small->beta,
-                       "bn_apply_pool: bad partial statistics");
-        t = BnPart{small->part, small->nrows, M, small->gamma, small->beta, small->running_mean, small->running_var,
-                   small->num_batches_tracked, small->momentum, small->eps};
-    }
+    BnSmall t;
+    MI3D_TRY(bn_small_arg("bn_apply_pool", small, C, M, t));
     DISPATCH_T(dtype, T, {
         bool v8 = vec8_ok(C, ycs, zcs, y, z, sizeof(T)) && pcs % 8 == 0 && ((uintptr_t)pooled % 16 == 0);
         int grid = v8 ? stream_grid(M / 8 * (C / 8), C / 8) : stream_grid(M / 8 * C, C);
@@ -886,19 +863,17 @@ int bn_apply_relu_drop_pool(int dtype, const void* y, int ycs, int C, Geo g, flo
         const bool pair = v8 && (G8 & (G8 - 1)) == 0 && G8 <= 32 && !mi3d_routes().no_pool_pair;
         if (pair) grid = stream_grid(M / 8 * G8 * 2, G8 * 2);
         if (small && small->nrows > SMALL_ROWS) {
-            if (pair && dtype == MI3D_BF16 && wide_shape_ok(C) && (int64_t)small->nrows * C <= (int64_t)WIDE_J * WNT * 2) {
+            if (pair && dtype == MI3D_BF16 && wide_rows_ok(C, small->nrows)) {
                 bn_apply_pool_wide_kernel<<<wide_grid(M / 8 * G8 * 2), WNT, 0, s>>>((const bf16*)y, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, (bf16*)z, zcs, (bf16*)pooled, pcs);
                 MI3D_LAUNCH_CHECK();
                 return 0;
             }
             MI3D_CHECK_ARG(small->nrows <= SMALL_ROWS, "bn_apply_pool: %d partial rows need the wide kernel (C = %d)", small->nrows, C);
         }
-        if (pair && small) bn_apply_pool_kernel<T, 8, true, true><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
-        else if (pair) bn_apply_pool_kernel<T, 8, false, true><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
-        else if (v8 && small) bn_apply_pool_kernel<T, 8, true><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
-        else if (v8) bn_apply_pool_kernel<T, 8, false><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
-        else if (small) bn_apply_pool_kernel<T, 1, true><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
-        else bn_apply_pool_kernel<T, 1, false><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
+        // pair implies v8: PAIR && VEC == 8 names no <1, *, true> instantiation
+        DISPATCH_VEC(v8, VEC, DISPATCH_FLAG(small != nullptr, TRAIN, DISPATCH_FLAG(pair, PAIR, {
+            bn_apply_pool_kernel<T, VEC, TRAIN, PAIR && VEC == 8><<<grid, BLK, 0, s>>>(yp, ycs, C, g.N, g.D, g.H, g.W, stat, t, drop, zp, zcs, pp, pcs);
+        });););
         MI3D_LAUNCH_CHECK();
     });
     return 0;
@@ -917,26 +892,28 @@ int bn_bwd(int dtype, const void* dz, int dzcs, const void* y, int ycs, int C, i
         MI3D_CHECK_ARG(!skp || (v8 && ks >= 1), "bn_bwd: split-K source needs the vector path");
         int G = v8 ? C / 8 : C, R = BLK / G;
         int nblk = reduce_grid(M, R);
-        if (small) nblk = bn_small_rows(nblk, C);
+        if (small) nblk = bn_small_rows(nblk);
         size_t lds = (size_t)2 * R * C * sizeof(float);
+        const T* dzp = (const T*)dz; const T* yp = (const T*)y; T* dyp = (T*)dy;
         if (extra && extra->nblocks > 0) {
             SlabJob j2 = (extra2 && extra2->nblocks > 0) ? *extra2 : SlabJob();
             int tot = nblk + extra->nblocks + j2.nblocks;
-            if (v8) bn_bwd_reduce_slab_kernel<T, 8><<<tot, BLK, lds, s>>>(nblk, (const T*)dz, dzcs, (const T*)y, ycs, C, M, V, stat, drop, part, *extra, j2, skp, ks);
-            else bn_bwd_reduce_slab_kernel<T, 1><<<tot, BLK, lds, s>>>(nblk, (const T*)dz, dzcs, (const T*)y, ycs, C, M, V, stat, drop, part, *extra, j2, nullptr, 0);
-        } else if (v8) bn_bwd_reduce_kernel<T, 8><<<nblk, BLK, lds, s>>>((const T*)dz, dzcs, (const T*)y, ycs, C, M, V, stat, drop, part, skp, ks);
-        else bn_bwd_reduce_kernel<T, 1><<<nblk, BLK, lds, s>>>((const T*)dz, dzcs, (const T*)y, ycs, C, M, V, stat, drop, part, nullptr, 0);
+            DISPATCH_VEC(v8, VEC, {
+                bn_bwd_reduce_slab_kernel<T, VEC><<<tot, BLK, lds, s>>>(nblk, dzp, dzcs, yp, ycs, C, M, V, stat, drop, part, *extra, j2, skp, ks);
+            });
+        } else
+            DISPATCH_VEC(v8, VEC, { bn_bwd_reduce_kernel<T, VEC><<<nblk, BLK, lds, s>>>(dzp, dzcs, yp, ycs, C, M, V, stat, drop, part, skp, ks); });
         MI3D_LAUNCH_CHECK();
         if (!small) {
             bn_bwd_finalize_kernel<<<C, FIN_T, 0, s>>>(part, nblk, C, M, stat, dgamma, dbeta, accumulate, coef);
             MI3D_LAUNCH_CHECK();
         }
         int grid = v8 ? stream_grid(M * (C / 8), C / 8) : stream_grid(M * C, C);
-        const T* dzp = (const T*)dz; const T* yp = (const T*)y; T* dyp = (T*)dy;
-        if (small && v8) bn_bwd_apply_kernel<T, 8, true><<<grid, BLK, 0, s>>>(dzp, dzcs, yp, ycs, C, M, V, stat, part, nblk, dgamma, dbeta, accumulate, drop, dyp, dycs);
-        else if (small) bn_bwd_apply_kernel<T, 1, true><<<grid, BLK, 0, s>>>(dzp, dzcs, yp, ycs, C, M, V, stat, part, nblk, dgamma, dbeta, accumulate, drop, dyp, dycs);
-        else if (v8) bn_bwd_apply_kernel<T, 8, false><<<grid, BLK, 0, s>>>(dzp, dzcs, yp, ycs, C, M, V, stat, coef, 0, nullptr, nullptr, 0, drop, dyp, dycs);
-        else bn_bwd_apply_kernel<T, 1, false><<<grid, BLK, 0, s>>>(dzp, dzcs, yp, ycs, C, M, V, stat, coef, 0, nullptr, nullptr, 0, drop, dyp, dycs);
+        // SMALL: the reduction's rows go in as `coef`, and workgroup 0 writes the parameter gradients; otherwise the finalize kernel did
+        DISPATCH_VEC(v8, VEC, DISPATCH_FLAG(small, SMALL, {
+            bn_bwd_apply_kernel<T, VEC, SMALL><<<grid, BLK, 0, s>>>(dzp, dzcs, yp, ycs, C, M, V, stat, SMALL ? part : coef, nblk, dgamma, dbeta,
+                                                                    accumulate, drop, dyp, dycs);
+        }););
         MI3D_LAUNCH_CHECK();
     });
     return 0;
@@ -952,14 +929,12 @@ int bn_train_stats_splitk(const float* skp, int ks, const float* bias, void* y, 
     int G = C / 8, R = BLK / G;
     int64_t want = (M + R - 1) / R;                 // one row per thread: the ks fp32 partial reads dominate, spread them wide
     int nblk = (int)(want > MAXBLK ? MAXBLK : want);
-    if (small) nblk = bn_small_rows(nblk, C);
+    if (small) nblk = bn_small_rows(nblk);
     size_t lds = (size_t)2 * R * C * sizeof(float);
     bn_stats_splitk_kernel<<<nblk, BLK, lds, s>>>(skp, ks, bias, (bf16*)y, ycs, C, M, ws);
     MI3D_LAUNCH_CHECK();
     if (small) { *small_rows = nblk; return 0; }
-    bn_stats_finalize_kernel<<<C, FIN_T, 0, s>>>(ws, nblk, C, M, gamma, beta, running_mean, running_var, nbt, momentum, eps, stat);
-    MI3D_LAUNCH_CHECK();
-    return 0;
+    return bn_train_finalize(ws, nblk, C, M, gamma, beta, running_mean, running_var, nbt, momentum, eps, stat, s);
 }
 
 int bn_deferred_apply(const BnDeferJobs& J, hipStream_t s) {

@@ -117,6 +117,7 @@ struct BnSmall {
     const float* part; int nrows;
     const float* gamma; const float* beta; float* running_mean; float* running_var; int64_t* num_batches_tracked;
     float momentum, eps;
+    int64_t M = 0;      // elements per channel: filled in by the launcher, which hands the kernels its own copy
 };
 // same finalize, fed by conv-epilogue partials part[nblk][2][C]
 int bn_train_finalize(const float* part, int nblk, int C, int64_t M, const float* gamma, const float* beta,
