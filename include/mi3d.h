@@ -296,6 +296,45 @@ int mi3d_zoom3_cubic(const float* in, float* out, int D, int H, int W, int Do, i
 int mi3d_zoom3_nearest_i64(const int64_t* in, int64_t* out, int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d,
                            int rows_d, const int32_t* index_h, int rows_h, const int32_t* index_w, int rows_w, void* stream);
 
+/* The same scan AS STORED: what the scripts do before the first zoom (reorient_to_ras, amos_ct_resample.py:29-36 = io_orientation
+ * -> ornt_transform -> apply_orientation, a host flip + transpose of the whole volume) folded into the reads.  The source is any
+ * dense 3-D array (a permutation of a contiguous one) of the dtype below; D, H, W are its sides in RAS order and stride_d/h/w the
+ * element strides of those axes in the stored array (orientation.py axis_map).  Nothing is copied on the host.  The entry points
+ * check that the strides are positive; that (D - 1) * stride_d + (H - 1) * stride_h + (W - 1) * stride_w lies inside the buffer is the
+ * caller's guarantee (resample.py admits dense tensors only, orientation.check_dense). */
+enum { MI3D_SRC_U8 = 0, MI3D_SRC_I16 = 1, MI3D_SRC_F32 = 2, MI3D_SRC_I64 = 3 };
+/* apply_orientation (amos_ct_resample.py:33): out (D, H, W) contiguous, float32 (out_i64 = 0; from uint8, int16, float32: the
+ * .astype(np.float32) of :47) or int64 (out_i64 = 1; from uint8, int16, int64), out[d][h][w] = in[d' * stride_d + h' * stride_h +
+ * w' * stride_w] with i' = n - 1 - i on the axes whose flip_mask bit is set (1: D, 2: H, 4: W).  A stored-fastest W is a streamed
+ * copy with 16-byte stores; a stored-fastest D or H goes through 32 x 32 LDS tiles, read and written coalesced. */
+int mi3d_reorient3(const void* in, int src_dtype, void* out, int out_i64, int D, int H, int W, int64_t stride_d, int64_t stride_h,
+                   int64_t stride_w, int flip_mask, void* stream);
+/* mi3d_zoom3_cubic of the reoriented scan without making it (amos_ct_resample.py:33 + :60).  Tables as there, built in RAS order;
+ * for a flipped axis the caller replaces every tap index i by n - 1 - i AFTER the clamp (weights unchanged).  Same taps, same
+ * float64 sums in the same order: bit-identical to mi3d_zoom3_cubic on mi3d_reorient3's float32 output.  Source: uint8, int16 or
+ * float32. */
+int mi3d_zoom3_cubic_src(const void* in, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, float* out, int D,
+                         int H, int W, int Do, int Ho, int Wo, const void* table_d, int rows_d, const void* table_h, int rows_h,
+                         const void* table_w, int rows_w, int ct_window, float window_min, float window_max, void* stream);
+/* mi3d_zoom3_nearest_i64 of the reoriented label (chaos_resample.py:40-44 + :83,87; amos_ct_resample.py:93,97), index tables
+ * remapped for flips in the same way.  Source: uint8, int16 or int64; out: int64. */
+int mi3d_zoom3_nearest_src(const void* in, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, int64_t* out, int D,
+                           int H, int W, int Do, int Ho, int Wo, const int32_t* index_d, int rows_d, const int32_t* index_h,
+                           int rows_h, const int32_t* index_w, int rows_w, void* stream);
+/* The TotalSegmentator mask merge (resample_totalseg_ras_mri.py:77-96: per organ reorient, two order-0 zooms,
+ * label_combined[label_resized > 0] = value) as ONE gather: out = 0, then for k = 0 .. n-1: if (mask_k[source voxel] > 0) out =
+ * value_k, so later entries win as in the script's loop; n = 0 gives zeros (the script's "file not found" branch for every organ).
+ * All masks share the shape, the strides, the dtype (uint8 or float32) and the composed index tables. */
+#define MI3D_MAX_MASKS 8
+typedef struct {
+    const void* mask[MI3D_MAX_MASKS];
+    int64_t value[MI3D_MAX_MASKS];
+    int32_t n;
+} mi3d_mask_list;
+int mi3d_merge_masks3(const mi3d_mask_list* masks, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, int64_t* out,
+                      int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d, int rows_d, const int32_t* index_h,
+                      int rows_h, const int32_t* index_w, int rows_w, void* stream);
+
 /* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
  * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)
  * with the random decisions already drawn by the host (spatial.py), as one gather pass.  img: float32, lab: int64, both

@@ -39,7 +39,15 @@ class AugParams(C.Structure):                      # mi3d_aug_params
                 ("hole_size", C.c_int32 * 3), ("hole_lo", (C.c_int32 * 3) * AUG_MAX_HOLES), ("fill_value", C.c_float)]
 
 
-_DP, _LP, _AP = C.POINTER(UNetDesc), C.POINTER(LossCfg), C.POINTER(AugParams)
+MAX_MASKS = 8
+SRC_U8, SRC_I16, SRC_F32, SRC_I64 = 0, 1, 2, 3
+
+
+class MaskList(C.Structure):                       # mi3d_mask_list
+    _fields_ = [("mask", C.c_void_p * MAX_MASKS), ("value", C.c_int64 * MAX_MASKS), ("n", C.c_int32)]
+
+
+_DP, _LP, _AP, _MP = C.POINTER(UNetDesc), C.POINTER(LossCfg), C.POINTER(AugParams), C.POINTER(MaskList)
 
 # name -> (restype, argtypes); one line per symbol declared in include/mi3d.h
 _SIGS = {
@@ -98,6 +106,10 @@ _SIGS = {
     "mi3d_zoom3_workspace_bytes": (sz, [i32, i32, i32]),
     "mi3d_zoom3_cubic": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
     "mi3d_zoom3_nearest_i64": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
+    "mi3d_reorient3": (i32, [vp, i32, vp, i32, i32, i32, i32, i64, i64, i64, i32, vp]),
+    "mi3d_zoom3_cubic_src": (i32, [vp, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
+    "mi3d_zoom3_nearest_src": (i32, [vp, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
+    "mi3d_merge_masks3": (i32, [_MP, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_plane_affine": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp]),
     "mi3d_augment_workspace_bytes": (sz, []),
     "mi3d_augment": (i32, [vp, vp, vp, i32, i32, i32, i32, _AP, vp, sz, vp]),

@@ -1,13 +1,24 @@
 """GPU mirror of the resampling that puts a decoded scan on the training grid: the four scipy.ndimage.zoom calls of the
 reference's offline scripts (scripts/resampling/amos_ct_resample.py:56-70,93-97; the same calls in
-chaos_resample.py:53,63,83,87 and resample_totalseg_ras_mri.py:57,65,92,94).  File decoding, RAS reorientation and the
-TotalSegmentator label merge stay outside: they are file and header work, not arithmetic.
+chaos_resample.py:53,63,83,87 and resample_totalseg_ras_mri.py:57,65,92,94), and what those scripts do around them per scan:
+reorient_to_ras (amos_ct_resample.py:29-36), the spacing from the reoriented affine (:51), the output affine (:77-78) and the
+TotalSegmentator mask merge (resample_totalseg_ras_mri.py:77-96).  File decoding (and get_fdata's scl_slope / scl_inter
+scaling) stays outside: callers pass the decoded array as it is stored, and its affine.
 
   zoom_output_shape(shape, factors)        scipy's output-shape rule
   axis_table(n_in, n_out, order)           float64 host tables of one axis (tap indices / weights, or nearest indices)
   zoom(volume, factors, order)             zoom(volume, factors, order=order, mode='nearest', prefilter=False), order 3 or 0
   resample_to_grid(image, spacing, ...)    the two-stage chain of the scripts (isotropic spacing, then the target shape)
   resample_labels_to_grid(label, spacing)  its label half alone: both order-0 stages composed into one gather
+  reorient_to_ras(volume, affine)          the scripts' reorient_to_ras of a stored device tensor: (RAS volume, new affine)
+  resample_scan(image, affine, ...)        the whole per-scan body: (image on the grid, label or None, output affine)
+  merge_masks_to_grid(masks, affine, ...)  the label of resample_scan(masks=...) alone
+
+A stored scan is any dense 3-D device tensor: a permutation of a contiguous array, such as the tensor made from nibabel's
+Fortran-ordered array without a host copy; int16 / uint8 / float32 images, uint8 / int16 / int64 labels, uint8 / float32 masks.
+Its orientation comes from the affine (orientation.py).  The kernels read it in place through element strides; flips go into
+the tables: they are built in RAS order exactly as below and index i of a flipped axis then becomes n - 1 - i (the zoom is not
+bitwise symmetric under a flip, so a table built in stored order would pick other voxels).
 
 Everything that decides WHICH voxels are read (coordinates, floor, rounding, clamping, spline weights) is computed here on
 the host in float64 exactly as scipy does it; the kernels (csrc/resample.hip) only gather and sum.
@@ -17,7 +28,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, orientation
 from ._lib import Mi3dError, call, ptr, stream_ptr
 
 # one row of a cubic table as the kernel reads it (csrc/resample.hip CubicRow, include/mi3d.h)
@@ -25,7 +36,7 @@ _ROW = np.dtype([("idx", "<i4", (4,)), ("w", "<f8", (4,))])
 assert _ROW.itemsize == 48
 
 TABLE_CACHE_SIZE = 256     # device tables kept (least recently used first out); one chain with labels uses at most 9
-_device_tables = collections.OrderedDict()     # (n_in, n_out, order, device) -> device tensor
+_device_tables = collections.OrderedDict()     # (n_in, n_out, order, device, flipped) -> device tensor
 table_uploads = 0          # host-to-device table copies made so far (a stream of same-shaped scans adds none)
 
 
@@ -50,10 +61,14 @@ def _coords(n_in, n_out):
     return np.arange(n_out, dtype=np.float64) * z
 
 
-def axis_table(n_in, n_out, order):
+def axis_table(n_in, n_out, order, flip=False):
     """Host tables of one axis, one row per output index.
     order 0: int32 (n_out,) input index floor(c + 0.5), clamped.
-    order 3: (int32 (n_out, 4) tap indices floor(c) - 1 .. floor(c) + 2, each clamped; float64 (n_out, 4) B-spline weights)."""
+    order 3: (int32 (n_out, 4) tap indices floor(c) - 1 .. floor(c) + 2, each clamped; float64 (n_out, 4) B-spline weights).
+    flip: the axis is stored reversed: the finished indices i become n_in - 1 - i, the weights stay."""
+    if flip:
+        t = axis_table(n_in, n_out, order)
+        return (int(n_in) - 1 - t).astype(np.int32) if order == 0 else ((int(n_in) - 1 - t[0]).astype(np.int32), t[1])
     n_in, n_out = int(n_in), int(n_out)
     if n_in < 1 or n_out < 1:
         raise Mi3dError(f"axis_table: sides must be positive, got {n_in} -> {n_out}")
@@ -92,21 +107,27 @@ def _cached(key, build, device):
     return t
 
 
-def _cubic_rows(n_in, n_out):
+def cubic_rows(n_in, n_out, flip=False):
+    """The order-3 table of one axis in the kernel's row format."""
     rows = np.zeros(int(n_out), dtype=_ROW)
-    rows["idx"], rows["w"] = axis_table(n_in, n_out, 3)
+    rows["idx"], rows["w"] = axis_table(n_in, n_out, 3, flip)
     return rows
 
 
-def _device_table(n_in, n_out, order, device):
-    key = (int(n_in), int(n_out), order, str(device))
-    return _cached(key, lambda: _cubic_rows(n_in, n_out) if order == 3 else axis_table(n_in, n_out, 0), device)
+def _device_table(n_in, n_out, order, device, flip=False):
+    key = (int(n_in), int(n_out), order, str(device), bool(flip))
+    return _cached(key, lambda: cubic_rows(n_in, n_out, flip) if order == 3 else axis_table(n_in, n_out, 0, flip), device)
 
 
-def _composed_index_table(n_in, n_mid, n_out, device):
-    """Two order-0 zooms along one axis as ONE gather: table1[table2]."""
-    key = (int(n_in), (int(n_mid), int(n_out)), 0, str(device))
-    return _cached(key, lambda: compose_index_tables(axis_table(n_in, n_mid, 0), axis_table(n_mid, n_out, 0)), device)
+def composed_index_table(n_in, n_mid, n_out, flip=False):
+    """Two order-0 zooms along one axis as ONE gather: table1[table2]; both built in RAS order, the result remapped for a flip."""
+    t = compose_index_tables(axis_table(n_in, n_mid, 0), axis_table(n_mid, n_out, 0))
+    return (int(n_in) - 1 - t).astype(np.int32) if flip else t
+
+
+def _composed_index_table(n_in, n_mid, n_out, device, flip=False):
+    key = (int(n_in), (int(n_mid), int(n_out)), 0, str(device), bool(flip))
+    return _cached(key, lambda: composed_index_table(n_in, n_mid, n_out, flip), device)
 
 
 def compose_index_tables(first, second):
@@ -233,3 +254,217 @@ def resample_to_grid(image, spacing, label=None, target_spacing=(1.0, 1.0, 1.0),
     if label is None:
         return out
     return out, resample_labels_to_grid(label, spacing, target_spacing, target_shape)
+
+
+# ---- scans as stored ----------------------------------------------------------------------------------------------------------
+_IMAGE_DTYPES = {torch.uint8: _lib.SRC_U8, torch.int16: _lib.SRC_I16, torch.float32: _lib.SRC_F32}
+_LABEL_DTYPES = {torch.uint8: _lib.SRC_U8, torch.int16: _lib.SRC_I16, torch.int64: _lib.SRC_I64}
+_MASK_DTYPES = {torch.uint8: _lib.SRC_U8, torch.float32: _lib.SRC_F32}
+MAX_MASKS = _lib.MAX_MASKS
+
+# Stage 1 of resample_scan by the RAS axis (0 = D, 1 = H, 2 = W) that is fastest in memory: "fused" reads the stored scan
+# inside the cubic kernel (mi3d_zoom3_cubic_src), "reorient" makes the float32 RAS copy (mi3d_reorient3) and runs the contiguous
+# kernel on it.  Both give the same bits, so the choice is invisible.  tools/time_resample.py has the rows that decide it per class;
+# they have not been measured yet, so the defaults are provisional: "reorient" where W is not fastest in
+# memory (a coalesced copy plus the measured contiguous kernel bounds the cost; fused, every tap of a lane is another cache
+# line), "fused" where it is (the same access pattern as the contiguous kernel, without the float32 copy).
+STAGE1_FORMS = ("fused", "reorient")
+STAGE1_DEFAULT = {0: "reorient", 1: "reorient", 2: "fused"}
+
+
+class _Stored:
+    """A stored tensor seen in RAS order: sides, element strides and flips of the RAS axes, and the reoriented affine."""
+
+    def __init__(self, volume, affine, what):
+        _check_volume(volume, what)
+        orientation.check_dense(volume.shape, volume.stride(), what)
+        amap = orientation.axis_map(affine, tuple(volume.shape), volume.stride())
+        self.shape = tuple(n for n, _, _ in amap)
+        self.strides = tuple(max(int(s), 1) if n > 1 else 1 for n, s, _ in amap)
+        self.flips = tuple(f and n > 1 for n, _, f in amap)
+        self.affine = orientation.reoriented_affine(affine, tuple(volume.shape))
+        self.device = volume.device
+        self.layout = (tuple(volume.shape), tuple(s for n, s in zip(volume.shape, volume.stride()) if n > 1))
+        # which RAS axis is fastest in memory (the one with stride 1 and more than one element; W where there is none)
+        self.fastest = next((a for a in (2, 1, 0) if self.shape[a] > 1 and self.strides[a] == 1), 2)
+
+    @property
+    def identity(self):
+        d, h, w = self.shape
+        return not any(self.flips) and all(n == 1 or s == c for n, s, c in zip(self.shape, self.strides, (h * w, w, 1)))
+
+    def ras_view(self, volume):
+        """The volume itself where its axes are the RAS axes, else the view of its memory in RAS order (no flips: a view
+        cannot hold one).  Contiguous where `identity` holds, e.g. for an F-ordered array stored with its axes reversed."""
+        if tuple(volume.shape) == self.shape and all(n == 1 or s == t for n, s, t in zip(self.shape, self.strides, volume.stride())):
+            return volume
+        return volume.as_strided(self.shape, self.strides, volume.storage_offset())
+
+    @property
+    def flip_mask(self):
+        return sum(1 << a for a in range(3) if self.flips[a])
+
+
+def _check_dtype(volume, table, what, kind):
+    code = table.get(volume.dtype)
+    if code is None:
+        raise Mi3dError(f"{what}: a stored {kind} is {' / '.join(str(d).replace('torch.', '') for d in table)}, got {volume.dtype}")
+    return code
+
+
+def _check_same_layout(other, image, src, what, kind):
+    _check_volume(other, what)
+    if other.device != image.device:
+        raise Mi3dError(f"{what}: the {kind} is on {other.device}, the image on {image.device}")
+    layout = (tuple(other.shape), tuple(s for n, s in zip(other.shape, other.stride()) if n > 1))
+    if layout != src.layout:
+        raise Mi3dError(f"{what}: the {kind} (shape {tuple(other.shape)}, strides {other.stride()}) is not laid out as the image "
+                        f"(shape {tuple(image.shape)}, strides {image.stride()})")
+
+
+def _reorient(volume, src, code, as_label):
+    out = torch.empty(src.shape, dtype=torch.int64 if as_label else torch.float32, device=volume.device)
+    call("mi3d_reorient3", ptr(volume), code, ptr(out), int(as_label), *src.shape, *src.strides, src.flip_mask, stream_ptr())
+    return out
+
+
+def reorient_to_ras(volume, affine, as_label=None):
+    """reorient_to_ras of the scripts (amos_ct_resample.py:29-36) for a stored device tensor: (contiguous RAS volume, affine of
+    that volume as host float64).  Images (uint8 / int16 / float32) come back as float32, labels (uint8 / int16 / int64) as int64;
+    as_label picks the kind where the dtype allows both (default: int64 is a label, everything else an image).  A volume
+    whose memory already is contiguous RAS of the output dtype is returned as it is, or as the view of it with the RAS axes."""
+    what = "reorient_to_ras"
+    src = _Stored(volume, affine, what)
+    if as_label is None:
+        as_label = volume.dtype == torch.int64
+    code = _check_dtype(volume, _LABEL_DTYPES if as_label else _IMAGE_DTYPES, what, "label" if as_label else "image")
+    if src.identity and volume.dtype == (torch.int64 if as_label else torch.float32):
+        return src.ras_view(volume), src.affine
+    return _reorient(volume, src, code, as_label), src.affine
+
+
+def _cubic_stored(volume, src, code, out_shape, out):
+    tabs = [_device_table(n, m, 3, src.device, f) for n, m, f in zip(src.shape, out_shape, src.flips)]
+    call("mi3d_zoom3_cubic_src", ptr(volume), code, *src.strides, ptr(out), *src.shape, *out_shape, ptr(tabs[0]), out_shape[0],
+         ptr(tabs[1]), out_shape[1], ptr(tabs[2]), out_shape[2], 0, 0.0, 1.0, stream_ptr())
+    return out
+
+
+def _composed_tables(src, shape1, target):
+    return [_composed_index_table(n, m, o, src.device, f) for n, m, o, f in zip(src.shape, shape1, target, src.flips)]
+
+
+def _nearest_stored(label, src, code, shape1, target):
+    tabs = _composed_tables(src, shape1, target)
+    out = torch.empty(target, dtype=torch.int64, device=src.device)
+    call("mi3d_zoom3_nearest_src", ptr(label), code, *src.strides, ptr(out), *src.shape, *target, ptr(tabs[0]), target[0],
+         ptr(tabs[1]), target[1], ptr(tabs[2]), target[2], stream_ptr())
+    return out
+
+
+def _check_masks(masks, what):
+    """[(tensor, value), ...] -> (tensors, values, dtype code); all of one layout, dtype and device."""
+    masks = list(masks)
+    if len(masks) > MAX_MASKS:
+        raise Mi3dError(f"{what}: {len(masks)} masks, at most {MAX_MASKS} are merged in one call")
+    tensors, values = [], []
+    for k, entry in enumerate(masks):
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise Mi3dError(f"{what}: masks is a list of (tensor, value) pairs; entry {k} is not")
+        t, v = entry
+        _check_volume(t, what)
+        if int(v) != v or not -2 ** 63 <= int(v) < 2 ** 63:
+            raise Mi3dError(f"{what}: the value of mask {k} is not an int64: {v!r}")
+        tensors.append(t)
+        values.append(int(v))
+    code = _lib.SRC_U8
+    for k, t in enumerate(tensors):
+        code = _check_dtype(t, _MASK_DTYPES, what, "mask")
+        if t.dtype != tensors[0].dtype:
+            raise Mi3dError(f"{what}: mask {k} is {t.dtype}, mask 0 is {tensors[0].dtype}")
+    return tensors, values, code
+
+
+def _merge_stored(tensors, values, code, src, shape1, target):
+    tabs = _composed_tables(src, shape1, target)
+    out = torch.empty(target, dtype=torch.int64, device=src.device)
+    m = _lib.MaskList()
+    m.n = len(tensors)
+    for k, (t, v) in enumerate(zip(tensors, values)):
+        m.mask[k], m.value[k] = ptr(t), v
+    call("mi3d_merge_masks3", m, code, *src.strides, ptr(out), *src.shape, *target, ptr(tabs[0]), target[0], ptr(tabs[1]),
+         target[1], ptr(tabs[2]), target[2], stream_ptr())
+    return out
+
+
+def _target(target_shape, what):
+    if len(target_shape) != 3:
+        raise Mi3dError(f"{what}: target_shape needs three sides, got {target_shape}")
+    return tuple(int(n) for n in target_shape)
+
+
+def _out_affine(src, target_spacing):
+    out = src.affine.copy()
+    out[:3, :3] = np.diag(np.asarray(target_spacing, dtype=np.float64))      # amos_ct_resample.py:77-78
+    return out
+
+
+def merge_masks_to_grid(masks, affine, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192)):
+    """The label of resample_scan(masks=...) alone: per-organ masks [(tensor, value), ...] as stored, all with this affine,
+    merged on the target grid in one gather (resample_totalseg_ras_mri.py:77-96).  Later entries win.  An empty list gives
+    zeros on the current device (no mask file was found)."""
+    what = "merge_masks_to_grid"
+    tensors, values, code = _check_masks(masks, what)
+    target = _target(target_shape, what)
+    if not tensors:
+        orientation.io_orientation(affine)
+        return torch.zeros(target, dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+    src = _Stored(tensors[0], affine, what)
+    for k, t in enumerate(tensors[1:], 1):
+        _check_same_layout(t, tensors[0], src, what, f"mask {k}")
+    _, shape1, _ = chain_shapes(src.shape, orientation.spacing_of(src.affine), target_spacing, target)
+    return _merge_stored(tensors, values, code, src, shape1, target)
+
+
+def resample_scan(image, affine, label=None, masks=None, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192),
+                  ct_window=None, stage1=None):
+    """The per-scan body of the resampling scripts for a decoded scan AS STORED and its 4x4 affine: orientation from the
+    affine, spacing from the reoriented affine (amos_ct_resample.py:51), the two-stage cubic chain with stage 1 reading the
+    stored tensor in place, and the label either from `label` (one composed order-0 gather) or from masks=[(tensor, value),
+    ...] (the TotalSegmentator merge, one gather for up to 8 masks).  Returns (float32 image, int64 label or None, output
+    affine): the reoriented affine with diag(target_spacing) as its 3x3 part (:77-78), host float64.
+    The bits are those of resample_to_grid on the host-reoriented float32 copy.  stage1 picks the form of stage 1
+    (STAGE1_FORMS; None = STAGE1_DEFAULT of the scan's memory-fastest axis)."""
+    what = "resample_scan"
+    src = _Stored(image, affine, what)
+    code = _check_dtype(image, _IMAGE_DTYPES, what, "image")
+    target = _target(target_shape, what)
+    if ct_window is not None and not float(ct_window[1]) > float(ct_window[0]):
+        raise Mi3dError(f"{what}: empty CT window {ct_window}")
+    if stage1 is not None and stage1 not in STAGE1_FORMS:
+        raise Mi3dError(f"{what}: stage1 is one of {STAGE1_FORMS} or None, got {stage1!r}")
+    if label is not None and masks is not None:
+        raise Mi3dError(f"{what}: pass label or masks, not both")
+    if label is not None:
+        _check_same_layout(label, image, src, what, "label")
+        label_code = _check_dtype(label, _LABEL_DTYPES, what, "label")
+    if masks is not None:
+        tensors, values, mask_code = _check_masks(masks, what)
+        for k, t in enumerate(tensors):
+            _check_same_layout(t, image, src, what, f"mask {k}")
+    _, shape1, _ = chain_shapes(src.shape, orientation.spacing_of(src.affine), target_spacing, target)
+    # everything is checked: launch
+    stage = _workspace(shape1, src.device)
+    if src.identity and image.dtype == torch.float32:
+        _cubic(src.ras_view(image), shape1, out=stage)                        # the contiguous float32 path, unchanged
+    elif (stage1 or STAGE1_DEFAULT[src.fastest]) == "fused":
+        _cubic_stored(image, src, code, shape1, stage)
+    else:
+        _cubic(_reorient(image, src, code, False), shape1, out=stage)
+    out = _cubic(stage, target, ct_window=ct_window)
+    out_label = None
+    if label is not None:
+        out_label = _nearest_stored(label, src, label_code, shape1, target)
+    elif masks is not None:
+        out_label = _merge_stored(tensors, values, mask_code, src, shape1, target)
+    return out, out_label, _out_affine(src, target_spacing)
