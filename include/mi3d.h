@@ -225,6 +225,26 @@ int mi3d_seg_metrics(const float* logits, const int64_t* labels, int N, int C, i
  * { n_inter[C] (pred==c && label==c), n_pred[C], n_label[C], n_correct };  same workspace as mi3d_seg_metrics. */
 int mi3d_seg_class_counts(const float* logits, const int64_t* labels, int N, int C, int64_t V, int64_t* counts,
                           void* workspace, void* stream);
+/* Segmenting with a trained model (test_model.py:242-285: model(x), torch.argmax(outputs, dim=1), the per-sample per-class
+ * counts, pred_classes.cpu()): the 1x1x1 head, the argmax and the counts in ONE pass over the decoder output, so the logits are
+ * never written.  z, zcs, Cin, w, bias: the operands of mi3d_conv1_forward (channels-last `dtype` [N][V] rows of stride zcs, any
+ * Cin; w (Cout,Cin), bias (Cout) float, bias may be NULL); Cout <= 8; any V >= 1, tails are handled in the kernel.
+ *   labels_out  uint8 (N,V): the first maximum, under a strict `>` scan from class 0, of the logits mi3d_conv1_forward gives for the
+ *               same dtype, bit for bit (both take them from one device function).  Finite logits are the contract; NaN behaves as
+ *               in mi3d_seg_class_counts: a NaN never wins a comparison, so a NaN logit is chosen only where it is logit 0.
+ *   target      int64 (N,V), or NULL.  With it, counts: device int64 (N, 3*Cout + 1), per SAMPLE { n_inter[Cout], n_pred[Cout],
+ *               n_label[Cout], n_correct } in the order of mi3d_seg_class_counts; exact integers, no atomics.  A target value
+ *               outside [0, Cout) counts nowhere; it is compared as int64, whereas mi3d_seg_class_counts narrows the label to
+ *               32 bits first (2^32 + 1 counts as class 1 there, nowhere here), so the sum over the samples equals
+ *               mi3d_seg_class_counts' row for targets inside the int32 range.  Both NULL or both given.
+ *   workspace   mi3d_head_labels_workspace_bytes(N, Cout) bytes, 8-byte aligned; read only with a target (else may be NULL).
+ * mi3d_unet_head_labels runs it on the decoder output that the last mi3d_unet_infer / mi3d_unet_forward called with logits = NULL
+ * left in `workspace` (the sibling of mi3d_unet_head_loss_forward); labels_out (N,D,H,W), head_workspace as above. */
+size_t mi3d_head_labels_workspace_bytes(int N, int Cout);
+int mi3d_head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int64_t V,
+                     uint8_t* labels_out, const int64_t* target, int64_t* counts, void* workspace, void* stream);
+int mi3d_unet_head_labels(const mi3d_unet_desc* d, const void* const* params, const int64_t* target, uint8_t* labels_out,
+                          int64_t* counts, void* head_workspace, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DANN head.  Replaces train_dann.py:34-49 (DomainDiscriminator MLP 256-256-128-64-2, ReLU, Dropout 0.2) and
@@ -334,6 +354,17 @@ typedef struct {
 int mi3d_merge_masks3(const mi3d_mask_list* masks, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, int64_t* out,
                       int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d, int rows_d, const int32_t* index_h,
                       int rows_h, const int32_t* index_w, int rows_w, void* stream);
+/* The way back: a uint8 label map on the training grid (Dg, Hg, Wg, contiguous) put onto the scan as stored.  The reference has no
+ * inverse, so it is defined here: RAS label = scipy.ndimage.zoom(grid, ras_shape / grid_shape, order=0, mode='nearest',
+ * prefilter=False), ONE zoom (the intermediate shape of the inbound chain carries no information for an order-0 gather), then the
+ * inverse of reorient_to_ras.  out is the stored uint8 tensor seen in RAS order: sides D, H, W and element strides as for
+ * mi3d_zoom3_nearest_src's source, here on the destination; index_* hold one grid index per RAS index of the axis (resample.py
+ * axis_table(n_grid, n, 0), D / H / W entries), built in RAS order and, for a flipped axis, read backwards: entry i is the table's
+ * entry n - 1 - i.  out[d*stride_d + h*stride_h + w*stride_w] = grid[index_d[d]][index_h[h]][index_w[w]].  The output is written
+ * in the stored tensor's memory order for every orientation, 16 bytes per store where the row is aligned.  grid != out. */
+int mi3d_restore_labels3(const uint8_t* grid, int Dg, int Hg, int Wg, uint8_t* out, int D, int H, int W, int64_t stride_d,
+                         int64_t stride_h, int64_t stride_w, const int32_t* index_d, const int32_t* index_h, const int32_t* index_w,
+                         void* stream);
 
 /* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
  * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)

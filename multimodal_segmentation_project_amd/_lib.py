@@ -92,6 +92,9 @@ _SIGS = {
     "mi3d_seg_metrics_workspace_bytes": (sz, [i32]),
     "mi3d_seg_metrics": (i32, [vp, vp, i32, i32, i32, i64, vp, vp, vp]),
     "mi3d_seg_class_counts": (i32, [vp, vp, i32, i32, i64, vp, vp, vp]),
+    "mi3d_head_labels_workspace_bytes": (sz, [i32, i32]),
+    "mi3d_head_labels": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
+    "mi3d_unet_head_labels": (i32, [_DP, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi3d_linear_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mi3d_linear_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp]),
     "mi3d_scale": (i32, [vp, vp, i64, f32, vp, vp]),
@@ -110,6 +113,7 @@ _SIGS = {
     "mi3d_zoom3_cubic_src": (i32, [vp, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, f32, f32, vp]),
     "mi3d_zoom3_nearest_src": (i32, [vp, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_merge_masks3": (i32, [_MP, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
+    "mi3d_restore_labels3": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp]),
     "mi3d_plane_affine": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp]),
     "mi3d_augment_workspace_bytes": (sz, []),
     "mi3d_augment": (i32, [vp, vp, vp, i32, i32, i32, i32, _AP, vp, sz, vp]),

@@ -83,6 +83,13 @@ int mi3d_seg_class_counts(const float* logits, const int64_t* labels, int N, int
     MI3D_CHECK_ARG(logits && labels && counts && workspace, "mi3d_seg_class_counts: null pointer");
     return seg_metrics(logits, labels, N, C, 0, V, nullptr, workspace, (hipStream_t)stream, counts);
 }
+size_t mi3d_head_labels_workspace_bytes(int N, int Cout) { return head_labels_ws_bytes(N, Cout); }
+int mi3d_head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int64_t V,
+                     uint8_t* labels_out, const int64_t* target, int64_t* counts, void* workspace, void* stream) {
+    MI3D_CHECK_ARG(z && w && labels_out, "mi3d_head_labels: null pointer");
+    MI3D_CHECK_ARG(dtype == MI3D_F32 || dtype == MI3D_BF16, "mi3d_head_labels: bad dtype %d", dtype);
+    return head_labels(dtype, z, zcs, Cin, w, bias, Cout, N, V, labels_out, target, counts, workspace, (hipStream_t)stream);
+}
 
 int mi3d_linear_forward(const float* x, const float* w, const float* b, float* y, int M, int K, int Nout, int relu,
                         const float* drop, void* stream) {

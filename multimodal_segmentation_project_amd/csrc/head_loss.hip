@@ -10,6 +10,8 @@
 //   L = w_ce*CE + w_reg*mean_{c>=1} R_c + w_kd*T^2*mean_{n,c,v} KL(p_t^T || p_s^T)
 //   dL/dz_k = w_ce/M (p_k - [t=k]) + p_k (g_k - sum_c g_c p_c) + w_kd*T/(M*C) (ps_k - pt_k),
 //   g_c = w_reg/(C-1) * (A_c [t=c] + B_c),  A_c, B_c = dR_c/dI_c-ish coefficients computed once from the sums.
+#include <type_traits>
+
 #include "mfma_tile.h"
 #include "ops.h"
 
@@ -37,6 +39,29 @@ __device__ __forceinline__ void load_cin_block(const T* zp, int nci, float (&zv)
     }
 }
 
+// The logits of ONE voxel, classes co0 .. co0 + nco - 1: acc[j] = bias[co0 + j], then fmaf(z[ci], w[co][ci], acc[j]) over ci in
+// ascending order.  The one place where the bits of a logit are decided: conv1_fwd_kernel stores what this returns and
+// head_labels_kernel takes its argmax, so a label is the first maximum of exactly the logits the head would have written.
+template <typename T, bool VEC, int NCO>
+__device__ __forceinline__ void conv1_voxel(const T* __restrict__ zrow, int Cin, const float* __restrict__ w,
+                                            const float* __restrict__ bias, int co0, int nco, float (&acc)[NCO]) {
+#pragma unroll
+    for (int j = 0; j < NCO; j++) acc[j] = (bias && j < nco) ? bias[co0 + j] : 0.f;
+    for (int c0 = 0; c0 < Cin; c0 += CINB) {
+        int nci = min(CINB, Cin - c0);
+        float zv[CINB];
+        load_cin_block<T, VEC>(zrow + c0, nci, zv);
+#pragma unroll
+        for (int j = 0; j < NCO; j++) {
+            if (j < nco) {
+#pragma unroll
+                for (int i = 0; i < CINB; i++)
+                    if (VEC || i < nci) acc[j] = fmaf(zv[i], w[(int64_t)(co0 + j) * Cin + c0 + i], acc[j]);
+            }
+        }
+    }
+}
+
 // logits[n][co][v] = bias[co] + sum_ci z[n,v,ci] * w[co][ci]       (Cout <= NCO per blockIdx.z group)
 // grid = (blocks over voxel groups, N, cout groups); a thread owns VV consecutive voxels of one sample so the fp32
 // class planes are written as 16-byte stores and no per-voxel 64-bit division is needed.
@@ -52,32 +77,14 @@ __global__ __launch_bounds__(BLK) void conv1_fwd_kernel(const T* __restrict__ z,
     int64_t ngrp = V / VV;
     for (int64_t grp = (int64_t)blockIdx.x * BLK + threadIdx.x; grp < ngrp; grp += (int64_t)gridDim.x * BLK) {
         int64_t v0 = grp * VV;
-        float acc[NCO][VV];
+        float acc[VV][NCO];
 #pragma unroll
-        for (int j = 0; j < NCO; j++)
-#pragma unroll
-            for (int k = 0; k < VV; k++) acc[j][k] = (bias && j < nco) ? bias[co0 + j] : 0.f;
-        for (int c0 = 0; c0 < Cin; c0 += CINB) {
-            int nci = min(CINB, Cin - c0);
-#pragma unroll
-            for (int k = 0; k < VV; k++) {
-                float zv[CINB];
-                load_cin_block<T, VEC>(zn + (v0 + k) * zcs + c0, nci, zv);
-#pragma unroll
-                for (int j = 0; j < NCO; j++) {
-                    if (j < nco) {
-#pragma unroll
-                        for (int i = 0; i < CINB; i++)
-                            if (VEC || i < nci) acc[j][k] = fmaf(zv[i], w[(int64_t)(co0 + j) * Cin + c0 + i], acc[j][k]);
-                    }
-                }
-            }
-        }
+        for (int k = 0; k < VV; k++) conv1_voxel<T, VEC, NCO>(zn + (v0 + k) * zcs, Cin, w, bias, co0, nco, acc[k]);
 #pragma unroll
         for (int j = 0; j < NCO; j++) {
             if (j < nco) {
-                if constexpr (VV == 4) *reinterpret_cast<float4*>(ln + (int64_t)j * V + v0) = float4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-                else ln[(int64_t)j * V + v0] = acc[j][0];
+                if constexpr (VV == 4) *reinterpret_cast<float4*>(ln + (int64_t)j * V + v0) = float4{acc[0][j], acc[1][j], acc[2][j], acc[3][j]};
+                else ln[(int64_t)j * V + v0] = acc[0][j];
             }
         }
     }
@@ -901,16 +908,69 @@ __global__ __launch_bounds__(C1W * 64) void head_loss_bwd_mfma_kernel(const bf16
 }
 
 // ------------------------------------------------------------------------------------------ metrics
+// The predicted class of one voxel: the first maximum under a strict `>` scan from class 0, which is torch.argmax for finite
+// logits.  A NaN never wins a comparison and, once it is the running maximum, never loses one: a NaN logit 0 gives class 0, a
+// NaN elsewhere is never chosen.
+template <int NC>
+__device__ __forceinline__ int first_argmax(const float (&z)[NC], int C) {
+    float bv = z[0];
+    int best = 0;
+#pragma unroll
+    for (int c = 1; c < NC; c++)
+        if (c < C && z[c] > bv) { bv = z[c]; best = c; }
+    return best;
+}
+
+// Exact argmax / label counts of the voxels one thread has seen, and their way into one partial row per block:
+// per-thread counts -> wave sums -> LDS -> 3C + 1 integers {n_inter[C], n_pred[C], n_label[C], n_correct} (no floating point,
+// no atomics).  A label outside [0, C) counts nowhere.  A thread sees < 2^32 voxels.
+template <int NC>
+struct VoxelCounts {
+    unsigned ni[NC], np[NC], nt[NC], nc;
+    __device__ __forceinline__ VoxelCounts() : nc(0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) ni[c] = np[c] = nt[c] = 0;
+    }
+    __device__ __forceinline__ void add(int best, int t) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            ni[c] += (best == c && t == c) ? 1u : 0u;
+            np[c] += (best == c) ? 1u : 0u;
+            nt[c] += (t == c) ? 1u : 0u;
+        }
+        nc += (best == t) ? 1u : 0u;
+    }
+    // every thread of the BLK-thread block calls this once; row: the block's 3C + 1 entries
+    __device__ __forceinline__ void store_block_row(int C, unsigned long long* __restrict__ row) const {
+        __shared__ unsigned red[BLK / 64][3 * NC + 1];
+        int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        auto wsum = [&](unsigned v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; };
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            unsigned a = wsum(ni[c]), b = wsum(np[c]), d = wsum(nt[c]);
+            if (lane == 0) { red[wave][c] = a; red[wave][NC + c] = b; red[wave][2 * NC + c] = d; }
+        }
+        unsigned e = wsum(nc);
+        if (lane == 0) red[wave][3 * NC] = e;
+        __syncthreads();
+        if ((int)threadIdx.x < 3 * C + 1) {                       // compact row: 3C + 1 counts
+            int i = threadIdx.x;
+            int src = i == 3 * C ? 3 * NC : (i / C) * NC + (i % C);
+            unsigned long long v = 0;
+#pragma unroll
+            for (int wv = 0; wv < BLK / 64; wv++) v += red[wv][src];
+            row[i] = v;
+        }
+    }
+};
+
 template <int NC, int VV>
 __global__ __launch_bounds__(BLK) void seg_metrics_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                           int C, int64_t V, unsigned long long* __restrict__ counts) {
-    // counts: [0..C) n_inter, [MAXC..) n_pred, [2*MAXC..) n_tgt, [3*MAXC] n_correct
     int n = blockIdx.y;
     const float* lg = logits + (int64_t)n * C * V;
     const int64_t* lb = labels + (int64_t)n * V;
-    unsigned ni[NC], np[NC], nt[NC], nc = 0;
-#pragma unroll
-    for (int c = 0; c < NC; c++) ni[c] = np[c] = nt[c] = 0;
+    VoxelCounts<NC> cnt;
     int64_t ngrp = V / VV;
     for (int64_t grp = (int64_t)blockIdx.x * BLK + threadIdx.x; grp < ngrp; grp += (int64_t)gridDim.x * BLK) {
         int64_t v0 = grp * VV;
@@ -919,39 +979,66 @@ __global__ __launch_bounds__(BLK) void seg_metrics_kernel(const float* __restric
         load_planes<NC, VV>(lg, C, V, v0, z);
         load_labels<VV>(lb + v0, t);
 #pragma unroll
-        for (int k = 0; k < VV; k++) {
-            float bv = z[k][0];
-            int best = 0;
+        for (int k = 0; k < VV; k++) cnt.add(first_argmax<NC>(z[k], C), t[k]);
+    }
+    cnt.store_block_row(C, counts + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (3 * C + 1));
+}
+
+// ---------------------------------------------------------------------------- head + argmax + per-sample counts in one pass
+// labels[n][v] = first_argmax(conv1_voxel(z[n][v])) as uint8, and with TARGET the exact counts of seg_metrics_kernel per
+// (sample, block).  HBM-bound: Cin * sizeof(T) bytes read and 1 byte written per voxel (+ 8 with a target).
+// A wave owns 64 * HLV consecutive voxels per iteration and takes them in HLV rounds of 64, lane l the voxel 64 k + l of round k:
+// consecutive lanes read consecutive channel rows, as conv1_fwd_kernel does (a thread that owns consecutive voxels
+// spreads every load instruction of the wave over 64 cache lines: the note at conv1_fwd's launch).  The 64 * HLV label bytes of the
+// wave go through its own LDS tile, written a byte per lane and round in voxel order and read back 16 bytes per lane, so a
+// thread still ends with its HLV = 16 labels in ONE 16-byte store and the wave writes 1 KiB contiguously.  A chunk that is
+// not whole (the tail of V) or whose first byte is not 16-byte aligned (n * V odd) stores its live bytes directly instead.
+// Out-of-range lanes of a tail chunk recompute the sample's last voxel and neither store nor count it.
+constexpr int HLV = 16;
+template <typename T, bool VEC, int NC, bool TARGET>
+__global__ __launch_bounds__(BLK) void head_labels_kernel(const T* __restrict__ z, int zcs, int Cin, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, int C, int64_t V,
+                                                          uint8_t* __restrict__ labels, const int64_t* __restrict__ target,
+                                                          unsigned long long* __restrict__ counts) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[BLK / 64][64 * HLV];
+    const int n = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const T* zn = z + (int64_t)n * V * zcs;
+    uint8_t* ln = labels + (int64_t)n * V;
+    const int64_t* tn = TARGET ? target + (int64_t)n * V : nullptr;
+    VoxelCounts<NC> cnt;
+    // ONE: the whole channel row is one block (the network's head: Cin = 16).  The channel loop of conv1_voxel then has a
+    // constant single trip and the loads of all rounds can be issued ahead of the arithmetic; same fmaf chain either way.
+    auto chunks = [&](auto ONE) {
+        const int cin = decltype(ONE)::value ? CINB : Cin;
+        for (int64_t base = ((int64_t)blockIdx.x * (BLK / 64) + wave) * (64 * HLV); base < V; base += (int64_t)gridDim.x * (BLK * HLV)) {
+            const bool wide = base + 64 * HLV <= V && (reinterpret_cast<uintptr_t>(ln + base) & 15) == 0;      // wave-uniform
 #pragma unroll
-            for (int c = 1; c < NC; c++)
-                if (c < C && z[k][c] > bv) { bv = z[k][c]; best = c; }       // first maximum wins, as torch.argmax
-#pragma unroll
-            for (int c = 0; c < NC; c++) {
-                ni[c] += (best == c && t[k] == c) ? 1u : 0u;
-                np[c] += (best == c) ? 1u : 0u;
-                nt[c] += (t[k] == c) ? 1u : 0u;
+            for (int k = 0; k < HLV; k++) {
+                const int64_t v = base + k * 64 + lane;
+                const bool live = v < V;
+                const int64_t vc = live ? v : V - 1;
+                float acc[NC];
+                conv1_voxel<T, VEC, NC>(zn + vc * zcs, cin, w, bias, 0, C, acc);
+                const int best = first_argmax<NC>(acc, C);
+                if constexpr (TARGET) {
+                    const int64_t tv = tn[vc];
+                    if (live) cnt.add(best, (tv >= 0 && tv < C) ? (int)tv : -1);
+                }
+                if (wide) tile[wave][k * 64 + lane] = (uint8_t)best;
+                else if (live) ln[v] = (uint8_t)best;
             }
-            nc += (best == t[k]) ? 1u : 0u;
+            if (wide) {
+                // the tile is private to this wave: its LDS writes are complete for the wave before the wide read
+                __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0)
+                __builtin_amdgcn_wave_barrier();
+                *reinterpret_cast<uint4*>(ln + base + lane * HLV) = *reinterpret_cast<const uint4*>(&tile[wave][lane * HLV]);
+                __builtin_amdgcn_wave_barrier();
+            }
         }
-    }
-    // per-thread counts -> wave sums -> LDS -> one partial row per block (exact integers, no atomics)
-    __shared__ unsigned red[4][3 * NC + 1];
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    auto wsum = [&](unsigned v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; };
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        unsigned a = wsum(ni[c]), b = wsum(np[c]), d = wsum(nt[c]);
-        if (lane == 0) { red[wave][c] = a; red[wave][NC + c] = b; red[wave][2 * NC + c] = d; }
-    }
-    unsigned e = wsum(nc);
-    if (lane == 0) red[wave][3 * NC] = e;
-    __syncthreads();
-    if ((int)threadIdx.x < 3 * C + 1) {                       // compact row: 3C + 1 counts
-        int i = threadIdx.x;
-        int src = i == 3 * C ? 3 * NC : (i / C) * NC + (i % C);
-        unsigned long long v = (unsigned long long)red[0][src] + red[1][src] + red[2][src] + red[3][src];
-        counts[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (3 * C + 1) + i] = v;
-    }
+    };
+    if (VEC && Cin == CINB) chunks(std::integral_constant<bool, VEC>{});
+    else chunks(std::false_type{});
+    if constexpr (TARGET) cnt.store_block_row(C, counts + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (3 * C + 1));
 }
 
 __device__ __forceinline__ void count_row_sum(const unsigned long long* part, int nblk, int C, int q, int lane, unsigned long long* counts);
@@ -1025,9 +1112,12 @@ __global__ __launch_bounds__(1024) void seg_loss_metrics_finalize_kernel(const d
 }
 
 // raw exact counts for the per-class evaluation metrics (test_model.py:242-285): out[0..C) n_inter, [C..2C) n_pred,
-// [2C..3C) n_tgt, [3C] n_correct  (int64)
+// [2C..3C) n_tgt, [3C] n_correct  (int64).  Block b sums rows [b * nblk, (b + 1) * nblk) into out[b]: one block for the sum over
+// the batch (seg_metrics), one block per sample for per-sample counts (head_labels)
 __global__ __launch_bounds__(1024) void seg_counts_finalize_kernel(const unsigned long long* part, int nblk, int C, long long* out) {
     int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    part += (int64_t)blockIdx.x * nblk * (3 * C + 1);
+    out += (int64_t)blockIdx.x * (3 * C + 1);
     for (int q = wave; q < 3 * C + 1; q += 16) {            // rows and output share the compact layout
         unsigned long long s = 0;
         for (int b = lane; b < nblk; b += 64) s += part[(int64_t)b * (3 * C + 1) + q];
@@ -1194,6 +1284,47 @@ int seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D,
     if (out) seg_metrics_finalize_kernel<<<1, 1024, 0, s>>>((const unsigned long long*)ws, bx * N, N, C, D, V, out);
     if (counts_out) seg_counts_finalize_kernel<<<1, 1024, 0, s>>>((const unsigned long long*)ws, bx * N, C, (long long*)counts_out);
     MI3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- head + argmax (+ per-sample counts)
+constexpr int HEAD_LABEL_BLOCKS = 2048;      // partial rows in all: a streaming grid of eight 256-thread blocks per CU
+static int head_labels_blocks(int N, int64_t V) {
+    int64_t want = (V + BLK * HLV - 1) / (BLK * HLV), cap = HEAD_LABEL_BLOCKS / N < 1 ? 1 : HEAD_LABEL_BLOCKS / N;
+    return (int)(want < cap ? want : cap);
+}
+size_t head_labels_ws_bytes(int N, int Cout) {
+    if (N < 1 || Cout < 1 || Cout > MAXC) return 0;
+    return (size_t)(N > HEAD_LABEL_BLOCKS ? N : HEAD_LABEL_BLOCKS) * (3 * Cout + 1) * sizeof(unsigned long long);
+}
+
+int head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int64_t V,
+                uint8_t* labels, const int64_t* target, int64_t* counts, void* ws, hipStream_t s) {
+    MI3D_CHECK_ARG(Cin >= 1 && zcs >= Cin, "head_labels: bad channels (Cin %d, stride %d)", Cin, zcs);
+    MI3D_CHECK_ARG(Cout >= 1 && Cout <= MAXC, "head_labels: %d classes unsupported (max %d)", Cout, MAXC);
+    MI3D_CHECK_ARG(N >= 1 && N <= 65535 && V >= 1, "head_labels: bad batch %d or volume %lld", N, (long long)V);
+    MI3D_CHECK_ARG(!target == !counts, "head_labels: target and counts come together");
+    MI3D_CHECK_ARG(!target || ws, "head_labels: counts need the workspace");
+    dim3 grid((unsigned)head_labels_blocks(N, V), (unsigned)N);
+    unsigned long long* rows = (unsigned long long*)ws;
+    const bool vec = Cin % CINB == 0 && zcs % 8 == 0 && al16(z);      // as conv1_fwd
+#define HLAB(VEC_, NC_)                                                                                                                          \
+    do {                                                                                                                                          \
+        if (target) head_labels_kernel<T, VEC_, NC_, true><<<grid, BLK, 0, s>>>((const T*)z, zcs, Cin, w, bias, Cout, V, labels, target, rows);   \
+        else head_labels_kernel<T, VEC_, NC_, false><<<grid, BLK, 0, s>>>((const T*)z, zcs, Cin, w, bias, Cout, V, labels, nullptr, nullptr);     \
+    } while (0)
+    DISPATCH_T(dtype, T, {
+        if (vec && Cout <= 4) HLAB(true, 4);
+        else if (vec) HLAB(true, MAXC);
+        else if (Cout <= 4) HLAB(false, 4);
+        else HLAB(false, MAXC);
+        MI3D_LAUNCH_CHECK();
+    });
+#undef HLAB
+    if (target) {
+        seg_counts_finalize_kernel<<<N, 1024, 0, s>>>(rows, (int)grid.x, Cout, (long long*)counts);
+        MI3D_LAUNCH_CHECK();
+    }
     return 0;
 }
 

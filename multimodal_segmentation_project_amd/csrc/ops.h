@@ -237,6 +237,12 @@ size_t seg_metrics_ws_bytes(int C);
 // out: device float[3] = {iou, dice, acc}; Q1 loop bound = first spatial dim D (utils/metrics.py:74,101)
 int seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out, void* ws,
                 hipStream_t s, int64_t* counts_out = nullptr);
+// head + argmax in one pass (inference: the logits are never written): labels[n][v] = first maximum of conv1_fwd's logits of that
+// voxel, uint8; with target (N,V) int64 also counts (N, 3*Cout + 1) int64 per sample, in seg_metrics' counts_out order.
+// ws: head_labels_ws_bytes(N, Cout), needed only with a target
+size_t head_labels_ws_bytes(int N, int Cout);
+int head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int64_t V,
+                uint8_t* labels, const int64_t* target, int64_t* counts, void* ws, hipStream_t s);
 
 // ---- spatial augmentation: flip + in-plane rotation of one (C, D, H, W) sample ------------- spatial.hip
 // Reference: random_flip / random_rotate, utils/dataloader.py:207-221.  Contract and arithmetic: include/mi3d.h mi3d_plane_affine.

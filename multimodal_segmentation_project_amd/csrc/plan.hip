@@ -728,6 +728,16 @@ int mi3d_unet_head_loss_forward(const mi3d_unet_desc* d, const void* const* para
                          logits_opt);
 }
 
+// head + argmax (+ per-sample counts) on that same decoder output: the sibling of mi3d_unet_head_loss_forward for inference
+int mi3d_unet_head_labels(const mi3d_unet_desc* d, const void* const* params, const int64_t* target, uint8_t* labels_out,
+                          int64_t* counts, void* head_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    Plan p;
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_head_labels", labels_out != nullptr, params, workspace, workspace_bytes, stream));
+    return head_labels(p.dt, c.at(p.zd[p.L - 1]), p.C[0], p.C[0], c.P(p.final_pidx()), c.P(p.final_pidx() + 1), d->out_channels, d->N,
+                       p.geo[0].V(), labels_out, target, counts, head_workspace, c.s);
+}
+
 int mi3d_unet_forward(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
                       const float* drop_scales, int training, float* logits, float* gap_out, void* workspace,
                       size_t workspace_bytes, void* stream) {

@@ -6,6 +6,8 @@
 // Every per-axis quantity (tap indices, already clamped; the four float64 weights; the nearest index) comes from tables the
 // host builds in float64 (resample.py axis_table), so the tap choice is scipy's bit for bit; the kernels do no floor, no
 // division on coordinates and no polynomial.  Direct form: each thread gathers its taps through L1/L2, no LDS, no atomics.
+#include <utility>
+
 #include "ops.h"
 #include "../../include/mi3d.h"
 
@@ -196,6 +198,44 @@ __global__ __launch_bounds__(BLK) void merge_masks3_kernel(MaskArgs m, int64_t* 
 #pragma unroll
         for (int j = 0; j < NWV; j++)
             if (ow0 + j < Wo) o[j] = v[j];
+    }
+}
+
+// Labels from the training grid back onto a scan as stored: the order-0 gather out[s][m][f] = grid[tS[s]][tM[m]][tF[f]] with the
+// DESTINATION strided.  The launcher sorts the stored tensor's three axes by stride: F is fastest in memory, then M, then S, so
+// the kernel walks the output in memory order whatever the orientation; each axis brings its table (one grid index per
+// destination index, already reversed for a flipped axis) and the grid's stride along it (gS, gM, gF: a permutation of
+// Hg * Wg, Wg, 1).  grid: x over (m, piece of the row along F), y = s.  The two slow-axis indices are read once per thread, the
+// fastest-axis index per element.  Pieces are cut where the row's bytes are 16-byte aligned: piece 0 is the (possibly empty)
+// head up to the first aligned byte, every later piece 16 bytes in one store, the last one the scalar tail; a fastest axis
+// that is not dense (oF != 1: no side > 1 has stride 1) is stored a byte at a time.
+// For F = the grid's W the 16 reads of a thread are neighbouring bytes; for F = D or H they are 16 different lines, shared with
+// the neighbouring rows.
+constexpr int RW = 16;
+__global__ __launch_bounds__(BLK) void restore_labels3_kernel(const uint8_t* __restrict__ grid, uint8_t* __restrict__ out, int nM,
+                                                              int nF, int FQ, const int32_t* __restrict__ tS,
+                                                              const int32_t* __restrict__ tM, const int32_t* __restrict__ tF,
+                                                              int64_t gS, int64_t gM, int64_t gF, int64_t oS, int64_t oM, int64_t oF) {
+    const int q = blockIdx.x * BLK + threadIdx.x;
+    if (q >= nM * FQ) return;
+    const int m = q / FQ, piece = q - m * FQ, s = blockIdx.y;
+    uint8_t* o = out + (s * oS + m * oM);
+    const int head = oF == 1 ? (int)((RW - (reinterpret_cast<uintptr_t>(o) & (RW - 1))) & (RW - 1)) : 0;
+    const int f0 = piece == 0 ? 0 : head + (piece - 1) * RW;
+    const int f1 = min(piece == 0 ? head : f0 + RW, nF);
+    if (f0 >= f1) return;
+    const uint8_t* row = grid + (tS[s] * gS + tM[m] * gM);
+    if (f1 - f0 == RW && oF == 1) {
+        uint32_t a[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            a[j] = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) a[j] |= (uint32_t)row[tF[f0 + 4 * j + b] * gF] << (8 * b);
+        }
+        *reinterpret_cast<uint4*>(o + f0) = uint4{a[0], a[1], a[2], a[3]};
+    } else {
+        for (int f = f0; f < f1; f++) o[f * oF] = row[tF[f] * gF];
     }
 }
 
@@ -411,6 +451,29 @@ int mi3d_merge_masks3(const mi3d_mask_list* masks, int src_dtype, int64_t stride
         if (vec) merge_masks3_kernel<float, true><<<grid, BLK, 0, s>>>(m, out, Ho, Wo, WQ, index_d, index_h, index_w, st);
         else merge_masks3_kernel<float, false><<<grid, BLK, 0, s>>>(m, out, Ho, Wo, WQ, index_d, index_h, index_w, st);
     }
+    MI3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int mi3d_restore_labels3(const uint8_t* grid, int Dg, int Hg, int Wg, uint8_t* out, int D, int H, int W, int64_t stride_d,
+                         int64_t stride_h, int64_t stride_w, const int32_t* index_d, const int32_t* index_h, const int32_t* index_w,
+                         void* stream) {
+    MI3D_CHECK_ARG(grid && out && grid != out && index_d && index_h && index_w, "mi3d_restore_labels3: null or aliased pointers");
+    MI3D_CHECK_ARG(dims_ok(Dg, Hg, Wg) && dims_ok(D, H, W), "mi3d_restore_labels3: sides must be in [1, %d]", MAX_SIDE);
+    MI3D_CHECK_ARG(strides_ok(stride_d, stride_h, stride_w), "mi3d_restore_labels3: strides must be positive element counts");
+    // the destination's axes by increasing stride, an axis of one element last among equals: a[0] = F, a[1] = M, a[2] = S
+    struct Axis { int n; int64_t os, gs; const int32_t* t; };
+    Axis a[3] = {{D, stride_d, (int64_t)Hg * Wg, index_d}, {H, stride_h, (int64_t)Wg, index_h}, {W, stride_w, 1, index_w}};
+    auto before = [](const Axis& x, const Axis& y) { return (x.n > 1) != (y.n > 1) ? x.n > 1 : x.os < y.os; };
+    if (before(a[1], a[0])) std::swap(a[0], a[1]);
+    if (before(a[2], a[1])) std::swap(a[1], a[2]);
+    if (before(a[1], a[0])) std::swap(a[0], a[1]);
+    const Axis &F = a[0], &M = a[1], &S = a[2];
+    const int FQ = 1 + (F.n + RW - 1) / RW;
+    MI3D_CHECK_ARG((int64_t)M.n * FQ < (int64_t)1 << 31, "mi3d_restore_labels3: output plane too large");
+    dim3 grd((unsigned)(((int64_t)M.n * FQ + BLK - 1) / BLK), (unsigned)S.n);
+    restore_labels3_kernel<<<grd, BLK, 0, (hipStream_t)stream>>>(grid, out, M.n, F.n, FQ, S.t, M.t, F.t, S.gs, M.gs, F.gs, S.os, M.os,
+                                                                 F.n > 1 ? F.os : 1);
     MI3D_LAUNCH_CHECK();
     return 0;
 }

@@ -161,28 +161,36 @@ def _infer(model, x, desc, hold, params, want_gap):
     return logits, gap
 
 
-def unet_forward(model, x, want_gap=False):
-    """Shared body of unet.UNet3D.forward and unet_dann.UNet3D.forward."""
-    _lib.require_cuda(x, "UNet3D.forward")
+def plan_call(model, x):
+    """What every whole-network call needs besides its outputs, checked: (descriptor, parameters, buffers, workspace bytes) for the
+    float32 (N,C,D,H,W) device input x.  Shared by unet_forward and segment.predict_labels."""
     params = list(model.parameters())
     for p in params:
         _lib.require_cuda(p, "UNet3D parameter")
+    desc = build_desc(model, x, resolve_compute_dtype(model))
+    buffers = list(model.buffers())
+    ws_bytes = _lib.lib().mi3d_unet_workspace_bytes(C.byref(desc))
+    if ws_bytes == 0:
+        _lib.check(-1, "mi3d_unet_workspace_bytes")
+    expect = _lib.lib().mi3d_unet_num_params(C.byref(desc))
+    if len(params) != expect or len(buffers) != _lib.lib().mi3d_unet_num_buffers(C.byref(desc)):
+        raise _lib.Mi3dError(f"module has {len(params)} parameters / {len(buffers)} buffers, plan expects {expect}")
+    return desc, params, buffers, ws_bytes
+
+
+def unet_forward(model, x, want_gap=False):
+    """Shared body of unet.UNet3D.forward and unet_dann.UNet3D.forward."""
+    _lib.require_cuda(x, "UNet3D.forward")
     x = x.detach().contiguous().float() if not x.requires_grad else x.contiguous().float()
-    dtype = resolve_compute_dtype(model)
-    desc = build_desc(model, x, dtype)
+    desc, params, buffers, ws_bytes = plan_call(model, x)
     hold = _Hold()
     hold.desc = desc
     hold.training = bool(model.training)
-    hold.buffers = list(model.buffers())
+    hold.buffers = buffers
     hold.want_gap = bool(want_gap)
-    hold.ws_bytes = _lib.lib().mi3d_unet_workspace_bytes(C.byref(desc))
-    if hold.ws_bytes == 0:
-        _lib.check(-1, "mi3d_unet_workspace_bytes")
+    hold.ws_bytes = ws_bytes
     hold.n_enc_params = 8 * (desc.n_levels + 1)
     hold.segment_hook = getattr(model, "_mi3d_segment_hook", None)
-    expect = _lib.lib().mi3d_unet_num_params(C.byref(desc))
-    if len(params) != expect or len(hold.buffers) != _lib.lib().mi3d_unet_num_buffers(C.byref(desc)):
-        raise _lib.Mi3dError(f"module has {len(params)} parameters / {len(hold.buffers)} buffers, plan expects {expect}")
     if not model.training and not (torch.is_grad_enabled() and any(q.requires_grad for q in params)):
         # inference (train_unet.py:259-305 evaluate, test_model.py:242-251, the distillation teacher): BatchNorm folded
         # into the convs, no saved activations, no autograd node

@@ -192,17 +192,24 @@ def class_counts(pred, target):
     return out
 
 
+def dice_iou_from_counts(counts, n_classes, classes=(1, 2, 3)):
+    """{class: (dice, iou)} from one row of exact counts {n_inter[C], n_pred[C], n_label[C], n_correct} (a list of Python
+    ints) by the formula of the reference's test script [test_model.py:269-276]: a class absent from the label, or one the
+    model does not have, scores 0.0 for both.  Shared by per_class_dice_iou (counts summed over the batch) and
+    segment.per_sample_dice_iou (one row per sample)."""
+    c = n_classes
+    res = {}
+    for k in classes:
+        if k >= c or counts[2 * c + k] == 0:
+            res[k] = (0.0, 0.0)
+            continue
+        inter, npred, nlab = float(counts[k]), float(counts[c + k]), float(counts[2 * c + k])
+        res[k] = ((2.0 * inter + 1e-5) / (npred + nlab + 1e-5), (inter + 1e-5) / (npred + nlab - inter + 1e-5))
+    return res
+
+
 def per_class_dice_iou(pred, target, classes=(1, 2, 3)):
     """Per-class Dice / IoU of the reference's test script [test_model.py:255-276]: a class absent from the label
     scores 0.0 for both (unlike calculate_dice/iou, which skip it).  Returns {class: (dice, iou)} of Python floats
     (one host sync, like the reference's .item() calls)."""
-    c = pred.shape[1]
-    cnt = class_counts(pred, target).cpu().tolist()
-    res = {}
-    for k in classes:
-        if k >= c or cnt[2 * c + k] == 0:
-            res[k] = (0.0, 0.0)
-            continue
-        inter, npred, nlab = float(cnt[k]), float(cnt[c + k]), float(cnt[2 * c + k])
-        res[k] = ((2.0 * inter + 1e-5) / (npred + nlab + 1e-5), (inter + 1e-5) / (npred + nlab - inter + 1e-5))
-    return res
+    return dice_iou_from_counts(class_counts(pred, target).cpu().tolist(), pred.shape[1], classes)

@@ -13,6 +13,7 @@ scaling) stays outside: callers pass the decoded array as it is stored, and its 
   reorient_to_ras(volume, affine)          the scripts' reorient_to_ras of a stored device tensor: (RAS volume, new affine)
   resample_scan(image, affine, ...)        the whole per-scan body: (image on the grid, label or None, output affine)
   merge_masks_to_grid(masks, affine, ...)  the label of resample_scan(masks=...) alone
+  restore_labels(labels, affine, stored)   the way back: uint8 labels on the grid put onto the scan as stored (one order-0 gather)
 
 A stored scan is any dense 3-D device tensor: a permutation of a contiguous array, such as the tensor made from nibabel's
 Fortran-ordered array without a host copy; int16 / uint8 / float32 images, uint8 / int16 / int64 labels, uint8 / float32 masks.
@@ -277,14 +278,27 @@ class _Stored:
 
     def __init__(self, volume, affine, what):
         _check_volume(volume, what)
-        orientation.check_dense(volume.shape, volume.stride(), what)
-        amap = orientation.axis_map(affine, tuple(volume.shape), volume.stride())
+        self._set_layout(tuple(volume.shape), tuple(volume.stride()), affine, what)
+        self.device = volume.device
+
+    @classmethod
+    def of_layout(cls, shape, strides, affine, what):
+        """The same view of a dense (shape, strides) layout that need not exist yet (restore_labels' destination)."""
+        self = cls.__new__(cls)
+        self._set_layout(tuple(int(n) for n in shape), tuple(int(s) for s in strides), affine, what)
+        self.device = None
+        return self
+
+    def _set_layout(self, shape, strides, affine, what):
+        if len(shape) != 3 or len(strides) != 3 or min(shape) < 1:
+            raise Mi3dError(f"{what}: a 3-D layout without an empty axis is expected, got shape {shape} strides {strides}")
+        orientation.check_dense(shape, strides, what)
+        amap = orientation.axis_map(affine, shape, strides)
         self.shape = tuple(n for n, _, _ in amap)
         self.strides = tuple(max(int(s), 1) if n > 1 else 1 for n, s, _ in amap)
         self.flips = tuple(f and n > 1 for n, _, f in amap)
-        self.affine = orientation.reoriented_affine(affine, tuple(volume.shape))
-        self.device = volume.device
-        self.layout = (tuple(volume.shape), tuple(s for n, s in zip(volume.shape, volume.stride()) if n > 1))
+        self.affine = orientation.reoriented_affine(affine, shape)
+        self.layout = (shape, tuple(s for n, s in zip(shape, strides) if n > 1))
         # which RAS axis is fastest in memory (the one with stride 1 and more than one element; W where there is none)
         self.fastest = next((a for a in (2, 1, 0) if self.shape[a] > 1 and self.strides[a] == 1), 2)
 
@@ -468,3 +482,54 @@ def resample_scan(image, affine, label=None, masks=None, target_spacing=(1.0, 1.
     elif masks is not None:
         out_label = _merge_stored(tensors, values, mask_code, src, shape1, target)
     return out, out_label, _out_affine(src, target_spacing)
+
+
+# ---- labels from the grid back onto the scan as stored -------------------------------------------------------------------------
+def _restore_table(n_grid, n_ras, flip):
+    t = axis_table(n_grid, n_ras, 0)
+    return np.ascontiguousarray(t[::-1]) if flip else t
+
+
+def restore_tables(grid_shape, affine, shape, strides, what="restore_labels"):
+    """Host side of restore_labels for a dense destination layout (shape, strides) with this affine: (RAS sides, element strides
+    of the RAS axes in the destination, three int32 tables).  Table a holds, per destination index along RAS axis a, the grid
+    index it takes: axis_table(n_grid, n_ras, 0), built in RAS order and read backwards where the axis is stored flipped
+    (stored index i is RAS index n - 1 - i).  out[sum_a i_a * stride_a] = grid[t_d[i_d], t_h[i_h], t_w[i_w]]."""
+    if len(grid_shape) != 3 or min(grid_shape) < 1:
+        raise Mi3dError(f"{what}: a 3-D grid without an empty axis is expected, got {tuple(grid_shape)}")
+    dst = _Stored.of_layout(shape, strides, affine, what)
+    return dst.shape, dst.strides, [_restore_table(g, n, f) for g, n, f in zip(grid_shape, dst.shape, dst.flips)]
+
+
+def restore_labels(labels, affine, stored):
+    """A uint8 (Dg, Hg, Wg) label map on the training grid put back onto the scan as stored: scipy.ndimage.zoom(labels,
+    ras_shape / grid_shape, order=0, mode='nearest', prefilter=False) (one zoom: the intermediate shape of the inbound chain
+    carries no information for an order-0 gather), then the inverse of reorient_to_ras, as ONE gather that writes the stored
+    layout in memory order.  `stored` is the stored scan tensor (only its shape, strides and device are read) or a (shape,
+    strides) pair of a dense layout; `affine` is the stored scan's.  Returns a uint8 tensor with that shape and those strides,
+    ready for a NIfTI writer next to the scan's own affine."""
+    what = "restore_labels"
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or min(labels.shape) < 1:
+        raise Mi3dError(f"{what}: one 3-D label map (Dg, Hg, Wg) expected, got {tuple(getattr(labels, 'shape', ()))}")
+    if labels.dtype != torch.uint8:
+        raise Mi3dError(f"{what}: the label map is uint8 (segment.predict_labels' output), got {labels.dtype}")
+    if isinstance(stored, torch.Tensor):
+        shape, strides = tuple(stored.shape), tuple(stored.stride())
+        if stored.device != labels.device:
+            raise Mi3dError(f"{what}: the stored scan is on {stored.device}, the labels on {labels.device}")
+    else:
+        try:
+            shape, strides = (tuple(int(v) for v in part) for part in stored)
+        except (TypeError, ValueError):
+            raise Mi3dError(f"{what}: `stored` is the stored tensor or a (shape, strides) pair, got {stored!r}") from None
+    dst = _Stored.of_layout(shape, strides, affine, what)
+    _lib.require_cuda(labels, what)
+    # everything is checked: launch
+    grid = labels.contiguous()
+    dev = grid.device
+    tabs = [_cached((int(g), int(n), "restore", str(dev), bool(f)), lambda g=g, n=n, f=f: _restore_table(g, n, f), dev)
+            for g, n, f in zip(grid.shape, dst.shape, dst.flips)]
+    out = torch.empty_strided(shape, strides, dtype=torch.uint8, device=dev)
+    call("mi3d_restore_labels3", ptr(grid), *grid.shape, ptr(out), *dst.shape, *dst.strides, ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]),
+         stream_ptr())
+    return out

@@ -1,0 +1,83 @@
+"""Segmenting with a trained model: the outbound half of the pipeline, the mirror of the loop body of the reference's
+test_model.py:242-309 (model(image), torch.argmax(outputs, dim=1), the per-sample per-class Dice / IoU, pred_classes.cpu()).
+
+  predict_labels(model, x, target=None)         uint8 (N, D, H, W) label map, and with a target the exact per-sample counts
+  per_sample_dice_iou(counts, classes)          [{class: (dice, iou)}] per sample from those counts (test_model.py:265-276)
+  segment_scan(model, image, affine, dataset)   a scan as stored -> its label map as stored: resample, predict, restore
+
+The logits never reach memory: the network runs with logits = NULL (mi3d_unet_infer) and the 1x1x1 head, the argmax and the counts
+are one pass over the decoder output (mi3d_unet_head_labels), which writes 1 byte per voxel where the logits route writes 16 and
+re-reads them twice.  Every label is the first maximum of exactly the logits model(x) would return.  File reading / writing,
+plots and sliding windows stay outside.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib, engine, metrics, preprocess, resample
+from ._lib import Mi3dError, call, ptr, ptr_table, stream_ptr
+
+CT_WINDOW = (-160.0, 240.0)      # preprocess.preprocess_ct's defaults (utils/dataloader.py:111-117)
+
+
+def predict_labels(model, x, target=None):
+    """torch.argmax(model(x), dim=1) as uint8 (N, D, H, W) for a model in eval(); with target (N, 1, D, H, W) also the exact
+    int64 (N, 3C + 1) counts {n_inter[C], n_pred[C], n_label[C], n_correct} of every sample (metrics.class_counts sums them
+    over the batch).  Same checks, compute dtype and descriptor as model(x) (engine.plan_call), and the bits of the logits that
+    model(x) returns under torch.no_grad() (the inference route, test_model.py:242).  Nothing synchronises."""
+    what = "predict_labels"
+    _lib.require_cuda(x, what)
+    if model.training:
+        raise Mi3dError(f"{what}: the model is in train() mode; call model.eval() (test_model.py:226)")
+    if model.output_activation is not None:
+        raise Mi3dError(f"{what}: the model has an output_activation; the argmax of activated logits is not this path "
+                        "(take torch.argmax of model(x))")
+    x = x.detach().contiguous().float()
+    desc, params, buffers, ws_bytes = engine.plan_call(model, x)
+    lib = _lib.lib()
+    n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
+    labels = counts = head_ws = None
+    if target is not None:
+        _lib.require_cuda(target, what)
+        if target.numel() != n * v:
+            raise Mi3dError(f"{what}: target shape {tuple(target.shape)} does not match the input {tuple(x.shape)}")
+        labels = target.reshape(n, v)
+        labels = (labels if labels.dtype == torch.int64 else labels.long()).contiguous()
+        head_bytes = lib.mi3d_head_labels_workspace_bytes(n, c)
+        if head_bytes == 0:
+            raise Mi3dError(f"{what}: {c} classes unsupported")
+        head_ws = torch.empty(head_bytes, dtype=torch.uint8, device=x.device)
+        counts = torch.empty((n, 3 * c + 1), dtype=torch.int64, device=x.device)
+    # everything is checked: launch
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty((n, desc.D, desc.H, desc.W), dtype=torch.uint8, device=x.device)
+    ptab = ptr_table([p.data_ptr() for p in params])
+    btab = ptr_table([b.data_ptr() for b in buffers])
+    call("mi3d_unet_infer", C.byref(desc), ptr(x), ptab, btab, None, None, ptr(ws), ws_bytes, stream_ptr())
+    call("mi3d_unet_head_labels", C.byref(desc), ptab, ptr(labels), ptr(out), ptr(counts), ptr(head_ws), ptr(ws), ws_bytes,
+         stream_ptr())
+    return out if target is None else (out, counts)
+
+
+def per_sample_dice_iou(counts, classes=(1, 2, 3)):
+    """One {class: (dice, iou)} of Python floats per sample from predict_labels' (N, 3C + 1) counts, by the formula of
+    test_model.py:269-276 (a class absent from the sample's label, or one the model does not have, scores 0.0 for both).
+    One host copy of the counts, like the reference's .item() calls."""
+    rows = counts.cpu().tolist() if isinstance(counts, torch.Tensor) else [list(r) for r in counts]
+    if not rows or any(len(r) != len(rows[0]) or len(r) % 3 != 1 for r in rows):
+        raise Mi3dError(f"per_sample_dice_iou: (N, 3C + 1) counts expected, got rows of {[len(r) for r in rows]}")
+    return [metrics.dice_iou_from_counts(r, len(r) // 3, classes) for r in rows]
+
+
+def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192)):
+    """A decoded scan AS STORED and its 4x4 affine -> (uint8 labels with the scan's shape and strides, uint8 labels on the
+    training grid, affine of the grid).  A composition only: resample.resample_scan (CT window fused into the last store for
+    '_ct' names, preprocess.preprocess_mri afterwards otherwise: the dispatch of preprocess.preprocess), predict_labels,
+    resample.restore_labels."""
+    ct = dataset_name.lower().endswith("_ct")
+    grid, _, grid_affine = resample.resample_scan(image, affine, target_spacing=target_spacing, target_shape=target_shape,
+                                                  ct_window=CT_WINDOW if ct else None)
+    if not ct:
+        grid = preprocess.preprocess_mri(grid)
+    on_grid = predict_labels(model, grid[None, None])[0]
+    return resample.restore_labels(on_grid, affine, image), on_grid, grid_affine

@@ -1064,6 +1064,28 @@ def gen_dp2(out):
     np.savez_compressed(os.path.join(out, "dp2.npz"), **d)
 
 
+def gen_segment(out):
+    """restore_labels.npz: the definition of resample.restore_labels' zoom, made by scipy itself.  Per case k a seeded uint8 label
+    map grid_k on a small training grid and ras_k = scipy.ndimage.zoom(grid_k, ras_shape / grid_shape, order=0, mode='nearest',
+    prefilter=False): down- and up-sampling, sides of 1, 5, 37 and 70 against grids of 8 and 12.  A few KB in all."""
+    from scipy.ndimage import zoom
+    import scipy
+    cases = (((12, 12, 12), (7, 10, 13)), ((12, 12, 12), (5, 37, 70)), ((8, 8, 8), (1, 9, 3)), ((12, 12, 12), (5, 9, 14)))
+    rng = np.random.default_rng(20260)
+    d = {"n_cases": np.int64(len(cases))}
+    for k, (gs, rs) in enumerate(cases):
+        g = rng.integers(0, 16, gs, dtype=np.uint8)
+        r = zoom(g, [n / m for n, m in zip(rs, gs)], order=0, mode="nearest", prefilter=False)
+        assert r.shape == rs and r.dtype == np.uint8, (r.shape, r.dtype)
+        d[f"grid_{k}"], d[f"ras_{k}"] = g, r
+    np.savez_compressed(os.path.join(out, "restore_labels.npz"), **d)
+    with open(os.path.join(out, "PROVENANCE_segment.txt"), "w") as f:
+        f.write("restore_labels.npz: generated by\ntools/gen_golden.py --only segment\n")
+        f.write("ras_k = scipy.ndimage.zoom(grid_k, ras_shape / grid_shape, order=0, mode='nearest', prefilter=False) of seeded uint8\n")
+        f.write("arrays; nothing of the reference is read or copied.\n")
+        f.write(f"scipy {scipy.__version__}, numpy {np.__version__}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1080,7 +1102,8 @@ def main():
     torch.use_deterministic_algorithms(False)
     if want("resample"): gen_resample(a.out)              # needs scipy only, not the reference tree
     if want("spatial"): gen_spatial(a.out)                # scipy + the reference's utils/dataloader.py
-    if only <= {"resample", "spatial"} and only:
+    if want("segment"): gen_segment(a.out)                # scipy only
+    if only <= {"resample", "spatial", "segment"} and only:
         return
     ref_unet, ref_unet_dann, ref_metrics, ref_train_unet, ref_train_dann = _import_reference()
     if want("small_unet"): gen_small_unet(ref_unet, ref_metrics, a.out)
