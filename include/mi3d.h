@@ -435,6 +435,26 @@ int mi3d_conv3_forward(int in_dtype, int out_dtype, const void* x, int xcs, int 
 int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int Cin, const float* w, const void* dy,
                         int dycs, int Cout, void* dx, int dxcs, float* dW, float* db, int accumulate, int N, int D,
                         int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+/* One half of a DoubleConv block as the training forward of the whole-network plan runs it: Conv3d(k=3,p=1) -> train-mode
+ * BatchNorm3d statistics -> ReLU + Dropout3d apply (-> MaxPool3d(2,2)), with the plan's own route decisions (the plan and this
+ * entry call ONE function).  in_dtype = dtype, or MI3D_F32 for the one-channel image of the first layer; y [M][Cout] is the conv
+ * output BatchNorm reads, z the activated tensor, pooled NULL or MaxPool3d(2,2)(z) on even volumes.  route_out (may be NULL)
+ * reports what was launched:
+ *   conv    0 direct fp32-FMA, 1 first-layer MFMA, 2 persistent MFMA, 3 MFMA with the 16-wide tile, 4 MFMA with the 8-wide tile
+ *   ksplit  split-K factor of the conv launch (1 = none);  ticket  1 = the split-K launch finished itself
+ *   stats   0 a statistics pass over y, 1 partial rows finished by the apply pass, 2 partial rows + a finalize launch,
+ *           3 split-K partials finished by the statistics pass
+ *   rows    partial rows handed on (0 = none);  rows_offset  byte offset in the workspace of those rows ([rows][2][Cout] float)
+ * The entry clears the split-K ticket counters in its weight-pack launch as the plan does; MI3D_CONV3_BN_KEEP_TICKETS in flags
+ * skips that (the previous call on this workspace left them at zero). */
+typedef struct mi3d_conv3_bn_route { int32_t conv, ksplit, ticket, stats, rows, rows_offset; } mi3d_conv3_bn_route;
+enum { MI3D_CONV3_BN_KEEP_TICKETS = 1 };
+size_t mi3d_conv3_bn_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W);
+int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias,
+                          const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          int64_t* num_batches_tracked, float momentum, float eps, const float* drop, void* y, void* z, int zcs,
+                          void* pooled, int pcs, float* stat, int flags, mi3d_conv3_bn_route* route_out, int Cout, int N, int D,
+                          int H, int W, void* workspace, size_t workspace_bytes, void* stream);
 /* BatchNorm3d(train) + ReLU + Dropout3d fused; stat: device float[4*C] saved for backward */
 size_t mi3d_bn_workspace_bytes(int C);
 int mi3d_bn_relu_drop_forward(int dtype, const void* y, int ycs, int C, int64_t M, int64_t V, const float* gamma,

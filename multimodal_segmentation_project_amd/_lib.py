@@ -47,6 +47,12 @@ class MaskList(C.Structure):                       # mi3d_mask_list
     _fields_ = [("mask", C.c_void_p * MAX_MASKS), ("value", C.c_int64 * MAX_MASKS), ("n", C.c_int32)]
 
 
+class Conv3BnRoute(C.Structure):                   # mi3d_conv3_bn_route
+    _fields_ = [(k, C.c_int32) for k in ("conv", "ksplit", "ticket", "stats", "rows", "rows_offset")]
+
+
+CONV3_BN_KEEP_TICKETS = 1
+
 _DP, _LP, _AP, _MP = C.POINTER(UNetDesc), C.POINTER(LossCfg), C.POINTER(AugParams), C.POINTER(MaskList)
 
 # name -> (restype, argtypes); one line per symbol declared in include/mi3d.h
@@ -122,6 +128,9 @@ _SIGS = {
     "mi3d_conv3_forward": (i32, [i32, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "mi3d_conv3_backward": (i32, [i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32,
                                   vp, sz, vp]),
+    "mi3d_conv3_bn_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "mi3d_conv3_bn_forward": (i32, [i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, i32, vp, i32,
+                                    C.POINTER(Conv3BnRoute), i32, i32, i32, i32, i32, vp, sz, vp]),
     "mi3d_bn_workspace_bytes": (sz, [i32]),
     "mi3d_bn_relu_drop_forward": (i32, [i32, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, i32,
                                         vp, vp, vp]),

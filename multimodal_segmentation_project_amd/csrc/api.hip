@@ -205,6 +205,75 @@ int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int C
     return 0;
 }
 
+}  // extern "C"
+
+// mi3d_conv3_bn_forward: the layer's route class as build_plan assigns it, and the plan's scratch areas in a workspace of its own
+namespace {
+struct ConvBnWs {
+    bool mfma, c1;
+    size_t statpart, tkcount, bnws, wpf, wpd, skws, total;
+};
+ConvBnWs conv_bn_ws(int dtype, int Cin, int Cout, Geo g) {
+    ConvBnWs L;
+    conv3_layer_class(dtype, Cin, Cout, L.mfma, L.c1);      // in_dtype is checked against the class by the entry
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    int rows = L.mfma ? conv3_mfma_stat_blocks(Cin, Cout, g) : L.c1 ? conv3_c1_fwd_stat_blocks(g) : 1;
+    L.statpart = take((size_t)rows * 2 * Cout * sizeof(float));
+    L.tkcount = take((size_t)CONV3_TK_COUNTERS * sizeof(int));
+    L.bnws = take(bn_ws_floats(Cout) * sizeof(float));
+    L.wpf = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cin, Cout) * sizeof(float));
+    L.wpd = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cout, Cin) * sizeof(float));
+    L.skws = take((L.mfma ? conv3_mfma_splitk_floats(Cin, Cout, g) : 0) * sizeof(float) + 16);
+    L.total = off;
+    return L;
+}
+}  // namespace
+
+extern "C" {
+
+size_t mi3d_conv3_bn_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W) {
+    if (Cin < 1 || Cout < 1 || N < 1 || D < 1 || H < 1 || W < 1) return 0;
+    return conv_bn_ws(dtype, Cin, Cout, Geo{N, D, H, W}).total;
+}
+int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias,
+                          const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          int64_t* num_batches_tracked, float momentum, float eps, const float* drop, void* y, void* z, int zcs,
+                          void* pooled, int pcs, float* stat, int flags, mi3d_conv3_bn_route* route_out, int Cout, int N, int D,
+                          int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+    MI3D_CHECK_ARG(x && w && bias && gamma && beta && y && z && stat && workspace, "mi3d_conv3_bn_forward: null pointer");
+    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
+                   "mi3d_conv3_bn_forward: bad dtypes %d -> %d", in_dtype, dtype);
+    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= Cin && zcs >= Cout && N >= 1 && D >= 1 && H >= 1 && W >= 1,
+                   "mi3d_conv3_bn_forward: bad shape");
+    MI3D_CHECK_ARG(!pooled || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && pcs >= Cout && (int64_t)N * D * H * W * Cout < (1ll << 31)),
+                   "mi3d_conv3_bn_forward: pooled needs even sides and fewer than 2^31 elements");
+    const Geo g{N, D, H, W};
+    const ConvBnWs L = conv_bn_ws(dtype, Cin, Cout, g);
+    MI3D_CHECK_ARG(!L.mfma || xcs % 8 == 0, "mi3d_conv3_bn_forward: input channel stride %d", xcs);
+    MI3D_CHECK_ARG(!L.c1 || in_dtype == MI3D_F32, "mi3d_conv3_bn_forward: the first-layer kernel reads an fp32 image");
+    MI3D_CHECK_ARG(workspace_bytes >= L.total, "mi3d_conv3_bn_forward: workspace too small: %zu < %zu", workspace_bytes, L.total);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "mi3d_conv3_bn_forward: workspace must be 256-byte aligned");
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    bool tk_zeroed = false;
+    if (L.mfma) {      // the plan's pack launch: the weight images, and block 0 clears the ticket counters
+        PackJobs J;
+        J.n = 0; J.nblocks = 0;
+        if (!(flags & MI3D_CONV3_BN_KEEP_TICKETS)) { J.zero = (int*)(ws + L.tkcount); J.nzero = CONV3_TK_COUNTERS; }
+        MI3D_TRY(pack_all_add_conv3(J, w, Cin, Cout, ws + L.wpf, ws + L.wpd, g));
+        MI3D_TRY(pack_all_launch(J, s));
+        tk_zeroed = true;
+    }
+    ConvBnHalf a{Cin, Cout, g, dtype, L.mfma, L.c1, x, xcs, in_dtype, Halves(), w, bias, gamma, beta, ws + L.wpf, ws + L.wpd,
+                 y, stat, running_mean, running_var, num_batches_tracked, momentum, eps, 1, tk_zeroed, false,
+                 (float*)(ws + L.statpart), (float*)(ws + L.skws), (int*)(ws + L.tkcount), (float*)(ws + L.bnws),
+                 drop, z, zcs, pooled, pcs};
+    MI3D_TRY(conv3_bn_half_forward(a, s, route_out));
+    if (route_out) route_out->rows_offset = (int32_t)(route_out->stats == 1 || route_out->stats == 2 ? L.statpart : L.bnws);
+    return 0;
+}
+
 size_t mi3d_bn_workspace_bytes(int C) { return bn_ws_floats(C) * sizeof(float); }
 int mi3d_bn_relu_drop_forward(int dtype, const void* y, int ycs, int C, int64_t M, int64_t V, const float* gamma,
                               const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,

@@ -34,8 +34,8 @@ template <int VEC> __device__ __forceinline__ bool row_map(int C, int& r, int& g
     return r < R;
 }
 
-// reduce K lane-private quantities per channel over the block; result to part[blockIdx.x][k][c]
-template <int VEC, int K> __device__ __forceinline__ void block_colreduce(const float (&acc)[K][VEC], int C, int r, int g, int R,
+// reduce K lane-private quantities per channel over the block; result to part[blockIdx.x][k][c].  S: type of the column sum
+template <int VEC, int K, typename S = float> __device__ __forceinline__ void block_colreduce(const float (&acc)[K][VEC], int C, int r, int g, int R,
                                                                            bool active, float* lds, float* part) {
     if (active) {
 #pragma unroll
@@ -46,9 +46,9 @@ template <int VEC, int K> __device__ __forceinline__ void block_colreduce(const 
     __syncthreads();
     for (int idx = threadIdx.x; idx < K * C; idx += BLK) {
         int k = idx / C, c = idx - k * C;
-        float s = 0.f;
+        S s = 0;
         for (int rr = 0; rr < R; rr++) s += lds[(k * R + rr) * C + c];
-        part[((size_t)blockIdx.x * K + k) * C + c] = s;
+        part[((size_t)blockIdx.x * K + k) * C + c] = (float)s;
     }
 }
 
@@ -58,18 +58,26 @@ __global__ __launch_bounds__(BLK) void bn_stats_kernel(const T* __restrict__ y, 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int r, g, R;
     bool active = row_map<VEC>(C, r, g, R);
-    float acc[2][VEC];
+    // The thread's and the block's sums run in double, rounded to fp32 once each.  A running fp32 sum of squares rounds at every
+    // step once it passes 2^24 units of its finest term, and var = E[y^2] - mean^2 magnifies each rounding by (mean^2 + var) / var
+    // (tests/test_conv_ref_cpu.py restates both orders).  What remains: one fp32 rounding per thread and per block row, i.e.
+    // 2^-24 * (mean^2 + var) / var on var at worst; the rows would have to be double to remove it.  The fp32 rows of
+    // bn_stats_splitk_kernel and of the conv epilogues keep running fp32 sums: their rows cover one tile or one row per thread
+    double dacc[2][VEC];
 #pragma unroll
-    for (int i = 0; i < VEC; i++) acc[0][i] = acc[1][i] = 0.f;
+    for (int i = 0; i < VEC; i++) dacc[0][i] = dacc[1][i] = 0.0;
     if (active) {
         for (int64_t row = (int64_t)blockIdx.x * R + r; row < M; row += (int64_t)gridDim.x * R) {
             float v[VEC];
             ldv<T, VEC>(y + row * ycs + g * VEC, v);
 #pragma unroll
-            for (int i = 0; i < VEC; i++) { acc[0][i] += v[i]; acc[1][i] += v[i] * v[i]; }
+            for (int i = 0; i < VEC; i++) { const double d = (double)v[i]; dacc[0][i] += d; dacc[1][i] += d * d; }
         }
     }
-    block_colreduce<VEC, 2>(acc, C, r, g, R, active, lds, part);
+    float acc[2][VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; i++) { acc[0][i] = (float)dacc[0][i]; acc[1][i] = (float)dacc[1][i]; }
+    block_colreduce<VEC, 2, double>(acc, C, r, g, R, active, lds, part);
 }
 
 // split-K convolutions (deep levels): the finishing pass y = bf16(bias + sum_k part[k]) runs HERE, fused with the

@@ -1164,7 +1164,7 @@ bool conv3_mfma_ticket_ok(int Cin, int Cout, Geo g) {
 
 int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float* bias, void* y, int ycs, int Cout, Geo g,
                    float* part, float* skws, hipStream_t s, Halves xh, Halves yh, int* ks_deferred, int relu, int split_target,
-                   float* tk_rows, int* tk_count) {
+                   float* tk_rows, int* tk_count, Conv3Launch* launched) {
     if (ks_deferred) *ks_deferred = 0;
     MI3D_CHECK_ARG(!tk_rows || (conv3_mfma_ticket_ok(Cin, Cout, g) && skws && split_target == 0), "conv3_mfma_fwd: no split-K ticket for %d->%d here", Cin, Cout);
     MI3D_CHECK_ARG((!xh.on() && !yh.on()) || persist_ok(Cin, Cout, g), "conv3_mfma_fwd: planar halves need the persistent kernel");
@@ -1174,6 +1174,7 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
     bool two = Cout % 32 == 0;
     if (persist_ok(Cin, Cout, g)) {
         int tz = cdiv(g.D, 4), ty = cdiv(g.H, 8), tx = cdiv(g.W, 16), nt = g.N * tz * ty * tx, grid = persist_grid(Cin, Cout, g);
+        if (launched) *launched = Conv3Launch{2, 1};
         // bit 1 of the relu word: 16-byte epilogue stores (two M-block rows trade halves through v_permlane16_swap)
         if (ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && yh.delta % 8 == 0) relu |= 2;
         // hook kind 2 = with BatchNorm partial sums (training forward), 3 = without (input gradient)
@@ -1193,6 +1194,7 @@ int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float*
     // bit 1 of the relu word: 16-byte epilogue stores in the eight-wave kernels (two output blocks per workgroup)
     if (ycs % 8 == 0 && ((uintptr_t)y % 16) == 0 && Cout % 32 == 0) relu |= 2;
     if (ks > 1) MI3D_CHECK_ARG(ycs % 8 == 0 && ((uintptr_t)y % 16) == 0, "conv3_mfma_fwd: split-K needs 16-B aligned output rows");
+    if (launched) *launched = Conv3Launch{big_geo(g) ? 3 : 4, big_geo(g) ? 1 : ks};
     if (big_geo(g)) {
         // (round 4: ONE 16-channel output block per workgroup at the 16-wide levels -- twice the workgroups, half the chain each, the
         // input tile staged twice -- measured slower: forward 98 -> 114 us/step, input gradients 80 -> 93; profiles/r04_experiments_misc.txt)

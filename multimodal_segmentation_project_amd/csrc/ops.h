@@ -56,10 +56,13 @@ bool conv3_mfma_halves_ok(int Cin, int Cout, Geo g);          // forward (Cin,Co
 // the consumer finishes <= 108 tile rows instead of 128 block rows.  Same bits in y as the separate finishing pass.
 bool conv3_mfma_ticket_ok(int Cin, int Cout, Geo g);
 constexpr int CONV3_TK_COUNTERS = 4096;         // ints of counter space a plan reserves
+// what conv3_mfma_fwd launched (filled in at the branch it took): kind 2 = persistent, 3 = 16-wide tile, 4 = 8-wide tile (the
+// codes of mi3d_conv3_bn_route::conv); ks = split-K factor of the launch
+struct Conv3Launch { int kind = 0, ks = 1; };
 int conv3_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float* bias, void* y, int ycs, int Cout,
                    Geo g, float* part, float* skws, hipStream_t s, Halves xh = Halves(), Halves yh = Halves(),
                    int* ks_deferred = nullptr, int relu = 0, int split_target = 0, float* tk_rows = nullptr,
-                   int* tk_count = nullptr);
+                   int* tk_count = nullptr, Conv3Launch* launched = nullptr);
 // split_target > 0: split-K workgroup target of this launch (0 = the forward default; a larger one is clamped to it, the planned
 // split-K scratch).  The input-gradient convs of the backward use CONV3_BWD_SPLITK_TARGET in the fused launch AND when they run
 // stand-alone, so both routes produce the same bits
@@ -163,6 +166,34 @@ int slab_job_launch(const SlabJob& q, hipStream_t s);
 int bn_train_stats_splitk(const float* skp, int ks, const float* bias, void* y, int ycs, int C, int64_t M, const float* gamma,
                           const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,
                           float momentum, float eps, float* stat, float* ws, hipStream_t s, int* small_rows = nullptr);
+
+// ---- one half of a DoubleConv block, forward: conv -> statistics -> apply (-> pool) ------------------ plan.hip
+// The ONE copy of the forward's route decisions (ticket, fused statistics, who finishes the partial rows, the split-K hand-over):
+// block_forward of the whole-network plan and the per-operator entry mi3d_conv3_bn_forward both call it.
+struct mi3d_conv3_bn_route;            // include/mi3d.h: what was launched, for the per-operator tests
+// route class of a conv layer whose activations have dtype dt (build_plan and mi3d_conv3_bn_forward): mfma = bf16 implicit GEMM,
+// c1 = first layer on the matrix cores (one input channel, read as fp32), neither = direct fp32 FMA
+inline void conv3_layer_class(int dt, int Cin, int Cout, bool& mfma, bool& c1) {
+    mfma = dt == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, 16, 16);
+    c1 = dt == MI3D_BF16 && Cin == 1 && Cout % 16 == 0;
+}
+struct ConvBnHalf {
+    int Cin, Cout; Geo g;
+    int dt;                            // dtype of y / out / pooled
+    bool mfma, c1;                     // bf16 implicit GEMM / first layer on the matrix cores / neither: direct fp32 FMA
+    const void* in; int ics, idt; Halves ih;
+    const float* w; const float* bias; const float* gamma; const float* beta;      // w: torch layout (c1 and direct read it)
+    void* wpf; void* wpd;              // mfma: the packed forward image (read); direct: both images are packed here
+    void* y; float* stat;
+    float* rm; float* rv; int64_t* nbt; float mom, eps;
+    int training;                      // 0: running statistics
+    bool tk_zeroed;                    // the split-K ticket counters at tkcount are zero
+    bool beside;                       // another forward runs beside this one (thin consumers only)
+    float* statpart; float* skws; int* tkcount; float* bnws;
+    const float* drop;                 // this layer's [N][Cout] scales or NULL
+    void* out; int ocs; void* pooled; int pcs;
+};
+int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_route* route = nullptr);
 
 // ---- MaxPool3d(2,2) ------------------------------------------------------------------------ pool.hip
 // Reference: models/unet.py:40,71.  g = INPUT geometry; odd sides floor like nn.MaxPool3d (last slice in no window).

@@ -14,6 +14,87 @@
 
 #include "ops.h"
 
+// One half of a DoubleConv block, forward (ops.h ConvBnHalf): conv -> BatchNorm statistics -> apply (-> MaxPool3d).  Every route
+// decision of the forward is made here and only here.  a.pooled != NULL (second half of an encoder block on an even volume): the
+// apply pass also writes MaxPool3d(2,2) of its output.  route: what was launched.
+int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_route* route) {
+    const Geo g = a.g;
+    const int training = a.training;
+    bool fused_stats = false;
+    int ksd = 0, c1_blocks = 0;
+    Conv3Launch ln;
+    bool tk = false;
+    if (a.mfma) {
+        // training: a split-K launch leaves its finishing pass to the statistics kernel (ksd = split factor).  (Deep levels
+        // WITHOUT split-K -- conv with fused partial sums -> apply, two launches instead of three -- measured +0.10 ms in
+        // round 2: the 8-16-chunk K loops on 32-216 workgroups cost more than the launch they save; that route is gone.)
+        // round 4: a split-K launch of a training forward finishes itself behind a per-tile ticket (y, BatchNorm partial rows)
+        tk = training && a.tk_zeroed && conv3_mfma_ticket_ok(a.Cin, a.Cout, g);
+        MI3D_TRY(conv3_mfma_fwd(a.in, a.ics, a.Cin, a.wpf, a.bias, a.y, a.Cout, a.Cout, g,
+                                training ? a.statpart : nullptr, a.skws, s, a.ih, Halves(),
+                                training ? &ksd : nullptr, 0, 0, tk ? a.statpart : nullptr,
+                                tk ? a.tkcount : nullptr, &ln));
+        fused_stats = training && (tk || conv3_mfma_fuses_stats(a.Cin, a.Cout, g));
+    } else if (a.c1) {
+        // BN partial sums fused like the other convs
+        MI3D_TRY(conv3_c1_fwd_mfma((const float*)a.in, a.w, a.bias, a.y, a.Cout, a.Cout, g,
+                                   training ? a.statpart : nullptr, s));
+        if (training) { fused_stats = true; c1_blocks = conv3_c1_fwd_stat_blocks(g); }
+        ln.kind = 1;
+    } else {
+        MI3D_TRY(conv3_direct_pack(a.w, a.Cin, a.Cout, (float*)a.wpf, (float*)a.wpd, s));
+        MI3D_TRY(conv3_direct_fwd(a.idt, a.dt, a.in, a.ics, a.Cin, (const float*)a.wpf, a.bias, a.y, a.Cout,
+                                  a.Cout, g, s));
+    }
+    int small_rows = 0;      // deep levels: the statistics' few partial rows are finished by the apply kernel (no finalize launch)
+    const float* rows_at = a.bnws;
+    int stats_code = 0, rows = 0;
+    if (fused_stats) {
+        // round 4: the apply pass finishes the conv epilogue's partial rows itself (bn.hip, wide consumer); the pooled pass only
+        // in its two-threads-per-window form
+        rows = c1_blocks ? c1_blocks : conv3_mfma_stat_blocks(a.Cin, a.Cout, g);
+        const bool pool_pass = a.pooled != nullptr;
+        if (a.dt == MI3D_BF16 && bn_rows_route_ok(a.Cout, g.M(), rows) && !(pool_pass && mi3d_routes().no_pool_pair) &&
+            !(a.beside && !bn_small_ok(a.Cout, g.M(), rows))) {
+            small_rows = rows;
+            rows_at = a.statpart;
+            stats_code = 1;
+        } else {
+            MI3D_TRY(bn_train_finalize(a.statpart, rows, a.Cout, g.M(), a.gamma, a.beta, a.rm, a.rv, a.nbt, a.mom, a.eps, a.stat, s));
+            stats_code = 2;
+        }
+    } else if (training && ksd > 0) {
+        MI3D_TRY(bn_train_stats_splitk(a.skws, ksd, a.bias, a.y, a.Cout, a.Cout, g.M(), a.gamma, a.beta, a.rm, a.rv, a.nbt, a.mom,
+                                       a.eps, a.stat, a.bnws, s, &small_rows));
+        stats_code = 3;
+        rows = small_rows;
+    } else if (training) {
+        MI3D_TRY(bn_train_stats(a.dt, a.y, a.Cout, a.Cout, g.M(), a.gamma, a.beta, a.rm, a.rv, a.nbt, a.mom, a.eps, a.stat,
+                                a.bnws, s, &small_rows));
+        rows = small_rows;
+    } else {
+        MI3D_CHECK_ARG(a.rm && a.rv, "eval-mode forward needs running statistics");
+        MI3D_TRY(bn_eval_stats(a.Cout, a.gamma, a.beta, a.rm, a.rv, a.eps, a.stat, s));
+    }
+    BnSmall sm{rows_at, small_rows, a.gamma, a.beta, a.rm, a.rv, a.nbt, a.mom, a.eps};
+    const float* drop = training ? a.drop : nullptr;
+    if (a.pooled)
+        MI3D_TRY(bn_apply_relu_drop_pool(a.dt, a.y, a.Cout, a.Cout, g, a.stat, drop, a.out, a.ocs, a.pooled, a.pcs, s,
+                                         small_rows > 0 ? &sm : nullptr));
+    else
+        MI3D_TRY(bn_apply_relu_drop(a.dt, a.y, a.Cout, a.Cout, g.M(), g.V(), a.stat, drop, a.out, a.ocs, s,
+                                    small_rows > 0 ? &sm : nullptr));
+    if (route) {
+        route->conv = ln.kind;
+        route->ksplit = ln.ks;
+        route->ticket = tk ? 1 : 0;
+        route->stats = stats_code;
+        route->rows = rows;
+        route->rows_offset = 0;      // relative to a workspace only the caller knows: mi3d_conv3_bn_forward fills it in
+    }
+    return 0;
+}
+
 namespace {
 
 constexpr int MAXL = MI3D_MAX_LEVELS;
@@ -132,8 +213,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             H.Cout = cout;
             H.y = take((size_t)g.M() * cout * p.esz);
             H.stat = take((size_t)4 * cout * sizeof(float));
-            H.mfma = p.dt == MI3D_BF16 && conv3_mfma_supported(H.Cin, H.Cout, 16, 16);
-            H.c1 = p.dt == MI3D_BF16 && H.Cin == 1 && H.Cout % 16 == 0;
+            conv3_layer_class(p.dt, H.Cin, H.Cout, H.mfma, H.c1);
             if (H.mfma) {
                 H.wpf = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
                 H.wpd = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
@@ -351,62 +431,12 @@ int block_forward(Ctx& c, int b, const float* x, void* const* buffers, const flo
         // training == 2: deferred running-statistics update -- buffers[bidx] is a double[2C] side buffer (ops.h bn_deferred_apply)
         const float mom = training == 2 ? -1.f : p.d.bn_momentum;
         if (training == 2) { rv = nullptr; nbt = nullptr; }
-        bool fused_stats = false;
-        int ksd = 0, c1_blocks = 0;
-        if (H.mfma) {
-            // training: a split-K launch leaves its finishing pass to the statistics kernel (ksd = split factor).  (Deep levels
-            // WITHOUT split-K -- conv with fused partial sums -> apply, two launches instead of three -- measured +0.10 ms in
-            // round 2: the 8-16-chunk K loops on 32-216 workgroups cost more than the launch they save; that route is gone.)
-            // round 4: a split-K launch of a training forward finishes itself behind a per-tile ticket (y, BatchNorm partial rows)
-            const bool tk = training && c.tk_zeroed && conv3_mfma_ticket_ok(H.Cin, H.Cout, g);
-            MI3D_TRY(conv3_mfma_fwd(v.in, v.ics, H.Cin, c.at(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
-                                    training ? c.at<float>(p.statpart) : nullptr, c.at<float>(p.skws), c.s, v.ih, Halves(),
-                                    training ? &ksd : nullptr, 0, 0, tk ? c.at<float>(p.statpart) : nullptr,
-                                    tk ? c.at<int>(p.tkcount) : nullptr));
-            fused_stats = training && (tk || conv3_mfma_fuses_stats(H.Cin, H.Cout, g));
-        } else if (H.c1) {
-            // BN partial sums fused like the other convs
-            MI3D_TRY(conv3_c1_fwd_mfma((const float*)v.in, c.P(H.pidx), c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g,
-                                       training ? c.at<float>(p.statpart) : nullptr, c.s));
-            if (training) { fused_stats = true; c1_blocks = conv3_c1_fwd_stat_blocks(g); }
-        } else {
-            MI3D_TRY(conv3_direct_pack(c.P(H.pidx), H.Cin, H.Cout, c.at<float>(H.wpf), c.at<float>(H.wpd), c.s));
-            MI3D_TRY(conv3_direct_fwd(v.idt, p.dt, v.in, v.ics, H.Cin, c.at<float>(H.wpf), c.P(H.pidx + 1), c.at(H.y), H.Cout,
-                                      H.Cout, g, c.s));
-        }
-        int small_rows = 0;      // deep levels: the statistics' few partial rows are finished by the apply kernel (no finalize launch)
-        const float* rows_at = c.at<float>(p.bnws);
-        if (fused_stats) {
-            // round 4: the apply pass finishes the conv epilogue's partial rows itself (bn.hip, wide consumer); the pooled pass only
-            // in its two-threads-per-window form
-            const int rows = c1_blocks ? c1_blocks : conv3_mfma_stat_blocks(H.Cin, H.Cout, g);
-            const bool pool_pass = h == 1 && pooled;
-            if (p.dt == MI3D_BF16 && bn_rows_route_ok(H.Cout, g.M(), rows) && !(pool_pass && mi3d_routes().no_pool_pair) &&
-                !(c.beside && !bn_small_ok(H.Cout, g.M(), rows))) {
-                small_rows = rows;
-                rows_at = c.at<float>(p.statpart);
-            } else
-                MI3D_TRY(bn_train_finalize(c.at<float>(p.statpart), rows, H.Cout, g.M(), c.P(H.pidx + 2),
-                                           c.P(H.pidx + 3), rm, rv, nbt, mom, p.d.bn_eps, c.at<float>(H.stat), c.s));
-        } else if (training && ksd > 0) {
-            MI3D_TRY(bn_train_stats_splitk(c.at<float>(p.skws), ksd, c.P(H.pidx + 1), c.at(H.y), H.Cout, H.Cout, g.M(), c.P(H.pidx + 2),
-                                           c.P(H.pidx + 3), rm, rv, nbt, mom, p.d.bn_eps, c.at<float>(H.stat),
-                                           c.at<float>(p.bnws), c.s, &small_rows));
-        } else if (training) {
-            MI3D_TRY(bn_train_stats(p.dt, c.at(H.y), H.Cout, H.Cout, g.M(), c.P(H.pidx + 2), c.P(H.pidx + 3), rm, rv, nbt,
-                                    mom, p.d.bn_eps, c.at<float>(H.stat), c.at<float>(p.bnws), c.s, &small_rows));
-        } else {
-            MI3D_CHECK_ARG(rm && rv, "eval-mode forward needs running statistics");
-            MI3D_TRY(bn_eval_stats(H.Cout, c.P(H.pidx + 2), c.P(H.pidx + 3), rm, rv, p.d.bn_eps, c.at<float>(H.stat), c.s));
-        }
-        BnSmall sm{rows_at, small_rows, c.P(H.pidx + 2), c.P(H.pidx + 3), rm, rv, nbt, mom, p.d.bn_eps};
-        if (h == 1 && pooled)
-            MI3D_TRY(bn_apply_relu_drop_pool(p.dt, c.at(H.y), H.Cout, H.Cout, g, c.at<float>(H.stat),
-                                             (drop && training) ? drop + H.drop_off : nullptr, v.out, v.ocs, pooled, pcs, c.s,
-                                             small_rows > 0 ? &sm : nullptr));
-        else
-            MI3D_TRY(bn_apply_relu_drop(p.dt, c.at(H.y), H.Cout, H.Cout, g.M(), g.V(), c.at<float>(H.stat),
-                                        (drop && training) ? drop + H.drop_off : nullptr, v.out, v.ocs, c.s, small_rows > 0 ? &sm : nullptr));
+        ConvBnHalf a{H.Cin, H.Cout, g, p.dt, H.mfma, H.c1, v.in, v.ics, v.idt, v.ih,
+                     c.P(H.pidx), c.P(H.pidx + 1), c.P(H.pidx + 2), c.P(H.pidx + 3), c.at(H.wpf), c.at(H.wpd),
+                     c.at(H.y), c.at<float>(H.stat), rm, rv, nbt, mom, p.d.bn_eps, training, c.tk_zeroed, c.beside,
+                     c.at<float>(p.statpart), c.at<float>(p.skws), c.at<int>(p.tkcount), c.at<float>(p.bnws),
+                     drop ? drop + H.drop_off : nullptr, v.out, v.ocs, h == 1 ? pooled : nullptr, pcs};
+        MI3D_TRY(conv3_bn_half_forward(a, c.s));
     }
     return 0;
 }

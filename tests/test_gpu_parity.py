@@ -4,6 +4,9 @@ Tolerances: fp32 path = kernels accumulate in fp32 in a different order than tor
 1e-4-class relative tolerances; bf16 path = activations stored in bf16 (8 significant bits), compared with
 norm-relative tolerances per tensor (SURVEY §7 hard part 9) and Dice within 1e-3 (BASELINE north_star).
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -15,6 +18,9 @@ from multimodal_segmentation_project_amd import metrics as M
 from multimodal_segmentation_project_amd import unet_dann
 from multimodal_segmentation_project_amd.dann import DomainDiscriminator, domain_ce, grad_reverse
 from multimodal_segmentation_project_amd.unet import DoubleConv, UNet3D
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from conv_ref import assert_bf16_rne_bits  # noqa: E402
 
 DEV = "cuda:0"
 LOSS_CASES = ["uniform", "absent2", "single0", "onehot", "c3_noncubic"]
@@ -524,6 +530,7 @@ def test_conv3_mfma_vs_c_oracle(orc, shape):
     ref = orc.conv3d_fwd(x, wgt, b)
     got = y.float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(got - ref).max() <= np.abs(ref).max() * 2 ** -8 + 1e-6
+    assert_bf16_rne_bits(y, ref, "y")               # every partial sum is exact in fp32: the stored value is bf16_rne(exact)
     dx = torch.empty_like(xcl)
     dW = torch.empty((cout, cin, 3, 3, 3), device=DEV)
     db = torch.empty(cout, device=DEV)
@@ -532,6 +539,7 @@ def test_conv3_mfma_vs_c_oracle(orc, shape):
     rgx, rgw, rgb = orc.conv3d_bwd(x, wgt, gy)
     gotx = dx.float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(gotx - rgx).max() <= np.abs(rgx).max() * 2 ** -8 + 1e-6
+    assert_bf16_rne_bits(dx, rgx, "dx")
     np.testing.assert_allclose(dW.cpu().numpy(), rgw, rtol=0, atol=1e-5)
     np.testing.assert_allclose(db.cpu().numpy(), rgb, rtol=0, atol=1e-5)
 
@@ -582,6 +590,7 @@ def test_upconv_mfma_vs_c_oracle(orc, shape):
     ref = orc.convT2_fwd(x, wgt, b)
     got = cat[..., cout:].float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(got - ref).max() <= np.abs(ref).max() * 2 ** -8 + 1e-6
+    assert_bf16_rne_bits(cat[..., cout:], ref, "y")
     assert float(cat[..., :cout].abs().max()) == 0.0
     gcat = torch.zeros_like(cat)
     gcat[..., cout:] = t(gy.transpose(0, 2, 3, 4, 1)).bfloat16()
@@ -592,6 +601,7 @@ def test_upconv_mfma_vs_c_oracle(orc, shape):
     rgx, rgw, rgb = orc.convT2_bwd(x, wgt, gy)
     gotx = dx.float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(gotx - rgx).max() <= np.abs(rgx).max() * 2 ** -8 + 1e-6
+    assert_bf16_rne_bits(dx, rgx, "dx")
     np.testing.assert_allclose(dW.cpu().numpy(), rgw, rtol=0, atol=1e-5)
     np.testing.assert_allclose(db.cpu().numpy(), rgb, rtol=0, atol=1e-5)
 

@@ -25,6 +25,11 @@ def battery():
     from multimodal_segmentation_project_amd._lib import call, ptr
     from multimodal_segmentation_project_amd.trainer import TrainStep, _loss_cfg
     from multimodal_segmentation_project_amd.unet import UNet3D
+    # an older build lacks the entries added since it was made; the battery calls none of them
+    have = C.CDLL(_lib.LIB_PATH)
+    for name in [k for k in _lib._SIGS if not hasattr(have, k)]:
+        print(f"ab_bits: {_lib.LIB_PATH} has no {name}", file=sys.stderr)
+        del _lib._SIGS[name]
     dev, lib, out = "cuda:0", _lib.lib(), {}
 
     def put(name, t):
