@@ -455,6 +455,46 @@ int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int C
                           int64_t* num_batches_tracked, float momentum, float eps, const float* drop, void* y, void* z, int zcs,
                           void* pooled, int pcs, float* stat, int flags, mi3d_conv3_bn_route* route_out, int Cout, int N, int D,
                           int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+/* One half of a DoubleConv block as the training backward of the whole-network plan runs it: BatchNorm3d + ReLU + Dropout3d
+ * backward (dz -> dy, dgamma, dbeta), then the conv's weight / bias gradient and input gradient, with the plan's own per-layer
+ * decisions (the plan and this entry call ONE function) on a workspace of its own.  x is the layer's input, y / stat / drop what
+ * the forward saved, dz the gradient of the activated output, dy [M][Cout] the buffer the conv's output gradient is written to.
+ *   stat == NULL          no BatchNorm: dz is the conv's dy (what mi3d_conv3_backward means); y, drop, dy, dgamma, dbeta unused
+ *   dz_partials, dz_ks    dz arrives as fp32 split-K partials [dz_ks][M][Cout]; the reduction sums and rounds them and WRITES dz
+ *   x_split, x_delta      planar halves of x: 16-channel block b >= x_split lies x_delta elements further (0, 0 = one plane);
+ *   dx_split, dx_delta    the same for dx.  Only the full-resolution (persistent) kernels and the weight gradient honour them
+ *   riders[2]             NULL, or up to two pending sums (nblocks > 0) carried in this call's BatchNorm-backward reduction
+ *   pending_out           with MI3D_CONV3_BN_BWD_LEAVE_PENDING: the layer's slab sum is NOT launched but returned here
+ * flags
+ *   MI3D_CONV3_BN_BWD_ALLOW_PARTIALS  a split-K dx may stay as fp32 partials [dx_ks][M][Cin] in the workspace at dx_offset (dx is
+ *                                     then not written); whoever reads them finishes them
+ *   MI3D_CONV3_BN_BWD_DEFER           the deferred layer's route, run in order on the given stream: the input gradient alone, then
+ *                                     the stand-alone weight gradient cut into the slabs of the layer's fused launch
+ *   MI3D_CONV3_BN_BWD_LEAVE_PENDING   see pending_out
+ * route_out (may be NULL) reports what was launched:
+ *   bn           0 none, 1 reduction + finalize + apply, 2 reduction + apply (the apply pass finishes the rows in its prologue)
+ *   riders       pending sums carried by the reduction (0, 1, 2);  dz_ks  split factor of the dz partials consumed (0 = stored dz)
+ *   conv         0 direct fp32-FMA kernels, 1 first-layer weight gradient only, 2 fused persistent, 3 fused with the 16-wide tile,
+ *                4 fused with the 8-wide tile, 5 stand-alone pair (weight gradient, then input gradient), 6 deferred pair
+ *   dgrad_ks     split-K factor of the input gradient (1 = none, 0 = no input gradient);  dx_ks  split factor of a dx LEFT as
+ *                partials (0 = dx written);  dx_offset  byte offset of those partials in the workspace
+ *   slabs, slab_layout, slab_ew   weight-gradient slabs summed, the sum's layout (0 element order, 1 MFMA order, 2 MFMA order
+ *                through an LDS transpose) and elements per block (0 for layout 2); all 0 for the direct kernels
+ *   pending      1 = the sum was left in pending_out */
+typedef struct mi3d_pending_sum { int64_t opaque[9]; } mi3d_pending_sum;      /* a slab sum waiting for a launch; plain data */
+typedef struct mi3d_conv3_bn_bwd_route {
+    int32_t bn, riders, dz_ks, conv, dgrad_ks, dx_ks, dx_offset, slabs, slab_layout, slab_ew, pending;
+} mi3d_conv3_bn_bwd_route;
+enum { MI3D_CONV3_BN_BWD_ALLOW_PARTIALS = 1, MI3D_CONV3_BN_BWD_DEFER = 2, MI3D_CONV3_BN_BWD_LEAVE_PENDING = 4 };
+size_t mi3d_conv3_bn_bwd_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W);
+int mi3d_conv3_bn_backward(int in_dtype, int dtype, const void* x, int xcs, int x_split, int64_t x_delta, int Cin, const float* w,
+                           const void* y, const float* stat, const float* drop, void* dz, int dzcs, const float* dz_partials,
+                           int dz_ks, void* dy, void* dx, int dxcs, int dx_split, int64_t dx_delta, float* dW, float* db,
+                           float* dgamma, float* dbeta, int accumulate, const mi3d_pending_sum* riders, mi3d_pending_sum* pending_out,
+                           int flags, mi3d_conv3_bn_bwd_route* route_out, int Cout, int N, int D, int H, int W, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* launches a pending sum on its own (what the plan does with the last one of a call) */
+int mi3d_pending_sum_launch(const mi3d_pending_sum* job, void* stream);
 /* BatchNorm3d(train) + ReLU + Dropout3d fused; stat: device float[4*C] saved for backward */
 size_t mi3d_bn_workspace_bytes(int C);
 int mi3d_bn_relu_drop_forward(int dtype, const void* y, int ycs, int C, int64_t M, int64_t V, const float* gamma,
@@ -474,6 +514,9 @@ int mi3d_maxpool2_forward(int dtype, const void* z, int zcs, int C, int N, int D
                           void* stream);
 int mi3d_maxpool2_backward(int dtype, const void* dp, int dpcs, const void* z, int zcs, const void* dskip, int dskipcs,
                            void* dz, int dzcs, int C, int N, int D, int H, int W, void* stream);
+/* the same with dp not yet written: it is still the ks fp32 split-K partials [ks][M/8][C] of the conv that produces it */
+int mi3d_maxpool2_backward_partials(int dtype, const float* dp_partials, int ks, const void* z, int zcs, const void* dskip,
+                                    int dskipcs, void* dz, int dzcs, int C, int N, int D, int H, int W, void* stream);
 /* ConvTranspose3d(k2,s2) unet.py:56-58.  w (Cin,Cout,2,2,2) float; geometry = INPUT volume */
 size_t mi3d_upconv2_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W);
 int mi3d_upconv2_forward(int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias, void* y, int ycs,

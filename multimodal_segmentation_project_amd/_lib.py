@@ -53,6 +53,18 @@ class Conv3BnRoute(C.Structure):                   # mi3d_conv3_bn_route
 
 CONV3_BN_KEEP_TICKETS = 1
 
+
+class Conv3BnBwdRoute(C.Structure):                # mi3d_conv3_bn_bwd_route
+    _fields_ = [(k, C.c_int32) for k in ("bn", "riders", "dz_ks", "conv", "dgrad_ks", "dx_ks", "dx_offset", "slabs", "slab_layout",
+                                         "slab_ew", "pending")]
+
+
+class PendingSum(C.Structure):                     # mi3d_pending_sum: opaque, plain data
+    _fields_ = [("opaque", C.c_int64 * 9)]
+
+
+CONV3_BN_BWD_ALLOW_PARTIALS, CONV3_BN_BWD_DEFER, CONV3_BN_BWD_LEAVE_PENDING = 1, 2, 4
+
 _DP, _LP, _AP, _MP = C.POINTER(UNetDesc), C.POINTER(LossCfg), C.POINTER(AugParams), C.POINTER(MaskList)
 
 # name -> (restype, argtypes); one line per symbol declared in include/mi3d.h
@@ -131,6 +143,11 @@ _SIGS = {
     "mi3d_conv3_bn_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
     "mi3d_conv3_bn_forward": (i32, [i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, i32, vp, i32,
                                     C.POINTER(Conv3BnRoute), i32, i32, i32, i32, i32, vp, sz, vp]),
+    "mi3d_conv3_bn_bwd_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "mi3d_conv3_bn_backward": (i32, [i32, i32, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, vp,
+                                     vp, vp, i32, C.POINTER(PendingSum), C.POINTER(PendingSum), i32, C.POINTER(Conv3BnBwdRoute),
+                                     i32, i32, i32, i32, i32, vp, sz, vp]),
+    "mi3d_pending_sum_launch": (i32, [C.POINTER(PendingSum), vp]),
     "mi3d_bn_workspace_bytes": (sz, [i32]),
     "mi3d_bn_relu_drop_forward": (i32, [i32, vp, i32, i32, i64, i64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, i32,
                                         vp, vp, vp]),
@@ -142,6 +159,7 @@ _SIGS = {
     "mi3d_conv1_backward": (i32, [i32, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, sz, vp]),
     "mi3d_maxpool2_forward": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "mi3d_maxpool2_backward": (i32, [i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mi3d_maxpool2_backward_partials": (i32, [i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mi3d_upconv2_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
     "mi3d_upconv2_forward": (i32, [i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "mi3d_upconv2_backward": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp,

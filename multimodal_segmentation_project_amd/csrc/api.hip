@@ -134,14 +134,88 @@ int mi3d_dropout_scales(float* out, int64_t n, float p, uint64_t* state_dev, voi
 }
 
 // ---- per-operator entry points ------------------------------------------------------------------
+}  // extern "C"
+
+// mi3d_conv3_bn_backward / mi3d_conv3_backward: the plan's scratch areas of one layer's backward in a workspace of its own
+namespace {
+struct ConvBnBwdWs {
+    size_t wpf, wpd, bnws, wgws, wgws_floats, skws, total;
+};
+ConvBnBwdWs conv_bn_bwd_ws(bool mfma, int Cin, int Cout, Geo g) {
+    ConvBnBwdWs L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    L.wpf = take(mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cin, Cout) * sizeof(float));
+    L.wpd = take(mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cout, Cin) * sizeof(float));
+    L.bnws = take(bn_ws_floats(Cout) * sizeof(float));
+    L.wgws_floats = conv3_direct_wgrad_ws_floats(Cin, Cout, g);
+    if ((mfma || (Cin == 1 && Cout % 16 == 0)) && conv3_mfma_wgrad_ws_floats(Cin, Cout, g) > L.wgws_floats)
+        L.wgws_floats = conv3_mfma_wgrad_ws_floats(Cin, Cout, g);
+    L.wgws = take(L.wgws_floats * sizeof(float));
+    L.skws = take((mfma ? conv3_mfma_splitk_floats(Cout, Cin, g) : 0) * sizeof(float) + 16);      // the input gradient's split-K partials
+    L.total = off;
+    return L;
+}
+static_assert(sizeof(mi3d_pending_sum) == sizeof(SlabJob) && alignof(mi3d_pending_sum) == alignof(SlabJob), "mi3d_pending_sum holds a SlabJob");
+
+struct ConvBwdCall {
+    int in_dtype, dtype; const void* x; int xcs; Halves xh; int Cin; const float* w; const void* y; const float* stat; const float* drop;
+    void* dz; int dzcs; const float* dz_partials; int dz_ks; void* dy; void* dx; int dxcs; Halves dxh; float* dW; float* db;
+    float* dgamma; float* dbeta; int accumulate; const mi3d_pending_sum* riders; mi3d_pending_sum* pending_out; int flags;
+    mi3d_conv3_bn_bwd_route* route_out; int Cout; Geo g; bool mfma, c1; char* ws;
+};
+// the plan's pack launch, then conv3_bn_half_backward with a Pending of the caller's riders; the layer's own sum is handed out or launched
+int conv_bn_bwd_run(const ConvBwdCall& k, const ConvBnBwdWs& L, hipStream_t s) {
+    if (k.mfma) {
+        PackJobs J;
+        J.n = 0; J.nblocks = 0;
+        MI3D_TRY(pack_all_add_conv3(J, k.w, k.Cin, k.Cout, k.ws + L.wpf, k.ws + L.wpd, k.g));
+        MI3D_TRY(pack_all_launch(J, s));
+    } else if (k.dx) {
+        MI3D_TRY(conv3_direct_pack(k.w, k.Cin, k.Cout, (float*)(k.ws + L.wpf), (float*)(k.ws + L.wpd), s));
+    }
+    Pending pending;
+    if (k.riders) {
+        memcpy(&pending.pend, &k.riders[0], sizeof(SlabJob));
+        memcpy(&pending.pend2, &k.riders[1], sizeof(SlabJob));
+        if (!Pending::waits(pending.pend) && Pending::waits(pending.pend2)) { pending.pend = pending.pend2; pending.pend2 = SlabJob(); }
+    }
+    const bool defer = (k.flags & MI3D_CONV3_BN_BWD_DEFER) != 0, leave = (k.flags & MI3D_CONV3_BN_BWD_LEAVE_PENDING) != 0;
+    ConvBnHalfBwd a{k.Cin, k.Cout, k.g, k.dtype, k.mfma, k.c1, k.x, k.xcs, k.in_dtype, k.xh, k.ws + L.wpd, k.y, k.stat, k.drop,
+                    k.dz, k.dzcs, k.dz_partials, k.dz_ks, k.dy, k.Cout, k.dx, k.dxcs, k.dxh, k.dW, k.db, k.dgamma, k.dbeta, k.accumulate,
+                    (float*)(k.ws + L.bnws), (float*)(k.ws + L.wgws), L.wgws_floats, (float*)(k.ws + L.skws),
+                    (k.flags & MI3D_CONV3_BN_BWD_ALLOW_PARTIALS) != 0, defer, nullptr, nullptr};
+    MI3D_TRY(conv3_bn_half_backward(a, pending, s, nullptr, k.route_out));
+    if (defer)      // what drain_aux of the plan launches on the aux stream, here in order on s
+        MI3D_TRY(conv3_deferred_wgrad(k.x, k.xcs, k.Cin, k.xh, k.stat ? k.dy : k.dz, k.stat ? k.Cout : k.dzcs, k.Cout, k.g, k.dx ? k.dxcs : 0,
+                                      k.dW, k.db, k.accumulate, (float*)(k.ws + L.wgws), L.wgws_floats, s));
+    if (k.pending_out) memset(k.pending_out, 0, sizeof(*k.pending_out));
+    if (leave && Pending::waits(pending.pend)) {
+        memcpy(k.pending_out, &pending.pend, sizeof(SlabJob));
+        pending.pend.nblocks = 0;
+    }
+    const bool left = leave && k.pending_out && ((const SlabJob*)k.pending_out)->nblocks > 0;
+    MI3D_TRY(pending.flush(s));
+    if (k.route_out) {
+        k.route_out->pending = left ? 1 : 0;
+        k.route_out->dx_offset = (int32_t)L.skws;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
 size_t mi3d_conv3_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W) {
     Geo g{N, D, H, W};
     size_t wg = conv3_direct_wgrad_ws_floats(Cin, Cout, g);
     if ((conv3_mfma_supported(Cin, Cout, 16, 16) || (Cin == 1 && Cout % 16 == 0)) && conv3_mfma_wgrad_ws_floats(Cin, Cout, g) > wg)
         wg = conv3_mfma_wgrad_ws_floats(Cin, Cout, g);
-    // + the split-K scratch of the fused (input-gradient + weight-gradient) deep-level launch
-    size_t sk = conv3_mfma_supported(Cin, Cout, 16, 16) ? conv3_mfma_splitk_floats(Cout, Cin, g) : 0;
-    return (conv3_direct_pack_floats(Cin, Cout) + conv3_direct_pack_floats(Cout, Cin) + wg + sk + 64) * sizeof(float);
+    size_t fwd = (conv3_direct_pack_floats(Cin, Cout) + conv3_direct_pack_floats(Cout, Cin) + wg + 64) * sizeof(float);
+    // the backward's areas (mi3d_conv3_backward aligns the workspace itself: + 256)
+    size_t bwd = conv_bn_bwd_ws(false, Cin, Cout, g).total;
+    if (conv3_mfma_supported(Cin, Cout, 16, 16) && conv_bn_bwd_ws(true, Cin, Cout, g).total > bwd) bwd = conv_bn_bwd_ws(true, Cin, Cout, g).total;
+    return (fwd > bwd ? fwd : bwd) + 256;
 }
 int mi3d_conv3_forward(int in_dtype, int out_dtype, const void* x, int xcs, int Cin, const float* w, const float* bias,
                        void* y, int ycs, int Cout, int N, int D, int H, int W, void* workspace, size_t workspace_bytes,
@@ -158,51 +232,73 @@ int mi3d_conv3_forward(int in_dtype, int out_dtype, const void* x, int xcs, int 
     MI3D_TRY(conv3_direct_pack(w, Cin, Cout, wpf, wpd, s));
     return conv3_direct_fwd(in_dtype, out_dtype, x, xcs, Cin, wpf, bias, y, ycs, Cout, Geo{N, D, H, W}, s);
 }
+// The conv half of conv3_bn_half_backward (no BatchNorm, no flags): the kernels the training step runs for this layer.  A layer
+// whose strides the MFMA kernels cannot take runs the direct kernels
 int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int Cin, const float* w, const void* dy,
                         int dycs, int Cout, void* dx, int dxcs, float* dW, float* db, int accumulate, int N, int D, int H,
                         int W, void* workspace, size_t workspace_bytes, void* stream) {
     MI3D_CHECK_ARG(x && w && dy && workspace, "mi3d_conv3_backward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_conv3_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_conv3_backward: workspace too small");
     Geo g{N, D, H, W};
-    float* wpf = (float*)workspace;
-    float* wpd = wpf + conv3_direct_pack_floats(Cin, Cout);
-    float* slabs = wpd + conv3_direct_pack_floats(Cout, Cin);
-    hipStream_t s = (hipStream_t)stream;
-    // the same kernel choice as the whole-network plan (plan.hip block_backward), so the per-operator parity tests pin
-    // the kernels the training step runs: both products of a layer in ONE fused launch where that exists
-    if (dx && (dW || db) && x_dtype == MI3D_BF16 && use_mfma(dy_dtype, dy_dtype, Cout, Cin, dycs, dxcs) &&
-        use_mfma(x_dtype, dy_dtype, Cin, Cout, xcs, dycs)) {
-        size_t wgf = conv3_mfma_wgrad_ws_floats(Cin, Cout, g);
-        if (conv3_direct_wgrad_ws_floats(Cin, Cout, g) > wgf) wgf = conv3_direct_wgrad_ws_floats(Cin, Cout, g);
-        float* skws = slabs + ((wgf + 63) & ~(size_t)63);
-        if (conv3_mfma_bwd_fused_persist_ok(Cin, Cout, xcs, dycs, g)) {
-            MI3D_TRY(conv3_mfma_pack(w, Cin, Cout, wpf, wpd, g, s));
-            return conv3_mfma_bwd_fused_persist(x, xcs, Cin, dy, dycs, Cout, wpd, dx, dxcs, g, dW, db, accumulate, slabs, wgf, s);
-        }
-        if (conv3_mfma_bwd_fused_ok(Cin, Cout, xcs, dycs, dxcs, g)) {
-            MI3D_TRY(conv3_mfma_pack(w, Cin, Cout, wpf, wpd, g, s));
-            return conv3_mfma_bwd_fused(x, xcs, Cin, dy, dycs, Cout, wpd, dx, dxcs, g, dW, db, accumulate, slabs, wgf, skws, s);
-        }
-    }
-    if (dx && use_mfma(dy_dtype, dy_dtype, Cout, Cin, dycs, dxcs)) {
-        MI3D_TRY(conv3_mfma_pack(w, Cin, Cout, wpf, wpd, g, s));
-        MI3D_TRY(conv3_mfma_fwd(dy, dycs, Cout, wpd, nullptr, dx, dxcs, Cin, g, nullptr, nullptr, s));      // skws NULL: single pass
-    } else {
-        MI3D_TRY(conv3_direct_pack(w, Cin, Cout, wpf, wpd, s));
-        if (dx) MI3D_TRY(conv3_direct_fwd(dy_dtype, dy_dtype, dy, dycs, Cout, wpd, nullptr, dx, dxcs, Cin, g, s));
-    }
-    if (dW || db) {
-        if (x_dtype == MI3D_F32 && dy_dtype == MI3D_BF16 && Cin == 1 && xcs == 1 && Cout % 16 == 0 && dycs % 8 == 0)
-            MI3D_TRY(conv3_mfma_wgrad_c1((const float*)x, dy, dycs, Cout, g, dW, db, accumulate, slabs,
-                                         conv3_mfma_wgrad_ws_floats(Cin, Cout, g), s));
-        else if (use_mfma(x_dtype, dy_dtype, Cin, Cout, xcs, dycs) && dycs % 8 == 0)
-            MI3D_TRY(conv3_mfma_wgrad(x, xcs, Cin, dy, dycs, Cout, g, dW, db, accumulate, slabs,
-                                      conv3_mfma_wgrad_ws_floats(Cin, Cout, g), s));
-        else
-            MI3D_TRY(conv3_direct_wgrad(x_dtype, dy_dtype, x, xcs, Cin, dy, dycs, Cout, g, dW, db, accumulate, slabs,
-                                        conv3_direct_wgrad_ws_floats(Cin, Cout, g), s));
-    }
-    return 0;
+    bool mfma, c1;
+    conv3_layer_class(dy_dtype, Cin, Cout, mfma, c1);
+    mfma = mfma && x_dtype == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, xcs, dycs) && dycs % 8 == 0 &&
+           (!dx || conv3_mfma_supported(Cout, Cin, dycs, dxcs));
+    c1 = c1 && x_dtype == MI3D_F32 && xcs == 1 && dycs % 8 == 0 && !dx;
+    const ConvBnBwdWs L = conv_bn_bwd_ws(mfma, Cin, Cout, g);
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    ConvBwdCall k{x_dtype, dy_dtype, x, xcs, Halves(), Cin, w, nullptr, nullptr, nullptr, const_cast<void*>(dy), dycs, nullptr, 0, nullptr,
+                  dx, dxcs, Halves(), dW, db, nullptr, nullptr, accumulate, nullptr, nullptr, 0, nullptr, Cout, g, mfma, c1, ws};
+    return conv_bn_bwd_run(k, L, (hipStream_t)stream);
+}
+
+size_t mi3d_conv3_bn_bwd_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W) {
+    if (Cin < 1 || Cout < 1 || N < 1 || D < 1 || H < 1 || W < 1) return 0;
+    bool mfma, c1;
+    conv3_layer_class(dtype, Cin, Cout, mfma, c1);
+    return conv_bn_bwd_ws(mfma, Cin, Cout, Geo{N, D, H, W}).total;
+}
+int mi3d_conv3_bn_backward(int in_dtype, int dtype, const void* x, int xcs, int x_split, int64_t x_delta, int Cin, const float* w,
+                           const void* y, const float* stat, const float* drop, void* dz, int dzcs, const float* dz_partials,
+                           int dz_ks, void* dy, void* dx, int dxcs, int dx_split, int64_t dx_delta, float* dW, float* db,
+                           float* dgamma, float* dbeta, int accumulate, const mi3d_pending_sum* riders, mi3d_pending_sum* pending_out,
+                           int flags, mi3d_conv3_bn_bwd_route* route_out, int Cout, int N, int D, int H, int W, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    const char* fn = "mi3d_conv3_bn_backward";
+    MI3D_CHECK_ARG(x && w && dz && workspace, "%s: null pointer", fn);
+    MI3D_CHECK_ARG(!stat || (y && dy), "%s: the BatchNorm backward needs y and dy", fn);
+    MI3D_CHECK_ARG(stat || (!dz_partials && !riders), "%s: dz partials and riders need the BatchNorm backward", fn);
+    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
+                   "%s: bad dtypes %d -> %d", fn, in_dtype, dtype);
+    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= (x_delta ? 16 : Cin) && dzcs >= Cout && N >= 1 && D >= 1 && H >= 1 && W >= 1,
+                   "%s: bad shape", fn);
+    MI3D_CHECK_ARG(!dz_partials || dz_ks >= 1, "%s: dz_ks=%d", fn, dz_ks);
+    MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_LEAVE_PENDING) || pending_out, "%s: LEAVE_PENDING needs pending_out", fn);
+    MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_DEFER) || !(flags & MI3D_CONV3_BN_BWD_LEAVE_PENDING), "%s: DEFER launches its own sum", fn);
+    const Geo g{N, D, H, W};
+    bool mfma, c1;
+    conv3_layer_class(dtype, Cin, Cout, mfma, c1);
+    MI3D_CHECK_ARG(!mfma || (xcs % 8 == 0 && dzcs % 8 == 0 && (!dx || dxcs % 4 == 0)), "%s: channel strides %d / %d / %d", fn, xcs, dzcs, dxcs);
+    MI3D_CHECK_ARG(!c1 || (in_dtype == MI3D_F32 && !dx), "%s: the first-layer kernel reads an fp32 image and has no input gradient", fn);
+    MI3D_CHECK_ARG(!dx || dxcs >= (dx_delta ? 16 : Cin), "%s: dx stride %d", fn, dxcs);
+    MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_DEFER) || (mfma && (dW || db)), "%s: only MFMA layers with a weight gradient defer it", fn);
+    MI3D_CHECK_ARG((!x_delta && !dx_delta) || (mfma && conv3_mfma_halves_ok(Cout, Cin, g)),
+                   "%s: planar halves need the full-resolution kernels", fn);
+    const ConvBnBwdWs L = conv_bn_bwd_ws(mfma, Cin, Cout, g);
+    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    Halves xh, dxh;
+    if (x_delta) { xh.split = x_split; xh.delta = x_delta; }
+    if (dx_delta) { dxh.split = dx_split; dxh.delta = dx_delta; }
+    ConvBwdCall k{in_dtype, dtype, x, xcs, xh, Cin, w, y, stat, drop, dz, dzcs, dz_partials, dz_ks, dy, dx, dxcs, dxh, dW, db, dgamma, dbeta,
+                  accumulate, riders, pending_out, flags, route_out, Cout, g, mfma, c1, (char*)workspace};
+    return conv_bn_bwd_run(k, L, (hipStream_t)stream);
+}
+int mi3d_pending_sum_launch(const mi3d_pending_sum* job, void* stream) {
+    MI3D_CHECK_ARG(job, "mi3d_pending_sum_launch: null job");
+    SlabJob q;
+    memcpy(&q, job, sizeof(q));
+    return slab_job_launch(q, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -356,6 +452,12 @@ int mi3d_maxpool2_backward(int dtype, const void* dp, int dpcs, const void* z, i
                            void* dz, int dzcs, int C, int N, int D, int H, int W, void* stream) {
     MI3D_CHECK_ARG(dp && z && dz, "mi3d_maxpool2_backward: null pointer");
     return maxpool2_bwd(dtype, dp, dpcs, z, zcs, dskip, dskipcs, dz, dzcs, C, Geo{N, D, H, W}, (hipStream_t)stream);
+}
+int mi3d_maxpool2_backward_partials(int dtype, const float* dp_partials, int ks, const void* z, int zcs, const void* dskip,
+                                    int dskipcs, void* dz, int dzcs, int C, int N, int D, int H, int W, void* stream) {
+    MI3D_CHECK_ARG(dp_partials && ks >= 1 && z && dz, "mi3d_maxpool2_backward_partials: null pointer or ks < 1");
+    // the kernels read dp only without partials; its stride still takes part in the choice of kernel (the plan passes the pooled tensor's C)
+    return maxpool2_bwd(dtype, dp_partials, C, z, zcs, dskip, dskipcs, dz, dzcs, C, Geo{N, D, H, W}, (hipStream_t)stream, dp_partials, ks);
 }
 size_t mi3d_upconv2_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W) {
     Geo g{N, D, H, W};

@@ -1888,6 +1888,8 @@ size_t conv3_mfma_wgrad_ws_floats(int Cin, int Cout, Geo g) {
 }
 
 bool conv3_mfma_big_geo(Geo g) { return big_geo(g); }
+int conv3_mfma_wgrad_slabs(int Cin, int Cout, Geo g, int wg_target) { return wgrad_cfg(Cin, Cout, g, wg_target).nsb; }
+int conv3_mfma_bwd_ksplit(int Cin, int Cout, Geo g) { return pick_ksplit(Cout, Cin, g, CONV3_BWD_SPLITK_TARGET); }
 
 int conv3_mfma_wgrad(const void* x, int xcs, int Cin, const void* dy, int dycs, int Cout, Geo g, float* dW, float* db,
                      int accumulate, float* ws, size_t ws_floats, hipStream_t s, Halves xh, SlabJob* pend, int wg_target) {

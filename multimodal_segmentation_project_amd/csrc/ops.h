@@ -79,6 +79,8 @@ int conv3_mfma_wgrad(const void* x, int xcs, int Cin, const void* dy, int dycs, 
 // backward launch uses for its weight-gradient half (0: the layer has no fused launch): a stand-alone weight gradient launched
 // with it cuts the tiles into the same slabs, i.e. sums in the same order and produces the same bits as the fused route
 int conv3_mfma_bwd_wg_target(int Cin, int Cout, int xcs, int dycs, int dxcs, Geo g);
+int conv3_mfma_wgrad_slabs(int Cin, int Cout, Geo g, int wg_target);      // slabs conv3_mfma_wgrad / the fused launches write
+int conv3_mfma_bwd_ksplit(int Cin, int Cout, Geo g);      // split-K factor of the layer's input-gradient conv when it has the scratch
 bool conv3_mfma_big_geo(Geo g);      // 16-wide tiles (levels 0-1 of a 96^3 net) vs the 8-wide deep-level tiling
 // pend != NULL (here and below): the final slab sum is NOT launched; its job is returned for the caller to attach to
 // the next kernel on the chain (bn_bwd) or to run with slab_job_launch
@@ -194,6 +196,87 @@ struct ConvBnHalf {
     void* out; int ocs; void* pooled; int pcs;
 };
 int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_route* route = nullptr);
+
+// ---- one half of a DoubleConv block, backward: BatchNorm backward -> weight gradient + input gradient ---------------- plan.hip
+// The weight-gradient slab sums that wait for a launch to ride in.  A launcher that is handed a slot leaves its final slab sum
+// there instead of launching it (nblocks > 0: a sum waits).  The rule, once:
+//   * a launch that writes the first slab workspace (wgws) takes `first`: older sums read their workspaces before it, with
+//     launches of their own;
+//   * the transposed conv's backward may take `carry` instead while the decoder conv's sum waits: it writes the SECOND
+//     workspace (wgws2) and both sums stay;
+//   * the next BatchNorm-backward reduction carries up to two (`riders`, then `rode` behind that launch);
+//   * an exchange mark is recorded behind the launch that carried its segment's sums (`rode`), or behind a flush when the
+//     segment launched no BatchNorm backward / the call ends (`finish`).
+struct Pending {
+    SlabJob pend, pend2;
+    hipEvent_t mark = nullptr;      // exchange mark waiting for the launch that completes its segment's gradients
+    static bool waits(const SlabJob& j) { return j.nblocks > 0; }
+    int flush(hipStream_t s) {
+        int rc = 0;
+        if (waits(pend)) { rc = slab_job_launch(pend, s); pend.nblocks = 0; }
+        if (waits(pend2)) { int r2 = slab_job_launch(pend2, s); pend2.nblocks = 0; if (!rc) rc = r2; }
+        return rc;
+    }
+    SlabJob* first(hipStream_t s) {      // where the launcher leaves its own slab sum instead of launching it
+        flush(s);
+        pend = SlabJob();
+        return &pend;
+    }
+    SlabJob* carry() {      // NULL: nothing to carry across, or the second slot is taken
+        if (!waits(pend) || waits(pend2)) return nullptr;
+        pend2 = SlabJob();
+        return &pend2;
+    }
+    void riders(const SlabJob*& extra, const SlabJob*& extra2) const {
+        extra = waits(pend) ? &pend : (waits(pend2) ? &pend2 : nullptr);
+        extra2 = (waits(pend) && waits(pend2)) ? &pend2 : nullptr;
+    }
+    int rode(hipStream_t s) {            // the sums `riders` handed out are in a launch on s
+        pend.nblocks = pend2.nblocks = 0;
+        if (mark) { MI3D_HIP(hipEventRecord(mark, s)); mark = nullptr; }
+        return 0;
+    }
+    int finish(hipStream_t s) {
+        MI3D_TRY(flush(s));
+        return rode(s);
+    }
+    // two marks on one launch cannot happen (one event per segment); an older mark still waiting means the segment in
+    // between launched no BatchNorm backward: complete it now
+    int set_mark(hipEvent_t ev, hipStream_t s) {
+        if (mark) MI3D_TRY(finish(s));
+        mark = ev;
+        return 0;
+    }
+};
+
+// The ONE copy of the backward's per-layer decisions (who carries the pending slab sums, deferred input gradient alone / fused
+// persistent / fused / stand-alone pair, where `first` is taken, a split-K dx left as partials): block_backward of the
+// whole-network plan and the per-operator entries mi3d_conv3_bn_backward / mi3d_conv3_backward both call it.
+struct mi3d_conv3_bn_bwd_route;        // include/mi3d.h: what was launched, for the per-operator tests
+struct ConvBnHalfBwd {
+    int Cin, Cout; Geo g;
+    int dt;                            // dtype of y / dz / dy / dx
+    bool mfma, c1;                     // the layer's route class (conv3_layer_class)
+    const void* in; int ics, idt; Halves ih;      // the layer's input
+    const void* wpd;                   // packed input-gradient image (mfma: bf16 MFMA image, otherwise the direct kernels' floats)
+    const void* y; const float* stat; const float* drop;      // saved by the forward; stat NULL: no BatchNorm, dz IS the conv's dy
+    const void* dz; int dzcs;          // gradient of the activated output; with dz_skp the reduction WRITES it (bf16 of the sums)
+    const float* dz_skp; int dz_ks;    // dz still as split-K partials [ks][M][Cout] fp32 (NULL / 0: dz is stored)
+    void* dy; int dycs;                // gradient of the conv output (written; unused without BatchNorm)
+    void* dx; int dxcs; Halves dxh;    // input gradient or NULL
+    float* dW; float* db; float* dgamma; float* dbeta; int accumulate;
+    float* bnws; float* wgws; size_t wgws_floats; float* skws;      // scratch: BatchNorm rows, weight-gradient slabs, split-K partials
+    bool allow_partials;               // a split-K dx may stay as fp32 partials [ks][M][Cin] in skws (*dx_ks says so)
+    bool deferred;                     // deferred route: the input gradient alone; the caller launches conv3_deferred_wgrad later
+    int (*after_bn)(void*); void* after_bn_arg;      // called behind the BatchNorm backward's launches (the plan's fork points) or NULL
+};
+// dx_ks (may be NULL): split factor of a dx left as partials (0 = dx was written)
+int conv3_bn_half_backward(const ConvBnHalfBwd& a, Pending& pending, hipStream_t s, int* dx_ks = nullptr,
+                           mi3d_conv3_bn_bwd_route* route = nullptr);
+// The weight gradient of a layer on the deferred route: the stand-alone kernel cut into the slabs of the layer's fused launch
+// (conv3_mfma_bwd_wg_target; dxcs = 0: the layer has no input gradient), so both routes produce the same bits
+int conv3_deferred_wgrad(const void* in, int ics, int Cin, Halves ih, const void* dy, int dycs, int Cout, Geo g, int dxcs, float* dW,
+                         float* db, int accumulate, float* ws, size_t ws_floats, hipStream_t s);
 
 // ---- MaxPool3d(2,2) ------------------------------------------------------------------------ pool.hip
 // Reference: models/unet.py:40,71.  g = INPUT geometry; odd sides floor like nn.MaxPool3d (last slice in no window).

@@ -95,6 +95,108 @@ int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_rout
     return 0;
 }
 
+int conv3_deferred_wgrad(const void* in, int ics, int Cin, Halves ih, const void* dy, int dycs, int Cout, Geo g, int dxcs, float* dW,
+                         float* db, int accumulate, float* ws, size_t ws_floats, hipStream_t s) {
+    return conv3_mfma_wgrad(in, ics, Cin, dy, dycs, Cout, g, dW, db, accumulate, ws, ws_floats, s, ih, nullptr,
+                            conv3_mfma_bwd_wg_target(Cin, Cout, ics, dycs, dxcs > 0 ? dxcs : 8, g));
+}
+
+// One half of a DoubleConv block, backward (ops.h ConvBnHalfBwd).  Every per-layer decision of the backward is made here and only
+// here, in the order of the data-gradient chain: the pending slab sums ride in the BatchNorm-backward reduction, then ONE of
+//   deferred      the input-gradient conv alone (the caller launches conv3_deferred_wgrad elsewhere, later)
+//   persistent    weight gradient + input gradient in one launch on the full-resolution bodies
+//   fused         the same on the generic tilings (16-wide or 8-wide tile; the 8-wide one may split K)
+//   stand-alone   the weight gradient (MFMA, first layer, or direct), then the input-gradient conv
+// A launch that writes the slab workspace takes pending.first (older sums are flushed before it).
+int conv3_bn_half_backward(const ConvBnHalfBwd& a, Pending& pending, hipStream_t s, int* dx_ks, mi3d_conv3_bn_bwd_route* route) {
+    const Geo g = a.g;
+    const bool wg = a.dW || a.db;
+    if (dx_ks) *dx_ks = 0;
+    MI3D_CHECK_ARG(a.stat || !a.dz_skp, "conv3_bn_half_backward: split-K partials of dz need the BatchNorm backward to finish them");
+    const void* dyb = a.stat ? a.dy : a.dz;
+    const int dycs = a.stat ? a.dycs : a.dzcs;
+    void* const dx = a.dx;
+    const int dxs = a.dxcs;
+    mi3d_conv3_bn_bwd_route r{};
+    int dgrad_ks = 1;
+    // the layer's input gradient as a launch of its own.  ksd != NULL: a split-K result may stay as partials (see below)
+    auto dgrad = [&](int* ksd) {
+        if (!a.mfma) return conv3_direct_fwd(a.dt, a.dt, dyb, dycs, a.Cout, (const float*)a.wpd, nullptr, dx, dxs, a.Cin, g, s);
+        Conv3Launch ln;
+        int rc = conv3_mfma_fwd(dyb, dycs, a.Cout, a.wpd, nullptr, dx, dxs, a.Cin, g, nullptr, (dxs % 8 == 0) ? a.skws : nullptr,
+                                s, Halves(), a.dxh, ksd, 0, CONV3_BWD_SPLITK_TARGET, nullptr, nullptr, &ln);
+        dgrad_ks = ln.ks;
+        return rc;
+    };
+    // half 1's input gradient feeds straight into half 0's BatchNorm-backward reduction, half 0's into the MaxPool3d backward of
+    // the next segment: a split-K result stays as partials and that launch finishes it (one launch less on the chain).  The launch
+    // reports its split factor in ksd (0 = dx was written as usual); the caller files it for whoever reads the partials
+    int ksd = 0;
+    int* const ksp = a.allow_partials && dx && dxs % 8 == 0 && !mi3d_routes().no_defer_tail ? &ksd : nullptr;
+    if (a.stat) {
+        const SlabJob *extra, *extra2;
+        pending.riders(extra, extra2);
+        r.riders = (extra ? 1 : 0) + (extra2 ? 1 : 0);
+        MI3D_TRY(bn_bwd(a.dt, a.dz, a.dzcs, a.y, a.Cout, a.Cout, g.M(), g.V(), a.stat, a.drop, a.dy, a.dycs, a.dgamma, a.dbeta,
+                        a.accumulate, a.bnws, s, extra, a.dz_skp, a.dz_skp ? a.dz_ks : 0, extra2));
+        MI3D_TRY(pending.rode(s));
+        r.bn = bn_small_ok(a.Cout, g.M(), 1) ? 2 : 1;
+        r.dz_ks = a.dz_skp ? a.dz_ks : 0;
+    }
+    if (a.after_bn) MI3D_TRY(a.after_bn(a.after_bn_arg));
+    auto report = [&](int conv) {
+        if (dx_ks) *dx_ks = ksd;
+        if (!route) return 0;
+        r.conv = conv;
+        r.dgrad_ks = dx ? dgrad_ks : 0;
+        r.dx_ks = ksd;
+        const SlabJob& j = pending.pend;
+        if (Pending::waits(j)) { r.slabs = j.nslab; r.slab_layout = j.layout; r.slab_ew = j.ew; r.pending = 1; }
+        *route = r;
+        return 0;
+    };
+    // a sum that no SlabJob describes (the fused launch's tail kernel, the deferred weight gradient): the same partition and layout rule
+    auto report_slabs = [&](int wg_target) {
+        const int64_t nW = (int64_t)a.Cout * a.Cin * 27, slab_sz = nW + a.Cout;
+        const SlabJob j = slab_job_make((a.dW && slab_sz >= (800 << 10)) ? 2 : 1, nullptr, conv3_mfma_wgrad_slabs(a.Cin, a.Cout, g, wg_target),
+                                        slab_sz, nW, a.dW, a.db, a.Cin, a.Cout, a.accumulate);
+        r.slabs = j.nslab; r.slab_layout = j.layout; r.slab_ew = j.ew;
+    };
+    if (a.deferred) {
+        // the chain runs the input-gradient conv alone; the weight gradient goes to the aux stream.  Its slab partition is the fused
+        // launch's (conv3_deferred_wgrad), the input gradient uses the fused launch's split-K factor and the same K order: both routes
+        // produce the same bits
+        MI3D_CHECK_ARG(a.mfma && wg, "conv3_bn_half_backward: only MFMA layers with a weight gradient can defer it");
+        if (dx) MI3D_TRY(dgrad(ksp));
+        report_slabs(conv3_mfma_bwd_wg_target(a.Cin, a.Cout, a.ics, dycs, dx ? dxs : 8, g));
+        return report(6);
+    }
+    if (a.mfma && dx && wg && conv3_mfma_bwd_fused_persist_ok(a.Cin, a.Cout, a.ics, dycs, g)) {
+        MI3D_TRY(conv3_mfma_bwd_fused_persist(a.in, a.ics, a.Cin, dyb, dycs, a.Cout, a.wpd, dx, dxs, g, a.dW, a.db, a.accumulate,
+                                              a.wgws, a.wgws_floats, s, a.ih, a.dxh, pending.first(s)));
+        return report(2);
+    }
+    if (a.mfma && dx && wg && !a.ih.on() && !a.dxh.on() && conv3_mfma_bwd_fused_ok(a.Cin, a.Cout, a.ics, dycs, dxs, g)) {
+        MI3D_TRY(conv3_mfma_bwd_fused(a.in, a.ics, a.Cin, dyb, dycs, a.Cout, a.wpd, dx, dxs, g, a.dW, a.db, a.accumulate, a.wgws,
+                                      a.wgws_floats, a.skws, s, pending.first(s), ksp));
+        dgrad_ks = conv3_mfma_bwd_ksplit(a.Cin, a.Cout, g);
+        if (!Pending::waits(pending.pend)) report_slabs(conv3_mfma_bwd_wg_target(a.Cin, a.Cout, a.ics, dycs, dxs, g));
+        return report(conv3_mfma_big_geo(g) ? 3 : 4);
+    }
+    if (wg) {
+        SlabJob* ps = pending.first(s);
+        if (a.mfma)
+            MI3D_TRY(conv3_mfma_wgrad(a.in, a.ics, a.Cin, dyb, dycs, a.Cout, g, a.dW, a.db, a.accumulate, a.wgws, a.wgws_floats, s, a.ih, ps));
+        else if (a.c1)
+            MI3D_TRY(conv3_mfma_wgrad_c1((const float*)a.in, dyb, dycs, a.Cout, g, a.dW, a.db, a.accumulate, a.wgws, a.wgws_floats, s, ps));
+        else
+            MI3D_TRY(conv3_direct_wgrad(a.idt, a.dt, a.in, a.ics, a.Cin, dyb, dycs, a.Cout, g, a.dW, a.db, a.accumulate, a.wgws,
+                                        a.wgws_floats, s));
+    }
+    if (dx) MI3D_TRY(dgrad(nullptr));
+    return report(a.mfma ? 5 : a.c1 ? 1 : 0);
+}
+
 namespace {
 
 constexpr int MAXL = MI3D_MAX_LEVELS;
@@ -292,57 +394,6 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
     return 0;
 }
 
-// The weight-gradient slab sums that wait for a launch to ride in.  A launcher that is handed a slot leaves its final slab sum
-// there instead of launching it (nblocks > 0: a sum waits).  The rule, once:
-//   * a launch that writes the first slab workspace (wgws) takes `first`: older sums read their workspaces before it, with
-//     launches of their own;
-//   * the transposed conv's backward may take `carry` instead while the decoder conv's sum waits: it writes the SECOND
-//     workspace (wgws2) and both sums stay;
-//   * the next BatchNorm-backward reduction carries up to two (`riders`, then `rode` behind that launch);
-//   * an exchange mark is recorded behind the launch that carried its segment's sums (`rode`), or behind a flush when the
-//     segment launched no BatchNorm backward / the call ends (`finish`).
-struct Pending {
-    SlabJob pend, pend2;
-    hipEvent_t mark = nullptr;      // exchange mark waiting for the launch that completes its segment's gradients
-    static bool waits(const SlabJob& j) { return j.nblocks > 0; }
-    int flush(hipStream_t s) {
-        int rc = 0;
-        if (waits(pend)) { rc = slab_job_launch(pend, s); pend.nblocks = 0; }
-        if (waits(pend2)) { int r2 = slab_job_launch(pend2, s); pend2.nblocks = 0; if (!rc) rc = r2; }
-        return rc;
-    }
-    SlabJob* first(hipStream_t s) {      // where the launcher leaves its own slab sum instead of launching it
-        flush(s);
-        pend = SlabJob();
-        return &pend;
-    }
-    SlabJob* carry() {      // NULL: nothing to carry across, or the second slot is taken
-        if (!waits(pend) || waits(pend2)) return nullptr;
-        pend2 = SlabJob();
-        return &pend2;
-    }
-    void riders(const SlabJob*& extra, const SlabJob*& extra2) const {
-        extra = waits(pend) ? &pend : (waits(pend2) ? &pend2 : nullptr);
-        extra2 = (waits(pend) && waits(pend2)) ? &pend2 : nullptr;
-    }
-    int rode(hipStream_t s) {            // the sums `riders` handed out are in a launch on s
-        pend.nblocks = pend2.nblocks = 0;
-        if (mark) { MI3D_HIP(hipEventRecord(mark, s)); mark = nullptr; }
-        return 0;
-    }
-    int finish(hipStream_t s) {
-        MI3D_TRY(flush(s));
-        return rode(s);
-    }
-    // two marks on one launch cannot happen (one event per segment); an older mark still waiting means the segment in
-    // between launched no BatchNorm backward: complete it now
-    int set_mark(hipEvent_t ev, hipStream_t s) {
-        if (mark) MI3D_TRY(finish(s));
-        mark = ev;
-        return 0;
-    }
-};
-
 // the state of one C call
 struct Ctx {
     const Plan& p;
@@ -354,13 +405,13 @@ struct Ctx {
     hipStream_t s2 = nullptr;
     hipEvent_t* ev = nullptr;
     int seq = 0;
-    struct DJob { int b, h, wg_target; };
+    struct DJob { int b, h, dxcs; };      // dxcs = 0: the layer has no input gradient
     DJob dq[4 * MAXL + 2];             // weight gradients whose dy is ready and that have not been forked yet
     // forked (their event is recorded on the chain) but not yet ENQUEUED on the aux stream: the host enqueues them a few at a
     // time between the chain's next launches (drain_aux).  A step is launched by ONE host thread, and at the end of the
     // launch-bound deep-level chain it is barely ahead of the GPU: enqueueing the ten deep-level weight gradients and their slab
     // sums in one go left the chain's queue empty for ~125 us (profiles/r04_defer_eager_streams_before.txt)
-    struct HJob { int b, h, wg_target, ev; };
+    struct HJob { int b, h, dxcs, ev; };
     HJob hq[4 * MAXL + 2];
     int nhq = 0, hq_head = 0, waited_ev = -1;
     int ndq = 0, nfork = 0;
@@ -451,8 +502,8 @@ int drain_aux(Ctx& c, const float* x, void* const* grads, int accumulate, int n)
         if (j.ev != c.waited_ev) { MI3D_HIP(hipStreamWaitEvent(c.s2, c.ev[j.ev % 3], 0)); c.waited_ev = j.ev; }
         const LayerIO v = layer_io(c, j.b, j.h, x);
         const HalfP& H = v.H;
-        MI3D_TRY(conv3_mfma_wgrad(v.in, v.ics, H.Cin, c.at(H.dyk), H.Cout, H.Cout, v.g, (float*)grads[H.pidx], (float*)grads[H.pidx + 1],
-                                  accumulate, c.at<float>(p.wgws3), p.wgws_floats, c.s2, v.ih, nullptr, j.wg_target));
+        MI3D_TRY(conv3_deferred_wgrad(v.in, v.ics, H.Cin, v.ih, c.at(H.dyk), H.Cout, H.Cout, v.g, j.dxcs, (float*)grads[H.pidx],
+                                      (float*)grads[H.pidx + 1], accumulate, c.at<float>(p.wgws3), p.wgws_floats, c.s2));
         c.aux_used = true;
     }
     if (c.hq_head == c.nhq) c.hq_head = c.nhq = 0;
@@ -466,13 +517,32 @@ int flush_deferred(Ctx& c, const float* x, void* const* grads, int accumulate, b
     MI3D_CHECK_ARG(c.nfork < 3, "flush_deferred: more than three forks in one call");
     const int e = c.nfork++;
     MI3D_HIP(hipEventRecord(c.ev[e % 3], c.s));
-    for (int q = 0; q < c.ndq; q++) c.hq[c.nhq++] = Ctx::HJob{c.dq[q].b, c.dq[q].h, c.dq[q].wg_target, e};
+    for (int q = 0; q < c.ndq; q++) c.hq[c.nhq++] = Ctx::HJob{c.dq[q].b, c.dq[q].h, c.dq[q].dxcs, e};
     c.ndq = 0;
     if (!lazy) MI3D_TRY(drain_aux(c, x, grads, accumulate, -1));
     return 0;
 }
 
-// backward of block b given dz2 (dtype T, stride dzcs); writes dxin (may be NULL) with stride dxcs
+// backward of block b given dz2 (dtype T, stride dzcs); writes dxin (may be NULL) with stride dxcs.  The per-layer decisions are
+// conv3_bn_half_backward's; what stays here is the aux stream: the queue of deferred weight gradients and the fork points
+struct ForkAt { Ctx* c; int b, h; const float* x; void* const* grads; int accumulate; bool dfr; int dxcs; };
+int fork_after_bn(void* arg) {
+    const ForkAt& f = *(const ForkAt*)arg;
+    Ctx& c = *f.c;
+    const Plan& p = c.p;
+    // deferred weight gradient: queued for the aux stream (conv3_deferred_wgrad, drain_aux)
+    if (f.dfr) c.dq[c.ndq++] = Ctx::DJob{f.b, f.h, f.dxcs};
+    // fork points: what is queued goes to the aux stream when the chain has finished the last layer of a group (its BatchNorm
+    // backward).  Group 1 forks when the GPU is still busy with the full-resolution decoder (the host is far ahead: enqueue at
+    // once); group 2 forks at the end of the launch-bound deep chain: its launches are fed in between the chain's next ones.
+    // (Measured and dropped, profiles/r04_experiments_aux_wgrad.txt and the fork-placement record beside it: one fork per layer +26 ... +43 us,
+    // per deep layer only +6 us, the decoder fork one block later -1 us, another workgroup count for the aux kernels +10 ... +40 us,
+    // deferring only some of the three groups 13 ... 102 us)
+    if (c.s2 != nullptr && c.ev != nullptr)
+        for (int q = 0; q < 2; q++)
+            if (f.b == p.flush_b[q] && f.h == p.flush_h[q]) MI3D_TRY(flush_deferred(c, f.x, f.grads, f.accumulate, q == 1));
+    return 0;
+}
 int block_backward(Ctx& c, int b, const float* x, void* const* grads, const float* drop, const void* dz2,
                    int dzcs, void* dxin, int dxcs, int accumulate) {
     const Plan& p = c.p;
@@ -484,83 +554,26 @@ int block_backward(Ctx& c, int b, const float* x, void* const* grads, const floa
     for (int h = 1; h >= 0; h--) {
         const LayerIO v = layer_io(c, b, h, x);
         const HalfP& H = v.H;
-        const Geo g = v.g;
         int k = c.seq++;
         if (aux && c.nhq) MI3D_TRY(drain_aux(c, x, grads, accumulate, 3));      // feed the aux stream between the chain's launches
         const bool wg = G(H.pidx) || G(H.pidx + 1);
         // deferred weight gradient: dy goes to the layer's own buffer, which nobody overwrites before the aux stream has read it
         const bool dfr = aux && H.defer && wg;
-        void* dyb = dfr ? c.at(H.dyk) : c.at((k & 1) ? p.sB2 : p.sB);
-        const void* dz = h == 1 ? dz2 : c.at(p.sC);
-        int dcs = h == 1 ? dzcs : H.Cout;
         void* dx = h == 1 ? c.at(p.sC) : dxin;
-        int dxs = h == 1 ? H.Cin : dxcs;
-        // the layer's input gradient as a launch of its own.  ksd != NULL: a split-K result may stay as partials (see below)
-        auto dgrad = [&](int* ksd) {
-            if (!H.mfma) return conv3_direct_fwd(p.dt, p.dt, dyb, H.Cout, H.Cout, c.at<float>(H.wpd), nullptr, dx, dxs, H.Cin, g, c.s);
-            return conv3_mfma_fwd(dyb, H.Cout, H.Cout, c.at(H.wpd), nullptr, dx, dxs, H.Cin, g, nullptr, (dxs % 8 == 0) ? skws : nullptr,
-                                  c.s, Halves(), v.ih, ksd, 0, CONV3_BWD_SPLITK_TARGET);
-        };
+        const int dxs = h == 1 ? H.Cin : dxcs;
+        ForkAt f{&c, b, h, x, grads, accumulate, dfr, dx ? dxs : 0};
         // half 1's input gradient feeds straight into half 0's BatchNorm-backward reduction, half 0's into the MaxPool3d backward of
-        // the next segment (pool_defer): a split-K result stays as partials and that launch finishes it (one launch less on the
-        // chain).  The launch reports its split factor in ksd (0 = dx was written as usual), filed for whoever reads the partials
+        // the next segment (pool_defer): a split-K result may stay as partials, filed here for whoever reads them
+        ConvBnHalfBwd a{H.Cin, H.Cout, v.g, p.dt, H.mfma, H.c1, v.in, v.ics, v.idt, v.ih, c.at(H.wpd),
+                        c.at(H.y), c.at<float>(H.stat), drop ? drop + H.drop_off : nullptr,
+                        h == 1 ? dz2 : c.at(p.sC), h == 1 ? dzcs : H.Cout, h == 0 ? dz_skp : nullptr, h == 0 ? dz_ks : 0,
+                        dfr ? c.at(H.dyk) : c.at((k & 1) ? p.sB2 : p.sB), H.Cout, dx, dxs, v.ih,
+                        G(H.pidx), G(H.pidx + 1), G(H.pidx + 2), G(H.pidx + 3), accumulate,
+                        c.at<float>(p.bnws), c.at<float>(p.wgws), p.wgws_floats, skws, h == 1 || c.pool_defer, dfr, fork_after_bn, &f};
         int ksd = 0;
-        int* const ksp = (h == 1 || c.pool_defer) && dxs % 8 == 0 && !mi3d_routes().no_defer_tail ? &ksd : nullptr;
-        auto file_partials = [&] {
-            if (ksd > 0 && h == 1) { dz_skp = skws; dz_ks = ksd; }
-            if (ksd > 0 && h == 0) c.pool_ks = ksd;
-        };
-        const SlabJob *extra, *extra2;
-        c.pending.riders(extra, extra2);
-        MI3D_TRY(bn_bwd(p.dt, dz, dcs, c.at(H.y), H.Cout, H.Cout, g.M(), g.V(), c.at<float>(H.stat),
-                        drop ? drop + H.drop_off : nullptr, dyb, H.Cout, G(H.pidx + 2), G(H.pidx + 3), accumulate,
-                        c.at<float>(p.bnws), c.s, extra, h == 0 ? dz_skp : nullptr, h == 0 ? dz_ks : 0, extra2));
-        MI3D_TRY(c.pending.rode(c.s));
-        if (dfr) {
-            // the chain runs the input-gradient conv alone; the weight gradient is queued for the aux stream.  Its slab partition
-            // is the fused launch's (conv3_mfma_bwd_wg_target), the input gradient uses the fused launch's split-K factor and the
-            // same K order: both routes produce the same bits
-            c.dq[c.ndq++] = Ctx::DJob{b, h, conv3_mfma_bwd_wg_target(H.Cin, H.Cout, v.ics, H.Cout, dx ? dxs : 8, g)};
-        }
-        // fork points: what is queued goes to the aux stream when the chain has finished the last layer of a group (its BatchNorm
-        // backward).  Group 1 forks when the GPU is still busy with the full-resolution decoder (the host is far ahead: enqueue at
-        // once); group 2 forks at the end of the launch-bound deep chain: its launches are fed in between the chain's next ones.
-        // (Measured and dropped, profiles/r04_experiments_aux_wgrad.txt and the fork-placement record beside it: one fork per layer +26 ... +43 us,
-        // per deep layer only +6 us, the decoder fork one block later -1 us, another workgroup count for the aux kernels +10 ... +40 us,
-        // deferring only some of the three groups 13 ... 102 us)
-        if (aux)
-            for (int q = 0; q < 2; q++)
-                if (b == p.flush_b[q] && h == p.flush_h[q]) MI3D_TRY(flush_deferred(c, x, grads, accumulate, q == 1));
-        if (dfr) {
-            if (dx) { MI3D_TRY(dgrad(ksp)); file_partials(); }
-            continue;
-        }
-        if (H.mfma && dx && wg && conv3_mfma_bwd_fused_persist_ok(H.Cin, H.Cout, v.ics, H.Cout, g)) {
-            MI3D_TRY(conv3_mfma_bwd_fused_persist(v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx, dxs, g, G(H.pidx),
-                                                  G(H.pidx + 1), accumulate, c.at<float>(p.wgws), p.wgws_floats, c.s, v.ih, v.ih,
-                                                  c.pending.first(c.s)));
-            continue;
-        }
-        if (H.mfma && dx && wg && !v.ih.on() && conv3_mfma_bwd_fused_ok(H.Cin, H.Cout, v.ics, H.Cout, dxs, g)) {
-            MI3D_TRY(conv3_mfma_bwd_fused(v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, c.at(H.wpd), dx, dxs, g, G(H.pidx), G(H.pidx + 1),
-                                          accumulate, c.at<float>(p.wgws), p.wgws_floats, skws, c.s, c.pending.first(c.s), ksp));
-            file_partials();
-            continue;
-        }
-        if (wg) {
-            float* wgws = c.at<float>(p.wgws);
-            SlabJob* ps = c.pending.first(c.s);
-            if (H.mfma)
-                MI3D_TRY(conv3_mfma_wgrad(v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
-                                          wgws, p.wgws_floats, c.s, v.ih, ps));
-            else if (H.c1)
-                MI3D_TRY(conv3_mfma_wgrad_c1((const float*)v.in, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1), accumulate,
-                                             wgws, p.wgws_floats, c.s, ps));
-            else
-                MI3D_TRY(conv3_direct_wgrad(v.idt, p.dt, v.in, v.ics, H.Cin, dyb, H.Cout, H.Cout, g, G(H.pidx), G(H.pidx + 1),
-                                            accumulate, wgws, p.wgws_floats, c.s));
-        }
-        if (dx) MI3D_TRY(dgrad(nullptr));
+        MI3D_TRY(conv3_bn_half_backward(a, c.pending, c.s, &ksd));
+        if (ksd > 0 && h == 1) { dz_skp = skws; dz_ks = ksd; }
+        if (ksd > 0 && h == 0) c.pool_ks = ksd;
     }
     return 0;
 }
@@ -645,7 +658,7 @@ int up_forward(Ctx& c, int i) {
 
 extern "C" {
 
-int mi3d_abi_version(void) { return 6; }
+int mi3d_abi_version(void) { return 7; }
 
 int mi3d_unet_num_params(const mi3d_unet_desc* d) { return d ? 8 * (2 * d->n_levels + 1) + 2 * d->n_levels + 2 : -1; }
 int mi3d_unet_num_buffers(const mi3d_unet_desc* d) { return d ? 6 * (2 * d->n_levels + 1) : -1; }

@@ -686,13 +686,13 @@ def test_conv3_backward_kernels_of_the_step_exact(orc, shape):
     gotx = dx.float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(gotx - rgx).max() <= np.abs(rgx).max() * 2 ** -8 + 1e-6
     assert_bf16_rne_bits(dx, rgx, "dx")      # exact fp32 partial sums (tests/test_conv_ref_cpu.py): the stored value is bf16_rne(exact)
-    np.testing.assert_allclose(dW.cpu().numpy(), rgw, rtol=0, atol=1e-5)
-    np.testing.assert_allclose(db.cpu().numpy(), rgb, rtol=0, atol=1e-5)
+    np.testing.assert_array_equal(dW.cpu().numpy(), rgw)          # EXACT: equality, no tolerance
+    np.testing.assert_array_equal(db.cpu().numpy(), rgb)
     # accumulate=1 adds onto what is there
     call("mi3d_conv3_backward", 1, 1, ptr(xcl), cin, cin, ptr(wd), ptr(gcl), cout, cout, ptr(dx), cin, ptr(dW), ptr(db), 1,
          n, d, h, w, ptr(ws), wsb, None)
-    np.testing.assert_allclose(dW.cpu().numpy(), 2 * rgw, rtol=0, atol=2e-5)
-    np.testing.assert_allclose(db.cpu().numpy(), 2 * rgb, rtol=0, atol=2e-5)
+    np.testing.assert_array_equal(dW.cpu().numpy(), 2 * rgw)
+    np.testing.assert_array_equal(db.cpu().numpy(), 2 * rgb)
 
 
 def test_conv3_fused_persist_16to32_exact():
@@ -721,8 +721,8 @@ def test_conv3_fused_persist_16to32_exact():
     gotx = dx.float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(gotx - rgx).max() <= np.abs(rgx).max() * 2 ** -8 + 1e-6
     assert_bf16_rne_bits(dx, rgx, "dx")      # exact fp32 partial sums (tests/test_conv_ref_cpu.py): the stored value is bf16_rne(exact)
-    np.testing.assert_allclose(dW.cpu().numpy(), wt_.grad.numpy(), rtol=0, atol=1e-4)
-    np.testing.assert_allclose(db.cpu().numpy(), gy.sum((0, 2, 3, 4), dtype=np.float64), rtol=0, atol=1e-4)
+    np.testing.assert_array_equal(dW.cpu().numpy().astype(np.float64), wt_.grad.numpy())          # EXACT: equality, no tolerance
+    np.testing.assert_array_equal(db.cpu().numpy().astype(np.float64), gy.sum((0, 2, 3, 4), dtype=np.float64))
 
 
 @pytest.mark.parametrize("shape", [(2, 32, 16, 3, 5, 7), (1, 64, 32, 4, 4, 6), (2, 256, 128, 6, 6, 6), (2, 128, 64, 12, 12, 12),
@@ -749,8 +749,8 @@ def test_upconv_backward_exact(orc, shape):
     gotx = dx.float().cpu().numpy().transpose(0, 4, 1, 2, 3)
     assert np.abs(gotx - rgx).max() <= np.abs(rgx).max() * 2 ** -8 + 1e-6
     assert_bf16_rne_bits(dx, rgx, "dx")      # exact fp32 partial sums (tests/test_conv_ref_cpu.py): the stored value is bf16_rne(exact)
-    np.testing.assert_allclose(dW.cpu().numpy(), rgw, rtol=0, atol=1e-5)
-    np.testing.assert_allclose(db.cpu().numpy(), rgb, rtol=0, atol=1e-5)
+    np.testing.assert_array_equal(dW.cpu().numpy(), rgw)          # EXACT: equality, no tolerance
+    np.testing.assert_array_equal(db.cpu().numpy(), rgb)
 
 
 def test_fused_backward_route_is_exactly_the_unfused_one_at_scale(routes):

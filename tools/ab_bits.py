@@ -160,6 +160,41 @@ def battery():
         for c in (5, 8):
             bn_ops(f"bn/dt={dt}/C={c}/eval", dt, c, (3, 5, 7), False, training=0)
 
+    # one half of a DoubleConv block backward as the plan runs it (mi3d_conv3_bn_backward), with its hand-overs: layer A (64 -> 32,
+    # fused launch, split-K dx) leaves its dx as partials and its slab sum pending; layer B (32 -> 64 at the same volume) finishes the
+    # partials in its BatchNorm-backward reduction, which also carries A's sum; then B again on the deferred route
+    def conv_bn_bwd(tag, n, d, h, w):
+        rng = np.random.default_rng(n + d + h + w)
+        ca, cb = 64, 32                                                      # A: ca -> cb, B: cb -> ca
+        m = n * d * h * w
+        xa, xb = rnd(rng, (n, d, h, w, ca), dt=bf), rnd(rng, (n, d, h, w, cb), dt=bf)
+        wa, wb = rnd(rng, (cb, ca, 3, 3, 3), 0.1), rnd(rng, (ca, cb, 3, 3, 3), 0.1)
+        dya, yb = rnd(rng, (n, d, h, w, cb), dt=bf), rnd(rng, (n, d, h, w, ca), dt=bf)
+        stat = torch.cat([rnd(rng, (ca,), 0.2), rnd(rng, (ca,), 0.2).abs() + 0.8, rnd(rng, (ca,), 0.3) + 1.0, rnd(rng, (ca,), 0.3)])
+        drop = torch.from_numpy((rng.random((n, ca)) >= 0.5).astype(np.float32) * 2.0).to(dev)
+        wsa = torch.zeros(lib.mi3d_conv3_bn_bwd_workspace_bytes(1, 1, ca, cb, n, d, h, w), dtype=torch.uint8, device=dev)
+        wsb = torch.zeros(lib.mi3d_conv3_bn_bwd_workspace_bytes(1, 1, cb, ca, n, d, h, w), dtype=torch.uint8, device=dev)
+        dxa, dWa, dba = torch.zeros_like(xa), torch.zeros_like(wa), torch.zeros(cb, device=dev)
+        ra, pend = _lib.Conv3BnBwdRoute(), (_lib.PendingSum * 2)()
+        call("mi3d_conv3_bn_backward", 1, 1, ptr(xa), ca, 0, 0, ca, ptr(wa), None, None, None, ptr(dya), cb, None, 0, None, ptr(dxa), ca, 0, 0,
+             ptr(dWa), ptr(dba), None, None, 0, None, pend, _lib.CONV3_BN_BWD_ALLOW_PARTIALS | _lib.CONV3_BN_BWD_LEAVE_PENDING,
+             C.byref(ra), cb, n, d, h, w, ptr(wsa), wsa.numel(), None)
+        assert ra.dx_ks > 1 and ra.pending == 1, (ra.dx_ks, ra.pending)
+        for flags in (0, _lib.CONV3_BN_BWD_DEFER):
+            dz, dyb, dxb = torch.zeros_like(yb), torch.zeros_like(yb), torch.zeros_like(xb)
+            dWb, dbb, dg, dbeta = torch.zeros_like(wb), torch.zeros(ca, device=dev), torch.zeros(ca, device=dev), torch.zeros(ca, device=dev)
+            call("mi3d_conv3_bn_backward", 1, 1, ptr(xb), cb, 0, 0, cb, ptr(wb), ptr(yb), ptr(stat), ptr(drop), ptr(dz), ca,
+                 wsa.data_ptr() + ra.dx_offset, ra.dx_ks, ptr(dyb), ptr(dxb), cb, 0, 0, ptr(dWb), ptr(dbb), ptr(dg), ptr(dbeta), 0,
+                 pend if flags == 0 else None, None, flags, None, ca, n, d, h, w, ptr(wsb), wsb.numel(), None)
+            for k, t in (("dz", dz), ("dy", dyb), ("dx", dxb), ("dW", dWb), ("db", dbb), ("dgamma", dg), ("dbeta", dbeta)):
+                put(f"{tag}/B/flags={flags}/{k}", t)
+        for k, t in (("dW", dWa), ("db", dba)):
+            put(f"{tag}/A/{k}", t)
+
+    if "mi3d_conv3_bn_backward" in _lib._SIGS:
+        for s in [(2, 5, 9, 12), (1, 6, 6, 6)]:
+            conv_bn_bwd(f"conv_bn_bwd{s}", *s)
+
     # whole network, eager: three steps at 32^3 (N = 2), one at 96^3 (N = 1); bf16, dropout 0.3
     for size, n, steps in ((32, 2, 3), (96, 1, 1)):
         torch.manual_seed(11)
@@ -228,8 +263,11 @@ def main():
     a, b = res
     for k in a:
         print(f"{'==' if a[k] == b.get(k) else '!='} {a[k][:16]} {str(b.get(k))[:16]} {k}")
-    diff = [k for k in a if a[k] != b.get(k)] + [k for k in b if k not in a]
-    print(f"{len(a)} buffers, {len(diff)} differ" + (f"; first: {diff[0]}" if diff else f": {sys.argv[1]} and {sys.argv[2]} agree bit for bit"))
+    only_b = [k for k in b if k not in a]          # sections of entries the first build does not have: nothing to compare with
+    for k in only_b:
+        print(f"++ {'':16} {b[k][:16]} {k}")
+    diff = [k for k in a if a[k] != b.get(k)]
+    print(f"{len(a)} buffers, {len(diff)} differ, {len(only_b)} only in the second build" + (f"; first: {diff[0]}" if diff else f": {sys.argv[1]} and {sys.argv[2]} agree bit for bit"))
     return 1 if diff else 0
 
 
