@@ -524,6 +524,44 @@ int mi3d_upconv2_forward(int dtype, const void* x, int xcs, int Cin, const float
 int mi3d_upconv2_backward(int dtype, const void* x, int xcs, int Cin, const float* w, const void* gy, int gycs, int Cout,
                           void* dx, int dxcs, float* dW, float* db, int accumulate, int N, int D, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* One decoder up step as the whole-network plan runs it (the plan and these entries call ONE function pair): ConvTranspose3d(k2,s2)
+ * of x (N,D,H,W,Cin) into the up half of a concat buffer, given as a pointer `up` and a channel stride `ucs` (interleaved halves:
+ * cat + Cout with ucs = 2 Cout; planar halves: ucs = Cout), whose geometry is (Do,Ho,Wo).  Where (Do,Ho,Wo) is not (2D,2H,2W) the
+ * transposed conv writes a temporary in the workspace and F.interpolate(mode="nearest") resizes it into the half (unet.py:81-83).
+ * mi3d_up_backward is the adjoint: gup is the gradient of that half; dx, dW, db may each be NULL.
+ * flags
+ *   MI3D_UP_BWD_LEAVE_PENDING      the MFMA route's slab sum is NOT launched but returned in pending_out (launch it with
+ *                                  mi3d_pending_sum_launch or hand it to mi3d_conv3_bn_backward as a rider)
+ *   MI3D_UP_BWD_SECOND_WORKSPACE   the slabs go to the second slab region of the workspace, as in the plan while the decoder conv's
+ *                                  sum waits in the first (the plan's carry)
+ * route_out (may be NULL) reports what was launched; fields that do not apply are 0:
+ *   forward    kind 0 direct fp32-FMA / 1 MFMA;  gy  grid size over output-channel blocks;  tap_split  1 = the 8 taps are spread over
+ *              workgroups;  wide  1 = 16-byte stores of x-neighbour pairs;  strided  1 = some workgroup takes more than one round of
+ *              voxel groups;  resized  1 = temporary + nearest resize
+ *   backward   kind 0 direct / 1 fused launch / 2 stand-alone pair / 3 dx only / 4 weights only;  ksplit  1 = K-split input
+ *              gradient;  persistent  1 = the input-gradient workgroups take more than one round;  slabs, slab_ew  weight-gradient
+ *              slabs summed and elements per block of the sum;  wgrad_blocks, dgrad_blocks  workgroups of each kind;
+ *              pending  1 = the sum was left in pending_out;  resized  1 = the resize adjoint ran first
+ * workspace: mi3d_up_workspace_bytes, 256-byte aligned; mi3d_up_workspace_region(..., which, &bytes) returns the byte offset of
+ * region which = 0 packed weights, 1 temporary, 2 first slab region, 3 second slab region. */
+typedef struct mi3d_up_route {
+    int32_t kind, gy, tap_split, wide, strided, resized, ksplit, persistent, slabs, slab_ew, wgrad_blocks, dgrad_blocks, pending;
+} mi3d_up_route;
+enum { MI3D_UP_BWD_LEAVE_PENDING = 1, MI3D_UP_BWD_SECOND_WORKSPACE = 2 };
+size_t mi3d_up_workspace_bytes(int dtype, int Cin, int Cout, int N, int D, int H, int W);
+size_t mi3d_up_workspace_region(int dtype, int Cin, int Cout, int N, int D, int H, int W, int which, size_t* bytes_out);
+int mi3d_up_forward(int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias, void* up, int ucs, int Cout,
+                    int N, int D, int H, int W, int Do, int Ho, int Wo, mi3d_up_route* route_out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int mi3d_up_backward(int dtype, const void* x, int xcs, int Cin, const float* w, const void* gup, int gucs, int Cout, void* dx,
+                     int dxcs, float* dW, float* db, int accumulate, int N, int D, int H, int W, int Do, int Ho, int Wo, int flags,
+                     mi3d_pending_sum* pending_out, mi3d_up_route* route_out, void* workspace, size_t workspace_bytes, void* stream);
+/* F.interpolate(x, size=(Do,Ho,Wo), mode="nearest") on channels-last tensors, any in / out sides >= 1, and its adjoint (gx[src] =
+ * the sum, ascending in (d,h,w), of gy over every destination voxel that reads src; deterministic) */
+int mi3d_nearest_resize_forward(int dtype, const void* x, int xcs, int C, int N, int Di, int Hi, int Wi, void* y, int ycs, int Do,
+                                int Ho, int Wo, void* stream);
+int mi3d_nearest_resize_backward(int dtype, const void* gy, int gycs, int C, int N, int Do, int Ho, int Wo, void* gx, int gxcs,
+                                 int Di, int Hi, int Wi, void* stream);
 /* final nn.Conv3d(C0, n_classes, 1) unet.py:62,87.  z: channels-last `dtype` [N][V][Cin] (stride zcs); w (Cout,Cin,1,1,1) float;
  * logits / dlogits: NCDHW float (the API layout).  backward: dz (channels-last, stride dzcs), dW (Cout,Cin), db (Cout) float;
  * workspace: mi3d_conv1_workspace_bytes.  The bf16 path runs the MFMA kernels of the training step. */

@@ -65,6 +65,14 @@ class PendingSum(C.Structure):                     # mi3d_pending_sum: opaque, p
 
 CONV3_BN_BWD_ALLOW_PARTIALS, CONV3_BN_BWD_DEFER, CONV3_BN_BWD_LEAVE_PENDING = 1, 2, 4
 
+
+class UpRoute(C.Structure):                        # mi3d_up_route
+    _fields_ = [(k, C.c_int32) for k in ("kind", "gy", "tap_split", "wide", "strided", "resized", "ksplit", "persistent", "slabs",
+                                         "slab_ew", "wgrad_blocks", "dgrad_blocks", "pending")]
+
+
+UP_BWD_LEAVE_PENDING, UP_BWD_SECOND_WORKSPACE = 1, 2
+
 _DP, _LP, _AP, _MP = C.POINTER(UNetDesc), C.POINTER(LossCfg), C.POINTER(AugParams), C.POINTER(MaskList)
 
 # name -> (restype, argtypes); one line per symbol declared in include/mi3d.h
@@ -164,6 +172,13 @@ _SIGS = {
     "mi3d_upconv2_forward": (i32, [i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "mi3d_upconv2_backward": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp,
                                     sz, vp]),
+    "mi3d_up_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "mi3d_up_workspace_region": (sz, [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(sz)]),
+    "mi3d_up_forward": (i32, [i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(UpRoute), vp, sz, vp]),
+    "mi3d_up_backward": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                               C.POINTER(PendingSum), C.POINTER(UpRoute), vp, sz, vp]),
+    "mi3d_nearest_resize_forward": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp]),
+    "mi3d_nearest_resize_backward": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp]),
     "mi3d_ncdhw_to_ndhwc": (i32, [i32, vp, vp, i32, i32, i32, i64, vp]),
     "mi3d_ndhwc_to_ncdhw": (i32, [i32, vp, i32, vp, i32, i32, i64, vp]),
     "mi3d_graph_begin": (i32, [vp]),

@@ -459,24 +459,53 @@ int mi3d_maxpool2_backward_partials(int dtype, const float* dp_partials, int ks,
     // the kernels read dp only without partials; its stride still takes part in the choice of kernel (the plan passes the pooled tensor's C)
     return maxpool2_bwd(dtype, dp_partials, C, z, zcs, dskip, dskipcs, dz, dzcs, C, Geo{N, D, H, W}, (hipStream_t)stream, dp_partials, ks);
 }
-size_t mi3d_upconv2_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W) {
-    Geo g{N, D, H, W};
+}  // extern "C"
+
+// mi3d_up_forward / mi3d_up_backward: the route class of a decoder up step and its scratch areas in a workspace of its own
+namespace {
+struct UpWs { size_t wp, wp_bytes, tmp, tmp_bytes, wgws, wgws2, wg_floats, total; };
+size_t up_wg_floats(int Cin, int Cout, Geo g) {
     size_t wsf = upconv2_bwd_ws_floats(Cin, Cout, g);
     if (upconv2_mfma_supported(Cin, Cout, 8, 8) && upconv2_mfma_bwd_ws_floats(Cin, Cout, g) > wsf) wsf = upconv2_mfma_bwd_ws_floats(Cin, Cout, g);
-    return (upconv2_pack_floats(Cin, Cout) + wsf) * sizeof(float);
+    return wsf;
 }
+UpWs up_ws(int dtype, int Cin, int Cout, Geo g) {
+    UpWs L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    L.wp_bytes = upconv2_pack_floats(Cin, Cout) * sizeof(float);       // >= the MFMA images (2 * Cin * Cout * 8 bf16)
+    L.wp = take(L.wp_bytes);
+    L.tmp_bytes = (size_t)g.M() * 8 * Cout * (dtype == MI3D_BF16 ? 2 : 4);
+    L.tmp = take(L.tmp_bytes);
+    L.wg_floats = up_wg_floats(Cin, Cout, g);
+    L.wgws = take(L.wg_floats * sizeof(float));
+    L.wgws2 = take(L.wg_floats * sizeof(float));
+    L.total = off;
+    return L;
+}
+// the direct kernels' two weight images inside the packed-weights area
+inline float* up_wpb(void* wp, int Cin, int Cout) { return (float*)wp + (size_t)cdiv(Cout, 8) * Cin * 64; }
+inline bool up_args_ok(int dtype, int Cin, int Cout, int N, int D, int H, int W, int Do, int Ho, int Wo) {
+    return (dtype == MI3D_F32 || dtype == MI3D_BF16) && Cin >= 1 && Cout >= 1 && N >= 1 && D >= 1 && H >= 1 && W >= 1 && Do >= 1 &&
+           Ho >= 1 && Wo >= 1;
+}
+}  // namespace
+
+extern "C" {
+
+size_t mi3d_upconv2_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W) {
+    return (upconv2_pack_floats(Cin, Cout) + up_wg_floats(Cin, Cout, Geo{N, D, H, W})) * sizeof(float);
+}
+// thin wrappers: the up step without a resize, the weight images at the start of the workspace and one slab region behind them
 int mi3d_upconv2_forward(int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias, void* y, int ycs,
                          int Cout, int N, int D, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
     MI3D_CHECK_ARG(x && w && y && workspace, "mi3d_upconv2_forward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_upconv2_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_upconv2_forward: workspace too small");
-    float* wf = (float*)workspace;
-    float* wb = wf + (size_t)cdiv(Cout, 8) * Cin * 64;
-    if (dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, ycs)) {
-        MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, (hipStream_t)stream));
-        return upconv2_mfma_fwd(x, xcs, Cin, workspace, bias, y, ycs, Cout, Geo{N, D, H, W}, (hipStream_t)stream);
-    }
-    MI3D_TRY(upconv2_pack(w, Cin, Cout, wf, wb, (hipStream_t)stream));
-    return upconv2_fwd(dtype, x, xcs, Cin, wf, bias, y, ycs, Cout, Geo{N, D, H, W}, (hipStream_t)stream);
+    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, ycs);
+    if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, (hipStream_t)stream));
+    UpHalf a{Cin, Cout, Geo{N, D, H, W}, dtype, mfma, x, xcs, w, bias, workspace, up_wpb(workspace, Cin, Cout), y, ycs,
+             Geo{N, 2 * D, 2 * H, 2 * W}, nullptr};
+    return up_half_forward(a, (hipStream_t)stream);
 }
 int mi3d_upconv2_backward(int dtype, const void* x, int xcs, int Cin, const float* w, const void* gy, int gycs, int Cout,
                           void* dx, int dxcs, float* dW, float* db, int accumulate, int N, int D, int H, int W,
@@ -484,17 +513,91 @@ int mi3d_upconv2_backward(int dtype, const void* x, int xcs, int Cin, const floa
     MI3D_CHECK_ARG(x && w && gy && workspace, "mi3d_upconv2_backward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_upconv2_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_upconv2_backward: workspace too small");
     Geo g{N, D, H, W};
-    float* wf = (float*)workspace;
-    float* wb = wf + (size_t)cdiv(Cout, 8) * Cin * 64;
-    float* slabs = (float*)workspace + upconv2_pack_floats(Cin, Cout);
-    if (dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, gycs) && (!dx || dxcs % 4 == 0)) {
-        MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, (hipStream_t)stream));
-        return upconv2_mfma_bwd(x, xcs, Cin, gy, gycs, Cout, workspace, dx, dxcs, dW, db, accumulate, slabs,
-                                upconv2_mfma_bwd_ws_floats(Cin, Cout, g), g, (hipStream_t)stream);
-    }
-    MI3D_TRY(upconv2_pack(w, Cin, Cout, wf, wb, (hipStream_t)stream));
-    return upconv2_bwd(dtype, x, xcs, Cin, gy, gycs, Cout, wb, dx, dxcs, dW, db, accumulate, slabs,
-                       upconv2_bwd_ws_floats(Cin, Cout, g), g, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    float* wb = up_wpb(workspace, Cin, Cout);
+    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, gycs) && (!dx || dxcs % 4 == 0);
+    if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, s));
+    else MI3D_TRY(upconv2_pack(w, Cin, Cout, (float*)workspace, wb, s));
+    Pending pending;
+    UpHalfBwd a{Cin, Cout, g, dtype, mfma, x, xcs, workspace, wb, gy, gycs, Geo{N, 2 * D, 2 * H, 2 * W}, nullptr, dx, dxcs, dW, db,
+                accumulate, (float*)workspace + upconv2_pack_floats(Cin, Cout), nullptr,
+                mfma ? upconv2_mfma_bwd_ws_floats(Cin, Cout, g) : upconv2_bwd_ws_floats(Cin, Cout, g), false};
+    return up_half_backward(a, pending, s);
+}
+
+size_t mi3d_up_workspace_bytes(int dtype, int Cin, int Cout, int N, int D, int H, int W) {
+    if (!up_args_ok(dtype, Cin, Cout, N, D, H, W, 1, 1, 1)) return 0;
+    return up_ws(dtype, Cin, Cout, Geo{N, D, H, W}).total;
+}
+size_t mi3d_up_workspace_region(int dtype, int Cin, int Cout, int N, int D, int H, int W, int which, size_t* bytes_out) {
+    if (!up_args_ok(dtype, Cin, Cout, N, D, H, W, 1, 1, 1) || which < 0 || which > 3) { if (bytes_out) *bytes_out = 0; return 0; }
+    const UpWs L = up_ws(dtype, Cin, Cout, Geo{N, D, H, W});
+    const size_t off[4] = {L.wp, L.tmp, L.wgws, L.wgws2}, len[4] = {L.wp_bytes, L.tmp_bytes, L.wg_floats * sizeof(float), L.wg_floats * sizeof(float)};
+    if (bytes_out) *bytes_out = len[which];
+    return off[which];
+}
+int mi3d_up_forward(int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias, void* up, int ucs, int Cout,
+                    int N, int D, int H, int W, int Do, int Ho, int Wo, mi3d_up_route* route_out, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    const char* fn = "mi3d_up_forward";
+    MI3D_CHECK_ARG(x && w && up && workspace, "%s: null pointer", fn);
+    MI3D_CHECK_ARG(up_args_ok(dtype, Cin, Cout, N, D, H, W, Do, Ho, Wo) && xcs >= Cin && ucs >= Cout, "%s: bad shape or dtype", fn);
+    const Geo g{N, D, H, W}, go{N, Do, Ho, Wo};
+    const UpWs L = up_ws(dtype, Cin, Cout, g);
+    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const bool rs = Do != 2 * D || Ho != 2 * H || Wo != 2 * W;
+    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, rs ? Cout : ucs);
+    if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, ws + L.wp, s));
+    UpHalf a{Cin, Cout, g, dtype, mfma, x, xcs, w, bias, ws + L.wp, up_wpb(ws + L.wp, Cin, Cout), up, ucs, go, ws + L.tmp};
+    return up_half_forward(a, s, route_out);
+}
+int mi3d_up_backward(int dtype, const void* x, int xcs, int Cin, const float* w, const void* gup, int gucs, int Cout, void* dx,
+                     int dxcs, float* dW, float* db, int accumulate, int N, int D, int H, int W, int Do, int Ho, int Wo, int flags,
+                     mi3d_pending_sum* pending_out, mi3d_up_route* route_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "mi3d_up_backward";
+    MI3D_CHECK_ARG(x && w && gup && workspace, "%s: null pointer", fn);
+    MI3D_CHECK_ARG(up_args_ok(dtype, Cin, Cout, N, D, H, W, Do, Ho, Wo) && xcs >= Cin && gucs >= Cout && (!dx || dxcs >= Cin),
+                   "%s: bad shape or dtype", fn);
+    const bool leave = (flags & MI3D_UP_BWD_LEAVE_PENDING) != 0, second = (flags & MI3D_UP_BWD_SECOND_WORKSPACE) != 0;
+    MI3D_CHECK_ARG(!leave || pending_out, "%s: LEAVE_PENDING needs pending_out", fn);
+    const Geo g{N, D, H, W}, go{N, Do, Ho, Wo};
+    const UpWs L = up_ws(dtype, Cin, Cout, g);
+    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const bool rs = Do != 2 * D || Ho != 2 * H || Wo != 2 * W;
+    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, rs ? Cout : gucs) && (!dx || dxcs % 4 == 0);
+    MI3D_CHECK_ARG(!second || (mfma && !mi3d_routes().no_upbwd_carry), "%s: only the MFMA route with the carry has a second slab workspace", fn);
+    float* wb = up_wpb(ws + L.wp, Cin, Cout);
+    if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, ws + L.wp, s));
+    else MI3D_TRY(upconv2_pack(w, Cin, Cout, (float*)(ws + L.wp), wb, s));
+    // SECOND_WORKSPACE: the plan's situation -- a sum waits in the first slot (it reads the first slab region); the stand-in is never launched
+    Pending pending;
+    if (second) pending.pend.nblocks = 1;
+    UpHalfBwd a{Cin, Cout, g, dtype, mfma, x, xcs, ws + L.wp, wb, gup, gucs, go, ws + L.tmp, dx, dxcs, dW, db, accumulate,
+                (float*)(ws + L.wgws), second ? (float*)(ws + L.wgws2) : nullptr, L.wg_floats, leave};
+    MI3D_TRY(up_half_backward(a, pending, s, route_out));
+    if (second) pending.pend.nblocks = 0;
+    if (pending_out) memset(pending_out, 0, sizeof(*pending_out));
+    SlabJob& mine = second ? pending.pend2 : pending.pend;
+    if (leave && Pending::waits(mine)) { memcpy(pending_out, &mine, sizeof(SlabJob)); mine.nblocks = 0; }
+    return pending.flush(s);
+}
+int mi3d_nearest_resize_forward(int dtype, const void* x, int xcs, int C, int N, int Di, int Hi, int Wi, void* y, int ycs, int Do,
+                                int Ho, int Wo, void* stream) {
+    MI3D_CHECK_ARG(x && y, "mi3d_nearest_resize_forward: null pointer");
+    MI3D_CHECK_ARG(up_args_ok(dtype, C, C, N, Di, Hi, Wi, Do, Ho, Wo) && xcs >= C && ycs >= C, "mi3d_nearest_resize_forward: bad shape or dtype");
+    return nearest_resize_fwd(dtype, x, xcs, C, Geo{N, Di, Hi, Wi}, y, ycs, Geo{N, Do, Ho, Wo}, (hipStream_t)stream);
+}
+int mi3d_nearest_resize_backward(int dtype, const void* gy, int gycs, int C, int N, int Do, int Ho, int Wo, void* gx, int gxcs,
+                                 int Di, int Hi, int Wi, void* stream) {
+    MI3D_CHECK_ARG(gy && gx, "mi3d_nearest_resize_backward: null pointer");
+    MI3D_CHECK_ARG(up_args_ok(dtype, C, C, N, Di, Hi, Wi, Do, Ho, Wo) && gycs >= C && gxcs >= C, "mi3d_nearest_resize_backward: bad shape or dtype");
+    return nearest_resize_bwd(dtype, gy, gycs, C, Geo{N, Do, Ho, Wo}, gx, gxcs, Geo{N, Di, Hi, Wi}, (hipStream_t)stream);
 }
 int mi3d_ncdhw_to_ndhwc(int dtype, const float* src, void* dst, int dcs, int C, int N, int64_t V, void* stream) {
     MI3D_CHECK_ARG(src && dst, "mi3d_ncdhw_to_ndhwc: null pointer");

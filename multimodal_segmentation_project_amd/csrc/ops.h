@@ -293,24 +293,58 @@ int nearest_resize_bwd(int dtype, const void* gy, int gycs, int C, Geo go, void*
 
 // ---- ConvTranspose3d(k=2,s=2) ------------------------------------------------------------ upconv.hip
 // Reference: models/unet.py:56-58,79.  Weight torch layout (Cin,Cout,2,2,2).  g = INPUT geometry.
+// what a forward / backward launcher of the transposed conv launched (filled in at the branch it took; the fields of
+// mi3d_up_route, include/mi3d.h)
+struct UpLaunch { int kind = 0, gy = 1, tap_split = 0, wide = 0, strided = 0; };
+struct UpBwdLaunch { int kind = 0, ksplit = 0, persistent = 0, slabs = 0, slab_ew = 0, wgrad_blocks = 0, dgrad_blocks = 0; };
 size_t upconv2_pack_floats(int Cin, int Cout);
 int upconv2_pack(const float* w, int Cin, int Cout, float* wp_fwd, float* wp_bwd, hipStream_t s);
 int upconv2_fwd(int dtype, const void* x, int xcs, int Cin, const float* wp_fwd, const float* bias, void* y,
-                int ycs, int Cout, Geo g, hipStream_t s);
+                int ycs, int Cout, Geo g, hipStream_t s, UpLaunch* launched = nullptr);
 size_t upconv2_bwd_ws_floats(int Cin, int Cout, Geo g);
 int upconv2_bwd(int dtype, const void* x, int xcs, int Cin, const void* gy, int gycs, int Cout,
                 const float* wp_bwd, void* dx, int dxcs, float* dW, float* db, int accumulate, float* ws,
-                size_t ws_floats, Geo g, hipStream_t s);
+                size_t ws_floats, Geo g, hipStream_t s, UpBwdLaunch* launched = nullptr);
 
 // MFMA versions (bf16, Cin % 32 == 0, Cout % 16 == 0)                                   upconv_mfma.hip
 bool upconv2_mfma_supported(int Cin, int Cout, int xcs, int ycs);
 size_t upconv2_mfma_pack_elems(int Cin, int Cout);           // bf16 elements (fwd + bwd images)
 int upconv2_mfma_pack(const float* w, int Cin, int Cout, void* wp, hipStream_t s);
 int upconv2_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float* bias, void* y, int ycs, int Cout,
-                     Geo g, hipStream_t s);
+                     Geo g, hipStream_t s, UpLaunch* launched = nullptr);
 size_t upconv2_mfma_bwd_ws_floats(int Cin, int Cout, Geo g);
 int upconv2_mfma_bwd(const void* x, int xcs, int Cin, const void* gy, int gycs, int Cout, const void* wp, void* dx,
-                     int dxcs, float* dW, float* db, int accumulate, float* ws, size_t ws_floats, Geo g, hipStream_t s, SlabJob* pend = nullptr);
+                     int dxcs, float* dW, float* db, int accumulate, float* ws, size_t ws_floats, Geo g, hipStream_t s, SlabJob* pend = nullptr,
+                     UpBwdLaunch* launched = nullptr);
+
+// ---- one decoder up step: transposed conv into the up half of a concat buffer (-> nearest resize), and its adjoint ---- plan.hip
+// The ONE copy of the up step's decisions (temporary + resize where the output geometry is not 2x the input, MFMA or direct
+// launcher, which pending slot and which slab workspace the backward takes): up_forward / the decoder segments of the
+// whole-network plan and the per-operator entries mi3d_up_forward / mi3d_up_backward / mi3d_upconv2_* all call it.
+struct mi3d_up_route;                  // include/mi3d.h: what was launched, for the per-operator tests
+struct UpHalf {
+    int Cin, Cout; Geo g;              // g: INPUT geometry
+    int dt; bool mfma;                 // bf16 MFMA kernels / the direct fp32-FMA kernels
+    const void* in; int ics;
+    const float* w; const float* bias; // w: torch layout (the direct route packs it here, in front of its launch)
+    void* wp; float* wpb;              // mfma: the packed image (read); direct: forward image / backward image (written)
+    void* up; int ucs; Geo go;         // the up half of the concat buffer, its channel stride and geometry
+    void* tmp;                         // [2D][2H][2W][Cout] temporary, needed where go is not (2D, 2H, 2W)
+};
+int up_half_forward(const UpHalf& a, hipStream_t s, mi3d_up_route* route = nullptr);
+struct UpHalfBwd {
+    int Cin, Cout; Geo g;              // g: INPUT geometry of the transposed conv
+    int dt; bool mfma;
+    const void* in; int ics;
+    const void* wp; const float* wpb;  // mfma: the packed image; direct: the backward image
+    const void* gup; int gucs; Geo go; // gradient of the up half of the concat buffer
+    void* tmp;                         // [2D][2H][2W][Cout] temporary of the resize adjoint
+    void* dx; int dxcs;                // input gradient or NULL
+    float* dW; float* db; int accumulate;
+    float* wgws; float* wgws2; size_t wgws_floats;      // first / second slab workspace (wgws2 NULL: no carry)
+    bool leave;                        // the MFMA route leaves its slab sum in `pending` (the plan) instead of launching it
+};
+int up_half_backward(const UpHalfBwd& a, Pending& pending, hipStream_t s, mi3d_up_route* route = nullptr);
 
 // ---- final 1x1x1 conv, losses, metrics ------------------------------------------------ head_loss.hip
 // Reference: nn.Conv3d(16,4,1) models/unet.py:62,87 ; utils/metrics.py:14-40,65-129,137-190.

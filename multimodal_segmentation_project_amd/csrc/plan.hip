@@ -197,6 +197,70 @@ int conv3_bn_half_backward(const ConvBnHalfBwd& a, Pending& pending, hipStream_t
     return report(a.mfma ? 5 : a.c1 ? 1 : 0);
 }
 
+// One decoder up step, forward (ops.h UpHalf): the transposed conv into the up half of the concat buffer; where that half's
+// geometry is not twice the input's (an odd side somewhere above, models/unet.py:81-83) it goes through the temporary and the
+// nearest resize.  route: what was launched.
+static inline bool up_resized(Geo g, Geo go) { return go.D != 2 * g.D || go.H != 2 * g.H || go.W != 2 * g.W; }
+int up_half_forward(const UpHalf& a, hipStream_t s, mi3d_up_route* route) {
+    const Geo g2{a.g.N, 2 * a.g.D, 2 * a.g.H, 2 * a.g.W};
+    const bool rs = up_resized(a.g, a.go);
+    MI3D_CHECK_ARG(!rs || a.tmp, "up_half_forward: the resize needs the temporary");
+    void* dst = rs ? a.tmp : a.up;
+    const int dcs = rs ? a.Cout : a.ucs;
+    UpLaunch L;
+    if (a.mfma) {
+        MI3D_TRY(upconv2_mfma_fwd(a.in, a.ics, a.Cin, a.wp, a.bias, dst, dcs, a.Cout, a.g, s, &L));
+    } else {
+        MI3D_TRY(upconv2_pack(a.w, a.Cin, a.Cout, (float*)a.wp, a.wpb, s));
+        MI3D_TRY(upconv2_fwd(a.dt, a.in, a.ics, a.Cin, (const float*)a.wp, a.bias, dst, dcs, a.Cout, a.g, s, &L));
+    }
+    if (rs) MI3D_TRY(nearest_resize_fwd(a.dt, dst, dcs, a.Cout, g2, a.up, a.ucs, a.go, s));
+    if (route) {
+        *route = mi3d_up_route{};
+        route->kind = L.kind; route->gy = L.gy; route->tap_split = L.tap_split; route->wide = L.wide; route->strided = L.strided;
+        route->resized = rs ? 1 : 0;
+    }
+    return 0;
+}
+
+// One decoder up step, backward (ops.h UpHalfBwd): the resize adjoint where the forward resized, then the transposed conv's
+// backward.  The slab-sum slots, once: while the decoder conv's sum waits in `pending` (it reads the first slab workspace) the
+// MFMA route takes `carry` and writes its slabs to the SECOND workspace, so both sums ride in the next BatchNorm-backward
+// reduction (not under no_upbwd_carry / without a second workspace); otherwise it takes `first`.  a.leave: the sum stays in the
+// slot it took; else it is launched here.  The direct kernels sum their slabs themselves, behind `first`.
+int up_half_backward(const UpHalfBwd& a, Pending& pending, hipStream_t s, mi3d_up_route* route) {
+    const Geo g2{a.g.N, 2 * a.g.D, 2 * a.g.H, 2 * a.g.W};
+    const bool rs = up_resized(a.g, a.go);
+    MI3D_CHECK_ARG(!rs || a.tmp, "up_half_backward: the resize adjoint needs the temporary");
+    const void* gup = a.gup;
+    int gucs = a.gucs;
+    if (rs) {       // adjoint of the nearest resize in front of the concat (models/unet.py:81-83)
+        MI3D_TRY(nearest_resize_bwd(a.dt, gup, gucs, a.Cout, a.go, a.tmp, a.Cout, g2, s));
+        gup = a.tmp; gucs = a.Cout;
+    }
+    UpBwdLaunch L;
+    bool left = false;
+    if (a.mfma) {
+        SlabJob* slot = (a.wgws2 && !mi3d_routes().no_upbwd_carry) ? pending.carry() : nullptr;
+        float* slabs = slot ? a.wgws2 : a.wgws;
+        if (!slot) slot = pending.first(s);
+        MI3D_TRY(upconv2_mfma_bwd(a.in, a.ics, a.Cin, gup, gucs, a.Cout, a.wp, a.dx, a.dxcs, a.dW, a.db, a.accumulate, slabs,
+                                  a.wgws_floats, a.g, s, a.leave ? slot : nullptr, &L));
+        left = a.leave && Pending::waits(*slot);
+    } else {
+        pending.first(s);
+        MI3D_TRY(upconv2_bwd(a.dt, a.in, a.ics, a.Cin, gup, gucs, a.Cout, a.wpb, a.dx, a.dxcs, a.dW, a.db, a.accumulate, a.wgws,
+                             a.wgws_floats, a.g, s, &L));
+    }
+    if (route) {
+        *route = mi3d_up_route{};
+        route->kind = L.kind; route->ksplit = L.ksplit; route->persistent = L.persistent; route->slabs = L.slabs;
+        route->slab_ew = L.slab_ew; route->wgrad_blocks = L.wgrad_blocks; route->dgrad_blocks = L.dgrad_blocks;
+        route->pending = left ? 1 : 0; route->resized = rs ? 1 : 0;
+    }
+    return 0;
+}
+
 namespace {
 
 constexpr int MAXL = MI3D_MAX_LEVELS;
@@ -641,24 +705,16 @@ int up_forward(Ctx& c, int i) {
     const Plan& p = c.p;
     const UpIO u = up_io(c, i);
     char* up = c.at<char>(p.cat[u.l]) + u.half;
-    const bool rs = p.resize[u.l];
-    void* dst = rs ? c.at(p.uptmp) : (void*)up;
-    int dcs = rs ? u.Cout : u.cs;
-    if (p.up_mfma[i]) {
-        MI3D_TRY(upconv2_mfma_fwd(u.in, u.Cin, u.Cin, u.w, c.P(p.up_pidx(i) + 1), dst, dcs, u.Cout, u.g, c.s));
-    } else {
-        MI3D_TRY(upconv2_pack(c.P(p.up_pidx(i)), u.Cin, u.Cout, u.w, u.wb, c.s));
-        MI3D_TRY(upconv2_fwd(p.dt, u.in, u.Cin, u.Cin, u.w, c.P(p.up_pidx(i) + 1), dst, dcs, u.Cout, u.g, c.s));
-    }
-    if (rs) MI3D_TRY(nearest_resize_fwd(p.dt, dst, dcs, u.Cout, p.up_geo(u.l), up, u.cs, p.geo[u.l], c.s));
-    return 0;
+    UpHalf a{u.Cin, u.Cout, u.g, p.dt, p.up_mfma[i], u.in, u.Cin, c.P(p.up_pidx(i)), c.P(p.up_pidx(i) + 1), u.w, u.wb,
+             up, u.cs, p.geo[u.l], p.resize[u.l] ? c.at(p.uptmp) : nullptr};
+    return up_half_forward(a, c.s);
 }
 
 }  // namespace
 
 extern "C" {
 
-int mi3d_abi_version(void) { return 7; }
+int mi3d_abi_version(void) { return 8; }
 
 int mi3d_unet_num_params(const mi3d_unet_desc* d) { return d ? 8 * (2 * d->n_levels + 1) + 2 * d->n_levels + 2 : -1; }
 int mi3d_unet_num_buffers(const mi3d_unet_desc* d) { return d ? 6 * (2 * d->n_levels + 1) : -1; }
@@ -921,26 +977,10 @@ static int unet_backward_impl(const mi3d_unet_desc* d, const float* x, const voi
             int l = seg - 1, i = L - 1 - l;       // decoder.i works at level l
             MI3D_TRY(block_backward(c, L + 1 + i, x, grads, drop_scales, c.at(p.gz[l]), p.C[l], c.at(p.gcat[l]), p.catcs(l), accumulate));
             const UpIO u = up_io(c, i);
-            const void* gup = c.at<char>(p.gcat[l]) + u.half;
-            int gupcs = u.cs;
-            if (p.resize[l]) {       // adjoint of the nearest resize in front of the concat (models/unet.py:81-83)
-                MI3D_TRY(nearest_resize_bwd(p.dt, gup, gupcs, u.Cout, p.geo[l], c.at(p.uptmp), u.Cout, p.up_geo(l), c.s));
-                gup = c.at(p.uptmp); gupcs = u.Cout;
-            }
-            if (p.up_mfma[i]) {
-                // the decoder conv's pending slab sum (it reads wgws) stays pending across the transposed conv's backward, which
-                // therefore writes its slabs to the second workspace; the next BatchNorm-backward reduction carries both sums: one
-                // chain link less per level (not with the two-stream weight gradients, which own that workspace)
-                SlabJob* ps = mi3d_routes().no_upbwd_carry ? nullptr : c.pending.carry();
-                float* slabs = ps ? c.at<float>(p.wgws2) : wgws;
-                if (!ps) ps = c.pending.first(c.s);
-                MI3D_TRY(upconv2_mfma_bwd(u.in, u.Cin, u.Cin, gup, gupcs, u.Cout, u.w, c.at(p.gz[l + 1]), u.Cin, G(p.up_pidx(i)),
-                                          G(p.up_pidx(i) + 1), accumulate, slabs, p.wgws_floats, u.g, c.s, ps));
-            } else {
-                c.pending.first(c.s);
-                MI3D_TRY(upconv2_bwd(p.dt, u.in, u.Cin, u.Cin, gup, gupcs, u.Cout, u.wb, c.at(p.gz[l + 1]), u.Cin, G(p.up_pidx(i)),
-                                     G(p.up_pidx(i) + 1), accumulate, wgws, p.wgws_floats, u.g, c.s));
-            }
+            UpHalfBwd a{u.Cin, u.Cout, u.g, p.dt, p.up_mfma[i], u.in, u.Cin, u.w, u.wb, c.at<char>(p.gcat[l]) + u.half, u.cs, p.geo[l],
+                        p.resize[l] ? c.at(p.uptmp) : nullptr, c.at(p.gz[l + 1]), u.Cin, G(p.up_pidx(i)), G(p.up_pidx(i) + 1), accumulate,
+                        wgws, c.at<float>(p.wgws2), p.wgws_floats, true};
+            MI3D_TRY(up_half_backward(a, c.pending, c.s));
         } else if (seg == L + 1) {
             if (dgap)
                 MI3D_TRY(gap_bwd(p.dt, dgap, gap_scale, c.at(p.gz[L]), p.C[L], p.C[L], d->N, p.geo[L].V(), dlogits ? 1 : 0, c.s));

@@ -192,7 +192,16 @@ __global__ __launch_bounds__(BLK) void nearest_resize_fwd_kernel(const T* __rest
         for (int c = 0; c < C; c++) y[v * ycs + c] = x[src * xcs + c];
     }
 }
-// gx[src] = sum of gy over the destination voxels that read src (gather form: deterministic, no atomics)
+// candidate destinations of source index i: every a with nn_src(a) == i has a * scale in [i, i + 1) (the last source index also
+// takes what the clamp sends there), i.e. a in [i / scale, (i + 1) / scale).  Both ends are computed in float, so each gets a
+// guard voxel; nn_src(a) == i stays the filter
+__device__ __forceinline__ void nn_window(int i, float scale, int in, int out, int& lo, int& hi) {
+    lo = (int)((float)i / scale) - 1;
+    hi = i >= in - 1 ? out - 1 : (int)((float)(i + 1) / scale) + 1;
+    if (lo < 0) lo = 0;
+    if (hi > out - 1) hi = out - 1;
+}
+// gx[src] = sum of gy over the destination voxels that read src (gather form: deterministic, no atomics), ascending in (a, b, e)
 template <typename T>
 __global__ __launch_bounds__(BLK) void nearest_resize_bwd_kernel(const T* __restrict__ gy, int gycs, int C, int N, int Do, int Ho, int Wo,
                                                                  T* __restrict__ gx, int gxcs, int Di, int Hi, int Wi) {
@@ -200,15 +209,17 @@ __global__ __launch_bounds__(BLK) void nearest_resize_bwd_kernel(const T* __rest
     int64_t total = (int64_t)N * Di * Hi * Wi;
     for (int64_t v = (int64_t)blockIdx.x * BLK + threadIdx.x; v < total; v += (int64_t)gridDim.x * BLK) {
         int w = (int)(v % Wi); int64_t r = v / Wi; int h = (int)(r % Hi); r /= Hi; int d = (int)(r % Di); int n = (int)(r / Di);
-        // candidate destinations per dimension: a window around src/scale
-        int d0 = (int)((float)d / sd) - 1, h0 = (int)((float)h / sh) - 1, w0 = (int)((float)w / sw) - 1;
+        int d0, d1, h0, h1, w0, w1;
+        nn_window(d, sd, Di, Do, d0, d1);
+        nn_window(h, sh, Hi, Ho, h0, h1);
+        nn_window(w, sw, Wi, Wo, w0, w1);
         for (int c = 0; c < C; c++) {
             float acc = 0.f;
-            for (int a = d0 < 0 ? 0 : d0; a < Do && a <= d0 + 3; a++) {
+            for (int a = d0; a <= d1; a++) {
                 if (nn_src(a, sd, Di) != d) continue;
-                for (int b = h0 < 0 ? 0 : h0; b < Ho && b <= h0 + 3; b++) {
+                for (int b = h0; b <= h1; b++) {
                     if (nn_src(b, sh, Hi) != h) continue;
-                    for (int e = w0 < 0 ? 0 : w0; e < Wo && e <= w0 + 3; e++) {
+                    for (int e = w0; e <= w1; e++) {
                         if (nn_src(e, sw, Wi) != w) continue;
                         acc += to_f<T>(gy[((((int64_t)n * Do + a) * Ho + b) * Wo + e) * gycs + c]);
                     }

@@ -217,7 +217,8 @@ int upconv2_pack(const float* w, int Cin, int Cout, float* wp_fwd, float* wp_bwd
 }
 
 int upconv2_fwd(int dtype, const void* x, int xcs, int Cin, const float* wp_fwd, const float* bias, void* y, int ycs,
-                int Cout, Geo g, hipStream_t s) {
+                int Cout, Geo g, hipStream_t s, UpLaunch* launched) {
+    if (launched) *launched = UpLaunch{0, cdiv(Cout, 8), 0, 0, 0};
     dim3 grid((unsigned)cdiv(g.M(), BLK), (unsigned)cdiv(Cout, 8));
     DISPATCH_T(dtype, T, {
         if (Cin % 8 == 0 && xcs % 8 == 0 && al16(x))
@@ -235,9 +236,14 @@ size_t upconv2_bwd_ws_floats(int Cin, int Cout, Geo g) {
 
 int upconv2_bwd(int dtype, const void* x, int xcs, int Cin, const void* gy, int gycs, int Cout, const float* wp_bwd,
                 void* dx, int dxcs, float* dW, float* db, int accumulate, float* ws, size_t ws_floats, Geo g,
-                hipStream_t s) {
+                hipStream_t s, UpBwdLaunch* launched) {
     int nsb = upw_nsb(Cin, Cout, g);
     int64_t nW = (int64_t)Cin * Cout * 8;
+    if (launched) {
+        const int64_t sz = nW + Cout;
+        *launched = UpBwdLaunch{0, 0, 0, nsb, sz < 128 ? 1 : sz < 1024 ? 4 : sz < (16 << 10) ? 8 : 32, nsb * cdiv(Cin, CB) * cdiv(Cout, CB),
+                                dx ? cdiv(g.M(), BLK) * cdiv(Cin, 8) : 0};
+    }
     MI3D_CHECK_ARG(ws_floats >= (size_t)nsb * (nW + Cout), "upconv2_bwd: workspace too small");
     DISPATCH_T(dtype, T, {
         if (dx) {

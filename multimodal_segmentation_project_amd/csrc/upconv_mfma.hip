@@ -430,7 +430,7 @@ int upconv2_mfma_pack(const float* w, int Cin, int Cout, void* wp, hipStream_t s
 }
 
 int upconv2_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const float* bias, void* y, int ycs, int Cout, Geo g,
-                     hipStream_t s) {
+                     hipStream_t s, UpLaunch* launched) {
     MI3D_CHECK_ARG(upconv2_mfma_supported(Cin, Cout, xcs, ycs), "upconv2_mfma_fwd: unsupported channels %d->%d", Cin, Cout);
     MI3D_CHECK_ARG(g.M() < (1ll << 31), "upconv2_mfma_fwd: more than 2^31 input voxels");
     const bf16* xp = (const bf16*)x; const bf16* wf = (const bf16*)wp; bf16* yp = (bf16*)y;
@@ -444,6 +444,7 @@ int upconv2_mfma_fwd(const void* x, int xcs, int Cin, const void* wp, const floa
     switch (Cin / 32) { case 1: UF(1); break; case 2: UF(2); break; case 4: UF(4); break; default: UF(8); break; }
 #undef UF
     MI3D_LAUNCH_CHECK();
+    if (launched) *launched = UpLaunch{1, gy, gz == 8 ? 1 : 0, wide, cdiv(g.M(), 16) > (int64_t)gx * 4 ? 1 : 0};
     return 0;
 }
 
@@ -452,7 +453,8 @@ size_t upconv2_mfma_bwd_ws_floats(int Cin, int Cout, Geo g) {
 }
 
 int upconv2_mfma_bwd(const void* x, int xcs, int Cin, const void* gy, int gycs, int Cout, const void* wp, void* dx, int dxcs,
-                     float* dW, float* db, int accumulate, float* ws, size_t ws_floats, Geo g, hipStream_t s, SlabJob* pend) {
+                     float* dW, float* db, int accumulate, float* ws, size_t ws_floats, Geo g, hipStream_t s, SlabJob* pend,
+                     UpBwdLaunch* launched) {
     MI3D_CHECK_ARG(upconv2_mfma_supported(Cin, Cout, xcs, gycs), "upconv2_mfma_bwd: unsupported channels");
     MI3D_CHECK_ARG(g.M() < (1ll << 31), "upconv2_mfma_bwd: more than 2^31 input voxels");
     const bf16* xp = (const bf16*)x; const bf16* gp = (const bf16*)gy;
@@ -492,12 +494,16 @@ int upconv2_mfma_bwd(const void* x, int xcs, int Cin, const void* gy, int gycs, 
         }
 #undef UFL
         MI3D_LAUNCH_CHECK();
+        if (launched)
+            *launched = UpBwdLaunch{1, ksp ? 1 : 0, !ksp && cdiv(g.M(), 16) > (int64_t)a.dgx * 4 ? 1 : 0, nsb, slab_sz < (16 << 10) ? 8 : 32,
+                                    a.wgx * a.wgy * a.wgz, a.dgx * a.dgy};
         if (pend) { *pend = slab_job_make(0, ws, nsb, slab_sz, nW, dW, db, Cin, Cout, accumulate); return 0; }
         if (slab_sz < (16 << 10)) slab_reduce3_kernel<8><<<cdiv(slab_sz, 8), BLK, 0, s>>>(ws, nsb, slab_sz, nW, dW, db, accumulate);
         else slab_reduce3_kernel<32><<<cdiv(slab_sz, 32), BLK, 0, s>>>(ws, nsb, slab_sz, nW, dW, db, accumulate);
         MI3D_LAUNCH_CHECK();
         return 0;
     }
+    if (launched) *launched = UpBwdLaunch{dx ? ((dW || db) ? 2 : 3) : 4, 0, 0, 0, 0, 0, 0};
     if (dx) {
         int gx = wave_grid(g.M());
         int gy = 1;
@@ -517,6 +523,11 @@ int upconv2_mfma_bwd(const void* x, int xcs, int Cin, const void* gy, int gycs, 
 #undef UBK
 #undef UB
         MI3D_LAUNCH_CHECK();
+        if (launched) {
+            launched->ksplit = ksp ? 1 : 0;
+            launched->persistent = !ksp && cdiv(g.M(), 16) > (int64_t)gx * 4 ? 1 : 0;
+            launched->dgrad_blocks = ksp ? (int)(gridk.x * gridk.y) : gx * gy;
+        }
     }
     if (dW || db) {
         int nsb = upw_nsb(Cin, Cout, g);
@@ -527,6 +538,10 @@ int upconv2_mfma_bwd(const void* x, int xcs, int Cin, const void* gy, int gycs, 
         dim3 grid((unsigned)nsb, (unsigned)(Cin / 32), (unsigned)cdiv(Cout, 32));
         upconv_mfma_bwd_weight_kernel<<<grid, BLK, lds, s>>>(xp, xcs, Cin, gp, gycs, Cout, g.N, g.D, g.H, g.W, ws);
         MI3D_LAUNCH_CHECK();
+        if (launched) {
+            launched->slabs = nsb; launched->slab_ew = slab_sz < (16 << 10) ? 8 : 32;
+            launched->wgrad_blocks = (int)(grid.x * grid.y * grid.z);
+        }
         if (pend) { *pend = slab_job_make(0, ws, nsb, slab_sz, nW, dW, db, Cin, Cout, accumulate); return 0; }
         if (slab_sz < (16 << 10)) slab_reduce3_kernel<8><<<cdiv(slab_sz, 8), BLK, 0, s>>>(ws, nsb, slab_sz, nW, dW, db, accumulate);
         else slab_reduce3_kernel<32><<<cdiv(slab_sz, 32), BLK, 0, s>>>(ws, nsb, slab_sz, nW, dW, db, accumulate);

@@ -88,6 +88,53 @@ def battery():
         for k, v in (("dx", dx), ("dW", dW), ("db", db)):
             put(f"upconv{s}/{k}", v)
 
+    # the decoder's up step per operator at the shapes of tests/up_ref.py (every forward and backward branch of upconv_mfma.hip, the
+    # direct kernels in bf16 and fp32), through the entries every build has: into / out of the upper half of a concat buffer, the
+    # argument forms of the backward, accumulate = 1; then the up step through the nearest resize where the build has the entry
+    def up(tag, dt, n, cin, cout, d, h, w):
+        rng = np.random.default_rng(cin + cout + d + h + w + dt)
+        tdt = bf if dt else torch.float32
+        x, wgt, b = rnd(rng, (n, d, h, w, cin), dt=tdt), rnd(rng, (cin, cout, 2, 2, 2), 0.1), rnd(rng, (cout,))
+        wsb = lib.mi3d_upconv2_workspace_bytes(cin, cout, n, d, h, w)
+        ws = empty(wsb, dt=torch.uint8)
+        cat = torch.zeros((n, 2 * d, 2 * h, 2 * w, 2 * cout), device=dev, dtype=tdt)
+        gcat = rnd(rng, tuple(cat.shape), dt=tdt)
+        es = cat.element_size()
+        call("mi3d_upconv2_forward", dt, ptr(x), cin, cin, ptr(wgt), ptr(b), cat.data_ptr() + cout * es, 2 * cout, cout, n, d, h, w,
+             ptr(ws), wsb, None)
+        put(f"{tag}/y", cat)
+        for form, (hx, hw, hb, acc) in {"all": (1, 1, 1, 0), "acc": (1, 1, 1, 1), "nodb": (1, 1, 0, 0), "dx": (1, 0, 0, 0), "w": (0, 1, 1, 0)}.items():
+            dx, dW, db = torch.zeros_like(x), torch.full_like(wgt, 0.5), torch.full((cout,), 0.25, device=dev)
+            call("mi3d_upconv2_backward", dt, ptr(x), cin, cin, ptr(wgt), gcat.data_ptr() + cout * es, 2 * cout, cout, ptr(dx) if hx else None,
+                 cin, ptr(dW) if hw else None, ptr(db) if hb else None, acc, n, d, h, w, ptr(ws), wsb, None)
+            for k, v in (("dx", dx), ("dW", dW), ("db", db)):
+                put(f"{tag}/{form}/{k}", v)
+
+    for s in [(2, 32, 16, 3, 5, 7), (1, 32, 16, 13, 27, 25), (1, 64, 32, 9, 13, 11), (1, 64, 32, 17, 31, 31), (1, 64, 32, 33, 32, 32),
+              (1, 128, 64, 19, 21, 21), (1, 256, 128, 13, 19, 17), (1, 256, 128, 2, 3, 2), (1, 32, 128, 2, 3, 5), (1, 128, 16, 3, 5, 7),
+              (1, 64, 16, 5, 7, 9), (1, 48, 24, 5, 6, 7), (1, 96, 48, 3, 4, 5)]:
+        up(f"up/bf16{s}", 1, *s)
+        if s[1] == 64 and s[3] == 17:
+            with _lib.routes(no_fused_upbwd=1):
+                up(f"up/bf16{s}/no_fused_upbwd", 1, *s)
+    for s in [(2, 6, 3, 3, 2, 4), (1, 24, 12, 4, 5, 3), (1, 40, 20, 3, 4, 5), (1, 8, 4, 17, 31, 32)]:
+        up(f"up/fp32{s}", 0, *s)
+    if "mi3d_up_forward" in _lib._SIGS:
+        for (n, cin, cout, d, h, w), go in (((1, 32, 16, 4, 3, 5), (9, 7, 11)), ((1, 64, 32, 4, 3, 5), (8, 7, 10))):
+            rng = np.random.default_rng(cin + sum(go))
+            x, wgt, b = rnd(rng, (n, d, h, w, cin), dt=bf), rnd(rng, (cin, cout, 2, 2, 2), 0.1), rnd(rng, (cout,))
+            wsb = lib.mi3d_up_workspace_bytes(1, cin, cout, n, d, h, w)
+            ws = empty(wsb, dt=torch.uint8)
+            cat = torch.zeros((n,) + go + (2 * cout,), device=dev, dtype=bf)
+            gcat = rnd(rng, tuple(cat.shape), dt=bf)
+            call("mi3d_up_forward", 1, ptr(x), cin, cin, ptr(wgt), ptr(b), cat.data_ptr() + 2 * cout, 2 * cout, cout, n, d, h, w, *go, None,
+                 ptr(ws), wsb, None)
+            dx, dW, db = torch.zeros_like(x), torch.zeros_like(wgt), torch.zeros(cout, device=dev)
+            call("mi3d_up_backward", 1, ptr(x), cin, cin, ptr(wgt), gcat.data_ptr() + 2 * cout, 2 * cout, cout, ptr(dx), cin, ptr(dW), ptr(db),
+                 0, n, d, h, w, *go, 0, None, None, ptr(ws), wsb, None)
+            for k, v in (("y", cat), ("dx", dx), ("dW", dW), ("db", db)):
+                put(f"up_resized{(n, cin, cout, d, h, w)}->{go}/{k}", v)
+
     for kd in (False, True):
         n, c, d, h, w, cin = 2, 4, 16, 16, 16, 16
         v = d * h * w
