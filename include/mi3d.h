@@ -332,7 +332,8 @@ int mi3d_reorient3(const void* in, int src_dtype, void* out, int out_i64, int D,
 /* mi3d_zoom3_cubic of the reoriented scan without making it (amos_ct_resample.py:33 + :60).  Tables as there, built in RAS order;
  * for a flipped axis the caller replaces every tap index i by n - 1 - i AFTER the clamp (weights unchanged).  Same taps, same
  * float64 sums in the same order: bit-identical to mi3d_zoom3_cubic on mi3d_reorient3's float32 output.  Source: uint8, int16 or
- * float32. */
+ * float32.  A float32 source with the strides of a contiguous (D, H, W) volume runs the kernel mi3d_zoom3_cubic runs; likewise an
+ * int64 source of mi3d_zoom3_nearest_src and mi3d_zoom3_nearest_i64. */
 int mi3d_zoom3_cubic_src(const void* in, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, float* out, int D,
                          int H, int W, int Do, int Ho, int Wo, const void* table_d, int rows_d, const void* table_h, int rows_h,
                          const void* table_w, int rows_w, int ct_window, float window_min, float window_max, void* stream);

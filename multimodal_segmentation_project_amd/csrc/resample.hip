@@ -6,6 +6,14 @@
 // Every per-axis quantity (tap indices, already clamped; the four float64 weights; the nearest index) comes from tables the
 // host builds in float64 (resample.py axis_table), so the tap choice is scipy's bit for bit; the kernels do no floor, no
 // division on coordinates and no polynomial.  Direct form: each thread gathers its taps through L1/L2, no LDS, no atomics.
+//
+// The kernels that write contiguous rows (cubic, nearest, mask merge, streamed reorient) share one walk:
+//   row_slot     grid x over (output row oh, group of NV consecutive W outputs from ow0), y = od; NV * sizeof(T) = 16
+//   tail_col     a lane past the row's end reads what the last column reads (index min(ow0 + j, Wo - 1)) and is never stored
+//   store_group  VEC: one 16-byte store (the launcher saw Wo % NV == 0 and an aligned output); else scalar stores of ow0 + j < Wo
+//   src_row      STRIDED = false: a contiguous volume (st unused); true: a stored scan read through its RAS element strides
+// Both STRIDED forms gather the same taps and sum them in the same order, so they give the same bits.
+#include <type_traits>
 #include <utility>
 
 #include "ops.h"
@@ -13,8 +21,8 @@
 
 namespace {
 constexpr int BLK = 256;
-constexpr int CW = 4;      // cubic: consecutive W outputs per thread (one 16-byte store)
-constexpr int NWV = 2;     // nearest: consecutive int64 W outputs per thread (one 16-byte store)
+constexpr int CW = 4;      // cubic: float outputs per thread
+constexpr int NWV = 2;     // nearest, merge: int64 outputs per thread
 
 struct CubicRow {          // one output index of one axis; layout shared with resample.py (_ROW)
     int32_t idx[4];        // input indices of the four taps, clamped to [0, n_in - 1]
@@ -28,21 +36,53 @@ struct SrcStrides {
     int64_t d, h, w;
 };
 
-// grid: x over (oh, group of CW outputs along W), y = od.  Sum over (kd, kh) of wd*wh * (sum over kw of x*ww), all fp64.
-// STRIDED = false is the contiguous float32 volume (st unused); STRIDED = true reads a stored scan of type S through st with the
-// same taps, the same order of sums and the same conversions ((double) of an int16 is what (double)(float) of it is).
+template <int NV>
+__device__ __forceinline__ bool row_slot(int Ho, int WQ, int& oh, int& ow0, int& od) {
+    const int q = blockIdx.x * BLK + threadIdx.x;
+    if (q >= Ho * WQ) return false;
+    oh = q / WQ, ow0 = (q - oh * WQ) * NV, od = blockIdx.y;
+    return true;
+}
+
+template <bool VEC>      // VEC: the launcher saw Wo % NV == 0, no lane is past the end
+__device__ __forceinline__ int tail_col(int ow, int Wo) { return VEC ? ow : min(ow, Wo - 1); }
+
+template <typename T, int NV, bool VEC>
+__device__ __forceinline__ void store_group(T* o, const T (&v)[NV], int ow0, int Wo) {
+    static_assert(NV * sizeof(T) == 16, "one 16-byte store");
+    if constexpr (VEC) {
+        typedef __attribute__((ext_vector_type(NV))) T vec_t;
+        vec_t a;
+#pragma unroll
+        for (int j = 0; j < NV; j++) a[j] = v[j];
+        *reinterpret_cast<vec_t*>(o) = a;
+    } else {
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            if (ow0 + j < Wo) o[j] = v[j];
+    }
+}
+
+template <bool STRIDED, typename S>
+__device__ __forceinline__ const S* src_row(const S* in, int id, int ih, int H, int W, SrcStrides st) {
+    return STRIDED ? in + (id * st.d + ih * st.h) : in + ((int64_t)id * H + ih) * W;
+}
+template <bool STRIDED>
+__device__ __forceinline__ int64_t src_sw(SrcStrides st) { return STRIDED ? st.w : 1; }
+
+// Sum over (kd, kh) of wd*wh * (sum over kw of x*ww), all fp64.  A stored scan of type S converts as the float32 copy of it would:
+// (double) of an int16 is what (double)(float) of it is.
 template <typename S, bool VEC, bool STRIDED>
 __global__ __launch_bounds__(BLK) void zoom3_cubic_kernel(const S* __restrict__ in, float* __restrict__ out, int H, int W,
                                                           int Ho, int Wo, int WQ, const CubicRow* __restrict__ td,
                                                           const CubicRow* __restrict__ th, const CubicRow* __restrict__ tw,
                                                           int ct, float lo, float hi, SrcStrides st) {
-    const int q = blockIdx.x * BLK + threadIdx.x;
-    if (q >= Ho * WQ) return;
-    const int oh = q / WQ, ow0 = (q - oh * WQ) * CW, od = blockIdx.y;
+    int oh, ow0, od;
+    if (!row_slot<CW>(Ho, WQ, oh, ow0, od)) return;
     const CubicRow rd = td[od], rh = th[oh];
     CubicRow rw[CW];
 #pragma unroll
-    for (int j = 0; j < CW; j++) rw[j] = tw[min(ow0 + j, Wo - 1)];       // tail lanes recompute the last column, never store it
+    for (int j = 0; j < CW; j++) rw[j] = tw[tail_col<false>(ow0 + j, Wo)];      // clamped in the vector form too: without, <uint8, VEC> takes 15 more AGPRs
     double acc[CW];
 #pragma unroll
     for (int j = 0; j < CW; j++) acc[j] = 0.0;
@@ -50,8 +90,8 @@ __global__ __launch_bounds__(BLK) void zoom3_cubic_kernel(const S* __restrict__ 
     for (int kd = 0; kd < 4; kd++) {
 #pragma unroll
         for (int kh = 0; kh < 4; kh++) {
-            const S* row = STRIDED ? in + (rd.idx[kd] * st.d + rh.idx[kh] * st.h) : in + ((int64_t)rd.idx[kd] * H + rh.idx[kh]) * W;
-            const int64_t sw = STRIDED ? st.w : 1;
+            const S* row = src_row<STRIDED>(in, rd.idx[kd], rh.idx[kh], H, W, st);
+            const int64_t sw = src_sw<STRIDED>(st);
             const double wdh = rd.w[kd] * rh.w[kh];
 #pragma unroll
             for (int j = 0; j < CW; j++) {
@@ -69,15 +109,7 @@ __global__ __launch_bounds__(BLK) void zoom3_cubic_kernel(const S* __restrict__ 
         v[j] = (float)acc[j];                                             // the one rounding to fp32
         if (ct) v[j] = ct_window_f32(v[j], lo, hi);
     }
-    float* o = out + ((int64_t)od * Ho + oh) * Wo + ow0;
-    if constexpr (VEC) {
-        f32x4 a = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(o) = a;
-    } else {
-#pragma unroll
-        for (int j = 0; j < CW; j++)
-            if (ow0 + j < Wo) o[j] = v[j];
-    }
+    store_group<float, CW, VEC>(out + ((int64_t)od * Ho + oh) * Wo + ow0, v, ow0, Wo);
 }
 
 template <typename S, bool VEC, bool STRIDED>
@@ -85,22 +117,14 @@ __global__ __launch_bounds__(BLK) void zoom3_nearest_kernel(const S* __restrict_
                                                             int Ho, int Wo, int WQ, const int32_t* __restrict__ td,
                                                             const int32_t* __restrict__ th, const int32_t* __restrict__ tw,
                                                             SrcStrides st) {
-    const int q = blockIdx.x * BLK + threadIdx.x;
-    if (q >= Ho * WQ) return;
-    const int oh = q / WQ, ow0 = (q - oh * WQ) * NWV, od = blockIdx.y;
-    const S* row = STRIDED ? in + (td[od] * st.d + th[oh] * st.h) : in + ((int64_t)td[od] * H + th[oh]) * W;
-    const int64_t sw = STRIDED ? st.w : 1;
-    int64_t* o = out + ((int64_t)od * Ho + oh) * Wo + ow0;
-    if constexpr (VEC) {
-        longlong2 a;
-        a.x = (int64_t)row[tw[ow0] * sw];
-        a.y = (int64_t)row[tw[ow0 + 1] * sw];
-        *reinterpret_cast<longlong2*>(o) = a;
-    } else {
+    int oh, ow0, od;
+    if (!row_slot<NWV>(Ho, WQ, oh, ow0, od)) return;
+    const S* row = src_row<STRIDED>(in, td[od], th[oh], H, W, st);
+    const int64_t sw = src_sw<STRIDED>(st);
+    int64_t v[NWV];
 #pragma unroll
-        for (int j = 0; j < NWV; j++)
-            if (ow0 + j < Wo) o[j] = (int64_t)row[tw[ow0 + j] * sw];
-    }
+    for (int j = 0; j < NWV; j++) v[j] = (int64_t)row[tw[tail_col<VEC>(ow0 + j, Wo)] * sw];
+    store_group<int64_t, NWV, VEC>(out + ((int64_t)od * Ho + oh) * Wo + ow0, v, ow0, Wo);
 }
 
 // ---- stored scans: reorientation to RAS, mask merge ------------------------------------------------------------------------
@@ -108,28 +132,19 @@ __global__ __launch_bounds__(BLK) void zoom3_nearest_kernel(const S* __restrict_
 __device__ __forceinline__ int stored_index(int i, int n, int flipped) { return flipped ? n - 1 - i : i; }
 
 // reorient_to_ras (amos_ct_resample.py:29-36) of a dense stored scan into a contiguous RAS volume, converted to T.
-// Streaming form: lanes along the destination W, 16 / sizeof(T) outputs per thread.  It is correct for every stride triple and
-// is the route when W is also the stored-fastest axis (a copy, reversed when W is flipped) or no axis has stride 1 with a side > 1.
+// Streaming form: lanes along the destination W.  It is correct for every stride triple and is the route when W is also the
+// stored-fastest axis (a copy, reversed when W is flipped) or no axis has stride 1 with a side > 1.
 template <typename S, typename T, bool VEC>
 __global__ __launch_bounds__(BLK) void reorient3_stream_kernel(const S* __restrict__ in, T* __restrict__ out, int D, int H, int W,
                                                                int WQ, SrcStrides st, int flips) {
     constexpr int NV = 16 / (int)sizeof(T);
-    const int q = blockIdx.x * BLK + threadIdx.x;
-    if (q >= H * WQ) return;
-    const int h = q / WQ, w0 = (q - h * WQ) * NV, d = blockIdx.y;
+    int h, w0, d;
+    if (!row_slot<NV>(H, WQ, h, w0, d)) return;
     const S* row = in + (stored_index(d, D, flips & 1) * st.d + stored_index(h, H, flips & 2) * st.h);
-    T* o = out + ((int64_t)d * H + h) * W + w0;
-    if constexpr (VEC) {
-        typedef __attribute__((ext_vector_type(NV))) T vec_t;
-        vec_t a;
+    T v[NV];
 #pragma unroll
-        for (int j = 0; j < NV; j++) a[j] = (T)row[stored_index(w0 + j, W, flips & 4) * st.w];
-        *reinterpret_cast<vec_t*>(o) = a;
-    } else {
-#pragma unroll
-        for (int j = 0; j < NV; j++)
-            if (w0 + j < W) o[j] = (T)row[stored_index(w0 + j, W, flips & 4) * st.w];
-    }
+    for (int j = 0; j < NV; j++) v[j] = (T)row[stored_index(tail_col<VEC>(w0 + j, W), W, flips & 4) * st.w];
+    store_group<T, NV, VEC>(out + ((int64_t)d * H + h) * W + w0, v, w0, W);
 }
 
 // Tiled form, for a stored-fastest axis F that is the RAS D or H: a TILE x TILE tile of the (F, W) plane goes through LDS, loaded
@@ -175,30 +190,19 @@ template <typename S, bool VEC>
 __global__ __launch_bounds__(BLK) void merge_masks3_kernel(MaskArgs m, int64_t* __restrict__ out, int Ho, int Wo, int WQ,
                                                            const int32_t* __restrict__ td, const int32_t* __restrict__ th,
                                                            const int32_t* __restrict__ tw, SrcStrides st) {
-    const int q = blockIdx.x * BLK + threadIdx.x;
-    if (q >= Ho * WQ) return;
-    const int oh = q / WQ, ow0 = (q - oh * WQ) * NWV, od = blockIdx.y;
+    int oh, ow0, od;
+    if (!row_slot<NWV>(Ho, WQ, oh, ow0, od)) return;
     const int64_t row = td[od] * st.d + th[oh] * st.h;
     int64_t v[NWV];
 #pragma unroll
     for (int j = 0; j < NWV; j++) {
         v[j] = 0;
-        const int64_t off = row + tw[min(ow0 + j, Wo - 1)] * st.w;      // a tail lane rereads the last column, never stores it
+        const int64_t off = row + tw[tail_col<VEC>(ow0 + j, Wo)] * st.w;
 #pragma unroll
         for (int k = 0; k < MAX_MASKS; k++)
             if (k < m.n && static_cast<const S*>(m.mask[k])[off] > (S)0) v[j] = m.value[k];
     }
-    int64_t* o = out + ((int64_t)od * Ho + oh) * Wo + ow0;
-    if constexpr (VEC) {
-        longlong2 a;
-        a.x = v[0];
-        a.y = v[1];
-        *reinterpret_cast<longlong2*>(o) = a;
-    } else {
-#pragma unroll
-        for (int j = 0; j < NWV; j++)
-            if (ow0 + j < Wo) o[j] = v[j];
-    }
+    store_group<int64_t, NWV, VEC>(out + ((int64_t)od * Ho + oh) * Wo + ow0, v, ow0, Wo);
 }
 
 // Labels from the training grid back onto a scan as stored: the order-0 gather out[s][m][f] = grid[tS[s]][tM[m]][tF[f]] with the
@@ -239,41 +243,124 @@ __global__ __launch_bounds__(BLK) void restore_labels3_kernel(const uint8_t* __r
     }
 }
 
+// ---- host side ------------------------------------------------------------------------------------------------------------------
 constexpr int MAX_SIDE = 65535;      // od rides in gridDim.y; in-plane indices stay far inside int32
-inline bool dims_ok(int D, int H, int W) { return D >= 1 && H >= 1 && W >= 1 && D <= MAX_SIDE && H <= MAX_SIDE && W <= MAX_SIDE; }
+struct Dims {
+    int d, h, w;
+    bool ok() const { return d >= 1 && h >= 1 && w >= 1 && d <= MAX_SIDE && h <= MAX_SIDE && w <= MAX_SIDE; }
+};
 
-// a stored scan's strides: positive (any value where the side is 1), and the last element's offset inside int64 with room to spare
-// (that the last element's offset lies inside the caller's buffer is the caller's to guarantee: include/mi3d.h; resample.py
-// passes dense tensors only)
-inline bool strides_ok(int64_t sd, int64_t sh, int64_t sw) {
-    const int64_t lim = (int64_t)1 << 44;      // 65535^3 < 2^48 elements; a dense tensor's largest stride is < 2^32
-    return sd >= 1 && sh >= 1 && sw >= 1 && sd < lim && sh < lim && sw < lim;
+// The argument check of every entry; `ptrs` is the entry's own null / alias test.  rows: the tables' row counts, which must be
+// the sides of `out`.  st: a stored scan's strides, positive (any value where the side is 1) and the last element's offset
+// inside int64 with room to spare: 65535^3 < 2^48 elements, a dense tensor's largest stride is < 2^32 (that the offset lies
+// inside the caller's buffer is the caller's to guarantee: include/mi3d.h).  tabs16: three tables that must be 16-byte aligned.
+int check_args(const char* name, bool ptrs, Dims in, Dims out, const int* rows, const SrcStrides* st = nullptr,
+               const void* const* tabs16 = nullptr) {
+    MI3D_CHECK_ARG(ptrs, "%s: null or aliased pointers", name);
+    MI3D_CHECK_ARG(in.ok() && out.ok(), "%s: sides must be in [1, %d]", name, MAX_SIDE);
+    const int64_t lim = (int64_t)1 << 44;
+    MI3D_CHECK_ARG(!st || (st->d >= 1 && st->h >= 1 && st->w >= 1 && st->d < lim && st->h < lim && st->w < lim),
+                   "%s: strides must be positive element counts", name);
+    MI3D_CHECK_ARG(!rows || (rows[0] == out.d && rows[1] == out.h && rows[2] == out.w),
+                   "%s: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", name, rows ? rows[0] : 0, rows ? rows[1] : 0,
+                   rows ? rows[2] : 0, out.d, out.h, out.w);
+    MI3D_CHECK_ARG(!tabs16 || (((uintptr_t)tabs16[0] | (uintptr_t)tabs16[1] | (uintptr_t)tabs16[2]) & 15) == 0,
+                   "%s: tables must be 16-byte aligned", name);
+    return 0;
+}
+
+// The launch shape of row_slot / store_group for NV outputs per thread
+struct RowGrid {
+    int WQ;
+    dim3 grid;
+    bool vec;
+};
+int row_grid(const char* name, Dims o, int NV, const void* out, RowGrid& g) {
+    g.WQ = (o.w + NV - 1) / NV;
+    MI3D_CHECK_ARG((int64_t)o.h * g.WQ < (int64_t)1 << 31, "%s: output plane too large", name);
+    g.grid = dim3((unsigned)(((int64_t)o.h * g.WQ + BLK - 1) / BLK), (unsigned)o.d);
+    g.vec = o.w % NV == 0 && ((uintptr_t)out & 15) == 0;
+    return 0;
+}
+
+// Source-dtype dispatch: f(S()) for the one type S of the list whose MI3D_SRC_* code is `code`; false where none is
+template <typename S> constexpr int src_code = -1;
+template <> constexpr int src_code<uint8_t> = MI3D_SRC_U8;
+template <> constexpr int src_code<int16_t> = MI3D_SRC_I16;
+template <> constexpr int src_code<float> = MI3D_SRC_F32;
+template <> constexpr int src_code<int64_t> = MI3D_SRC_I64;
+template <typename... S> struct Types {};
+template <typename... S, typename F>
+bool dispatch_src(int code, Types<S...>, F&& f) {
+    return ((code == src_code<S> && (f(S()), true)) || ...);
+}
+
+// every axis with more than one element has the stride of a contiguous (D, H, W) volume
+bool dense_ras(Dims n, SrcStrides st) {
+    return (n.d == 1 || st.d == (int64_t)n.h * n.w) && (n.h == 1 || st.h == n.w) && (n.w == 1 || st.w == 1);
+}
+
+// One launcher per zoom family, behind the contiguous and the _src entry alike.  A float32 (cubic) / int64 (nearest) source with
+// dense RAS strides takes the STRIDED = false instantiation: the same bits, without the stride arithmetic.
+int cubic_launch(const char* name, const void* in, int src_dtype, SrcStrides st, float* out, Dims n, Dims o, const void* const (&tab)[3],
+                 const int (&rows)[3], int ct, float lo, float hi, void* stream) {
+    MI3D_TRY(check_args(name, in && out && in != (const void*)out && tab[0] && tab[1] && tab[2], n, o, rows, &st, tab));
+    MI3D_CHECK_ARG(!ct || hi > lo, "%s: empty CT window", name);
+    RowGrid g;
+    MI3D_TRY(row_grid(name, o, CW, out, g));
+    const bool known = dispatch_src(src_dtype, Types<uint8_t, int16_t, float>(), [&](auto tag) {
+        using S = decltype(tag);
+        auto launch = [&](auto kernel) {
+            kernel<<<g.grid, BLK, 0, (hipStream_t)stream>>>((const S*)in, out, n.h, n.w, o.h, o.w, g.WQ, (const CubicRow*)tab[0],
+                                                            (const CubicRow*)tab[1], (const CubicRow*)tab[2], ct, lo, hi, st);
+        };
+        if constexpr (std::is_same<S, float>::value)
+            if (dense_ras(n, st)) return launch(g.vec ? zoom3_cubic_kernel<S, true, false> : zoom3_cubic_kernel<S, false, false>);
+        launch(g.vec ? zoom3_cubic_kernel<S, true, true> : zoom3_cubic_kernel<S, false, true>);
+    });
+    MI3D_CHECK_ARG(known, "%s: the source is uint8, int16 or float32, not dtype code %d", name, src_dtype);
+    MI3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int nearest_launch(const char* name, const void* in, int src_dtype, SrcStrides st, int64_t* out, Dims n, Dims o,
+                   const int32_t* const (&tab)[3], const int (&rows)[3], void* stream) {
+    MI3D_TRY(check_args(name, in && out && in != (const void*)out && tab[0] && tab[1] && tab[2], n, o, rows, &st));
+    RowGrid g;
+    MI3D_TRY(row_grid(name, o, NWV, out, g));
+    const bool known = dispatch_src(src_dtype, Types<uint8_t, int16_t, int64_t>(), [&](auto tag) {
+        using S = decltype(tag);
+        auto launch = [&](auto kernel) {
+            kernel<<<g.grid, BLK, 0, (hipStream_t)stream>>>((const S*)in, out, n.h, n.w, o.h, o.w, g.WQ, tab[0], tab[1], tab[2], st);
+        };
+        if constexpr (std::is_same<S, int64_t>::value)
+            if (dense_ras(n, st)) return launch(g.vec ? zoom3_nearest_kernel<S, true, false> : zoom3_nearest_kernel<S, false, false>);
+        launch(g.vec ? zoom3_nearest_kernel<S, true, true> : zoom3_nearest_kernel<S, false, true>);
+    });
+    MI3D_CHECK_ARG(known, "%s: the source is uint8, int16 or int64, not dtype code %d", name, src_dtype);
+    MI3D_LAUNCH_CHECK();
+    return 0;
 }
 
 template <typename S, typename T>
-int reorient3_launch(const S* in, T* out, int D, int H, int W, int64_t sd, int64_t sh, int64_t sw, int flips, hipStream_t s) {
-    constexpr int NV = 16 / (int)sizeof(T);
+int reorient3_launch(const S* in, T* out, Dims n, SrcStrides st, int flips, hipStream_t s) {
     // the stored-fastest axis, where it is not W: D or H with stride 1 and more than one element
-    const int fast = (sw == 1 || W == 1) ? 2 : (sh == 1 && H > 1) ? 1 : (sd == 1 && D > 1) ? 0 : 2;
+    const int fast = (st.w == 1 || n.w == 1) ? 2 : (st.h == 1 && n.h > 1) ? 1 : (st.d == 1 && n.d > 1) ? 0 : 2;
     if (fast == 2) {
-        const int WQ = (W + NV - 1) / NV;
-        MI3D_CHECK_ARG((int64_t)H * WQ < (int64_t)1 << 31, "mi3d_reorient3: plane too large");
-        dim3 grid((unsigned)(((int64_t)H * WQ + BLK - 1) / BLK), (unsigned)D);
-        const SrcStrides st{sd, sh, sw};
-        if (W % NV == 0 && ((uintptr_t)out & 15) == 0)
-            reorient3_stream_kernel<S, T, true><<<grid, BLK, 0, s>>>(in, out, D, H, W, WQ, st, flips);
-        else
-            reorient3_stream_kernel<S, T, false><<<grid, BLK, 0, s>>>(in, out, D, H, W, WQ, st, flips);
+        RowGrid g;
+        MI3D_TRY(row_grid("mi3d_reorient3", n, 16 / (int)sizeof(T), out, g));
+        auto kernel = g.vec ? reorient3_stream_kernel<S, T, true> : reorient3_stream_kernel<S, T, false>;
+        kernel<<<g.grid, BLK, 0, s>>>(in, out, n.d, n.h, n.w, g.WQ, st, flips);
     } else {
-        const int nF = fast == 1 ? H : D, nG = fast == 1 ? D : H;
-        const int tilesW = (W + TILE - 1) / TILE, tilesF = (nF + TILE - 1) / TILE;
+        const int nF = fast == 1 ? n.h : n.d, nG = fast == 1 ? n.d : n.h;
+        const int tilesW = (n.w + TILE - 1) / TILE, tilesF = (nF + TILE - 1) / TILE;
         dim3 grid((unsigned)(tilesF * tilesW), (unsigned)nG);
         if (fast == 1)
-            reorient3_tile_kernel<S, T><<<grid, BLK, 0, s>>>(in, out, nF, nG, W, tilesW, sh, sd, sw, flips & 2, flips & 1, flips & 4,
-                                                             (int64_t)W, (int64_t)H * W);
+            reorient3_tile_kernel<S, T><<<grid, BLK, 0, s>>>(in, out, nF, nG, n.w, tilesW, st.h, st.d, st.w, flips & 2, flips & 1, flips & 4,
+                                                             (int64_t)n.w, (int64_t)n.h * n.w);
         else
-            reorient3_tile_kernel<S, T><<<grid, BLK, 0, s>>>(in, out, nF, nG, W, tilesW, sd, sh, sw, flips & 1, flips & 2, flips & 4,
-                                                             (int64_t)H * W, (int64_t)W);
+            reorient3_tile_kernel<S, T><<<grid, BLK, 0, s>>>(in, out, nF, nG, n.w, tilesW, st.d, st.h, st.w, flips & 1, flips & 2, flips & 4,
+                                                             (int64_t)n.h * n.w, (int64_t)n.w);
     }
     MI3D_LAUNCH_CHECK();
     return 0;
@@ -283,7 +370,7 @@ int reorient3_launch(const S* in, T* out, int D, int H, int W, int64_t sd, int64
 extern "C" {
 
 size_t mi3d_zoom3_workspace_bytes(int D, int H, int W) {
-    if (!dims_ok(D, H, W)) {
+    if (!Dims{D, H, W}.ok()) {
         mi3d_set_error("mi3d_zoom3_workspace_bytes: sides must be in [1, %d]", MAX_SIDE);
         return 0;
     }
@@ -293,164 +380,72 @@ size_t mi3d_zoom3_workspace_bytes(int D, int H, int W) {
 int mi3d_zoom3_cubic(const float* in, float* out, int D, int H, int W, int Do, int Ho, int Wo, const void* table_d, int rows_d,
                      const void* table_h, int rows_h, const void* table_w, int rows_w, int ct_window, float window_min,
                      float window_max, void* stream) {
-    MI3D_CHECK_ARG(in && out && in != out && table_d && table_h && table_w, "mi3d_zoom3_cubic: null or aliased pointers");
-    MI3D_CHECK_ARG(dims_ok(D, H, W) && dims_ok(Do, Ho, Wo), "mi3d_zoom3_cubic: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(rows_d == Do && rows_h == Ho && rows_w == Wo,
-                   "mi3d_zoom3_cubic: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", rows_d, rows_h, rows_w, Do, Ho, Wo);
-    MI3D_CHECK_ARG((((uintptr_t)table_d | (uintptr_t)table_h | (uintptr_t)table_w) & 15) == 0,
-                   "mi3d_zoom3_cubic: tables must be 16-byte aligned");
-    MI3D_CHECK_ARG(!ct_window || window_max > window_min, "mi3d_zoom3_cubic: empty CT window");
-    const int WQ = (Wo + CW - 1) / CW;
-    MI3D_CHECK_ARG((int64_t)Ho * WQ < (int64_t)1 << 31, "mi3d_zoom3_cubic: output plane too large");
-    dim3 grid((unsigned)(((int64_t)Ho * WQ + BLK - 1) / BLK), (unsigned)Do);
-    const CubicRow *td = (const CubicRow*)table_d, *th = (const CubicRow*)table_h, *tw = (const CubicRow*)table_w;
-    hipStream_t s = (hipStream_t)stream;
-    if (Wo % CW == 0 && ((uintptr_t)out & 15) == 0)
-        zoom3_cubic_kernel<float, true, false><<<grid, BLK, 0, s>>>(in, out, H, W, Ho, Wo, WQ, td, th, tw, ct_window, window_min, window_max, SrcStrides{});
-    else
-        zoom3_cubic_kernel<float, false, false><<<grid, BLK, 0, s>>>(in, out, H, W, Ho, Wo, WQ, td, th, tw, ct_window, window_min, window_max, SrcStrides{});
-    MI3D_LAUNCH_CHECK();
-    return 0;
-}
-
-int mi3d_zoom3_nearest_i64(const int64_t* in, int64_t* out, int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d,
-                           int rows_d, const int32_t* index_h, int rows_h, const int32_t* index_w, int rows_w, void* stream) {
-    MI3D_CHECK_ARG(in && out && in != out && index_d && index_h && index_w, "mi3d_zoom3_nearest_i64: null or aliased pointers");
-    MI3D_CHECK_ARG(dims_ok(D, H, W) && dims_ok(Do, Ho, Wo), "mi3d_zoom3_nearest_i64: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(rows_d == Do && rows_h == Ho && rows_w == Wo,
-                   "mi3d_zoom3_nearest_i64: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", rows_d, rows_h, rows_w, Do, Ho, Wo);
-    const int WQ = (Wo + NWV - 1) / NWV;
-    MI3D_CHECK_ARG((int64_t)Ho * WQ < (int64_t)1 << 31, "mi3d_zoom3_nearest_i64: output plane too large");
-    dim3 grid((unsigned)(((int64_t)Ho * WQ + BLK - 1) / BLK), (unsigned)Do);
-    hipStream_t s = (hipStream_t)stream;
-    if (Wo % NWV == 0 && ((uintptr_t)out & 15) == 0)
-        zoom3_nearest_kernel<int64_t, true, false><<<grid, BLK, 0, s>>>(in, out, H, W, Ho, Wo, WQ, index_d, index_h, index_w, SrcStrides{});
-    else
-        zoom3_nearest_kernel<int64_t, false, false><<<grid, BLK, 0, s>>>(in, out, H, W, Ho, Wo, WQ, index_d, index_h, index_w, SrcStrides{});
-    MI3D_LAUNCH_CHECK();
-    return 0;
-}
-
-int mi3d_reorient3(const void* in, int src_dtype, void* out, int out_i64, int D, int H, int W, int64_t stride_d, int64_t stride_h,
-                   int64_t stride_w, int flip_mask, void* stream) {
-    MI3D_CHECK_ARG(in && out && in != out, "mi3d_reorient3: null or aliased pointers");
-    MI3D_CHECK_ARG(dims_ok(D, H, W), "mi3d_reorient3: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(strides_ok(stride_d, stride_h, stride_w), "mi3d_reorient3: strides must be positive element counts");
-    MI3D_CHECK_ARG(flip_mask >= 0 && flip_mask <= 7, "mi3d_reorient3: flip_mask %d outside 0..7", flip_mask);
-    hipStream_t s = (hipStream_t)stream;
-#define MI3D_REORIENT(S, T) return reorient3_launch<S, T>((const S*)in, (T*)out, D, H, W, stride_d, stride_h, stride_w, flip_mask, s)
-    if (!out_i64) {
-        if (src_dtype == MI3D_SRC_U8) MI3D_REORIENT(uint8_t, float);
-        if (src_dtype == MI3D_SRC_I16) MI3D_REORIENT(int16_t, float);
-        if (src_dtype == MI3D_SRC_F32) MI3D_REORIENT(float, float);
-        MI3D_CHECK_ARG(false, "mi3d_reorient3: a float32 volume is made from uint8, int16 or float32, not dtype code %d", src_dtype);
-    }
-    if (src_dtype == MI3D_SRC_U8) MI3D_REORIENT(uint8_t, int64_t);
-    if (src_dtype == MI3D_SRC_I16) MI3D_REORIENT(int16_t, int64_t);
-    if (src_dtype == MI3D_SRC_I64) MI3D_REORIENT(int64_t, int64_t);
-#undef MI3D_REORIENT
-    MI3D_CHECK_ARG(false, "mi3d_reorient3: an int64 volume is made from uint8, int16 or int64, not dtype code %d", src_dtype);
+    return cubic_launch("mi3d_zoom3_cubic", in, MI3D_SRC_F32, {(int64_t)H * W, W, 1}, out, {D, H, W}, {Do, Ho, Wo},
+                        {table_d, table_h, table_w}, {rows_d, rows_h, rows_w}, ct_window, window_min, window_max, stream);
 }
 
 int mi3d_zoom3_cubic_src(const void* in, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, float* out, int D,
                          int H, int W, int Do, int Ho, int Wo, const void* table_d, int rows_d, const void* table_h, int rows_h,
                          const void* table_w, int rows_w, int ct_window, float window_min, float window_max, void* stream) {
-    MI3D_CHECK_ARG(in && out && in != (const void*)out && table_d && table_h && table_w, "mi3d_zoom3_cubic_src: null or aliased pointers");
-    MI3D_CHECK_ARG(dims_ok(D, H, W) && dims_ok(Do, Ho, Wo), "mi3d_zoom3_cubic_src: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(strides_ok(stride_d, stride_h, stride_w), "mi3d_zoom3_cubic_src: strides must be positive element counts");
-    MI3D_CHECK_ARG(rows_d == Do && rows_h == Ho && rows_w == Wo,
-                   "mi3d_zoom3_cubic_src: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", rows_d, rows_h, rows_w, Do, Ho, Wo);
-    MI3D_CHECK_ARG((((uintptr_t)table_d | (uintptr_t)table_h | (uintptr_t)table_w) & 15) == 0,
-                   "mi3d_zoom3_cubic_src: tables must be 16-byte aligned");
-    MI3D_CHECK_ARG(!ct_window || window_max > window_min, "mi3d_zoom3_cubic_src: empty CT window");
-    MI3D_CHECK_ARG(src_dtype == MI3D_SRC_U8 || src_dtype == MI3D_SRC_I16 || src_dtype == MI3D_SRC_F32,
-                   "mi3d_zoom3_cubic_src: the source is uint8, int16 or float32, not dtype code %d", src_dtype);
-    const int WQ = (Wo + CW - 1) / CW;
-    MI3D_CHECK_ARG((int64_t)Ho * WQ < (int64_t)1 << 31, "mi3d_zoom3_cubic_src: output plane too large");
-    dim3 grid((unsigned)(((int64_t)Ho * WQ + BLK - 1) / BLK), (unsigned)Do);
-    const CubicRow *td = (const CubicRow*)table_d, *th = (const CubicRow*)table_h, *tw = (const CubicRow*)table_w;
-    const SrcStrides st{stride_d, stride_h, stride_w};
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec = Wo % CW == 0 && ((uintptr_t)out & 15) == 0;
-#define MI3D_CUBIC_SRC(S)                                                                                                       \
-    do {                                                                                                                        \
-        if (vec)                                                                                                                \
-            zoom3_cubic_kernel<S, true, true><<<grid, BLK, 0, s>>>((const S*)in, out, H, W, Ho, Wo, WQ, td, th, tw, ct_window,   \
-                                                                   window_min, window_max, st);                                 \
-        else                                                                                                                    \
-            zoom3_cubic_kernel<S, false, true><<<grid, BLK, 0, s>>>((const S*)in, out, H, W, Ho, Wo, WQ, td, th, tw, ct_window,  \
-                                                                    window_min, window_max, st);                                \
-    } while (0)
-    if (src_dtype == MI3D_SRC_U8) MI3D_CUBIC_SRC(uint8_t);
-    else if (src_dtype == MI3D_SRC_I16) MI3D_CUBIC_SRC(int16_t);
-    else MI3D_CUBIC_SRC(float);
-#undef MI3D_CUBIC_SRC
-    MI3D_LAUNCH_CHECK();
-    return 0;
+    return cubic_launch("mi3d_zoom3_cubic_src", in, src_dtype, {stride_d, stride_h, stride_w}, out, {D, H, W}, {Do, Ho, Wo},
+                        {table_d, table_h, table_w}, {rows_d, rows_h, rows_w}, ct_window, window_min, window_max, stream);
+}
+
+int mi3d_zoom3_nearest_i64(const int64_t* in, int64_t* out, int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d,
+                           int rows_d, const int32_t* index_h, int rows_h, const int32_t* index_w, int rows_w, void* stream) {
+    return nearest_launch("mi3d_zoom3_nearest_i64", in, MI3D_SRC_I64, {(int64_t)H * W, W, 1}, out, {D, H, W}, {Do, Ho, Wo},
+                          {index_d, index_h, index_w}, {rows_d, rows_h, rows_w}, stream);
 }
 
 int mi3d_zoom3_nearest_src(const void* in, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, int64_t* out, int D,
                            int H, int W, int Do, int Ho, int Wo, const int32_t* index_d, int rows_d, const int32_t* index_h,
                            int rows_h, const int32_t* index_w, int rows_w, void* stream) {
-    MI3D_CHECK_ARG(in && out && in != (const void*)out && index_d && index_h && index_w, "mi3d_zoom3_nearest_src: null or aliased pointers");
-    MI3D_CHECK_ARG(dims_ok(D, H, W) && dims_ok(Do, Ho, Wo), "mi3d_zoom3_nearest_src: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(strides_ok(stride_d, stride_h, stride_w), "mi3d_zoom3_nearest_src: strides must be positive element counts");
-    MI3D_CHECK_ARG(rows_d == Do && rows_h == Ho && rows_w == Wo,
-                   "mi3d_zoom3_nearest_src: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", rows_d, rows_h, rows_w, Do, Ho, Wo);
-    MI3D_CHECK_ARG(src_dtype == MI3D_SRC_U8 || src_dtype == MI3D_SRC_I16 || src_dtype == MI3D_SRC_I64,
-                   "mi3d_zoom3_nearest_src: the source is uint8, int16 or int64, not dtype code %d", src_dtype);
-    const int WQ = (Wo + NWV - 1) / NWV;
-    MI3D_CHECK_ARG((int64_t)Ho * WQ < (int64_t)1 << 31, "mi3d_zoom3_nearest_src: output plane too large");
-    dim3 grid((unsigned)(((int64_t)Ho * WQ + BLK - 1) / BLK), (unsigned)Do);
+    return nearest_launch("mi3d_zoom3_nearest_src", in, src_dtype, {stride_d, stride_h, stride_w}, out, {D, H, W}, {Do, Ho, Wo},
+                          {index_d, index_h, index_w}, {rows_d, rows_h, rows_w}, stream);
+}
+
+int mi3d_reorient3(const void* in, int src_dtype, void* out, int out_i64, int D, int H, int W, int64_t stride_d, int64_t stride_h,
+                   int64_t stride_w, int flip_mask, void* stream) {
+    const Dims n{D, H, W};
     const SrcStrides st{stride_d, stride_h, stride_w};
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec = Wo % NWV == 0 && ((uintptr_t)out & 15) == 0;
-#define MI3D_NEAREST_SRC(S)                                                                                                      \
-    do {                                                                                                                         \
-        if (vec)                                                                                                                 \
-            zoom3_nearest_kernel<S, true, true><<<grid, BLK, 0, s>>>((const S*)in, out, H, W, Ho, Wo, WQ, index_d, index_h, index_w, st);  \
-        else                                                                                                                     \
-            zoom3_nearest_kernel<S, false, true><<<grid, BLK, 0, s>>>((const S*)in, out, H, W, Ho, Wo, WQ, index_d, index_h, index_w, st); \
-    } while (0)
-    if (src_dtype == MI3D_SRC_U8) MI3D_NEAREST_SRC(uint8_t);
-    else if (src_dtype == MI3D_SRC_I16) MI3D_NEAREST_SRC(int16_t);
-    else MI3D_NEAREST_SRC(int64_t);
-#undef MI3D_NEAREST_SRC
-    MI3D_LAUNCH_CHECK();
-    return 0;
+    MI3D_TRY(check_args("mi3d_reorient3", in && out && in != out, n, n, nullptr, &st));
+    MI3D_CHECK_ARG(flip_mask >= 0 && flip_mask <= 7, "mi3d_reorient3: flip_mask %d outside 0..7", flip_mask);
+    int rc = 0;
+    auto run = [&](auto dst, auto sources) {
+        return dispatch_src(src_dtype, sources, [&](auto tag) {
+            rc = reorient3_launch((const decltype(tag)*)in, (decltype(dst)*)out, n, st, flip_mask, (hipStream_t)stream);
+        });
+    };
+    const bool known = out_i64 ? run(int64_t(), Types<uint8_t, int16_t, int64_t>()) : run(float(), Types<uint8_t, int16_t, float>());
+    MI3D_CHECK_ARG(known, "mi3d_reorient3: %s volume is made from uint8, int16 or %s, not dtype code %d",
+                   out_i64 ? "an int64" : "a float32", out_i64 ? "int64" : "float32", src_dtype);
+    return rc;
 }
 
 int mi3d_merge_masks3(const mi3d_mask_list* masks, int src_dtype, int64_t stride_d, int64_t stride_h, int64_t stride_w, int64_t* out,
                       int D, int H, int W, int Do, int Ho, int Wo, const int32_t* index_d, int rows_d, const int32_t* index_h,
                       int rows_h, const int32_t* index_w, int rows_w, void* stream) {
-    MI3D_CHECK_ARG(masks && out && index_d && index_h && index_w, "mi3d_merge_masks3: null pointers");
-    MI3D_CHECK_ARG(masks->n >= 0 && masks->n <= MAX_MASKS, "mi3d_merge_masks3: %d masks, at most %d fit one launch", masks->n, MAX_MASKS);
-    MI3D_CHECK_ARG(dims_ok(D, H, W) && dims_ok(Do, Ho, Wo), "mi3d_merge_masks3: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(strides_ok(stride_d, stride_h, stride_w), "mi3d_merge_masks3: strides must be positive element counts");
-    MI3D_CHECK_ARG(rows_d == Do && rows_h == Ho && rows_w == Wo,
-                   "mi3d_merge_masks3: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", rows_d, rows_h, rows_w, Do, Ho, Wo);
-    MI3D_CHECK_ARG(src_dtype == MI3D_SRC_U8 || src_dtype == MI3D_SRC_F32,
-                   "mi3d_merge_masks3: masks are uint8 or float32, not dtype code %d", src_dtype);
+    const char* name = "mi3d_merge_masks3";
+    const Dims o{Do, Ho, Wo};
+    const SrcStrides st{stride_d, stride_h, stride_w};
+    const int rows[3] = {rows_d, rows_h, rows_w};
+    MI3D_TRY(check_args(name, masks && out && index_d && index_h && index_w, {D, H, W}, o, rows, &st));
+    MI3D_CHECK_ARG(masks->n >= 0 && masks->n <= MAX_MASKS, "%s: %d masks, at most %d fit one launch", name, masks->n, MAX_MASKS);
     MaskArgs m{};
     m.n = masks->n;
     for (int k = 0; k < masks->n; k++) {
-        MI3D_CHECK_ARG(masks->mask[k] && masks->mask[k] != (const void*)out, "mi3d_merge_masks3: mask %d is null or is the output", k);
+        MI3D_CHECK_ARG(masks->mask[k] && masks->mask[k] != (const void*)out, "%s: mask %d is null or is the output", name, k);
         m.mask[k] = masks->mask[k];
         m.value[k] = masks->value[k];
     }
-    const int WQ = (Wo + NWV - 1) / NWV;
-    MI3D_CHECK_ARG((int64_t)Ho * WQ < (int64_t)1 << 31, "mi3d_merge_masks3: output plane too large");
-    dim3 grid((unsigned)(((int64_t)Ho * WQ + BLK - 1) / BLK), (unsigned)Do);
-    const SrcStrides st{stride_d, stride_h, stride_w};
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec = Wo % NWV == 0 && ((uintptr_t)out & 15) == 0;
-    if (src_dtype == MI3D_SRC_U8) {
-        if (vec) merge_masks3_kernel<uint8_t, true><<<grid, BLK, 0, s>>>(m, out, Ho, Wo, WQ, index_d, index_h, index_w, st);
-        else merge_masks3_kernel<uint8_t, false><<<grid, BLK, 0, s>>>(m, out, Ho, Wo, WQ, index_d, index_h, index_w, st);
-    } else {
-        if (vec) merge_masks3_kernel<float, true><<<grid, BLK, 0, s>>>(m, out, Ho, Wo, WQ, index_d, index_h, index_w, st);
-        else merge_masks3_kernel<float, false><<<grid, BLK, 0, s>>>(m, out, Ho, Wo, WQ, index_d, index_h, index_w, st);
-    }
+    RowGrid g;
+    MI3D_TRY(row_grid(name, o, NWV, out, g));
+    const bool known = dispatch_src(src_dtype, Types<uint8_t, float>(), [&](auto tag) {
+        using S = decltype(tag);
+        auto kernel = g.vec ? merge_masks3_kernel<S, true> : merge_masks3_kernel<S, false>;
+        kernel<<<g.grid, BLK, 0, (hipStream_t)stream>>>(m, out, Ho, Wo, g.WQ, index_d, index_h, index_w, st);
+    });
+    MI3D_CHECK_ARG(known, "%s: masks are uint8 or float32, not dtype code %d", name, src_dtype);
     MI3D_LAUNCH_CHECK();
     return 0;
 }
@@ -458,9 +453,9 @@ int mi3d_merge_masks3(const mi3d_mask_list* masks, int src_dtype, int64_t stride
 int mi3d_restore_labels3(const uint8_t* grid, int Dg, int Hg, int Wg, uint8_t* out, int D, int H, int W, int64_t stride_d,
                          int64_t stride_h, int64_t stride_w, const int32_t* index_d, const int32_t* index_h, const int32_t* index_w,
                          void* stream) {
-    MI3D_CHECK_ARG(grid && out && grid != out && index_d && index_h && index_w, "mi3d_restore_labels3: null or aliased pointers");
-    MI3D_CHECK_ARG(dims_ok(Dg, Hg, Wg) && dims_ok(D, H, W), "mi3d_restore_labels3: sides must be in [1, %d]", MAX_SIDE);
-    MI3D_CHECK_ARG(strides_ok(stride_d, stride_h, stride_w), "mi3d_restore_labels3: strides must be positive element counts");
+    const SrcStrides st{stride_d, stride_h, stride_w};
+    MI3D_TRY(check_args("mi3d_restore_labels3", grid && out && grid != out && index_d && index_h && index_w, {Dg, Hg, Wg}, {D, H, W},
+                        nullptr, &st));
     // the destination's axes by increasing stride, an axis of one element last among equals: a[0] = F, a[1] = M, a[2] = S
     struct Axis { int n; int64_t os, gs; const int32_t* t; };
     Axis a[3] = {{D, stride_d, (int64_t)Hg * Wg, index_d}, {H, stride_h, (int64_t)Wg, index_h}, {W, stride_w, 1, index_w}};

@@ -37,7 +37,7 @@ _ROW = np.dtype([("idx", "<i4", (4,)), ("w", "<f8", (4,))])
 assert _ROW.itemsize == 48
 
 TABLE_CACHE_SIZE = 256     # device tables kept (least recently used first out); one chain with labels uses at most 9
-_device_tables = collections.OrderedDict()     # (n_in, n_out, order, device, flipped) -> device tensor
+_device_tables = collections.OrderedDict()     # (n_in, order or kind, output side(s), device, flipped) -> device tensor
 table_uploads = 0          # host-to-device table copies made so far (a stream of same-shaped scans adds none)
 
 
@@ -62,20 +62,22 @@ def _coords(n_in, n_out):
     return np.arange(n_out, dtype=np.float64) * z
 
 
+def _flipped(idx, n_in, flip):
+    """The one place a flip reaches a finished index table: RAS index i of an axis stored reversed is stored index n_in - 1 - i."""
+    return (int(n_in) - 1 - idx).astype(np.int32) if flip else idx
+
+
 def axis_table(n_in, n_out, order, flip=False):
     """Host tables of one axis, one row per output index.
     order 0: int32 (n_out,) input index floor(c + 0.5), clamped.
     order 3: (int32 (n_out, 4) tap indices floor(c) - 1 .. floor(c) + 2, each clamped; float64 (n_out, 4) B-spline weights).
     flip: the axis is stored reversed: the finished indices i become n_in - 1 - i, the weights stay."""
-    if flip:
-        t = axis_table(n_in, n_out, order)
-        return (int(n_in) - 1 - t).astype(np.int32) if order == 0 else ((int(n_in) - 1 - t[0]).astype(np.int32), t[1])
     n_in, n_out = int(n_in), int(n_out)
     if n_in < 1 or n_out < 1:
         raise Mi3dError(f"axis_table: sides must be positive, got {n_in} -> {n_out}")
     cc = _coords(n_in, n_out)
     if order == 0:
-        return np.clip(np.floor(cc + 0.5), 0, n_in - 1).astype(np.int32)
+        return _flipped(np.clip(np.floor(cc + 0.5), 0, n_in - 1).astype(np.int32), n_in, flip)
     if order != 3:
         raise Mi3dError(f"axis_table: order {order} is not supported (3 = cubic B-spline, 0 = nearest)")
     f = np.floor(cc)
@@ -85,7 +87,7 @@ def axis_table(n_in, n_out, order, flip=False):
                   (3.0 * t ** 3 - 6.0 * t ** 2 + 4.0) / 6.0,
                   (-3.0 * t ** 3 + 3.0 * t ** 2 + 3.0 * t + 1.0) / 6.0,
                   t ** 3 / 6.0], axis=1)
-    return idx, w
+    return _flipped(idx, n_in, flip), w
 
 
 def _upload(host, device):
@@ -115,20 +117,24 @@ def cubic_rows(n_in, n_out, flip=False):
     return rows
 
 
-def _device_table(n_in, n_out, order, device, flip=False):
-    key = (int(n_in), int(n_out), order, str(device), bool(flip))
-    return _cached(key, lambda: cubic_rows(n_in, n_out, flip) if order == 3 else axis_table(n_in, n_out, 0, flip), device)
-
-
 def composed_index_table(n_in, n_mid, n_out, flip=False):
     """Two order-0 zooms along one axis as ONE gather: table1[table2]; both built in RAS order, the result remapped for a flip."""
-    t = compose_index_tables(axis_table(n_in, n_mid, 0), axis_table(n_mid, n_out, 0))
-    return (int(n_in) - 1 - t).astype(np.int32) if flip else t
+    return _flipped(compose_index_tables(axis_table(n_in, n_mid, 0), axis_table(n_mid, n_out, 0)), n_in, flip)
 
 
-def _composed_index_table(n_in, n_mid, n_out, device, flip=False):
-    key = (int(n_in), (int(n_mid), int(n_out)), 0, str(device), bool(flip))
-    return _cached(key, lambda: composed_index_table(n_in, n_mid, n_out, flip), device)
+def _host_table(n_in, sides, order, flip):
+    if order == 3:
+        return cubic_rows(n_in, *sides, flip)
+    if order == "restore":
+        return _restore_table(n_in, *sides, flip)
+    return composed_index_table(n_in, *sides, flip) if len(sides) == 2 else axis_table(n_in, *sides, 0, flip)
+
+
+def _device_table(n_in, n_out, order, device, flip=False):
+    """The device table of one axis, through the cache.  order 3: cubic rows; order 0: nearest indices, or for n_out =
+    (n_mid, n_out) the composed ones; order "restore": restore_labels' table from a grid of n_in onto n_out."""
+    sides = n_out if isinstance(n_out, tuple) else (int(n_out),)
+    return _cached((int(n_in), order, *sides, device, bool(flip)), lambda: _host_table(n_in, sides, order, flip), device)
 
 
 def compose_index_tables(first, second):
@@ -169,22 +175,46 @@ def _labels(volume, what):
     return volume.contiguous().long()
 
 
-def _cubic(x, out_shape, out=None, ct_window=None):
-    dev = x.device
+_RasView = collections.namedtuple("_RasView", "shape strides flips device")
+
+
+def _ras(volume):
+    """A contiguous RAS tensor presented as a _Stored one, for the launch wrappers: its sides, their dense strides, no flips."""
+    _, h, w = volume.shape
+    return _RasView(volume.shape, (h * w, w, 1), (False, False, False), volume.device)
+
+
+def _gather(entry, source, code, src, out_shape, dtype, tabs, tail=(), out=None):
+    """The one launch form of the cubic, nearest and merge entries: source of dtype `code` seen through `src` (a _Stored, or a
+    contiguous tensor presented as one), the output and its three tables with their row counts."""
     if out is None:
-        out = torch.empty(out_shape, dtype=torch.float32, device=dev)
-    tabs = [_device_table(n, m, 3, dev) for n, m in zip(x.shape, out_shape)]
+        out = torch.empty(out_shape, dtype=dtype, device=src.device)
+    call(entry, source, code, *src.strides, ptr(out), *src.shape, *out_shape, ptr(tabs[0]), out_shape[0], ptr(tabs[1]), out_shape[1],
+         ptr(tabs[2]), out_shape[2], *tail, stream_ptr())
+    return out
+
+
+def _cubic(x, src, code, out_shape, out=None, ct_window=None):
+    tabs = [_device_table(n, m, 3, src.device, f) for n, m, f in zip(src.shape, out_shape, src.flips)]
     lo, hi = (float(ct_window[0]), float(ct_window[1])) if ct_window is not None else (0.0, 1.0)
-    call("mi3d_zoom3_cubic", ptr(x), ptr(out), *x.shape, *out_shape, ptr(tabs[0]), out_shape[0], ptr(tabs[1]), out_shape[1],
-         ptr(tabs[2]), out_shape[2], int(ct_window is not None), lo, hi, stream_ptr())
-    return out
+    return _gather("mi3d_zoom3_cubic_src", ptr(x), code, src, out_shape, torch.float32, tabs, (int(ct_window is not None), lo, hi), out)
 
 
-def _nearest(x, out_shape, tabs):
-    out = torch.empty(out_shape, dtype=torch.int64, device=x.device)
-    call("mi3d_zoom3_nearest_i64", ptr(x), ptr(out), *x.shape, *out_shape, ptr(tabs[0]), out_shape[0], ptr(tabs[1]),
-         out_shape[1], ptr(tabs[2]), out_shape[2], stream_ptr())
-    return out
+def _index_tables(src, shapes):
+    """Order-0 tables onto shapes[-1]; two shapes (stage 1, target) give both stages composed into one gather."""
+    return [_device_table(n, sides, 0, src.device, f) for n, sides, f in zip(src.shape, zip(*shapes), src.flips)]
+
+
+def _nearest(x, src, code, *shapes):
+    return _gather("mi3d_zoom3_nearest_src", ptr(x), code, src, shapes[-1], torch.int64, _index_tables(src, shapes))
+
+
+def _merge(tensors, values, code, src, *shapes):
+    m = _lib.MaskList()
+    m.n = len(tensors)
+    for k, (t, v) in enumerate(zip(tensors, values)):
+        m.mask[k], m.value[k] = ptr(t), v
+    return _gather("mi3d_merge_masks3", m, code, src, shapes[-1], torch.int64, _index_tables(src, shapes))
 
 
 def zoom(volume, factors, order=3):
@@ -196,8 +226,8 @@ def zoom(volume, factors, order=3):
     x = _image(volume, "zoom") if order == 3 else _labels(volume, "zoom")
     out_shape = _check_out_shape(zoom_output_shape(x.shape, factors), "zoom")
     if order == 3:
-        return _cubic(x, out_shape)
-    return _nearest(x, out_shape, [_device_table(n, m, 0, x.device) for n, m in zip(x.shape, out_shape)])
+        return _cubic(x, _ras(x), _lib.SRC_F32, out_shape)
+    return _nearest(x, _ras(x), _lib.SRC_I64, out_shape)
 
 
 def chain_shapes(shape, spacing, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192)):
@@ -218,9 +248,7 @@ def resample_labels_to_grid(label, spacing, target_spacing=(1.0, 1.0, 1.0), targ
     _check_volume(label, "resample_labels_to_grid")
     lab = _labels(label, "resample_labels_to_grid")
     _, shape1, _ = chain_shapes(lab.shape, spacing, target_spacing, target_shape)
-    target = tuple(int(n) for n in target_shape)
-    tabs = [_composed_index_table(n, m, o, lab.device) for n, m, o in zip(lab.shape, shape1, target)]
-    return _nearest(lab, target, tabs)
+    return _nearest(lab, _ras(lab), _lib.SRC_I64, shape1, tuple(int(n) for n in target_shape))
 
 
 def _workspace(shape1, device):
@@ -236,25 +264,36 @@ def resample_to_grid(image, spacing, label=None, target_spacing=(1.0, 1.0, 1.0),
     """The two-stage chain of the resampling scripts: zoom by spacing / target_spacing, then zoom to target_shape.
     Returns the float32 image on the target grid, and with `label` also the int64 label (both order-0 stages composed into
     one gather).  ct_window=(lo, hi) fuses preprocess_ct(lo, hi) into the last store."""
-    _check_volume(image, "resample_to_grid")
-    x = _image(image, "resample_to_grid")
-    if len(target_shape) != 3:
-        raise Mi3dError(f"resample_to_grid: target_shape needs three sides, got {target_shape}")
-    if ct_window is not None and not float(ct_window[1]) > float(ct_window[0]):
-        raise Mi3dError(f"resample_to_grid: empty CT window {ct_window}")
+    what = "resample_to_grid"
+    _check_volume(image, what)
+    x = _image(image, what)
+    target = _check_chain(what, target_shape, ct_window, image, label)
     if label is not None:
-        _check_volume(label, "resample_to_grid")
-        if tuple(label.shape) != tuple(image.shape):
-            raise Mi3dError(f"resample_to_grid: label {tuple(label.shape)} and image {tuple(image.shape)} differ in shape")
-        _check_integer(label, "resample_to_grid")            # before anything is launched
+        _check_integer(label, what)                          # before anything is launched
     _, shape1, _ = chain_shapes(x.shape, spacing, target_spacing, target_shape)
-    target = tuple(int(n) for n in target_shape)
-    stage1 = _workspace(shape1, x.device)
-    _cubic(x, shape1, out=stage1)
-    out = _cubic(stage1, target, ct_window=ct_window)
+    out = _cubic_chain(x, _ras(x), _lib.SRC_F32, _workspace(shape1, x.device), target, ct_window)
     if label is None:
         return out
     return out, resample_labels_to_grid(label, spacing, target_spacing, target_shape)
+
+
+def _check_chain(what, target_shape, ct_window=None, image=None, label=None):
+    """What resample_to_grid and resample_scan check alike; the target shape as a tuple of ints."""
+    if len(target_shape) != 3:
+        raise Mi3dError(f"{what}: target_shape needs three sides, got {target_shape}")
+    if ct_window is not None and not float(ct_window[1]) > float(ct_window[0]):
+        raise Mi3dError(f"{what}: empty CT window {ct_window}")
+    if label is not None:
+        _check_volume(label, what)
+        if tuple(label.shape) != tuple(image.shape):
+            raise Mi3dError(f"{what}: label {tuple(label.shape)} and image {tuple(image.shape)} differ in shape")
+    return tuple(int(n) for n in target_shape)
+
+
+def _cubic_chain(x, src, code, stage, target, ct_window):
+    """Both cubic stages: x seen through src onto the stage-1 workspace, that onto the target."""
+    _cubic(x, src, code, tuple(stage.shape), out=stage)
+    return _cubic(stage, _ras(stage), _lib.SRC_F32, target, ct_window=ct_window)
 
 
 # ---- scans as stored ----------------------------------------------------------------------------------------------------------
@@ -337,6 +376,9 @@ def _check_same_layout(other, image, src, what, kind):
 
 
 def _reorient(volume, src, code, as_label):
+    """The contiguous RAS copy of a stored volume; the volume itself (seen with the RAS axes) where its memory already is that."""
+    if src.identity and volume.dtype == (torch.int64 if as_label else torch.float32):
+        return src.ras_view(volume)
     out = torch.empty(src.shape, dtype=torch.int64 if as_label else torch.float32, device=volume.device)
     call("mi3d_reorient3", ptr(volume), code, ptr(out), int(as_label), *src.shape, *src.strides, src.flip_mask, stream_ptr())
     return out
@@ -352,28 +394,7 @@ def reorient_to_ras(volume, affine, as_label=None):
     if as_label is None:
         as_label = volume.dtype == torch.int64
     code = _check_dtype(volume, _LABEL_DTYPES if as_label else _IMAGE_DTYPES, what, "label" if as_label else "image")
-    if src.identity and volume.dtype == (torch.int64 if as_label else torch.float32):
-        return src.ras_view(volume), src.affine
     return _reorient(volume, src, code, as_label), src.affine
-
-
-def _cubic_stored(volume, src, code, out_shape, out):
-    tabs = [_device_table(n, m, 3, src.device, f) for n, m, f in zip(src.shape, out_shape, src.flips)]
-    call("mi3d_zoom3_cubic_src", ptr(volume), code, *src.strides, ptr(out), *src.shape, *out_shape, ptr(tabs[0]), out_shape[0],
-         ptr(tabs[1]), out_shape[1], ptr(tabs[2]), out_shape[2], 0, 0.0, 1.0, stream_ptr())
-    return out
-
-
-def _composed_tables(src, shape1, target):
-    return [_composed_index_table(n, m, o, src.device, f) for n, m, o, f in zip(src.shape, shape1, target, src.flips)]
-
-
-def _nearest_stored(label, src, code, shape1, target):
-    tabs = _composed_tables(src, shape1, target)
-    out = torch.empty(target, dtype=torch.int64, device=src.device)
-    call("mi3d_zoom3_nearest_src", ptr(label), code, *src.strides, ptr(out), *src.shape, *target, ptr(tabs[0]), target[0],
-         ptr(tabs[1]), target[1], ptr(tabs[2]), target[2], stream_ptr())
-    return out
 
 
 def _check_masks(masks, what):
@@ -399,24 +420,6 @@ def _check_masks(masks, what):
     return tensors, values, code
 
 
-def _merge_stored(tensors, values, code, src, shape1, target):
-    tabs = _composed_tables(src, shape1, target)
-    out = torch.empty(target, dtype=torch.int64, device=src.device)
-    m = _lib.MaskList()
-    m.n = len(tensors)
-    for k, (t, v) in enumerate(zip(tensors, values)):
-        m.mask[k], m.value[k] = ptr(t), v
-    call("mi3d_merge_masks3", m, code, *src.strides, ptr(out), *src.shape, *target, ptr(tabs[0]), target[0], ptr(tabs[1]),
-         target[1], ptr(tabs[2]), target[2], stream_ptr())
-    return out
-
-
-def _target(target_shape, what):
-    if len(target_shape) != 3:
-        raise Mi3dError(f"{what}: target_shape needs three sides, got {target_shape}")
-    return tuple(int(n) for n in target_shape)
-
-
 def _out_affine(src, target_spacing):
     out = src.affine.copy()
     out[:3, :3] = np.diag(np.asarray(target_spacing, dtype=np.float64))      # amos_ct_resample.py:77-78
@@ -429,7 +432,7 @@ def merge_masks_to_grid(masks, affine, target_spacing=(1.0, 1.0, 1.0), target_sh
     zeros on the current device (no mask file was found)."""
     what = "merge_masks_to_grid"
     tensors, values, code = _check_masks(masks, what)
-    target = _target(target_shape, what)
+    target = _check_chain(what, target_shape)
     if not tensors:
         orientation.io_orientation(affine)
         return torch.zeros(target, dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
@@ -437,7 +440,7 @@ def merge_masks_to_grid(masks, affine, target_spacing=(1.0, 1.0, 1.0), target_sh
     for k, t in enumerate(tensors[1:], 1):
         _check_same_layout(t, tensors[0], src, what, f"mask {k}")
     _, shape1, _ = chain_shapes(src.shape, orientation.spacing_of(src.affine), target_spacing, target)
-    return _merge_stored(tensors, values, code, src, shape1, target)
+    return _merge(tensors, values, code, src, shape1, target)
 
 
 def resample_scan(image, affine, label=None, masks=None, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192),
@@ -452,9 +455,7 @@ def resample_scan(image, affine, label=None, masks=None, target_spacing=(1.0, 1.
     what = "resample_scan"
     src = _Stored(image, affine, what)
     code = _check_dtype(image, _IMAGE_DTYPES, what, "image")
-    target = _target(target_shape, what)
-    if ct_window is not None and not float(ct_window[1]) > float(ct_window[0]):
-        raise Mi3dError(f"{what}: empty CT window {ct_window}")
+    target = _check_chain(what, target_shape, ct_window, image, label)
     if stage1 is not None and stage1 not in STAGE1_FORMS:
         raise Mi3dError(f"{what}: stage1 is one of {STAGE1_FORMS} or None, got {stage1!r}")
     if label is not None and masks is not None:
@@ -469,23 +470,22 @@ def resample_scan(image, affine, label=None, masks=None, target_spacing=(1.0, 1.
     _, shape1, _ = chain_shapes(src.shape, orientation.spacing_of(src.affine), target_spacing, target)
     # everything is checked: launch
     stage = _workspace(shape1, src.device)
-    if src.identity and image.dtype == torch.float32:
-        _cubic(src.ras_view(image), shape1, out=stage)                        # the contiguous float32 path, unchanged
-    elif (stage1 or STAGE1_DEFAULT[src.fastest]) == "fused":
-        _cubic_stored(image, src, code, shape1, stage)
+    if (stage1 or STAGE1_DEFAULT[src.fastest]) == "fused":
+        out = _cubic_chain(image, src, code, stage, target, ct_window)      # a contiguous float32 scan takes the contiguous kernel
     else:
-        _cubic(_reorient(image, src, code, False), shape1, out=stage)
-    out = _cubic(stage, target, ct_window=ct_window)
+        ras = _reorient(image, src, code, False)
+        out = _cubic_chain(ras, _ras(ras), _lib.SRC_F32, stage, target, ct_window)
     out_label = None
     if label is not None:
-        out_label = _nearest_stored(label, src, label_code, shape1, target)
+        out_label = _nearest(label, src, label_code, shape1, target)
     elif masks is not None:
-        out_label = _merge_stored(tensors, values, mask_code, src, shape1, target)
+        out_label = _merge(tensors, values, mask_code, src, shape1, target)
     return out, out_label, _out_affine(src, target_spacing)
 
 
 # ---- labels from the grid back onto the scan as stored -------------------------------------------------------------------------
 def _restore_table(n_grid, n_ras, flip):
+    """Not _flipped: here the flipped axis is the OUTPUT's, so the table is read backwards and its values (grid indices) stay."""
     t = axis_table(n_grid, n_ras, 0)
     return np.ascontiguousarray(t[::-1]) if flip else t
 
@@ -527,8 +527,7 @@ def restore_labels(labels, affine, stored):
     # everything is checked: launch
     grid = labels.contiguous()
     dev = grid.device
-    tabs = [_cached((int(g), int(n), "restore", str(dev), bool(f)), lambda g=g, n=n, f=f: _restore_table(g, n, f), dev)
-            for g, n, f in zip(grid.shape, dst.shape, dst.flips)]
+    tabs = [_device_table(g, n, "restore", dev, f) for g, n, f in zip(grid.shape, dst.shape, dst.flips)]
     out = torch.empty_strided(shape, strides, dtype=torch.uint8, device=dev)
     call("mi3d_restore_labels3", ptr(grid), *grid.shape, ptr(out), *dst.shape, *dst.strides, ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]),
          stream_ptr())

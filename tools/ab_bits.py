@@ -242,6 +242,61 @@ def battery():
         for s in [(2, 5, 9, 12), (1, 6, 6, 6)]:
             conv_bn_bwd(f"conv_bn_bwd{s}", *s)
 
+    # the resampling path (resample.hip) through resample.py: the small shapes of tests/test_gpu_orient_resample.py.  Target W = 11:
+    # scalar stores with a tail; W = 16: 16-byte stores.  One stored orientation per memory-fastest RAS axis (C-ordered: the last
+    # stored axis, RAS axis perm[2]), each with one flip; (5, 37, 70) for the tiles of the reorient kernel
+    def resample_ops():
+        from multimodal_segmentation_project_amd import resample
+        stored, spacing, targets = (7, 10, 13), (2.0, 0.8, 1.5), ((12, 9, 11), (12, 8, 16))
+        rng = np.random.default_rng(77)
+
+        def affine(perm, signs):
+            a = np.eye(4)
+            a[:3, :3] = 0.0
+            for i in range(3):
+                a[perm[i], i] = signs[i] * spacing[i]
+            return a
+
+        def store(arr, order="C"):
+            if order == "C":
+                return torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
+            return torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 1, 0))).to(dev).permute(2, 1, 0)
+
+        image = rng.integers(-1024, 3000, stored).astype(np.int16)
+        label = rng.integers(0, 16, stored, dtype=np.uint8)
+        x, lab = store(image.astype(np.float32)), store(label.astype(np.int64))
+        for fac in ((1.7, 0.9, 0.85), (1.7, 0.8, 1.25)):
+            put(f"resample/zoom3{fac}", resample.zoom(x, fac, order=3))
+            put(f"resample/zoom0{fac}", resample.zoom(lab, fac, order=0))
+        for target in targets:
+            img, out_lab = resample.resample_to_grid(x, spacing, label=lab, target_shape=target)
+            put(f"resample/to_grid{target}/image", img)
+            put(f"resample/to_grid{target}/label", out_lab)
+            put(f"resample/to_grid{target}/ct_window", resample.resample_to_grid(x, spacing, target_shape=target, ct_window=(-160.0, 240.0)))
+        masks = [(rng.random(stored) < 0.4).astype(np.uint8) * rng.integers(1, 256, stored, dtype=np.uint8) for _ in range(4)]
+        for perm, signs in (((1, 2, 0), (1, -1, 1)), ((0, 2, 1), (-1, 1, 1)), ((0, 1, 2), (1, 1, -1))):
+            aff, tag = affine(perm, signs), f"resample/fastest={perm[2]}"
+            for target in targets:
+                for form in resample.STAGE1_FORMS:
+                    for idt, ldt in ((np.int16, np.uint8), (np.float32, np.int64)):
+                        img, out_lab, _ = resample.resample_scan(store(image.astype(idt)), aff, label=store(label.astype(ldt)),
+                                                                 target_shape=target, stage1=form)
+                        put(f"{tag}/scan{target}/{form}/{np.dtype(idt).name}/image", img)
+                        put(f"{tag}/scan{target}/{form}/{np.dtype(ldt).name}/label", out_lab)
+                for mdt in (np.uint8, np.float32):
+                    got = resample.merge_masks_to_grid([(store(m.astype(mdt)), v) for m, v in zip(masks, (1, 2, 3, 3))], aff, target_shape=target)
+                    put(f"{tag}/merge{target}/{np.dtype(mdt).name}", got)
+            for order in "CF":
+                for shape in (stored, (5, 37, 70)):
+                    vol = np.random.default_rng(sum(shape)).integers(-1024, 3000, shape)
+                    for sdt, as_label in ((np.int16, False), (np.float32, False), (np.uint8, True), (np.int64, True)):
+                        got, _ = resample.reorient_to_ras(store(vol.astype(sdt), order), aff, as_label=as_label)
+                        put(f"{tag}/reorient{shape}/{order}/{np.dtype(sdt).name}", got)
+                grid = torch.from_numpy(rng.integers(0, 16, targets[0], dtype=np.uint8)).to(dev)
+                put(f"{tag}/restore/{order}", resample.restore_labels(grid, aff, store(image, order)))
+
+    resample_ops()
+
     # whole network, eager: three steps at 32^3 (N = 2), one at 96^3 (N = 1); bf16, dropout 0.3
     for size, n, steps in ((32, 2, 3), (96, 1, 1)):
         torch.manual_seed(11)
