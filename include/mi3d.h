@@ -367,6 +367,59 @@ int mi3d_restore_labels3(const uint8_t* grid, int Dg, int Hg, int Wg, uint8_t* o
                          int64_t stride_h, int64_t stride_w, const int32_t* index_d, const int32_t* index_h, const int32_t* index_w,
                          void* stream);
 
+/* The preview figure of the reference's test loop (visualize_prediction, test_model.py:66-193, called at :299-305 on whole host
+ * copies of the image, the label and the prediction) and the slider of visualize_nifti.py:29-52, computed where the volumes are.
+ * Every volume is a dense 3-D array of sides D, H, W (the reference's axes 0, 1, 2) seen through element strides, as the source
+ * of mi3d_zoom3_nearest_src: a contiguous training-grid tensor and a scan as stored go through the same code.  Labels are uint8
+ * or int64, images float32 or int16 (an int16 voxel counts as the float32 of it).  The image must be finite: the minimum and
+ * maximum of a slice with a NaN or an Inf are not defined here.  All entries allocate nothing, do not synchronise and return a
+ * negative value for null pointers, sides outside [1, 65535], non-positive strides and unknown dtype / mode codes.
+ *
+ * mi3d_preview_workspace_bytes: enough for the counts (D + H + W int64), three int32 indices (16 bytes) and 2 keys for every
+ * slice of the longest axis; the caller lays the pieces out, ZEROES counts and keys before the calls below, and may hand counts
+ * and indices to its user.  0 (and an error) for bad sides. */
+size_t mi3d_preview_workspace_bytes(int D, int H, int W);
+/* find_best_slice's np.sum(label_volume > 0, axis=...) (test_model.py:77-82) for all three axes in ONE read of the label:
+ * counts[i] += #{label > 0 in slice i of axis 0}, counts[D + i] of axis 1, counts[D + H + i] of axis 2; counts zeroed by the
+ * caller.  A label >= 4 counts, a negative one does not.  The volume is walked in memory order whichever axis is stored fastest:
+ * register columns per lane along it, shuffle sums along the next, then LDS and 64-bit integer atomics; integer sums in any
+ * order are the same sum, so the result is exact and the same bits every run.  16-byte loads where the rows are 16-byte aligned
+ * and the fastest side is a multiple of 16 (uint8) or 2 (int64); one element per lane otherwise. */
+int mi3d_foreground_profiles(const void* label, int label_dtype, int D, int H, int W, int64_t stride_d, int64_t stride_h,
+                             int64_t stride_w, int64_t* counts, void* stream);
+/* best[a] = np.argmax(counts of axis a), the FIRST maximum, or n_a // 2 where that maximum is 0 (test_model.py:85-89), for
+ * a = 0, 1, 2; counts as mi3d_foreground_profiles leaves them.  The indices stay on the device for the two entries below. */
+int mi3d_best_slices(const int64_t* counts, int D, int H, int W, int32_t* best, void* stream);
+/* Which slices an entry covers.  STACK: every slice of `axis`, slot i = slice i.  ONE: one slice of `axis`, slot 0; its index is
+ * read from index[0] on the device when index != NULL, else it is k (checked).  THREE: the slice index[a] of every axis a, slot
+ * a (`axis` and k unused).  An index read from device memory is clamped to the axis. */
+enum { MI3D_PREVIEW_STACK = 0, MI3D_PREVIEW_ONE = 1, MI3D_PREVIEW_THREE = 2 };
+/* overlay.min() and overlay.max() (test_model.py:110) of each covered slice, as two uint32 keys per slot that start from ZERO
+ * (the caller's): keys[2 s] = max over the slice of key(v), keys[2 s + 1] = max of ~key(v), with key(v) = bits ^ 0xffffffff for a
+ * negative float and bits | 0x80000000 otherwise (the float order as an unsigned order; never 0 for a finite v).  Unsigned
+ * atomic maxima: any order gives the same pair.  -0.0 orders below +0.0 here; which of the two numpy returns is not defined. */
+int mi3d_slice_minmax(const void* image, int image_dtype, int D, int H, int W, int64_t stride_d, int64_t stride_h, int64_t stride_w,
+                      int axis, int mode, const int32_t* index, int k, uint32_t* keys, void* stream);
+/* create_overlay (test_model.py:103-125, the same function as visualize_nifti.py:29-52) per output pixel, in IEEE double with
+ * every operation rounded on its own: g = ((double)v - min) / (max - min) from the slice's keys, rgb = (g, g, g), replaced by
+ * (1, 0, 0) for label 1, (1, 0.65, 0) for label 2, (0, 0.5, 0) for label 3; any other label keeps the grey; a flat slice gives
+ * 0 / 0 = NaN wherever no colour replaces it, as numpy does.  The slice of axis 0 / 1 / 2 is the 2-D array over axes (1, 2) /
+ * (0, 2) / (0, 1), sides (A, B); rot90 != 0 writes np.rot90 of it, out[i][j] = slice[j][B - 1 - i], (B, A) pixels.
+ * out_dtype: F64 the reference's own bits, F32 one rounding of them, U8 (255 * value).astype(np.uint8): truncation, NaN -> 0.
+ *   STACK, ONE   outs[0] = (n_axis, R, C, 3) or (R, C, 3); pred must be NULL.  16-byte stores where C is a multiple of 2 (F64),
+ *                4 (F32) or 16 (U8) pixels and outs[0] is 16-byte aligned.  A stack whose image is stored fastest along the slice
+ *                axis or along R is read with lanes along that axis and turned through LDS tiles; the bits do not depend on it.
+ *   THREE        the 3 x 3 figure of test_model.py:127-179 in one launch, rot90 required: outs[3 v + 0 / 1 / 2] = float32 (R, C)
+ *                raw slice, overlay of `label`, overlay of `pred`, for v = 0, 1, 2 = axial (axis 2), sagittal (axis 0), coronal
+ *                (axis 1).  label and pred may differ in dtype and strides.
+ * *_strides: three element strides each, HOST arrays read before the call returns.  outs: a HOST array of device pointers.
+ * keys: what mi3d_slice_minmax left for the same axis / mode / index. */
+enum { MI3D_OVERLAY_F64 = 0, MI3D_OVERLAY_F32 = 1, MI3D_OVERLAY_U8 = 2 };
+int mi3d_overlay_render(const void* image, int image_dtype, const int64_t* image_strides, const void* label, int label_dtype,
+                        const int64_t* label_strides, const void* pred, int pred_dtype, const int64_t* pred_strides, int D, int H, int W,
+                        int axis, int mode, const int32_t* index, int k, int rot90, const uint32_t* keys, int out_dtype,
+                        void* const* outs, void* stream);
+
 /* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
  * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)
  * with the random decisions already drawn by the host (spatial.py), as one gather pass.  img: float32, lab: int64, both

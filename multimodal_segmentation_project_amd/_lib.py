@@ -41,6 +41,8 @@ class AugParams(C.Structure):                      # mi3d_aug_params
 
 MAX_MASKS = 8
 SRC_U8, SRC_I16, SRC_F32, SRC_I64 = 0, 1, 2, 3
+PREVIEW_STACK, PREVIEW_ONE, PREVIEW_THREE = 0, 1, 2      # mi3d_slice_minmax / mi3d_overlay_render modes
+OVERLAY_F64, OVERLAY_F32, OVERLAY_U8 = 0, 1, 2
 
 
 class MaskList(C.Structure):                       # mi3d_mask_list
@@ -140,6 +142,12 @@ _SIGS = {
     "mi3d_zoom3_nearest_src": (i32, [vp, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_merge_masks3": (i32, [_MP, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_restore_labels3": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp]),
+    "mi3d_preview_workspace_bytes": (sz, [i32, i32, i32]),
+    "mi3d_foreground_profiles": (i32, [vp, i32, i32, i32, i32, i64, i64, i64, vp, vp]),
+    "mi3d_best_slices": (i32, [vp, i32, i32, i32, vp, vp]),
+    "mi3d_slice_minmax": (i32, [vp, i32, i32, i32, i32, i64, i64, i64, i32, i32, vp, i32, vp, vp]),
+    "mi3d_overlay_render": (i32, [vp, i32, C.POINTER(i64), vp, i32, C.POINTER(i64), vp, i32, C.POINTER(i64), i32, i32, i32, i32, i32, vp,
+                                  i32, i32, vp, i32, C.POINTER(vp), vp]),
     "mi3d_plane_affine": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp]),
     "mi3d_augment_workspace_bytes": (sz, []),
     "mi3d_augment": (i32, [vp, vp, vp, i32, i32, i32, i32, _AP, vp, sz, vp]),

@@ -7,8 +7,9 @@ test_model.py:242-309 (model(image), torch.argmax(outputs, dim=1), the per-sampl
 
 The logits never reach memory: the network runs with logits = NULL (mi3d_unet_infer) and the 1x1x1 head, the argmax and the counts
 are one pass over the decoder output (mi3d_unet_head_labels), which writes 1 byte per voxel where the logits route writes 16 and
-re-reads them twice.  Every label is the first maximum of exactly the logits model(x) would return.  File reading / writing,
-plots and sliding windows stay outside.
+re-reads them twice.  Every label is the first maximum of exactly the logits model(x) would return.  The arrays of the loop's preview figure (visualize_prediction, test_model.py:299-305)
+are preview.prediction_panels' work, on the device as well.  File reading / writing, drawing (matplotlib) and sliding windows
+stay outside.
 """
 import ctypes as C
 

@@ -1086,6 +1086,62 @@ def gen_segment(out):
         f.write(f"scipy {scipy.__version__}, numpy {np.__version__}\n")
 
 
+def gen_preview(out):
+    """preview.npz: the nine arrays the reference's own visualize_prediction (test_model.py:66-193) hands to imshow, for the cases of
+    tests/preview_ref.py (RECORDED).  test_model is imported through the stubs, its plt replaced by a stand-in whose axes keep every
+    imshow argument; nothing is drawn.  Per case: image (float32), label and pred (uint8 copies; the reference is called with an
+    int64 label and a uint8 prediction), panel_0 .. panel_8 in figure order (float32 raw slices, float64 (H, W, 3) overlays, all
+    after np.rot90) and best, the slice indices by axis that the raw panels imply (checked below)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import preview_ref as P
+    _import_reference()
+    import test_model as ref_test
+
+    class _Quiet:                                  # fig, plt: every attribute is a callable that does nothing
+        def __getattr__(self, name):
+            return lambda *a, **k: None
+
+    class _Axes(_Quiet):
+        def __init__(self):
+            self.shown = []
+
+        def imshow(self, array, **kw):
+            self.shown.append(np.array(array, copy=True))
+
+    class _Plt(_Quiet):
+        def subplots(self, rows, cols, **kw):
+            self.axes = np.empty((rows, cols), dtype=object)
+            for i in range(rows * cols):
+                self.axes.flat[i] = _Axes()
+            return _Quiet(), self.axes
+
+    d = {}
+    for case, shape in P.RECORDED:
+        image, label, pred = P.make_case(case, shape)
+        plt = ref_test.plt = _Plt()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ref_test.visualize_prediction(image, label[None], pred[None], "unused.png")      # np.squeeze drops the batch dim (:72-73)
+        shown = [ax.shown for ax in plt.axes.flat]
+        assert all(len(s) == 1 for s in shown), [len(s) for s in shown]
+        best = P.best_slices(label)
+        pre = P.key(case, shape)
+        for v, a in enumerate(P.VIEW_AXES):
+            raw, gt, pr = (shown[3 * v + j][0] for j in range(3))
+            assert raw.dtype == np.float32 and gt.dtype == np.float64 and pr.dtype == np.float64
+            assert np.array_equal(raw, np.rot90(P.take_slice(image, a, best[a]))), (case, shape, a)
+            assert gt.shape == raw.shape + (3,) and pr.shape == gt.shape
+            d[f"{pre}/panel_{3 * v}"], d[f"{pre}/panel_{3 * v + 1}"], d[f"{pre}/panel_{3 * v + 2}"] = raw, gt, pr
+        assert label.max() <= 255
+        d[f"{pre}/image"], d[f"{pre}/label"], d[f"{pre}/pred"], d[f"{pre}/best"] = image, label.astype(np.uint8), pred, best
+    np.savez_compressed(os.path.join(out, "preview.npz"), **d)
+    with open(os.path.join(out, "PROVENANCE_preview.txt"), "w") as f:
+        f.write("preview.npz: generated by\ntools/gen_golden.py --only preview\n")
+        f.write("panel_0 .. panel_8: the arrays the reference's own visualize_prediction (test_model.py:66-193,\n")
+        f.write("fransiskusbudi/multimodal_segmentation_project @ 2025-08-24) passed to imshow, in figure order, recorded by a stand-in for\n")
+        f.write("its plt; inputs are the seeded cases of tests/preview_ref.py (make_case, RECORDED).  Nothing of the reference is copied.\n")
+        f.write(f"numpy {np.__version__}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -1103,7 +1159,8 @@ def main():
     if want("resample"): gen_resample(a.out)              # needs scipy only, not the reference tree
     if want("spatial"): gen_spatial(a.out)                # scipy + the reference's utils/dataloader.py
     if want("segment"): gen_segment(a.out)                # scipy only
-    if only <= {"resample", "spatial", "segment"} and only:
+    if want("preview"): gen_preview(a.out)                # the reference's test_model.py, numpy only
+    if only <= {"resample", "spatial", "segment", "preview"} and only:
         return
     ref_unet, ref_unet_dann, ref_metrics, ref_train_unet, ref_train_dann = _import_reference()
     if want("small_unet"): gen_small_unet(ref_unet, ref_metrics, a.out)
