@@ -232,6 +232,13 @@ def call(name, *args):
     check(getattr(lib(), name)(*args), name)
 
 
+def new_event():
+    """Handle of a new event (mi3d_event_create); whoever keeps it destroys it with mi3d_event_destroy."""
+    e = C.c_void_p()
+    call("mi3d_event_create", C.byref(e))
+    return e.value
+
+
 def get_route(name):
     """Current value of a kernel-selection switch (include/mi3d.h mi3d_debug_get_route; the table is in INTEGRATION.md)."""
     v = C.c_int()

@@ -1,21 +1,21 @@
 """Host-side engine: binds the reference's nn.Module surface to the whole-network HIP plan (csrc/plan.hip).
 
-One autograd node per network forward: ``_UNetFn.forward`` makes ONE C call that launches every forward kernel,
+``Plan`` is the call layer every host path goes through: it owns the descriptor, the pointer tables and the argument order of
+each mi3d_unet_* entry; ``LossGroup`` is what the loss calls share.  One autograd node per network forward: ``_UNetFn.forward`` makes ONE C call that launches every forward kernel,
 ``_UNetFn.backward`` makes one C call per backward segment (so data-parallel gradient all-reduces can be
 interleaved, see dp.py).  PyTorch only owns memory (params, buffers, logits, the workspace) and the stream.
 
 Reference surface mirrored here: models/unet.py:64-90 and models/unet_dann.py:65-98 (forward), the autograd
 backward triggered by train_unet.py:225 / train_dann.py:286.
 """
+import copy
 import ctypes as C
-import threading
 
 import torch
 
 from . import _lib
 from ._lib import UNetDesc, call, ptr, ptr_table, stream_ptr
 
-_state = threading.local()
 _default_compute_dtype = None
 
 
@@ -43,8 +43,10 @@ def resolve_compute_dtype(model):
 
 
 def build_desc(model, x, dtype):
-    if x.dim() != 5:
-        raise _lib.Mi3dError(f"expected a (N,C,D,H,W) input, got shape {tuple(x.shape)}")
+    """Descriptor for the input x (a tensor or its shape)."""
+    shape = tuple(getattr(x, "shape", x))
+    if len(shape) != 5:
+        raise _lib.Mi3dError(f"expected a (N,C,D,H,W) input, got shape {shape}")
     feats = [blk.double_conv[0].out_channels for blk in model.encoder]
     if len(feats) > _lib.MAX_LEVELS:
         raise _lib.Mi3dError(f"{len(feats)} levels > {_lib.MAX_LEVELS}")
@@ -54,9 +56,9 @@ def build_desc(model, x, dtype):
     d.n_levels = len(feats)
     for i, f in enumerate(feats):
         d.features[i] = f
-    d.N, d.D, d.H, d.W = x.shape[0], x.shape[2], x.shape[3], x.shape[4]
-    if x.shape[1] != d.in_channels:
-        raise _lib.Mi3dError(f"input has {x.shape[1]} channels, model expects {d.in_channels}")
+    d.N, d.D, d.H, d.W = shape[0], shape[2], shape[3], shape[4]
+    if shape[1] != d.in_channels:
+        raise _lib.Mi3dError(f"input has {shape[1]} channels, model expects {d.in_channels}")
     d.dtype = _lib.dtype_code(dtype)
     bn = model.encoder[0].double_conv[1]
     if bn.momentum is None:
@@ -67,11 +69,6 @@ def build_desc(model, x, dtype):
     return d
 
 
-class _Hold:
-    """Per-call context handed to the autograd node (not a tensor)."""
-    __slots__ = ("desc", "training", "buffers", "want_gap", "ws_bytes", "n_enc_params", "segment_hook")
-
-
 def _rng_state(model, device):
     st = getattr(model, "_mi3d_rng_state", None)
     if st is None or st.device != device:
@@ -80,33 +77,157 @@ def _rng_state(model, device):
     return st
 
 
-def make_drop_scales(model, desc, p, device, injected=None):
-    """Dropout3d channel scales for all 2*(2L+1) dropout layers (models/unet.py:14,18) in ONE kernel launch."""
-    n = _lib.lib().mi3d_unet_dropout_count(C.byref(desc))
+def fill_drop_scales(buf, p, rng, injected=None, stream=None):
+    """Dropout scales into the device float buffer `buf`: the injected ones (tests), or ONE mi3d_dropout_scales draw of rate p
+    that advances the device RNG state `rng` (a callable: a draw that does not happen creates no state).  Returns buf, or None
+    for "no dropout" (p = 0 and nothing injected)."""
     if injected is not None:
-        if injected.numel() != n:
-            raise _lib.Mi3dError(f"injected dropout scales have {injected.numel()} entries, plan needs {n}")
-        return injected.to(device=device, dtype=torch.float32).contiguous()
-    out = torch.empty(n, dtype=torch.float32, device=device)
-    call("mi3d_dropout_scales", ptr(out), n, float(p), ptr(_rng_state(model, device)), stream_ptr())
-    return out
+        if injected.numel() != buf.numel():
+            raise _lib.Mi3dError(f"injected dropout scales have {injected.numel()} entries, plan needs {buf.numel()}")
+        buf.copy_(injected.reshape(buf.shape))
+        return buf
+    if p > 0.0:
+        call("mi3d_dropout_scales", ptr(buf), buf.numel(), p, ptr(rng()), stream_ptr() if stream is None else stream)
+        return buf
+    return None
+
+
+def make_drop_scales(model, desc, p, device, injected=None):
+    """Dropout3d channel scales for all 2*(2L+1) dropout layers (models/unet.py:14,18) in ONE kernel launch: a new buffer holding
+    the injected scales or a draw of rate p; None when p == 0 and nothing is injected."""
+    out = torch.empty(_lib.lib().mi3d_unet_dropout_count(C.byref(desc)), dtype=torch.float32, device=device)
+    return fill_drop_scales(out, float(p), lambda: _rng_state(model, device), injected)
+
+
+# `training` of Plan.forward / forward_loss (include/mi3d.h, mi3d_unet_forward): 0 = eval mode (running statistics), else
+TRAIN = 1               # batch statistics, running statistics updated in place
+BN_PUBLISH = 2          # batch statistics, the update deferred: (mean, unbiased variance) published as doubles into the side buffers
+#                         the running_mean slots of the buffer table point at; Plan.bn_apply_deferred applies them later
+THIN_CONSUMERS = 4      # or-ed to either: another forward runs beside this one, the BatchNorm apply passes stay thin
+
+
+class LossGroup:
+    """What the loss calls share: the configuration, metrics = {loss, iou, dice, acc, ...} (device float[n_metrics]; the loss
+    is written to [0], the three metrics to [1:4]), the 20 loss coefficients the backward reads, and the two workspaces."""
+
+    def __init__(self, cfg, classes, device, n_metrics=4):
+        lib = _lib.lib()
+        self.cfg = cfg
+        self.metrics = torch.empty(n_metrics, dtype=torch.float32, device=device)
+        self.coef = torch.empty(_lib.LOSS_COEF_FLOATS, dtype=torch.float32, device=device)
+        self.loss_ws = torch.empty(lib.mi3d_seg_loss_workspace_bytes(classes), dtype=torch.uint8, device=device)
+        self.met_ws = torch.empty(lib.mi3d_seg_metrics_workspace_bytes(classes), dtype=torch.uint8, device=device)
+        m = self.metrics.data_ptr()
+        self.cfg_ref = C.byref(cfg)
+        self.fwd = (self.cfg_ref, m, ptr(self.coef), m + 4, ptr(self.loss_ws), ptr(self.met_ws))      # as every forward takes them
+
+    def metrics_forward(self, logits, labels, *, teacher=None, stream):
+        """Loss + metrics of (N, C, D, H, W) float logits in one pass (mi3d_seg_loss_metrics_forward)."""
+        n, c, d = logits.shape[:3]
+        call("mi3d_seg_loss_metrics_forward", ptr(logits), ptr(labels), ptr(teacher), n, c, d, logits.numel() // (n * c), *self.fwd, stream)
+
+    def backward(self, logits, labels, dlogits, *, teacher=None, grad_scale, stream):
+        """dlogits = grad_scale[0] * d loss / d logits (mi3d_seg_loss_backward) from the coefficients the forward left."""
+        n, c = logits.shape[:2]
+        call("mi3d_seg_loss_backward", ptr(logits), ptr(labels), ptr(teacher), n, c, logits.numel() // (n * c), self.cfg_ref, ptr(self.coef),
+             ptr(grad_scale), ptr(dlogits), stream)
+
+
+class Plan:
+    """One whole-network call sequence: descriptor, workspace size (queried once), parameter / buffer / gradient pointer tables
+    and, after own_workspace(), the workspace.  One method per mi3d_unet_* entry, keyword arguments, tensors (or None) for
+    pointers: the argument order of include/mi3d.h is written down here and nowhere else."""
+
+    def __init__(self, model, shape, dtype, params=None, buffers=None, grads=None):
+        self.desc = build_desc(model, shape, dtype)
+        self.d = C.byref(self.desc)
+        self.ws_bytes = _lib.lib().mi3d_unet_workspace_bytes(self.d)
+        if self.ws_bytes == 0:
+            _lib.check(-1, "mi3d_unet_workspace_bytes")
+        self.ws = self.ws_ptr = self.gtab = None
+        self.set_tables(list(model.parameters()) if params is None else params,
+                        list(model.buffers()) if buffers is None else buffers, grads)
+
+    def set_tables(self, params=None, buffers=None, grads=None):
+        """Tables from tensors (grads: device addresses, None = no gradient wanted); what is None stays."""
+        if params is not None:
+            self.params, self.ptab = list(params), ptr_table([p.data_ptr() for p in params])
+        if buffers is not None:
+            self.buffers, self.btab = list(buffers), ptr_table([ptr(b) for b in buffers])
+        if grads is not None:
+            self.gtab = ptr_table(list(grads))
+
+    def own_workspace(self, device):
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+        self.ws_ptr = self.ws.data_ptr()
+        return self
+
+    def release_workspace(self):
+        """Give the workspace back; a call made afterwards passes NULL, which the library refuses."""
+        self.ws = self.ws_ptr = None
+
+    def sibling(self, device, **tables):
+        """A second call sequence of the same descriptor with a workspace of its own (the distillation teacher, DANN's target
+        graph); tables that are not given are shared."""
+        p = copy.copy(self)
+        p.set_tables(**tables)
+        return p.own_workspace(device)
+
+    def forward(self, x, *, drop=None, training=TRAIN, logits=None, gap=None, stream):
+        call("mi3d_unet_forward", self.d, ptr(x), self.ptab, self.btab, ptr(drop), training, ptr(logits), ptr(gap),
+             self.ws_ptr, self.ws_bytes, stream)
+
+    def infer(self, x, *, logits=None, gap=None, stream):
+        call("mi3d_unet_infer", self.d, ptr(x), self.ptab, self.btab, ptr(logits), ptr(gap), self.ws_ptr, self.ws_bytes, stream)
+
+    def forward_loss(self, x, loss, *, drop=None, training=TRAIN, labels, teacher=None, logits=None, gap=None, stream):
+        call("mi3d_unet_forward_loss", self.d, ptr(x), self.ptab, self.btab, ptr(drop), training, ptr(labels), ptr(teacher),
+             *loss.fwd, ptr(logits), ptr(gap), self.ws_ptr, self.ws_bytes, stream)
+
+    def head_loss_forward(self, loss, *, labels, teacher=None, logits=None, stream):
+        call("mi3d_unet_head_loss_forward", self.d, self.ptab, ptr(labels), ptr(teacher), *loss.fwd, ptr(logits),
+             self.ws_ptr, self.ws_bytes, stream)
+
+    def backward(self, x, *, drop=None, dlogits=None, dgap=None, gap_scale=1.0, accumulate=0, start, end, stream, aux=None,
+                 events=None, join=1):
+        call("mi3d_unet_backward", self.d, ptr(x), self.ptab, self.gtab, ptr(drop), ptr(dlogits), ptr(dgap), gap_scale,
+             accumulate, start, end, self.ws_ptr, self.ws_bytes, stream, aux, events, join)
+
+    def backward_loss(self, x, loss, *, drop=None, labels, teacher=None, grad_scale, dgap=None, gap_scale=1.0, accumulate=0,
+                      start, end, stream, aux=None, events=None, join=1):
+        call("mi3d_unet_backward_loss", self.d, ptr(x), self.ptab, self.gtab, ptr(drop), ptr(labels), ptr(teacher), loss.cfg_ref,
+             ptr(loss.coef), ptr(grad_scale), ptr(dgap), gap_scale, accumulate, start, end, self.ws_ptr, self.ws_bytes, stream,
+             aux, events, join)
+
+    def head_labels(self, *, labels=None, out, counts=None, head_ws=None, stream):
+        call("mi3d_unet_head_labels", self.d, self.ptab, ptr(labels), ptr(out), ptr(counts), ptr(head_ws), self.ws_ptr,
+             self.ws_bytes, stream)
+
+    def bn_apply_deferred(self, side, *, stream):
+        """side: the Plan whose buffer table holds the side buffers a BN_PUBLISH forward filled."""
+        call("mi3d_unet_bn_apply_deferred", self.d, self.btab, side.btab, stream)
+
+
+def _outputs(desc, want_gap, device):
+    logits = torch.empty((desc.N, desc.out_channels, desc.D, desc.H, desc.W), dtype=torch.float32, device=device)
+    gap = None
+    if want_gap:
+        gap = torch.empty((desc.N, 2 * desc.features[desc.n_levels - 1]), dtype=torch.float32, device=device)
+    return logits, gap
+
+
+class _Hold:
+    """Per-call context handed to the autograd node (not a tensor)."""
+    __slots__ = ("plan", "training", "want_gap", "segment_hook")
 
 
 class _UNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hold, x, drop, *params):
-        desc = hold.desc
-        dev = x.device
-        ws = torch.empty(hold.ws_bytes, dtype=torch.uint8, device=dev)
-        logits = torch.empty((desc.N, desc.out_channels, desc.D, desc.H, desc.W), dtype=torch.float32, device=dev)
-        gap = None
-        if hold.want_gap:
-            gap = torch.empty((desc.N, 2 * desc.features[desc.n_levels - 1]), dtype=torch.float32, device=dev)
-        ptab = ptr_table([p.data_ptr() for p in params])
-        btab = ptr_table([b.data_ptr() for b in hold.buffers])
-        call("mi3d_unet_forward", C.byref(desc), ptr(x), ptab, btab, ptr(drop), int(hold.training), ptr(logits),
-             ptr(gap), ptr(ws), hold.ws_bytes, stream_ptr())
-        ctx.hold, ctx.ws, ctx.drop = hold, ws, drop
+        plan = hold.plan.own_workspace(x.device)
+        logits, gap = _outputs(plan.desc, hold.want_gap, x.device)
+        plan.forward(x, drop=drop, training=int(hold.training), logits=logits, gap=gap, stream=stream_ptr())
+        ctx.hold, ctx.drop = hold, drop
         ctx.save_for_backward(x, *params)
         ctx.set_materialize_grads(False)
         if gap is None:
@@ -116,7 +237,7 @@ class _UNetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, dgap=None):
         hold = ctx.hold
-        desc = hold.desc
+        plan = hold.plan
         x, *params = ctx.saved_tensors
         if dlogits is None and dgap is None:
             return (None, None, None) + (None,) * len(params)
@@ -130,81 +251,53 @@ class _UNetFn(torch.autograd.Function):
         if dgap is not None:
             dgap = dgap.contiguous().float()
         # without a logits gradient only encoder + bottleneck parameters receive gradient (DANN target pass)
-        n_live = len(params) if dlogits is not None else hold.n_enc_params
+        n_live = len(params) if dlogits is not None else 8 * (plan.desc.n_levels + 1)
         grads = [torch.empty_like(p) if (i < n_live and ctx.needs_input_grad[3 + i]) else None
                  for i, p in enumerate(params)]
-        ptab = ptr_table([p.data_ptr() for p in params])
-        gtab = ptr_table([g.data_ptr() if g is not None else None for g in grads])
-        nseg = 2 * desc.n_levels + 2
-        hook = hold.segment_hook
-        for seg in range(nseg):
-            call("mi3d_unet_backward", C.byref(desc), ptr(x), ptab, gtab, ptr(ctx.drop), ptr(dlogits), ptr(dgap),
-                 1.0, 0, seg, seg + 1, ptr(ctx.ws), hold.ws_bytes, stream_ptr(), None, None, 1)
-            if hook is not None:
-                hook(seg, grads)
-        ctx.ws = None
+        plan.set_tables(grads=[ptr(g) for g in grads])
+        for seg in range(2 * plan.desc.n_levels + 2):      # one call per segment: the hook may exchange gradients between them (dp.py)
+            plan.backward(x, drop=ctx.drop, dlogits=dlogits, dgap=dgap, start=seg, end=seg + 1, stream=stream_ptr())
+            if hold.segment_hook is not None:
+                hold.segment_hook(seg, grads)
+        plan.release_workspace()
         return (None, None, None) + tuple(grads)
 
 
-def _infer(model, x, desc, hold, params, want_gap):
-    dev = x.device
-    ws = torch.empty(hold.ws_bytes, dtype=torch.uint8, device=dev)
-    logits = torch.empty((desc.N, desc.out_channels, desc.D, desc.H, desc.W), dtype=torch.float32, device=dev)
-    gap = None
-    if want_gap:
-        gap = torch.empty((desc.N, 2 * desc.features[desc.n_levels - 1]), dtype=torch.float32, device=dev)
-    ptab = ptr_table([p.data_ptr() for p in params])
-    btab = ptr_table([b.data_ptr() for b in hold.buffers])
-    call("mi3d_unet_infer", C.byref(desc), ptr(x), ptab, btab, ptr(logits), ptr(gap), ptr(ws), hold.ws_bytes, stream_ptr())
-    if model.output_activation is not None:
-        logits = model.output_activation(logits)
-    return logits, gap
-
-
 def plan_call(model, x):
-    """What every whole-network call needs besides its outputs, checked: (descriptor, parameters, buffers, workspace bytes) for the
-    float32 (N,C,D,H,W) device input x.  Shared by unet_forward and segment.predict_labels."""
+    """The checked Plan of a whole-network call on the float32 (N,C,D,H,W) device input x (no workspace yet).  Shared by
+    unet_forward and segment.predict_labels."""
     params = list(model.parameters())
     for p in params:
         _lib.require_cuda(p, "UNet3D parameter")
-    desc = build_desc(model, x, resolve_compute_dtype(model))
-    buffers = list(model.buffers())
-    ws_bytes = _lib.lib().mi3d_unet_workspace_bytes(C.byref(desc))
-    if ws_bytes == 0:
-        _lib.check(-1, "mi3d_unet_workspace_bytes")
-    expect = _lib.lib().mi3d_unet_num_params(C.byref(desc))
-    if len(params) != expect or len(buffers) != _lib.lib().mi3d_unet_num_buffers(C.byref(desc)):
-        raise _lib.Mi3dError(f"module has {len(params)} parameters / {len(buffers)} buffers, plan expects {expect}")
-    return desc, params, buffers, ws_bytes
+    plan = Plan(model, x.shape, resolve_compute_dtype(model), params=params)
+    expect = _lib.lib().mi3d_unet_num_params(plan.d)
+    if len(params) != expect or len(plan.buffers) != _lib.lib().mi3d_unet_num_buffers(plan.d):
+        raise _lib.Mi3dError(f"module has {len(params)} parameters / {len(plan.buffers)} buffers, plan expects {expect}")
+    return plan
 
 
 def unet_forward(model, x, want_gap=False):
     """Shared body of unet.UNet3D.forward and unet_dann.UNet3D.forward."""
     _lib.require_cuda(x, "UNet3D.forward")
     x = x.detach().contiguous().float() if not x.requires_grad else x.contiguous().float()
-    desc, params, buffers, ws_bytes = plan_call(model, x)
-    hold = _Hold()
-    hold.desc = desc
-    hold.training = bool(model.training)
-    hold.buffers = buffers
-    hold.want_gap = bool(want_gap)
-    hold.ws_bytes = ws_bytes
-    hold.n_enc_params = 8 * (desc.n_levels + 1)
-    hold.segment_hook = getattr(model, "_mi3d_segment_hook", None)
-    if not model.training and not (torch.is_grad_enabled() and any(q.requires_grad for q in params)):
+    plan = plan_call(model, x)
+    if not model.training and not (torch.is_grad_enabled() and any(q.requires_grad for q in plan.params)):
         # inference (train_unet.py:259-305 evaluate, test_model.py:242-251, the distillation teacher): BatchNorm folded
         # into the convs, no saved activations, no autograd node
-        return _infer(model, x, desc, hold, params, want_gap)
-    drop = None
-    p = float(getattr(model, "dropout_rate", 0.0))
-    injected = getattr(model, "_mi3d_injected_drop_scales", None)
-    if model.training and (p > 0.0 or injected is not None):
-        drop = make_drop_scales(model, desc, p, x.device, injected)
-    out = _UNetFn.apply(hold, x, drop, *params)
-    if want_gap:
-        logits, gap = out
+        plan.own_workspace(x.device)
+        logits, gap = _outputs(plan.desc, want_gap, x.device)
+        plan.infer(x, logits=logits, gap=gap, stream=stream_ptr())
     else:
-        logits, gap = out, None
+        hold = _Hold()
+        hold.plan, hold.training, hold.want_gap = plan, bool(model.training), bool(want_gap)
+        hold.segment_hook = getattr(model, "_mi3d_segment_hook", None)
+        drop = None
+        p = float(getattr(model, "dropout_rate", 0.0))
+        injected = getattr(model, "_mi3d_injected_drop_scales", None)
+        if model.training and (p > 0.0 or injected is not None):
+            drop = make_drop_scales(model, plan.desc, p, x.device, injected)
+        out = _UNetFn.apply(hold, x, drop, *plan.params)
+        logits, gap = out if want_gap else (out, None)
     if model.output_activation is not None:
         logits = model.output_activation(logits)
     return logits, gap

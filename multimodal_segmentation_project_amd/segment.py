@@ -11,12 +11,10 @@ re-reads them twice.  Every label is the first maximum of exactly the logits mod
 are preview.prediction_panels' work, on the device as well.  File reading / writing, drawing (matplotlib) and sliding windows
 stay outside.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib, engine, metrics, preprocess, resample
-from ._lib import Mi3dError, call, ptr, ptr_table, stream_ptr
+from ._lib import Mi3dError, stream_ptr
 
 CT_WINDOW = (-160.0, 240.0)      # preprocess.preprocess_ct's defaults (utils/dataloader.py:111-117)
 
@@ -34,8 +32,8 @@ def predict_labels(model, x, target=None):
         raise Mi3dError(f"{what}: the model has an output_activation; the argmax of activated logits is not this path "
                         "(take torch.argmax of model(x))")
     x = x.detach().contiguous().float()
-    desc, params, buffers, ws_bytes = engine.plan_call(model, x)
-    lib = _lib.lib()
+    plan = engine.plan_call(model, x)
+    desc = plan.desc
     n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
     labels = counts = head_ws = None
     if target is not None:
@@ -44,19 +42,16 @@ def predict_labels(model, x, target=None):
             raise Mi3dError(f"{what}: target shape {tuple(target.shape)} does not match the input {tuple(x.shape)}")
         labels = target.reshape(n, v)
         labels = (labels if labels.dtype == torch.int64 else labels.long()).contiguous()
-        head_bytes = lib.mi3d_head_labels_workspace_bytes(n, c)
+        head_bytes = _lib.lib().mi3d_head_labels_workspace_bytes(n, c)
         if head_bytes == 0:
             raise Mi3dError(f"{what}: {c} classes unsupported")
         head_ws = torch.empty(head_bytes, dtype=torch.uint8, device=x.device)
         counts = torch.empty((n, 3 * c + 1), dtype=torch.int64, device=x.device)
     # everything is checked: launch
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    plan.own_workspace(x.device)
     out = torch.empty((n, desc.D, desc.H, desc.W), dtype=torch.uint8, device=x.device)
-    ptab = ptr_table([p.data_ptr() for p in params])
-    btab = ptr_table([b.data_ptr() for b in buffers])
-    call("mi3d_unet_infer", C.byref(desc), ptr(x), ptab, btab, None, None, ptr(ws), ws_bytes, stream_ptr())
-    call("mi3d_unet_head_labels", C.byref(desc), ptab, ptr(labels), ptr(out), ptr(counts), ptr(head_ws), ptr(ws), ws_bytes,
-         stream_ptr())
+    plan.infer(x, stream=stream_ptr())
+    plan.head_labels(labels=labels, out=out, counts=counts, head_ws=head_ws, stream=stream_ptr())
     return out if target is None else (out, counts)
 
 

@@ -31,6 +31,7 @@ import torch.distributed as dist
 
 from . import _lib, engine
 from ._lib import Mi3dError, call, ptr, ptr_table, stream_ptr
+from .engine import BN_PUBLISH, THIN_CONSUMERS, TRAIN
 from . import metrics as M
 from .dp import DataParallelComm, ParamArena
 
@@ -146,8 +147,33 @@ class _Graphs:
         self.by_variant = {}
 
 
+class _State:
+    """Static buffers of one (input shape, compute dtype, trainable set, mode).  Attributes; st["name"] reads them as well
+    (tests and tools do) and raises KeyError for a name this state does not have."""
+
+    def __getitem__(self, name):
+        try:
+            return getattr(self, name)
+        except AttributeError:
+            raise KeyError(name) from None
+
+
+def _segment_runs(nseg, due):
+    """The backward as runs of segments: (start, end, buckets, is_last) for every run [start, end) that ends behind a segment with
+    gradient buckets due (due: segment -> buckets complete after it) or behind the last one.  One C call per run: kernels of
+    adjacent segments share launches (a weight-gradient slab sum rides in the next BatchNorm reduction), which a call
+    boundary would cut."""
+    start = 0
+    for seg in range(nseg):
+        buckets = tuple(due.get(seg) or ())
+        if buckets or seg == nseg - 1:
+            yield start, seg + 1, buckets, seg == nseg - 1
+            start = seg + 1
+
+
 class _StepBase:
-    """Arena / communication / graph machinery shared by TrainStep and DannStep."""
+    """Arena / communication / graph machinery and the static state shared by TrainStep and DannStep."""
+    _n_metrics = 4
 
     def _init_common(self, model, lr, weight_decay, betas, eps, grad_accum, process_group, compute_dtype, use_graph,
                      force_comm):
@@ -178,10 +204,73 @@ class _StepBase:
         self.comm_serial = bool(os.environ.get("MI3D_COMM_SERIAL"))
         self._mark_handles = []          # exchange-mark events (mi3d_unet_backward_marks)
         self.use_graph = bool(use_graph)
+        self.keep_logits = False
         self._statics = {}
         self._static = None
         self.inv_accum = torch.full((), 1.0 / self.accum, dtype=torch.float32, device=self.device)
         self._closed = False
+
+    # ---- static state for one (shape, dtype, trainable set, mode)
+    def _prepare(self, x, mode="train"):
+        dt = self.dtype or engine.resolve_compute_dtype(self.model)
+        # frozen parameters (requires_grad=False: encoder/bottleneck freezing of train_unet.py:31-43, finetune_ct.py:270-304)
+        # are part of the static state: they get no gradient, no optimizer update, and trailing all-frozen backward
+        # segments are not run at all
+        trainable = tuple(bool(p.requires_grad) for p in self.arena.params)
+        key = (tuple(x.shape), dt, trainable, mode)
+        st = self._statics.get(key)
+        if st is None:
+            st = self._new_state(key, self.cfg if mode == "train" else self.eval_cfg)
+            self._extend(st)
+            self._statics[key] = st
+        if mode == "train":
+            self._static = st
+        return st
+
+    def _new_state(self, key, cfg):
+        """What every step needs: the Plan with its workspace, input / label / logits buffers, the loss group and, for training,
+        the Dropout scale buffer and whether the head folds into the loss."""
+        shape, dt, trainable, mode = key
+        dev = self.device
+        st = _State()
+        st.mode, st.trainable, st.graphs = mode, trainable, _Graphs()
+        st.plan = engine.Plan(self.model, shape, dt, params=self.arena.params,
+                              grads=[g if t else None for g, t in zip(self.arena.grad_ptrs(), trainable)]).own_workspace(dev)
+        desc = st.desc = st.plan.desc
+        st.L = desc.n_levels
+        st.x = torch.empty(shape, dtype=torch.float32, device=dev)
+        st.y = torch.empty((desc.N, desc.D * desc.H * desc.W), dtype=torch.int64, device=dev)
+        st.loss = engine.LossGroup(cfg, desc.out_channels, dev, self._n_metrics)
+        st.metrics = st.loss.metrics
+        st.logits_shape = (desc.N, desc.out_channels, desc.D, desc.H, desc.W)
+        keep = True
+        if mode == "train":
+            st.fused_head = (not _lib.get_route("no_head_loss") and
+                             _lib.lib().mi3d_unet_head_loss_supported(st.plan.d, st.loss.cfg_ref) == 1)
+            st.drop = torch.empty(_lib.lib().mi3d_unet_dropout_count(st.plan.d), dtype=torch.float32, device=dev)
+            # the fused head never writes logits / dlogits: there is no buffer to read stale values from (ts._static["logits"]
+            # is None; keep_logits=True keeps a copy)
+            keep = not st.fused_head or self.keep_logits
+            st.dlogits = torch.empty(st.logits_shape, dtype=torch.float32, device=dev) if keep else None
+        st.logits = torch.empty(st.logits_shape, dtype=torch.float32, device=dev) if keep else None
+        return st
+
+    def _extend(self, st):
+        pass
+
+    # ---- the step surface: each class declares step() / load_batch() with its own arguments over these two
+    def _load(self, st, non_blocking, **tensors):
+        """Copy a batch into the static buffers named by the keywords, in their order."""
+        for name, t in tensors.items():
+            st[name].copy_(t.reshape(st[name].shape), non_blocking=non_blocking)
+
+    def step_static(self, last_batch=False):
+        """Run on the data already resident in the static buffers (bench path: inputs in HBM when timing starts)."""
+        st = self._static
+        if st is None:
+            raise Mi3dError("step_static() before any step()/load_batch()")
+        self._run(st, last_batch=last_batch)      # a partial window on the last batch: the (first, True) variant (captured like the others)
+        return st.metrics
 
     # ---- optimizer surface
     @property
@@ -201,7 +290,7 @@ class _StepBase:
 
     def _drop_graphs(self):
         for st in self._statics.values():
-            st["graphs"].drop()
+            st.graphs.drop()
 
     def close(self):
         """Destroy captured graph executables and events (also run by __del__)."""
@@ -284,7 +373,7 @@ class _StepBase:
             self._enqueue(st, variant, lambda fn: fn())
             self.micro += bump
             return
-        gr = st["graphs"]
+        gr = st.graphs
         hyper = self._hyper()
         if gr.hyper != hyper:
             gr.drop()
@@ -389,14 +478,8 @@ class TrainStep(_StepBase):
             # 0.45 ms of encoder backward it hides under; the exchange is worth more than the ~20 us the deferral buys
             aux_wgrad = not use_graph and not self.do_comm
         self.aux_stream = concurrent_stream(self.device) if aux_wgrad else None
-        self._events = None
-        self._event_handles = []
-        if aux_wgrad:
-            for _ in range(4):
-                e = C.c_void_p()
-                call("mi3d_event_create", C.byref(e))
-                self._event_handles.append(e.value)
-            self._events = ptr_table(self._event_handles)
+        self._event_handles = [_lib.new_event() for _ in range(4)] if aux_wgrad else []
+        self._events = ptr_table(self._event_handles) if aux_wgrad else None
         if self.world > 1:
             self.broadcast_parameters()
 
@@ -434,83 +517,36 @@ class TrainStep(_StepBase):
         self._statics = {}
         self._static = None
 
-    # ---- static state for one (shape, dtype, trainable set, mode)
-    def _prepare(self, x, mode="train"):
-        dt = self.dtype or engine.resolve_compute_dtype(self.model)
-        # frozen parameters (requires_grad=False: encoder/bottleneck freezing of train_unet.py:31-43, finetune_ct.py:270-304)
-        # are part of the static state: they get no gradient, no optimizer update, and trailing all-frozen backward
-        # segments are not run at all
-        trainable = tuple(bool(p.requires_grad) for p in self.arena.params)
-        key = (tuple(x.shape), dt, trainable, mode)
-        st = self._statics.get(key)
-        if st is not None:
-            if mode == "train":
-                self._static = st
-            return st
-        desc = engine.build_desc(self.model, x, dt)
-        L = desc.n_levels
-        lib = _lib.lib()
-        st = {"key": key, "desc": desc, "L": L, "trainable": trainable, "graphs": _Graphs()}
-        st["ws_bytes"] = lib.mi3d_unet_workspace_bytes(C.byref(desc))
-        if st["ws_bytes"] == 0:
-            _lib.check(-1, "mi3d_unet_workspace_bytes")
-        dev = self.device
-        st["ws"] = torch.empty(st["ws_bytes"], dtype=torch.uint8, device=dev)
-        n, c = desc.N, desc.out_channels
-        st["x"] = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)
-        st["y"] = torch.empty((n, desc.D * desc.H * desc.W), dtype=torch.int64, device=dev)
-        st["logits"] = torch.empty((n, c, desc.D, desc.H, desc.W), dtype=torch.float32, device=dev)
-        st["loss"] = torch.empty((), dtype=torch.float32, device=dev)
-        st["coef"] = torch.empty(_lib.LOSS_COEF_FLOATS, dtype=torch.float32, device=dev)
-        st["loss_ws"] = torch.empty(lib.mi3d_seg_loss_workspace_bytes(c), dtype=torch.uint8, device=dev)
-        st["metrics"] = torch.empty(4, dtype=torch.float32, device=dev)       # loss, iou, dice, acc
-        st["met_ws"] = torch.empty(lib.mi3d_seg_metrics_workspace_bytes(c), dtype=torch.uint8, device=dev)
-        st["ptab"] = ptr_table([p.data_ptr() for p in self.arena.params])
-        st["btab"] = ptr_table([b.data_ptr() for b in self.model.buffers()])
-        if mode == "train":
-            st["dlogits"] = torch.empty_like(st["logits"])
-            st["fused_head"] = (not _lib.get_route("no_head_loss") and
-                                lib.mi3d_unet_head_loss_supported(C.byref(desc), C.byref(self.cfg)) == 1)
-            st["ndrop"] = lib.mi3d_unet_dropout_count(C.byref(desc))
-            st["drop"] = torch.empty(st["ndrop"], dtype=torch.float32, device=dev)
-            st["gtab"] = ptr_table([gp if t else None for gp, t in zip(self.arena.grad_ptrs(), trainable)])
-            st["opt_ranges"] = self._trainable_ranges(self.arena, trainable)
-            nseg, last = 2 * L + 2, -1
-            r = (C.c_int * 4)()
-            seg_train = []
-            for seg in range(nseg):
-                _lib.check(lib.mi3d_unet_segment_params(C.byref(desc), seg, r), "mi3d_unet_segment_params")
-                idx = list(range(r[0], r[1])) + (list(range(r[2], r[3])) if r[2] >= 0 else [])
-                seg_train.append(any(trainable[i] for i in idx))
-                if seg_train[-1]:
-                    last = seg
-            st["nseg_run"] = last + 1
-            # exchange schedule: bucket -> the segment after which it is complete AND will still be run; buckets with
-            # no trainable parameter are not reduced at all
-            sched = {}
-            for seg, (lo, hi) in self.comm.buckets.items():
-                live = any(t and lo <= o < hi for o, t in zip(self.arena.offsets, trainable))
-                if live and last >= 0:
-                    sched.setdefault(min(seg, last), []).append(seg)
-            if self.comm_serial and sched and last >= 0:
-                # every bucket behind the last segment, on the compute stream: no second hardware queue in the step at all (any
-                # kernel on another queue costs this step 100-250 us on this runtime, profiles/r04_experiments_second_queue.txt),
-                # at the price of an all-reduce that hides under nothing
-                sched = {last: [b for sg in sorted(sched) for b in sched[sg]]}
-            st["comm_after"] = sched
-            if self.teacher is not None:
-                st["t_ws"] = torch.empty(st["ws_bytes"], dtype=torch.uint8, device=dev)
-                st["t_logits"] = torch.empty_like(st["logits"])
-                st["t_ptab"] = ptr_table([p.data_ptr() for p in self.teacher.parameters()])
-                st["t_btab"] = ptr_table([b.data_ptr() for b in self.teacher.buffers()])
-            if st["fused_head"] and not self.keep_logits:
-                # the fused head never writes logits / dlogits: there is no buffer to read stale values from (ts._static["logits"]
-                # is None; keep_logits=True keeps a copy)
-                st["logits"] = None
-                st["dlogits"] = None
-            self._static = st
-        self._statics[key] = st
-        return st
+    # ---- TrainStep's part of a static state: the segment and exchange schedule, the teacher
+    def _extend(self, st):
+        if st.mode != "train":
+            return
+        desc, trainable, dev = st.desc, st.trainable, self.device
+        st.opt_ranges = self._trainable_ranges(self.arena, trainable)
+        last = -1
+        r = (C.c_int * 4)()
+        for seg in range(2 * st.L + 2):
+            _lib.check(_lib.lib().mi3d_unet_segment_params(st.plan.d, seg, r), "mi3d_unet_segment_params")
+            idx = list(range(r[0], r[1])) + (list(range(r[2], r[3])) if r[2] >= 0 else [])
+            if any(trainable[i] for i in idx):
+                last = seg
+        st.nseg_run = last + 1
+        # exchange schedule: bucket -> the segment after which it is complete AND will still be run; buckets with
+        # no trainable parameter are not reduced at all
+        sched = {}
+        for seg, (lo, hi) in self.comm.buckets.items():
+            live = any(t and lo <= o < hi for o, t in zip(self.arena.offsets, trainable))
+            if live and last >= 0:
+                sched.setdefault(min(seg, last), []).append(seg)
+        if self.comm_serial and sched and last >= 0:
+            # every bucket behind the last segment, on the compute stream: no second hardware queue in the step at all (any
+            # kernel on another queue costs this step 100-250 us on this runtime, profiles/r04_experiments_second_queue.txt),
+            # at the price of an all-reduce that hides under nothing
+            sched = {last: [b for sg in sorted(sched) for b in sched[sg]]}
+        st.comm_after = sched
+        if self.teacher is not None:
+            st.teacher = st.plan.sibling(dev, params=list(self.teacher.parameters()), buffers=list(self.teacher.buffers()))
+            st.t_logits = torch.empty(st.logits_shape, dtype=torch.float32, device=dev)
 
     def _check_mode(self):
         if not self.model.training:
@@ -529,173 +565,126 @@ class TrainStep(_StepBase):
         drop, t_logits = self._forward_loss(st, s)
         self._backward_exchange(st, s, comm, drop, t_logits, accumulate, boundary, run_backward)
         if boundary:
-            self._optimizer(st, s)
+            self._adamw(self.arena, st.opt_ranges, self._hyper(), s)
 
     def _forward_loss(self, st, s):
         """Dropout scales, the teacher's forward, the student's forward with loss and metrics.  Returns (drop, t_logits)."""
-        desc = st["desc"]
-        model = self.model
-        drop = None
-        p = float(getattr(model, "dropout_rate", 0.0))
-        injected = getattr(model, "_mi3d_injected_drop_scales", None)
-        if injected is not None:
-            if injected.numel() != st["ndrop"]:
-                raise Mi3dError(f"injected dropout scales have {injected.numel()} entries, plan needs {st['ndrop']}")
-            st["drop"].copy_(injected.reshape(-1).to(self.device))
-            drop = st["drop"]
-        elif p > 0.0:
-            call("mi3d_dropout_scales", ptr(st["drop"]), st["ndrop"], p, ptr(engine._rng_state(model, self.device)), s)
-            drop = st["drop"]
-        t_logits = None
-        if self.teacher is not None and self.kd_stream is not None:
-            ks = self.kd_stream
+        model, plan, loss = self.model, st.plan, st.loss
+        drop = engine.fill_drop_scales(st.drop, float(getattr(model, "dropout_rate", 0.0)),
+                                       lambda: engine._rng_state(model, self.device),
+                                       getattr(model, "_mi3d_injected_drop_scales", None), s)
+        teacher, ks = (st.teacher if self.teacher is not None else None), self.kd_stream
+        if teacher is not None and ks is not None:
             ks.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(ks):
-                call("mi3d_unet_infer", C.byref(desc), ptr(st["x"]), st["t_ptab"], st["t_btab"],
-                     ptr(st["t_logits"]), None, ptr(st["t_ws"]), st["ws_bytes"], ks.cuda_stream)
-        n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
-        fused = st["fused_head"]
-        keep = ptr(st["logits"]) if self.keep_logits else None
-        if fused and self.teacher is None:
+                teacher.infer(st.x, logits=st.t_logits, stream=ks.cuda_stream)
+        fused = st.fused_head
+        keep = st.logits if self.keep_logits else None
+        if fused and teacher is None:
             # 1x1x1 head + loss + metrics in one pass: the logits are never written (mi3d.h, mi3d_unet_forward_loss)
-            call("mi3d_unet_forward_loss", C.byref(desc), ptr(st["x"]), st["ptab"], st["btab"], ptr(drop), 1, ptr(st["y"]), None,
-                 C.byref(self.cfg), ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]),
-                 ptr(st["met_ws"]), keep, None, ptr(st["ws"]), st["ws_bytes"], s)
-        elif fused:
-            # distillation: the student's body now, its head + loss after the join with the teacher's stream (below)
-            call("mi3d_unet_forward", C.byref(desc), ptr(st["x"]), st["ptab"], st["btab"], ptr(drop), 1,
-                 None, None, ptr(st["ws"]), st["ws_bytes"], s)
+            plan.forward_loss(st.x, loss, drop=drop, labels=st.y, logits=keep, stream=s)
         else:
-            call("mi3d_unet_forward", C.byref(desc), ptr(st["x"]), st["ptab"], st["btab"], ptr(drop), 1,
-                 ptr(st["logits"]), None, ptr(st["ws"]), st["ws_bytes"], s)
-        if self.teacher is not None:
-            if self.kd_stream is not None:
-                torch.cuda.current_stream().wait_stream(self.kd_stream)
+            # distillation with a fused head: the student's body now, its head + loss after the join with the teacher's stream
+            plan.forward(st.x, drop=drop, logits=None if fused else st.logits, stream=s)
+        t_logits = None
+        if teacher is not None:
+            if ks is not None:
+                torch.cuda.current_stream().wait_stream(ks)
             else:
                 # frozen teacher (distill_unet.py:109-111): the BatchNorm-folded inference forward
-                call("mi3d_unet_infer", C.byref(desc), ptr(st["x"]), st["t_ptab"], st["t_btab"],
-                     ptr(st["t_logits"]), None, ptr(st["t_ws"]), st["ws_bytes"], s)
-            t_logits = st["t_logits"]
-        if fused and self.teacher is not None:
-            call("mi3d_unet_head_loss_forward", C.byref(desc), st["ptab"], ptr(st["y"]), ptr(t_logits), C.byref(self.cfg),
-                 ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]), ptr(st["met_ws"]), keep,
-                 ptr(st["ws"]), st["ws_bytes"], s)
+                teacher.infer(st.x, logits=st.t_logits, stream=s)
+            t_logits = st.t_logits
+            if fused:
+                plan.head_loss_forward(loss, labels=st.y, teacher=t_logits, logits=keep, stream=s)
         # loss + metrics (SURVEY Q1 loop bound D) of the same logits in one pass (replaces 3 argmaxes + 2(D-1) host syncs)
         if not fused:
-            call("mi3d_seg_loss_metrics_forward", ptr(st["logits"]), ptr(st["y"]), ptr(t_logits), n, c, desc.D, v,
-                 C.byref(self.cfg), ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]),
-                 ptr(st["met_ws"]), s)
+            loss.metrics_forward(st.logits, st.y, teacher=t_logits, stream=s)
         return drop, t_logits
 
     def _backward_exchange(self, st, s, comm, drop, t_logits, accumulate, boundary, run_backward):
         """The backward in runs of segments, with the gradient exchange (and the metrics' all-reduce) between them."""
-        desc = st["desc"]
-        n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
-        fused = st["fused_head"]
         # SURVEY C4: the four scalar gathers fused into one 4-float all-reduce; it rides on the first gradient exchange
         # point (one fork of the comm stream less) and is in flight under the rest of the backward
-        met = st["metrics"]
+        met = st.metrics
         met_pending = self.do_comm
         joined = False
-        join_fn = self._join_comm
+
+        def exchange(buckets):
+            """The collectives of one exchange point; whichever comes first takes the metrics along."""
+            nonlocal met_pending
+            with_met, met_pending = met_pending, False
+
+            def fn():
+                if with_met:
+                    self.comm.average_(met)
+                for k in buckets:
+                    self.comm.reduce_bucket(k)
+            return fn
+
         if run_backward:
-            if not fused:
-                call("mi3d_seg_loss_backward", ptr(st["logits"]), ptr(st["y"]), ptr(t_logits), n, c, v, C.byref(self.cfg),
-                     ptr(st["coef"]), ptr(self.inv_accum), ptr(st["dlogits"]), s)
-            nseg = st["nseg_run"]
-            do_comm = self.do_comm and boundary
+            if not st.fused_head:
+                st.loss.backward(st.logits, st.y, st.dlogits, teacher=t_logits, grad_scale=self.inv_accum, stream=s)
+            nseg = st.nseg_run
+            due = st.comm_after if (self.do_comm and boundary) else {}
             aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
             aux_open = False        # aux-stream work of an earlier call that nothing on the compute stream has waited for yet
-            # one C call per run of segments between exchange steps: kernels of adjacent segments share launches (a
-            # weight-gradient slab sum rides in the next BatchNorm reduction), which a call boundary would cut
-            start = 0
             # exchange marks (include/mi3d.h, mi3d_unet_backward_marks): an eagerly launched step keeps the backward ONE call;
-            # the library records an event when a bucket's gradients are complete and the exchange stream waits for THAT
-            mid = [(sg, tuple(st["comm_after"][sg])) for sg in range(nseg - 1) if do_comm and st["comm_after"].get(sg)]
+            # the library records an event when a bucket's gradients are complete and the exchange stream waits for THAT.
+            # Recomputed every step: use_graph may be flipped on a live object, boundary changes per micro-step
+            mid = [(sg, tuple(due[sg])) for sg in range(nseg - 1) if due.get(sg)]
             use_marks = bool(mid) and not self.use_graph and aux is None and len(mid) <= 4 and not self.no_marks
             if use_marks:
                 while len(self._mark_handles) < len(mid):
-                    e = C.c_void_p()
-                    call("mi3d_event_create", C.byref(e))
-                    self._mark_handles.append(e.value)
+                    self._mark_handles.append(_lib.new_event())
                 call("mi3d_unet_backward_marks", (C.c_int * len(mid))(*[sg for sg, _ in mid]),
                      ptr_table(self._mark_handles[:len(mid)]), len(mid))
-            for seg in range(nseg):
-                last = seg == nseg - 1
-                exch = st["comm_after"].get(seg) if do_comm else None
-                if use_marks and not last:
-                    continue
-                if last or exch:
-                    # the compute stream joins the aux stream at the end of the LAST call only (in front of the optimizer); a call
-                    # that is followed by a gradient exchange leaves the join to the exchange stream (_on_comm_stream), so the
-                    # deep-level weight gradients keep running under the next segments.  Segmented graphs end a capture at every
-                    # exchange: there every call joins
-                    join = 1 if (last or self.use_graph or aux is None) else 0
-                    aux_open = aux_open or (aux is not None and not join)
-                    if fused:
-                        call("mi3d_unet_backward_loss", C.byref(desc), ptr(st["x"]), st["ptab"], st["gtab"], ptr(drop),
-                             ptr(st["y"]), ptr(t_logits), C.byref(self.cfg), ptr(st["coef"]), ptr(self.inv_accum), None, 1.0,
-                             accumulate, start, seg + 1, ptr(st["ws"]), st["ws_bytes"], s, aux, self._events, join)
-                    else:
-                        call("mi3d_unet_backward", C.byref(desc), ptr(st["x"]), st["ptab"], st["gtab"], ptr(drop),
-                             ptr(st["dlogits"]), None, 1.0, accumulate, start, seg + 1, ptr(st["ws"]), st["ws_bytes"], s, aux,
-                             self._events, join)
-                    start = seg + 1
-                    if use_marks:
-                        cs = self.comm_stream
-                        for i, (sg, b) in enumerate(mid):
-                            with_met, met_pending = met_pending, False
-                            call("mi3d_stream_wait_event", cs.cuda_stream, self._mark_handles[i])
-                            with torch.cuda.stream(cs):
-                                if with_met:
-                                    self.comm.average_(met)
-                                for k in b:
-                                    self.comm.reduce_bucket(k)
-                    if exch and not last:
-                        with_met, met_pending = met_pending, False
-                        comm(lambda b=tuple(exch), wm=with_met: self._on_comm_stream(
-                            lambda: ([self.comm.average_(met)] if wm else []) + [self.comm.reduce_bucket(k) for k in b]))
-                    elif exch:
-                        # the exchange behind the LAST segment has nothing left to hide under: it runs on the compute stream
-                        # itself, after the join with the exchange stream (collectives of one communicator never overlap each
-                        # other) -- one fork / join pair per step instead of two (a cross-queue dependency costs ~12 us)
-                        with_met, met_pending = met_pending, False
-                        joined = True
-                        comm(join_fn)
-                        comm(lambda b=tuple(exch), wm=with_met: ([self.comm.average_(met)] if wm else []) +
-                             [self.comm.reduce_bucket(k) for k in b])
+                due = {sg: b for sg, b in due.items() if sg >= nseg - 1}       # one run; only the last exchange is left to it
+            for start, end, buckets, last in _segment_runs(nseg, due):
+                # the compute stream joins the aux stream at the end of the LAST call only (in front of the optimizer); a call
+                # that is followed by a gradient exchange leaves the join to the exchange stream (_on_comm_stream), so the
+                # deep-level weight gradients keep running under the next segments.  Segmented graphs end a capture at every
+                # exchange: there every call joins
+                join = 1 if (last or self.use_graph or aux is None) else 0
+                aux_open = aux_open or (aux is not None and not join)
+                kw = dict(drop=drop, accumulate=accumulate, start=start, end=end, stream=s, aux=aux, events=self._events, join=join)
+                if st.fused_head:
+                    st.plan.backward_loss(st.x, st.loss, labels=st.y, teacher=t_logits, grad_scale=self.inv_accum, **kw)
+                else:
+                    st.plan.backward(st.x, dlogits=st.dlogits, **kw)
+                if use_marks:
+                    cs = self.comm_stream
+                    for i, (sg, b) in enumerate(mid):
+                        fn = exchange(b)
+                        call("mi3d_stream_wait_event", cs.cuda_stream, self._mark_handles[i])
+                        with torch.cuda.stream(cs):
+                            fn()
+                if buckets and not last:
+                    comm(lambda fn=exchange(buckets): self._on_comm_stream(fn))
+                elif buckets:
+                    # the exchange behind the LAST segment has nothing left to hide under: it runs on the compute stream
+                    # itself, after the join with the exchange stream (collectives of one communicator never overlap each
+                    # other) -- one fork / join pair per step instead of two (a cross-queue dependency costs ~12 us)
+                    joined = True
+                    comm(self._join_comm)
+                    comm(exchange(buckets))
             if aux_open:       # the last call may have had nothing for the aux stream: join what earlier calls left there
                 torch.cuda.current_stream().wait_stream(self.aux_stream)
         if met_pending:
             comm(lambda: self._on_comm_stream(lambda: self.comm.average_(met)))
         if self.do_comm and not joined:
-            comm(join_fn)
+            comm(self._join_comm)
 
-    def _optimizer(self, st, s):
-        self._adamw(self.arena, st["opt_ranges"], self._hyper(), s)
+    def load_batch(self, images, labels):
+        """Copy a batch into the static buffers (then step_static() runs on it)."""
+        self._load(self._prepare(images), False, x=images, y=labels)
 
     def step(self, images, labels, last_batch=False):
         """One micro-step on (images (N,Cin,D,H,W) float, labels (N,1,D,H,W) int64).  Returns a device float32[4]
         tensor {loss, iou, dice, acc} (already averaged over ranks when world > 1).
         last_batch=True on the final batch of an epoch: the optimizer steps there even inside an accumulation window and
         the next epoch starts a new window, as accelerate does for the reference's prepared loaders (see _run)."""
-        st = self._prepare(images)
-        st["x"].copy_(images, non_blocking=True)
-        st["y"].copy_(labels.reshape(st["y"].shape), non_blocking=True)
+        self._load(self._prepare(images), True, x=images, y=labels)
         return self.step_static(last_batch=last_batch)
-
-    def step_static(self, last_batch=False):
-        """Run on the data already resident in the static buffers (bench path: inputs in HBM when timing starts)."""
-        st = self._static
-        if st is None:
-            raise Mi3dError("step_static() before any step()/load_batch()")
-        self._run(st, last_batch=last_batch)
-        return st["metrics"]
-
-    def load_batch(self, images, labels):
-        st = self._prepare(images)
-        st["x"].copy_(images)
-        st["y"].copy_(labels.reshape(st["y"].shape))
 
     @torch.no_grad()
     def evaluate(self, images, labels):
@@ -707,26 +696,18 @@ class TrainStep(_StepBase):
         if self.do_comm:
             self.sync_buffers()
         st = self._prepare(images, mode="eval")
-        st["x"].copy_(images)
-        st["y"].copy_(labels.reshape(st["y"].shape))
-        desc = st["desc"]
-        s = stream_ptr()
-        n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
+        st.x.copy_(images)
+        st.y.copy_(labels.reshape(st.y.shape))
+        plan, loss, s = st.plan, st.loss, stream_ptr()
         fused = (not _lib.get_route("no_head_loss") and not self.keep_logits and
-                 _lib.lib().mi3d_unet_head_loss_supported(C.byref(desc), C.byref(self.eval_cfg)) == 1)
+                 _lib.lib().mi3d_unet_head_loss_supported(plan.d, loss.cfg_ref) == 1)
         if fused:       # head + loss + metrics on the decoder output: the validation logits are never written either
-            call("mi3d_unet_infer", C.byref(desc), ptr(st["x"]), st["ptab"], st["btab"], None, None,
-                 ptr(st["ws"]), st["ws_bytes"], s)
-            call("mi3d_unet_head_loss_forward", C.byref(desc), st["ptab"], ptr(st["y"]), None, C.byref(self.eval_cfg),
-                 ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]), ptr(st["met_ws"]), None,
-                 ptr(st["ws"]), st["ws_bytes"], s)
+            plan.infer(st.x, stream=s)
+            plan.head_loss_forward(loss, labels=st.y, stream=s)
         else:
-            call("mi3d_unet_infer", C.byref(desc), ptr(st["x"]), st["ptab"], st["btab"], ptr(st["logits"]), None,
-                 ptr(st["ws"]), st["ws_bytes"], s)
-            call("mi3d_seg_loss_metrics_forward", ptr(st["logits"]), ptr(st["y"]), None, n, c, desc.D, v,
-                 C.byref(self.eval_cfg), ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]),
-                 ptr(st["met_ws"]), s)
-        out = st["metrics"].clone()
+            plan.infer(st.x, logits=st.logits, stream=s)
+            loss.metrics_forward(st.logits, st.y, stream=s)
+        out = st.metrics.clone()
         self.comm.average_(out)
         return out
 
@@ -742,6 +723,7 @@ class DannStep(_StepBase):
     -lambda^2 dL_dom/df, Q3) interleaved segment by segment with the backward of the target graph (dgap only:
     bottleneck + encoder, accumulating into the same gradient arena) ; two arena AdamW updates.
     Under DP the discriminator arena is one more bucket, in flight under the whole U-Net backward."""
+    _n_metrics = 5
 
     def __init__(self, seg_model, disc_model, loss="ce_tversky", lambda_domain=0.1, lr=1e-3, weight_decay=0.01,
                  betas=(0.9, 0.999), eps=1e-8, grad_accum=1, process_group=None, compute_dtype=None, use_graph=False,
@@ -793,209 +775,132 @@ class DannStep(_StepBase):
         if tuple(xs.shape) != tuple(xt.shape):
             raise Mi3dError(f"source batch {tuple(xs.shape)} and target batch {tuple(xt.shape)} must have one shape "
                             "(train_dann.py:399-400: both loaders use args.batch_size)")
-        dt = self.dtype or engine.resolve_compute_dtype(self.model)
-        trainable = tuple(bool(p.requires_grad) for p in self.arena.params)
-        key = (tuple(xs.shape), dt, trainable)
-        st = self._statics.get(key)
-        if st is not None:
-            self._static = st
-            return st
-        if not all(trainable):
+        if not all(p.requires_grad for p in self.arena.params):
             raise Mi3dError("DannStep: frozen segmentation parameters are not supported")
-        desc = engine.build_desc(self.model, xs, dt)
-        lib = _lib.lib()
-        L = desc.n_levels
-        dev = self.device
-        st = {"key": key, "desc": desc, "L": L, "graphs": _Graphs()}
-        st["ws_bytes"] = lib.mi3d_unet_workspace_bytes(C.byref(desc))
-        if st["ws_bytes"] == 0:
-            _lib.check(-1, "mi3d_unet_workspace_bytes")
-        n, c = desc.N, desc.out_channels
-        F = 2 * desc.features[L - 1]
+        return super()._prepare(xs)
+
+    def _extend(self, st):
+        """DannStep's part of a static state: the target graph (input, workspace, Dropout scales), the discriminator's
+        activations and the side table of the deferred BatchNorm update."""
+        desc, dev = st.desc, self.device
+        n, F = desc.N, 2 * desc.features[st.L - 1]
         if self.lins[0].in_features != F:
             raise Mi3dError(f"discriminator expects {self.lins[0].in_features} features, the bottleneck has {F}")
-        for k in ("ws_s", "ws_t"):
-            st[k] = torch.empty(st["ws_bytes"], dtype=torch.uint8, device=dev)
-        st["xs"] = torch.empty(tuple(xs.shape), dtype=torch.float32, device=dev)
-        st["xt"] = torch.empty(tuple(xs.shape), dtype=torch.float32, device=dev)
-        st["y"] = torch.empty((n, desc.D * desc.H * desc.W), dtype=torch.int64, device=dev)
-        st["logits"] = torch.empty((n, c, desc.D, desc.H, desc.W), dtype=torch.float32, device=dev)
-        st["dlogits"] = torch.empty_like(st["logits"])
-        st["fused_head"] = (not _lib.get_route("no_head_loss") and
-                            lib.mi3d_unet_head_loss_supported(C.byref(desc), C.byref(self.cfg)) == 1)
-        st["coef"] = torch.empty(_lib.LOSS_COEF_FLOATS, dtype=torch.float32, device=dev)
-        st["loss_ws"] = torch.empty(lib.mi3d_seg_loss_workspace_bytes(c), dtype=torch.uint8, device=dev)
-        st["met_ws"] = torch.empty(lib.mi3d_seg_metrics_workspace_bytes(c), dtype=torch.uint8, device=dev)
-        st["metrics"] = torch.empty(5, dtype=torch.float32, device=dev)       # task, iou, dice, acc, domain
-        st["ndrop"] = lib.mi3d_unet_dropout_count(C.byref(desc))
-        st["drop_s"] = torch.empty(st["ndrop"], dtype=torch.float32, device=dev)
-        st["drop_t"] = torch.empty(st["ndrop"], dtype=torch.float32, device=dev)
-        st["feat"] = torch.empty((2 * n, F), dtype=torch.float32, device=dev)
-        st["dfeat"] = torch.empty((2 * n, F), dtype=torch.float32, device=dev)
+        st.xt = torch.empty_like(st.x)
+        st.drop_t = torch.empty_like(st.drop)
+        st.feat = torch.empty((2 * n, F), dtype=torch.float32, device=dev)
+        st.dfeat = torch.empty((2 * n, F), dtype=torch.float32, device=dev)
+        st.gap, st.dgap = (st.feat[:n], st.feat[n:]), (st.dfeat[:n], st.dfeat[n:])       # (source rows, target rows)
+        st.domain_loss = st.metrics[4:]                   # metrics = task, iou, dice, acc, domain
         widths = [l.out_features for l in self.lins]
-        st["acts"] = [torch.empty((2 * n, w), dtype=torch.float32, device=dev) for w in widths]
-        st["gacts"] = [torch.empty((2 * n, w), dtype=torch.float32, device=dev) for w in widths]
-        st["lin_ws"] = torch.empty(2 * n * max(widths), dtype=torch.float32, device=dev)
-        st["ddrop"] = [torch.empty((2 * n, widths[i]), dtype=torch.float32, device=dev) for i in (0, 1)]
-        st["dlabels"] = torch.cat([torch.zeros(n, dtype=torch.int64), torch.ones(n, dtype=torch.int64)]).to(dev)
-        st["ptab"] = ptr_table([p.data_ptr() for p in self.arena.params])
-        st["gtab"] = ptr_table(self.arena.grad_ptrs())
-        bufs = list(self.model.buffers())
-        st["btab"] = ptr_table([b.data_ptr() for b in bufs])
-        # side buffers of the deferred BatchNorm update: double[2C] per layer, addressed through the running_mean slots
-        rms = [b for i, b in enumerate(bufs) if i % 3 == 0]
-        st["side"] = torch.zeros(sum(2 * b.numel() for b in rms), dtype=torch.float64, device=dev)
-        side_ptrs, off = [], 0
-        for i, b in enumerate(bufs):
-            if i % 3 == 0:
-                side_ptrs.append(st["side"].data_ptr() + 8 * off)
-                off += 2 * b.numel()
-            else:
-                side_ptrs.append(None)
-        st["btab_side"] = ptr_table(side_ptrs)
-        st["opt_ranges"] = [(0, self.arena.numel)]
-        self._statics[key] = st
-        self._static = st
-        return st
+        st.acts = [torch.empty((2 * n, w), dtype=torch.float32, device=dev) for w in widths]
+        st.gacts = [torch.empty((2 * n, w), dtype=torch.float32, device=dev) for w in widths]
+        st.lin_ws = torch.empty(2 * n * max(widths), dtype=torch.float32, device=dev)
+        st.ddrop = [torch.empty((2 * n, widths[i]), dtype=torch.float32, device=dev) for i in (0, 1)]
+        st.dlabels = torch.cat([torch.zeros(n, dtype=torch.int64), torch.ones(n, dtype=torch.int64)]).to(dev)
+        # the target graph: the source's tables and a workspace of its own; when its forward runs beside the source's, the side
+        # buffers of the deferred BatchNorm update (double[2C] per layer) stand in the running_mean slots of its buffer table
+        side = None
+        if self.fwd_stream is not None:
+            bufs = st.plan.buffers
+            st.side = torch.zeros(sum(2 * b.numel() for b in bufs[::3]), dtype=torch.float64, device=dev)
+            side, off = [], 0
+            for i, b in enumerate(bufs):
+                side.append(st.side[off:off + 2 * b.numel()] if i % 3 == 0 else None)
+                off += 2 * b.numel() if i % 3 == 0 else 0
+        st.target = st.plan.sibling(dev, buffers=side)
+        st.opt_ranges = [(0, self.arena.numel)]
 
     def _enqueue(self, st, variant, comm):
         first, boundary = variant
-        desc, L = st["desc"], st["L"]
         s = stream_ptr()
-        seg, disc = self.model, self.disc
+        seg, disc, src, tgt, loss = self.model, self.disc, st.plan, st.target, st.loss
         accumulate = 0 if first else 1
-        n, c, v = desc.N, desc.out_channels, desc.D * desc.H * desc.W
-        lam = self.lam
+        n, lam = st.desc.N, self.lam
         # Dropout3d masks: one independent draw per forward (source, then target), like two module calls
         p = float(getattr(seg, "dropout_rate", 0.0))
-        injected = getattr(seg, "_mi3d_injected_drop_scales", None)       # tests: (source scales, target scales)
-        drop_s = drop_t = None
-        if injected is not None:
-            st["drop_s"].copy_(injected[0].reshape(-1))
-            st["drop_t"].copy_(injected[1].reshape(-1))
-            drop_s, drop_t = st["drop_s"], st["drop_t"]
-        elif p > 0.0:
-            rng = engine._rng_state(seg, self.device)
-            call("mi3d_dropout_scales", ptr(st["drop_s"]), st["ndrop"], p, ptr(rng), s)
-            call("mi3d_dropout_scales", ptr(st["drop_t"]), st["ndrop"], p, ptr(rng), s)
-            drop_s, drop_t = st["drop_s"], st["drop_t"]
-        feat = st["feat"]
-        F = feat.shape[1]
-        fs = self.fwd_stream
+        rng = lambda: engine._rng_state(seg, self.device)      # noqa: E731
+        injected = getattr(seg, "_mi3d_injected_drop_scales", None) or (None, None)       # tests: (source scales, target scales)
+        drop_s = engine.fill_drop_scales(st.drop, p, rng, injected[0], s)
+        drop_t = engine.fill_drop_scales(st.drop_t, p, rng, injected[1], s)
+        (gap_s, gap_t), fs = st.gap, self.fwd_stream
         if fs is not None:
             fs.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(fs):
-                call("mi3d_unet_forward", C.byref(desc), ptr(st["xt"]), st["ptab"], st["btab_side"], ptr(drop_t), 2 | 4,
-                     None, feat.data_ptr() + 4 * n * F, ptr(st["ws_t"]), st["ws_bytes"], fs.cuda_stream)
-        fused = st["fused_head"]
-        beside = 4       # two forwards side by side: thin BatchNorm consumers (include/mi3d.h); also in the serial order, so that
-        #                  both orders run the same kernels and stay bitwise equal
+                tgt.forward(st.xt, drop=drop_t, training=BN_PUBLISH | THIN_CONSUMERS, gap=gap_t, stream=fs.cuda_stream)
+        fused = st.fused_head
+        beside = TRAIN | THIN_CONSUMERS      # two forwards side by side; also in the serial order, so that both orders run the
+        #                                      same kernels and stay bitwise equal
         if fused:       # source head + loss + metrics in one pass, logits never written (mi3d_unet_forward_loss)
-            call("mi3d_unet_forward_loss", C.byref(desc), ptr(st["xs"]), st["ptab"], st["btab"], ptr(drop_s), 1 | beside, ptr(st["y"]), None,
-                 C.byref(self.cfg), ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]),
-                 ptr(st["met_ws"]), None, feat.data_ptr(), ptr(st["ws_s"]), st["ws_bytes"], s)
+            src.forward_loss(st.x, loss, drop=drop_s, training=beside, labels=st.y, gap=gap_s, stream=s)
         else:
-            call("mi3d_unet_forward", C.byref(desc), ptr(st["xs"]), st["ptab"], st["btab"], ptr(drop_s), 1 | beside,
-                 ptr(st["logits"]), feat.data_ptr(), ptr(st["ws_s"]), st["ws_bytes"], s)
+            src.forward(st.x, drop=drop_s, training=beside, logits=st.logits, gap=gap_s, stream=s)
         if fs is not None:
             torch.cuda.current_stream().wait_stream(fs)
-            call("mi3d_unet_bn_apply_deferred", C.byref(desc), st["btab"], st["btab_side"], s)
+            src.bn_apply_deferred(tgt, stream=s)
         else:
-            call("mi3d_unet_forward", C.byref(desc), ptr(st["xt"]), st["ptab"], st["btab"], ptr(drop_t), 1 | beside,
-                 None, feat.data_ptr() + 4 * n * F, ptr(st["ws_t"]), st["ws_bytes"], s)      # the target logits are never read
+            tgt.forward(st.xt, drop=drop_t, training=beside, gap=gap_t, stream=s)      # the target logits are never read
         if not fused:
-            call("mi3d_seg_loss_metrics_forward", ptr(st["logits"]), ptr(st["y"]), None, n, c, desc.D, v,
-                 C.byref(self.cfg), ptr(st["metrics"]), ptr(st["coef"]), ptr(st["metrics"][1:]), ptr(st["loss_ws"]),
-                 ptr(st["met_ws"]), s)
-            call("mi3d_seg_loss_backward", ptr(st["logits"]), ptr(st["y"]), None, n, c, v, C.byref(self.cfg),
-                 ptr(st["coef"]), ptr(self.inv_accum), ptr(st["dlogits"]), s)
+            loss.metrics_forward(st.logits, st.y, stream=s)
+            loss.backward(st.logits, st.y, st.dlogits, grad_scale=self.inv_accum, stream=s)
         # ---- discriminator on the 2N feature rows (train_dann.py:34-49,276-283)
-        dd = [None, None, None, None]
-        dinj = getattr(disc, "_mi3d_injected_drop_scales", None)          # tests: [mask after net.1, mask after net.4]
-        for i in (0, 1):
-            if dinj is not None:
-                st["ddrop"][i].copy_(dinj[i])
-                dd[i] = st["ddrop"][i]
-            elif self.disc_p[i] > 0.0:
-                call("mi3d_dropout_scales", ptr(st["ddrop"][i]), st["ddrop"][i].numel(), self.disc_p[i],
-                     ptr(self._disc_rng()), s)
-                dd[i] = st["ddrop"][i]
+        dinj = getattr(disc, "_mi3d_injected_drop_scales", None) or (None, None)      # tests: [mask after net.1, mask after net.4]
+        dd = [engine.fill_drop_scales(st.ddrop[i], self.disc_p[i], self._disc_rng, dinj[i], s) for i in (0, 1)] + [None, None]
         relus = (1, 1, 1, 0)
-        inp = feat
+        feat = inp = st.feat
         for i, l in enumerate(self.lins):
-            call("mi3d_linear_forward", ptr(inp), ptr(l.weight), ptr(l.bias), ptr(st["acts"][i]), 2 * n, l.in_features,
+            call("mi3d_linear_forward", ptr(inp), ptr(l.weight), ptr(l.bias), ptr(st.acts[i]), 2 * n, l.in_features,
                  l.out_features, relus[i], ptr(dd[i]), s)
-            inp = st["acts"][i]
+            inp = st.acts[i]
         # domain_loss = CE/accum (train_dann.py:283); its gradient enters `total` with weight lambda (:285)
-        call("mi3d_softmax_ce_rows", ptr(st["acts"][3]), ptr(st["dlabels"]), 2 * n, 2, ptr(st["metrics"][4:]),
-             ptr(st["gacts"][3]), lam / self.accum, s)
+        call("mi3d_softmax_ce_rows", ptr(st.acts[3]), ptr(st.dlabels), 2 * n, 2, ptr(st.domain_loss),
+             ptr(st.gacts[3]), lam / self.accum, s)
         da = self.disc_arena
         dgp = da.grad_ptrs()
         for i in (3, 2, 1, 0):
             l = self.lins[i]
-            x_in = feat if i == 0 else st["acts"][i - 1]
-            gx = st["dfeat"] if i == 0 else st["gacts"][i - 1]
-            call("mi3d_linear_backward", ptr(x_in), ptr(l.weight), ptr(st["acts"][i]), ptr(st["gacts"][i]), 2 * n,
+            x_in = feat if i == 0 else st.acts[i - 1]
+            gx = st.dfeat if i == 0 else st.gacts[i - 1]
+            call("mi3d_linear_backward", ptr(x_in), ptr(l.weight), ptr(st.acts[i]), ptr(st.gacts[i]), 2 * n,
                  l.in_features, l.out_features, relus[i], ptr(dd[i]), ptr(gx), dgp[2 * i], dgp[2 * i + 1], accumulate, 1.0,
-                 ptr(st["lin_ws"]), s)
+                 ptr(st.lin_ws), s)
         do_comm = self.do_comm and boundary
         if self.do_comm:
-            met = st["metrics"]
+            met = st.metrics
             comm(lambda: self._on_comm_stream(lambda: self.comm.average_(met)))
         if do_comm:
             dg = da.g
             comm(lambda: self._on_comm_stream(lambda: self.comm.average_(dg)))
-        # ---- one backward over both graphs, segment by segment: gradient reversal = gap_scale -lambda
-        nseg = 2 * L + 2
-        dgs, dgt = st["dfeat"].data_ptr(), st["dfeat"].data_ptr() + 4 * n * F
-        start = 0
-        for sg in range(nseg):
-            last = sg == nseg - 1
-            exch = sg in self.comm.buckets and do_comm
-            if last or exch:
-                if fused:
-                    call("mi3d_unet_backward_loss", C.byref(desc), ptr(st["xs"]), st["ptab"], st["gtab"], ptr(drop_s), ptr(st["y"]),
-                         None, C.byref(self.cfg), ptr(st["coef"]), ptr(self.inv_accum), dgs, -lam, accumulate, start, sg + 1,
-                         ptr(st["ws_s"]), st["ws_bytes"], s, None, None, 1)
-                else:
-                    call("mi3d_unet_backward", C.byref(desc), ptr(st["xs"]), st["ptab"], st["gtab"], ptr(drop_s),
-                         ptr(st["dlogits"]), dgs, -lam, accumulate, start, sg + 1, ptr(st["ws_s"]), st["ws_bytes"], s, None, None, 1)
-                t0 = max(start, L + 1)            # the target graph has no decoder part
-                if sg + 1 > t0:
-                    call("mi3d_unet_backward", C.byref(desc), ptr(st["xt"]), st["ptab"], st["gtab"], ptr(drop_t),
-                         None, dgt, -lam, 1, t0, sg + 1, ptr(st["ws_t"]), st["ws_bytes"], s, None, None, 1)
-                start = sg + 1
-                if exch:
-                    comm(lambda k=sg: self._on_comm_stream(lambda: self.comm.reduce_bucket(k)))
+        # ---- one backward over both graphs, run by run: gradient reversal = gap_scale -lambda
+        L = st.L
+        due = {sg: (sg,) for sg in self.comm.buckets} if do_comm else {}
+        for start, end, buckets, _ in _segment_runs(2 * L + 2, due):
+            kw = dict(drop=drop_s, dgap=st.dgap[0], gap_scale=-lam, accumulate=accumulate, start=start, end=end, stream=s)
+            if fused:
+                src.backward_loss(st.x, loss, labels=st.y, grad_scale=self.inv_accum, **kw)
+            else:
+                src.backward(st.x, dlogits=st.dlogits, **kw)
+            t0 = max(start, L + 1)            # the target graph has no decoder part
+            if end > t0:
+                tgt.backward(st.xt, drop=drop_t, dgap=st.dgap[1], gap_scale=-lam, accumulate=1, start=t0, end=end, stream=s)
+            for k in buckets:
+                comm(lambda k=k: self._on_comm_stream(lambda: self.comm.reduce_bucket(k)))
         if self.do_comm:
             comm(self._join_comm)
         if boundary:
             h = self._hyper()
-            self._adamw(self.arena, st["opt_ranges"], h[:5], s)
+            self._adamw(self.arena, st.opt_ranges, h[:5], s)
             self._adamw(self.disc_arena, [(0, self.disc_arena.numel)], h[5:], s)
 
     def load_batch(self, source_images, source_labels, target_images):
-        st = self._prepare(source_images, target_images)
-        st["xs"].copy_(source_images)
-        st["xt"].copy_(target_images)
-        st["y"].copy_(source_labels.reshape(st["y"].shape))
+        self._load(self._prepare(source_images, target_images), False, x=source_images, xt=target_images, y=source_labels)
 
     def step(self, source_images, source_labels, target_images, last_batch=False):
         """One micro-step.  Returns device float32[5] = {task_loss, iou, dice, acc, domain_loss} (source-domain metrics,
         train_dann.py:291-299; losses un-divided by the accumulation count like the reference's running sums).
         last_batch: train_dann.py:287 also steps on the final batch of an epoch."""
-        st = self._prepare(source_images, target_images)
-        st["xs"].copy_(source_images, non_blocking=True)
-        st["xt"].copy_(target_images, non_blocking=True)
-        st["y"].copy_(source_labels.reshape(st["y"].shape), non_blocking=True)
+        self._load(self._prepare(source_images, target_images), True, x=source_images, xt=target_images, y=source_labels)
         return self.step_static(last_batch=last_batch)
-
-    def step_static(self, last_batch=False):
-        st = self._static
-        if st is None:
-            raise Mi3dError("step_static() before any step()/load_batch()")
-        self._run(st, last_batch=last_batch)       # a partial window on the last batch: the (first, True) variant (captured like the others)
-        return st["metrics"]
 
     @torch.no_grad()
     def evaluate(self, images, labels):
@@ -1008,11 +913,8 @@ class DannStep(_StepBase):
         finally:
             self.model.train(was)
         n, c, v, lab = M._prep(logits, labels)
-        out = torch.empty(4, dtype=torch.float32, device=self.device)
-        coef = torch.empty(_lib.LOSS_COEF_FLOATS, dtype=torch.float32, device=self.device)
-        lws = torch.empty(_lib.lib().mi3d_seg_loss_workspace_bytes(c), dtype=torch.uint8, device=self.device)
-        mws = torch.empty(_lib.lib().mi3d_seg_metrics_workspace_bytes(c), dtype=torch.uint8, device=self.device)
-        call("mi3d_seg_loss_metrics_forward", ptr(logits), ptr(lab), None, n, c, logits.shape[2], v, C.byref(self.eval_cfg),
-             ptr(out), ptr(coef), ptr(out[1:]), ptr(lws), ptr(mws), stream_ptr())
+        loss = engine.LossGroup(self.eval_cfg, c, self.device)
+        loss.metrics_forward(logits, lab, stream=stream_ptr())
+        out = loss.metrics
         self.comm.average_(out)
         return out
