@@ -420,6 +420,43 @@ int mi3d_overlay_render(const void* image, int image_dtype, const int64_t* image
                         int axis, int mode, const int32_t* index, int k, int rot90, const uint32_t* keys, int out_dtype,
                         void* const* outs, void* stream);
 
+/* Connected components of a label map, the largest of them per class, and the cleaned map: what follows a prediction on the host
+ * today (scipy.ndimage.label(labels == c, scipy.ndimage.generate_binary_structure(3, connectivity)) per class, np.bincount of the
+ * ids, np.isin of the kept ones).  The reference writes its predictions out uncleaned (test_model.py:299-309), so scipy.ndimage.label
+ * is the contract.  labels: N samples of sides D, H, W seen through element strides (any dense layout per sample), uint8 or int64.
+ *   component   two voxels of one sample with the same SELECTED value (a subset of 1..255; 0, and int64 values outside 0..255, never)
+ *               joined by a path of neighbours of that value; connectivity 1, 2, 3 = 6, 18, 26 neighbours.  Components never
+ *               cross samples; unselected voxels belong to none.
+ *   root        the C-order index d * H * W + h * W + w (logical axes, within the sample) of the component's first voxel: the
+ *               labelling is canonical, independent of launch order, tile size and strides.
+ *   ranking     within one (sample, class): size descending, then root ascending.
+ * Only integer atomics are used: the same bits every run.  Nothing allocates or synchronises.  status_out: one int32 the entry
+ * zeroes first; a kernel whose parent-following loop reaches its bound (it cannot, a chain has fewer than D * H * W links) ORs
+ * a MI3D_COMPONENTS_STATUS_* bit into it and leaves, so every kernel terminates; the outputs mean nothing unless it is 0.
+ * workspace: mi3d_components_workspace_bytes bytes (13 per voxel, rounded up), 256-byte aligned; 0 (and an error) for N outside
+ * [1, 65535], a side < 1 or D * H * W >= 2^31. */
+#define MI3D_COMPONENTS_TILE 8            /* a workgroup labels a tile of 8 x 8 x 64 voxels (d, h, w) before the tiles are joined */
+#define MI3D_COMPONENTS_MAX_CLASSES 8
+#define MI3D_COMPONENTS_MAX_KEEP 8
+enum { MI3D_COMPONENTS_STATUS_TILE = 1, MI3D_COMPONENTS_STATUS_SEAM = 2, MI3D_COMPONENTS_STATUS_FLATTEN = 4 };
+size_t mi3d_components_workspace_bytes(int N, int D, int H, int W);
+/* roots_out (N, D, H, W) int32, contiguous: the root of every voxel's component, -1 where the voxel's value is not selected; the
+ * np.unique(ids, return_index=True) of scipy's labelling of every selected class, at every voxel.  class_select: a HOST array of
+ * 256 bytes read before the call returns, non-zero at the selected values; class_select[0] must be 0. */
+int mi3d_component_roots(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d,
+                         int64_t stride_h, int64_t stride_w, int connectivity, const uint8_t* class_select, int32_t* roots_out,
+                         int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
+/* labels_out (dtype and strides of labels; may be labels itself): a voxel of listed class j keeps its value iff its component is
+ * kept, else it becomes fill (0..255); every other voxel is copied.  A component of class j is kept iff its rank is below
+ * keep_k[j] (1..8) and its size is at least min_size (>= 1).  class_values / keep_k: HOST arrays of n_classes (1..8) distinct
+ * values in 1..255 and their counts.  stats_out: (N, n_classes, 3 + 2 * 8) int64, one row per listed class:
+ *   [0] n_components  [1] voxels_before  [2] voxels_kept  [3..10] sizes of the kept components in rank order, 0 where there are
+ *   fewer  [11..18] their roots, -1 where there are fewer. */
+int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d,
+                         int64_t stride_h, int64_t stride_w, int connectivity, int n_classes, const int32_t* class_values,
+                         const int32_t* keep_k, int64_t min_size, int fill, void* labels_out, int64_t* stats_out, int32_t* status_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
  * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)
  * with the random decisions already drawn by the host (spatial.py), as one gather pass.  img: float32, lab: int64, both

@@ -13,7 +13,7 @@ stay outside.
 """
 import torch
 
-from . import _lib, engine, metrics, preprocess, resample
+from . import _lib, components, engine, metrics, preprocess, resample
 from ._lib import Mi3dError, stream_ptr
 
 CT_WINDOW = (-160.0, 240.0)      # preprocess.preprocess_ct's defaults (utils/dataloader.py:111-117)
@@ -65,15 +65,21 @@ def per_sample_dice_iou(counts, classes=(1, 2, 3)):
     return [metrics.dice_iou_from_counts(r, len(r) // 3, classes) for r in rows]
 
 
-def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192)):
+def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192), keep_largest=None,
+                 connectivity=1):
     """A decoded scan AS STORED and its 4x4 affine -> (uint8 labels with the scan's shape and strides, uint8 labels on the
     training grid, affine of the grid).  A composition only: resample.resample_scan (CT window fused into the last store for
     '_ct' names, preprocess.preprocess_mri afterwards otherwise: the dispatch of preprocess.preprocess), predict_labels,
-    resample.restore_labels."""
+    resample.restore_labels.  keep_largest: a dict {class: components to keep} such as components.ORGANS; the grid map is then
+    cleaned by components.keep_largest (with `connectivity`) before it is restored, the second element is the cleaned grid map
+    and a fourth, the Cleaned record (stats, status), is appended.  None: no cleaning, three elements."""
     ct = dataset_name.lower().endswith("_ct")
     grid, _, grid_affine = resample.resample_scan(image, affine, target_spacing=target_spacing, target_shape=target_shape,
                                                   ct_window=CT_WINDOW if ct else None)
     if not ct:
         grid = preprocess.preprocess_mri(grid)
     on_grid = predict_labels(model, grid[None, None])[0]
-    return resample.restore_labels(on_grid, affine, image), on_grid, grid_affine
+    if keep_largest is None:
+        return resample.restore_labels(on_grid, affine, image), on_grid, grid_affine
+    cleaned = components.keep_largest(on_grid, keep=keep_largest, connectivity=connectivity)
+    return resample.restore_labels(cleaned.labels, affine, image), cleaned.labels, grid_affine, cleaned
