@@ -546,6 +546,22 @@ int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int C
                           int64_t* num_batches_tracked, float momentum, float eps, const float* drop, void* y, void* z, int zcs,
                           void* pooled, int pcs, float* stat, int flags, mi3d_conv3_bn_route* route_out, int Cout, int N, int D,
                           int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+/* One half of a DoubleConv block as the inference forward of the whole-network plan (mi3d_unet_infer) runs it: eval-mode
+ * BatchNorm3d folded into the conv, ReLU in the conv's epilogue, z = relu(conv(x, w * scale) + fbias) with
+ *   scale = gamma / sqrt(running_var + eps),  fbias = (bias - running_mean) * scale + beta       (bias NULL = 0)
+ * through the plan's own launches in the plan's order (the fold, the weight pack carrying the scale, then the ONE function the
+ * plan calls per layer).  in_dtype = dtype, or MI3D_F32 for the one-channel image of the first layer; z has channel stride zcs
+ * (the concat buffer's 2 * Cout, say).  x_split, x_delta: planar halves of x as in mi3d_conv3_bn_backward (0, 0 = one plane; only
+ * the persistent kernels take them).  fold_out (may be NULL): device float[2 * Cout] that receives scale, then fbias.  route_out
+ * (may be NULL): conv = the codes of mi3d_conv3_bn_route, ksplit = split-K factor of the launch (1 = none; the scratch is handed
+ * over only to an output with 16-byte aligned rows). */
+typedef struct mi3d_conv3_infer_route { int32_t conv, ksplit; } mi3d_conv3_infer_route;
+size_t mi3d_conv3_infer_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W);
+int mi3d_conv3_infer_forward(int in_dtype, int dtype, const void* x, int xcs, int x_split, int64_t x_delta, int Cin,
+                             const float* w, const float* bias, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, void* z, int zcs, float* fold_out,
+                             mi3d_conv3_infer_route* route_out, int Cout, int N, int D, int H, int W, void* workspace,
+                             size_t workspace_bytes, void* stream);
 /* One half of a DoubleConv block as the training backward of the whole-network plan runs it: BatchNorm3d + ReLU + Dropout3d
  * backward (dz -> dy, dgamma, dbeta), then the conv's weight / bias gradient and input gradient, with the plan's own per-layer
  * decisions (the plan and this entry call ONE function) on a workspace of its own.  x is the layer's input, y / stat / drop what

@@ -57,6 +57,10 @@ class Conv3BnRoute(C.Structure):                   # mi3d_conv3_bn_route
 CONV3_BN_KEEP_TICKETS = 1
 
 
+class Conv3InferRoute(C.Structure):                # mi3d_conv3_infer_route
+    _fields_ = [(k, C.c_int32) for k in ("conv", "ksplit")]
+
+
 class Conv3BnBwdRoute(C.Structure):                # mi3d_conv3_bn_bwd_route
     _fields_ = [(k, C.c_int32) for k in ("bn", "riders", "dz_ks", "conv", "dgrad_ks", "dx_ks", "dx_offset", "slabs", "slab_layout",
                                          "slab_ew", "pending")]
@@ -164,6 +168,9 @@ _SIGS = {
     "mi3d_conv3_bn_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
     "mi3d_conv3_bn_forward": (i32, [i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, i32, vp, i32, vp, i32,
                                     C.POINTER(Conv3BnRoute), i32, i32, i32, i32, i32, vp, sz, vp]),
+    "mi3d_conv3_infer_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "mi3d_conv3_infer_forward": (i32, [i32, i32, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, f32, vp, i32, vp,
+                                       C.POINTER(Conv3InferRoute), i32, i32, i32, i32, i32, vp, sz, vp]),
     "mi3d_conv3_bn_bwd_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
     "mi3d_conv3_bn_backward": (i32, [i32, i32, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, i32, i32, i64, vp, vp,
                                      vp, vp, i32, C.POINTER(PendingSum), C.POINTER(PendingSum), i32, C.POINTER(Conv3BnBwdRoute),

@@ -370,6 +370,76 @@ int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int C
     return 0;
 }
 
+}  // extern "C"
+
+// mi3d_conv3_infer_forward: the areas of the plan's workspace an inference layer touches, in a workspace of its own
+namespace {
+struct ConvInferWs {
+    bool mfma, c1;
+    size_t fold, wpf, wpd, skws, total;
+};
+ConvInferWs conv_infer_ws(int dtype, int Cin, int Cout, Geo g) {
+    ConvInferWs L;
+    conv3_layer_class(dtype, Cin, Cout, L.mfma, L.c1);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    L.fold = take((size_t)2 * Cout * sizeof(float));      // scale, then the folded bias: the plan's stat[0..2C) of an inference call
+    L.wpf = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cin, Cout) * sizeof(float));
+    L.wpd = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : 0);      // the pack launch writes both images
+    L.skws = take((L.mfma ? conv3_mfma_splitk_floats(Cin, Cout, g) : 0) * sizeof(float) + 16);
+    L.total = off;
+    return L;
+}
+}  // namespace
+
+extern "C" {
+
+size_t mi3d_conv3_infer_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W) {
+    if (Cin < 1 || Cout < 1 || N < 1 || D < 1 || H < 1 || W < 1) return 0;
+    return conv_infer_ws(dtype, Cin, Cout, Geo{N, D, H, W}).total;
+}
+int mi3d_conv3_infer_forward(int in_dtype, int dtype, const void* x, int xcs, int x_split, int64_t x_delta, int Cin,
+                             const float* w, const float* bias, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, void* z, int zcs, float* fold_out,
+                             mi3d_conv3_infer_route* route_out, int Cout, int N, int D, int H, int W, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    const char* fn = "mi3d_conv3_infer_forward";
+    MI3D_CHECK_ARG(x && w && gamma && beta && running_mean && running_var && z && workspace, "%s: null pointer", fn);
+    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
+                   "%s: bad dtypes %d -> %d", fn, in_dtype, dtype);
+    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= (x_delta ? 16 : Cin) && zcs >= Cout && N >= 1 && D >= 1 && H >= 1 && W >= 1,
+                   "%s: bad shape", fn);
+    const Geo g{N, D, H, W};
+    const ConvInferWs L = conv_infer_ws(dtype, Cin, Cout, g);
+    MI3D_CHECK_ARG(!L.mfma || (xcs % 8 == 0 && zcs % 4 == 0 && ((uintptr_t)x % 16) == 0), "%s: channel strides %d / %d", fn, xcs, zcs);
+    MI3D_CHECK_ARG(!L.c1 || (in_dtype == MI3D_F32 && zcs % 4 == 0), "%s: the first-layer kernel reads an fp32 image", fn);
+    MI3D_CHECK_ARG(!(L.mfma || L.c1) || ((uintptr_t)z % 8) == 0, "%s: misaligned output", fn);
+    MI3D_CHECK_ARG(!L.mfma || ((uintptr_t)w % 16) == 0, "%s: the weight tensor must be 16-byte aligned", fn);
+    MI3D_CHECK_ARG(!x_delta || (L.mfma && conv3_mfma_halves_ok(Cin, Cout, g)), "%s: planar halves need the full-resolution kernels", fn);
+    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    float* scale = (float*)(ws + L.fold);
+    BnFoldJobs F;      // launch 1 of mi3d_unet_infer with one job
+    F.n = 1; F.eps = eps;
+    F.j[0] = BnFoldJob{gamma, beta, running_mean, running_var, bias, scale, scale + Cout, Cout};
+    MI3D_TRY(bn_fold_all(F, s));
+    if (L.mfma) {      // launch 2: the weight images, BatchNorm scale multiplied into the forward one
+        PackJobs J;
+        J.n = 0; J.nblocks = 0;
+        MI3D_TRY(pack_all_add_conv3(J, w, Cin, Cout, ws + L.wpf, ws + L.wpd, g, scale));
+        MI3D_TRY(pack_all_launch(J, s));
+    }
+    Halves xh;
+    if (x_delta) { xh.split = x_split; xh.delta = x_delta; }
+    ConvBnHalfInfer a{Cin, Cout, g, dtype, L.mfma, L.c1, x, xcs, in_dtype, xh, w, ws + L.wpf, scale, scale + Cout, z, zcs,
+                      (float*)(ws + L.skws)};
+    MI3D_TRY(conv3_bn_half_infer(a, s, route_out));
+    if (fold_out) MI3D_HIP(hipMemcpyAsync(fold_out, scale, (size_t)2 * Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 size_t mi3d_bn_workspace_bytes(int C) { return bn_ws_floats(C) * sizeof(float); }
 int mi3d_bn_relu_drop_forward(int dtype, const void* y, int ycs, int C, int64_t M, int64_t V, const float* gamma,
                               const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked,

@@ -197,6 +197,24 @@ struct ConvBnHalf {
 };
 int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_route* route = nullptr);
 
+// ---- one half of a DoubleConv block, inference: conv with BatchNorm folded in, ReLU in the epilogue ------------------ plan.hip
+// The ONE copy of the inference forward's per-layer decisions (which kernel, whether the split-K scratch is handed over, the
+// direct pack with the scale): block_infer of the whole-network plan and the per-operator entry mi3d_conv3_infer_forward both
+// call it.  scale / fbias: what bn_fold_all left (ops.h BnFoldJob); an MFMA layer's packed image already carries the scale.
+struct mi3d_conv3_infer_route;         // include/mi3d.h: what was launched, for the per-operator tests
+struct ConvBnHalfInfer {
+    int Cin, Cout; Geo g;
+    int dt;                            // dtype of out
+    bool mfma, c1;                     // the layer's route class (conv3_layer_class)
+    const void* in; int ics, idt; Halves ih;
+    const float* w;                    // torch layout (c1 and direct read it)
+    void* wpf;                         // mfma: the packed forward image, scale folded in (read); direct: packed here
+    const float* scale; const float* fbias;
+    void* out; int ocs;
+    float* skws;                       // split-K scratch (conv3_mfma_splitk_floats); handed on only to 16-byte aligned output rows
+};
+int conv3_bn_half_infer(const ConvBnHalfInfer& a, hipStream_t s, mi3d_conv3_infer_route* route = nullptr);
+
 // ---- one half of a DoubleConv block, backward: BatchNorm backward -> weight gradient + input gradient ---------------- plan.hip
 // The weight-gradient slab sums that wait for a launch to ride in.  A launcher that is handed a slot leaves its final slab sum
 // there instead of launching it (nblocks > 0: a sum waits).  The rule, once:

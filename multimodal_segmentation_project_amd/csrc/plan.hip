@@ -95,6 +95,30 @@ int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_rout
     return 0;
 }
 
+// One half of a DoubleConv block, inference (ops.h ConvBnHalfInfer): BatchNorm (running statistics) folded into the conv (scale in
+// the filter, bias replaced), ReLU in the conv epilogue, output written straight to where the activated tensor lives.  Every
+// per-layer decision of the inference forward is made here and only here.  route: what was launched.
+int conv3_bn_half_infer(const ConvBnHalfInfer& a, hipStream_t s, mi3d_conv3_infer_route* route) {
+    Conv3Launch ln;
+    if (a.mfma) {
+        // the stand-alone split-K finish stores 16 bytes per thread: no scratch (a single pass) for any other output
+        float* skws = (a.ocs % 8 == 0 && ((uintptr_t)a.out % 16) == 0) ? a.skws : nullptr;
+        MI3D_TRY(conv3_mfma_fwd(a.in, a.ics, a.Cin, a.wpf, a.fbias, a.out, a.ocs, a.Cout, a.g, nullptr, skws, s, a.ih, Halves(),
+                                nullptr, 1, 0, nullptr, nullptr, &ln));
+    } else if (a.c1) {
+        MI3D_TRY(conv3_c1_fwd_mfma((const float*)a.in, a.w, a.fbias, a.out, a.ocs, a.Cout, a.g, nullptr, s, a.scale, 1));
+        ln.kind = 1;
+    } else {
+        MI3D_TRY(conv3_direct_pack(a.w, a.Cin, a.Cout, (float*)a.wpf, nullptr, s, a.scale));
+        MI3D_TRY(conv3_direct_fwd(a.idt, a.dt, a.in, a.ics, a.Cin, (const float*)a.wpf, a.fbias, a.out, a.ocs, a.Cout, a.g, s, 1));
+    }
+    if (route) {
+        route->conv = ln.kind;
+        route->ksplit = ln.ks;
+    }
+    return 0;
+}
+
 int conv3_deferred_wgrad(const void* in, int ics, int Cin, Halves ih, const void* dy, int dycs, int Cout, Geo g, int dxcs, float* dW,
                          float* db, int accumulate, float* ws, size_t ws_floats, hipStream_t s) {
     return conv3_mfma_wgrad(in, ics, Cin, dy, dycs, Cout, g, dW, db, accumulate, ws, ws_floats, s, ih, nullptr,
@@ -642,26 +666,17 @@ int block_backward(Ctx& c, int b, const float* x, void* const* grads, const floa
     return 0;
 }
 
-// inference forward of block b: BatchNorm (running statistics) folded into the conv (scale in the packed filter, bias
-// replaced), ReLU in the conv epilogue, output written straight to where the activated tensor lives -- no raw conv
-// output, no statistics, no separate normalisation pass.  stat[0..C) = scale, stat[C..2C) = folded bias (bn_fold_all).
+// inference forward of block b (conv3_bn_half_infer per half): no raw conv output, no statistics, no separate normalisation
+// pass.  stat[0..C) = scale, stat[C..2C) = folded bias (bn_fold_all).
 int block_infer(Ctx& c, int b, const float* x) {
     const Plan& p = c.p;
     for (int h = 0; h < 2; h++) {
         const LayerIO v = layer_io(c, b, h, x);
         const HalfP& H = v.H;
         const float* scale = c.at<float>(H.stat);
-        const float* fbias = scale + H.Cout;
-        if (H.mfma) {
-            MI3D_TRY(conv3_mfma_fwd(v.in, v.ics, H.Cin, c.at(H.wpf), fbias, v.out, v.ocs, H.Cout, v.g, nullptr,
-                                    (v.ocs % 8 == 0 && ((uintptr_t)v.out % 16) == 0) ? c.at<float>(p.skws) : nullptr, c.s,
-                                    v.ih, Halves(), nullptr, 1));
-        } else if (H.c1) {
-            MI3D_TRY(conv3_c1_fwd_mfma((const float*)v.in, c.P(H.pidx), fbias, v.out, v.ocs, H.Cout, v.g, nullptr, c.s, scale, 1));
-        } else {
-            MI3D_TRY(conv3_direct_pack(c.P(H.pidx), H.Cin, H.Cout, c.at<float>(H.wpf), nullptr, c.s, scale));
-            MI3D_TRY(conv3_direct_fwd(v.idt, p.dt, v.in, v.ics, H.Cin, c.at<float>(H.wpf), fbias, v.out, v.ocs, H.Cout, v.g, c.s, 1));
-        }
+        ConvBnHalfInfer a{H.Cin, H.Cout, v.g, p.dt, H.mfma, H.c1, v.in, v.ics, v.idt, v.ih, c.P(H.pidx), c.at(H.wpf),
+                          scale, scale + H.Cout, v.out, v.ocs, c.at<float>(p.skws)};
+        MI3D_TRY(conv3_bn_half_infer(a, c.s));
     }
     return 0;
 }
@@ -714,7 +729,7 @@ int up_forward(Ctx& c, int i) {
 
 extern "C" {
 
-int mi3d_abi_version(void) { return 8; }
+int mi3d_abi_version(void) { return 9; }
 
 int mi3d_unet_num_params(const mi3d_unet_desc* d) { return d ? 8 * (2 * d->n_levels + 1) + 2 * d->n_levels + 2 : -1; }
 int mi3d_unet_num_buffers(const mi3d_unet_desc* d) { return d ? 6 * (2 * d->n_levels + 1) : -1; }

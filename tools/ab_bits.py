@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Bit-for-bit A/B of two builds of libmi3d.so: one fixed battery per library, SHA-256 of every output buffer, no tolerance.
 
-    python tools/ab_bits.py <libA.so> <libB.so>
-Each library runs in its own child process (selected through MI3D_LIB_PATH), one after the other, each under a time limit;
-the first failing child stops the tool.  Inputs are seeded on the host (numpy / torch CPU), never by a device generator.
+    python tools/ab_bits.py [--only infer] <libA.so> <libB.so>
+--only infer runs the inference-forward section alone.  Each library runs in its own child process (selected through
+MI3D_LIB_PATH), one after the other, each under a time limit; the first failing child stops the tool.  Inputs are seeded on the host (numpy / torch CPU), never by a device generator.
 Exit status 0 = every digest equal; 1 = the first differing buffer is named."""
 import ctypes as C
 import hashlib
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300
 
 
-def battery():
+def battery(only=None):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
@@ -43,6 +43,35 @@ def battery():
         return torch.empty(shape, device=dev, dtype=dt)
 
     bf = torch.bfloat16
+
+    # the inference forward (mi3d_unet_infer: BatchNorm folded into the convs) of the default net with non-trivial running
+    # statistics and affine parameters: logits on 2 x 32^3 in bf16 and fp32, and on an odd volume in bf16
+    def infer_net():
+        for tag, shape, dt in (("infer32/bf16", (2, 1, 32, 32, 32), bf), ("infer32/fp32", (2, 1, 32, 32, 32), torch.float32),
+                               ("infer_odd/bf16", (1, 1, 18, 20, 22), bf)):
+            torch.manual_seed(14)
+            m = UNet3D(in_channels=1, out_channels=4, dropout_rate=0.3)
+            gen = torch.Generator().manual_seed(42)
+            with torch.no_grad():
+                for k, b in m.named_buffers():
+                    if k.endswith("running_mean"):
+                        b.copy_(0.2 * torch.randn(b.shape, generator=gen))
+                    if k.endswith("running_var"):
+                        b.copy_(0.5 + torch.rand(b.shape, generator=gen))
+                for k, p in m.named_parameters():
+                    if p.dim() == 1:
+                        p.add_(0.2 * torch.randn(p.shape, generator=gen))
+            m = m.to(dev).eval()
+            m.compute_dtype = dt
+            x = rnd(np.random.default_rng(sum(shape)), shape)
+            with torch.no_grad():
+                logits = m(x)
+            assert logits.grad_fn is None
+            put(f"{tag}/logits", logits)
+
+    if only == "infer":
+        infer_net()
+        return out
 
     def conv3(tag, n, cin, cout, d, h, w):
         rng = np.random.default_rng(n + cin + cout + d + h + w)
@@ -343,19 +372,23 @@ def battery():
     for k, b in seg.named_buffers():
         put(f"dann32/buffer/{k}", b)
     ds.close()
+    infer_net()
     return out
 
 
 def main():
     if sys.argv[1] == "--child":
-        json.dump(battery(), open(sys.argv[2], "w"), indent=0)
+        json.dump(battery(sys.argv[3] if len(sys.argv) > 3 else None), open(sys.argv[2], "w"), indent=0)
         return 0
+    args, only = sys.argv[1:], []
+    if args[0] == "--only":
+        only, args = [args[1]], args[2:]
     res = []
-    for path in sys.argv[1:3]:
+    for path in args[:2]:
         with tempfile.NamedTemporaryFile(suffix=".json") as f:
             env = dict(os.environ, MI3D_LIB_PATH=os.path.abspath(path))
             try:
-                rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f.name], env=env, timeout=CHILD_TIMEOUT).returncode
+                rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f.name] + only, env=env, timeout=CHILD_TIMEOUT).returncode
             except subprocess.TimeoutExpired:
                 rc = 124
             if rc != 0:
@@ -369,7 +402,7 @@ def main():
     for k in only_b:
         print(f"++ {'':16} {b[k][:16]} {k}")
     diff = [k for k in a if a[k] != b.get(k)]
-    print(f"{len(a)} buffers, {len(diff)} differ, {len(only_b)} only in the second build" + (f"; first: {diff[0]}" if diff else f": {sys.argv[1]} and {sys.argv[2]} agree bit for bit"))
+    print(f"{len(a)} buffers, {len(diff)} differ, {len(only_b)} only in the second build" + (f"; first: {diff[0]}" if diff else f": {args[0]} and {args[1]} agree bit for bit"))
     return 1 if diff else 0
 
 
