@@ -457,6 +457,57 @@ int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int 
                          const int32_t* keep_k, int64_t min_size, int fill, void* labels_out, int64_t* stats_out, int32_t* status_out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Surface distances between two label maps: the exact Euclidean distance transform and, from it, the Hausdorff distance, its
+ * percentile (HD95), the average symmetric surface distance (ASSD) and the surface Dice (NSD) per (sample, class): what a user does
+ * on the host today with scipy.ndimage.binary_erosion and scipy.ndimage.distance_transform_edt per class and direction.  The
+ * reference computes no surface metric, so scipy (the conventions of monai.metrics and medpy) is the contract.  Maps: N samples of
+ * sides D, H, W seen through element strides (any dense layout per sample), uint8 or int64.  spacing: 3 HOST doubles (sd, sh, sw),
+ * mm per voxel along d, h, w, positive and finite, read before the call returns.
+ *   surface    S(M) = M & ~scipy.ndimage.binary_erosion(M, scipy.ndimage.generate_binary_structure(3, connectivity)), border_value 0:
+ *              a voxel of M with a neighbour (connectivity 1, 2, 3 = 6, 18, 26 neighbours) outside M or outside the volume.
+ *   g3         the squared distance to a set F, in IEEE double, every operation rounded on its own, defined separably:
+ *                g1[d,h,w] = min over w' with F[d,h,w'] of fl((sw (w - w'))^2), +inf if the row has none
+ *                g2[d,h,w] = min over h' of fl(g1[d,h',w] + fl((sh (h - h'))^2))
+ *                g3[d,h,w] = min over d' of fl(g2[d',h,w] + fl((sd (d - d'))^2))
+ *              the minimum of these expressions themselves; +inf everywhere for an empty F.  sqrt(g3) is
+ *              scipy.ndimage.distance_transform_edt(~F, sampling=spacing): bit for bit where every term is exact in double (spacings
+ *              such as (1, 1, 1), (2.5, 0.75, 0.75), (3, 1, 1.5)), within rounding elsewhere (scipy adds the terms in another order).
+ * The same bits on every run (integer atomics; the float sum through fixed slots in a fixed order).  Nothing allocates or
+ * synchronises; no loop is unbounded, so there is no status word.  workspace: mi3d_surface_workspace_bytes bytes (34 per voxel plus
+ * the partial sums, rounded up), 256-byte aligned, for every entry below; 0 (and an error) for N outside [1, 65535], a side < 1,
+ * D * H * W >= 2^31 or n_classes outside [1, MI3D_COMPONENTS_MAX_CLASSES]. */
+#define MI3D_SURFACE_MAX_TOLERANCES 4
+#define MI3D_SURFACE_COUNT_COLUMNS (2 + 2 * MI3D_SURFACE_MAX_TOLERANCES)
+#define MI3D_SURFACE_TABLE_COLUMNS 8
+size_t mi3d_surface_workspace_bytes(int N, int D, int H, int W, int n_classes);
+/* dist2_out (N, D, H, W) float64, contiguous: g3 to F = the non-zero voxels of mask, at every voxel;
+ * numpy.sqrt(dist2_out) replaces scipy.ndimage.distance_transform_edt(mask == 0, sampling=spacing).  The workspace of
+ * mi3d_surface_workspace_bytes(N, D, H, W, 1). */
+int mi3d_distance_transform(const void* mask, int mask_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
+                            int64_t stride_w, const double* spacing, double* dist2_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* surface_out (N, D, H, W) uint8, contiguous: 1 on S(labels == class_value), else 0; replaces
+ * M & ~scipy.ndimage.binary_erosion(M, scipy.ndimage.generate_binary_structure(3, connectivity)) of M = (labels == class_value).
+ * Any int32 class_value; a value a uint8 map cannot hold has an empty surface. */
+int mi3d_surface_mask(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
+                      int64_t stride_w, int connectivity, int class_value, uint8_t* surface_out, void* stream);
+/* Per (sample, listed class c), with P = S(pred == c), G = S(target == c), direction 0 the distances A = {sqrt(g3 to G)[p] : p in P}
+ * and direction 1 B = {sqrt(g3 to P)[g] : g in G}; replaces, per class and direction, distance_transform_edt(~G, sampling=spacing)[P].
+ * class_values: a HOST array of n_classes (1..8) distinct int32 values.  q in [0, 1]: the quantile of the order statistics
+ * (percentile / 100); with n values they are those of rank lo = floor((n - 1) q) and hi = ceil((n - 1) q) in ascending order
+ * (numpy.percentile's linear method interpolates between them).  tol_mm: a HOST array of n_tol (0..4) finite tolerances >= 0 in mm.
+ * counts_out (N, n_classes, 10) int64: [0] |P|  [1] |G|  [2 + 4 dir + t] how many of the direction have g3 <= fl(tol_mm[t]^2), 0 for
+ *   t >= n_tol.
+ * table_out (N, n_classes, 8) float64, per direction dir four columns from 4 dir: [0] max g3  [1] g3 of rank lo  [2] g3 of rank hi
+ *   [3] the sum of sqrt(g3).  Squared where it can be: the host's correctly rounded sqrt then makes the Hausdorff distance and the
+ *   order statistics exact.  For a direction without voxels the three g3 entries are +inf and the sum is 0; where only the other
+ *   surface is empty they and the sum are +inf. */
+int mi3d_surface_distances(const void* pred, int pred_dtype, int64_t pred_stride_n, int64_t pred_stride_d, int64_t pred_stride_h,
+                           int64_t pred_stride_w, const void* target, int target_dtype, int64_t target_stride_n, int64_t target_stride_d,
+                           int64_t target_stride_h, int64_t target_stride_w, int N, int D, int H, int W, int connectivity, int n_classes,
+                           const int32_t* class_values, const double* spacing, double q, int n_tol, const double* tol_mm,
+                           int64_t* counts_out, double* table_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
  * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)
  * with the random decisions already drawn by the host (spatial.py), as one gather pass.  img: float32, lab: int64, both
