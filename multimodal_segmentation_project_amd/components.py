@@ -16,18 +16,17 @@ has the same bits on every run.  Nothing here synchronises.  Kernels: csrc/compo
 """
 import collections
 import ctypes as C
-import operator
 
 import numpy as np
 import torch
 
-from . import _lib, orientation
+from . import _lib
 from ._lib import Mi3dError, call, ptr, stream_ptr
+from ._volume import _connectivity, _integer, _samples, _strides, _workspace
 
 ORGANS = {1: 1, 2: 1, 3: 2}          # spleen, liver, kidneys (the classes of test_model.py:265): how many of each a body has
 MAX_CLASSES, MAX_KEEP = _lib.COMPONENTS_MAX_CLASSES, _lib.COMPONENTS_MAX_KEEP
 STATS_COLUMNS = 3 + 2 * MAX_KEEP      # n_components, voxels_before, voxels_kept, MAX_KEEP sizes, MAX_KEEP roots
-_LABEL = {torch.uint8: _lib.SRC_U8, torch.int64: _lib.SRC_I64}
 
 Cleaned = collections.namedtuple("Cleaned", "labels stats status classes")
 Cleaned.__doc__ = """keep_largest's result.  labels: the cleaned map (dtype, shape and strides of the input).  stats: int64 device
@@ -36,57 +35,13 @@ sizes of the kept components in rank order (0 where fewer), their roots (-1 wher
 a kernel gave up (then labels and stats mean nothing).  classes: the listed class values, one per stats row."""
 
 
-def _integer(v, what, name):
-    try:
-        return operator.index(v)
-    except TypeError:
-        raise Mi3dError(f"{what}: {name} {v!r} is not an integer") from None
-
-
-def _volume(labels, what):
-    """The (N, D, H, W) view of a label argument, its dtype code and whether it came as 3-D; every check that needs no device."""
-    if not isinstance(labels, torch.Tensor):
-        raise Mi3dError(f"{what}: the labels are a torch tensor, got {type(labels).__name__}")
-    if labels.dtype not in _LABEL:
-        raise Mi3dError(f"{what}: labels are {' or '.join(str(d) for d in _LABEL)}, got {labels.dtype}")
-    if labels.dim() not in (3, 4) or min(labels.shape) < 1:
-        raise Mi3dError(f"{what}: a (D, H, W) or (N, D, H, W) label volume expected, got {tuple(labels.shape)}")
-    single = labels.dim() == 3
-    t = labels[None] if single else labels
-    orientation.check_dense(t.shape[1:], t.stride()[1:], what)
-    v = t.shape[1] * t.shape[2] * t.shape[3]
-    if v >= 2 ** 31:
-        raise Mi3dError(f"{what}: a sample of {v} voxels; fewer than 2^31 expected")
-    if t.shape[0] > 1 and t.stride(0) < v:
-        raise Mi3dError(f"{what}: samples overlap (shape {tuple(t.shape)}, strides {tuple(t.stride())})")
-    return t, _LABEL[labels.dtype], single
-
-
-def _connectivity(connectivity, what):
-    if connectivity not in (1, 2, 3):
-        raise Mi3dError(f"{what}: connectivity {connectivity!r} is not 1, 2 or 3 (6, 18 or 26 neighbours)")
-    return int(connectivity)
-
-
-def _strides(t):
-    return [max(int(s), 1) for s in t.stride()]          # the stride of a one-element axis is never used
-
-
-def _workspace(t, what):
-    n, d, h, w = t.shape
-    nbytes = _lib.lib().mi3d_components_workspace_bytes(n, d, h, w)
-    if nbytes == 0:
-        raise Mi3dError(f"{what}: {tuple(t.shape)} is outside the library's range")
-    return nbytes
-
-
 def component_roots(labels, connectivity=1, classes=None):
     """The root of every voxel's component as int32, C-contiguous, shape of `labels`; -1 where the voxel's value is not selected.
     classes: the selected values (any iterable of integers in 1..255), None for every value 1..255.  At the voxels of class c this
     is np.unique(ids, return_index=True)[1][ids - 1] of ids = scipy.ndimage.label(labels == c, structure)[0].  The same for every
     memory layout of the same logical volume.  The status word is not returned: keep_largest hands it out."""
     what = "component_roots"
-    t, code, _ = _volume(labels, what)
+    t, code, _ = _samples(labels, what)
     connectivity = _connectivity(connectivity, what)
     select = (C.c_uint8 * 256)()
     for v in range(1, 256) if classes is None else classes:
@@ -95,7 +50,7 @@ def component_roots(labels, connectivity=1, classes=None):
             raise Mi3dError(f"{what}: class {v} cannot be selected: values 1..255 can")
         select[v] = 1
     _lib.require_cuda(t, what)
-    nbytes = _workspace(t, what)
+    nbytes = _workspace("mi3d_components_workspace_bytes", t, what)
     # everything is checked: allocate and launch
     ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
     status = torch.empty((), dtype=torch.int32, device=t.device)
@@ -128,7 +83,7 @@ def keep_largest(labels, keep=ORGANS, connectivity=1, min_size=1, fill=0):
     ids, n = scipy.ndimage.label(labels == c, structure); sizes = np.bincount(ids.ravel())[1:]; the keep[c] first of a stable
     argsort of -sizes; labels[(labels == c) & ~np.isin(ids, kept + 1)] = fill.  Every argument is checked before the first launch."""
     what = "keep_largest"
-    t, code, single = _volume(labels, what)
+    t, code, single = _samples(labels, what)
     connectivity = _connectivity(connectivity, what)
     table = _keep_table(keep, what)
     min_size, fill = _integer(min_size, what, "min_size"), _integer(fill, what, "fill")
@@ -137,7 +92,7 @@ def keep_largest(labels, keep=ORGANS, connectivity=1, min_size=1, fill=0):
     if not 0 <= fill <= 255:
         raise Mi3dError(f"{what}: fill {fill} is outside 0..255")
     _lib.require_cuda(t, what)
-    nbytes = _workspace(t, what)
+    nbytes = _workspace("mi3d_components_workspace_bytes", t, what)
     # everything is checked: allocate and launch
     n, nc = t.shape[0], len(table)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)

@@ -12,10 +12,7 @@
 // does not depend on launch order, tile size or strides.  Only integer atomics (min, add, max of unique keys) are used: every
 // output has the same bits on every run.  No workgroup waits on another; every parent-following loop counts its steps and, past
 // its bound, sets the status word and leaves.
-#include <cstdint>
-
-#include "ops.h"
-#include "../../include/mi3d.h"
+#include "volume.h"
 
 namespace {
 constexpr int BLK = 256, NW = BLK / 64;
@@ -24,16 +21,8 @@ constexpr int MAXC = MI3D_COMPONENTS_MAX_CLASSES, MAXK = MI3D_COMPONENTS_MAX_KEE
 constexpr unsigned SELECT_BLOCKS = 512;          // the select pass strides over the sample: a workgroup's candidates meet 512 others at most
 typedef unsigned long long u64;
 
-struct Vol {
-    int N, D, H, W;
-    int64_t sn, sd, sh, sw;          // element strides of the labels
-    MI3D_HD int64_t V() const { return (int64_t)D * H * W; }
-};
 struct Select {                      // bit v: label value v is selected; bit 0 is never set
     u64 m[4];
-};
-struct Listed {                      // the listed classes of mi3d_keep_components
-    int n, value[MAXC], k[MAXC];
 };
 
 __device__ __forceinline__ int selected(const Select& s, int64_t v) {
@@ -43,14 +32,12 @@ __device__ __forceinline__ int selected(const Select& s, int64_t v) {
 }
 template <typename T> __device__ __forceinline__ int64_t label_value(const T* p, int64_t off) { return (int64_t)p[off]; }
 
-// The preceding half of the 26 neighbours in C order, without the left neighbour (0, 0, -1): (dd, dh, dw) with dd < 0, or dd == 0
-// and dh < 0.  Offset j is part of connectivity c iff it has at most c non-zero coordinates.
+// The preceding half of the 26 neighbours in C order, without the left neighbour (0, 0, -1): dd < 0, or dd == 0 and dh < 0.
 __device__ __forceinline__ void back_offset(int j, int& dd, int& dh, int& dw) {
     dd = j < 9 ? -1 : 0;
     dh = j < 9 ? j / 3 - 1 : -1;
     dw = j % 3 - 1;
 }
-__device__ __forceinline__ int nonzeros(int dd, int dh, int dw) { return (dd != 0) + (dh != 0) + (dw != 0); }
 
 // Which pairs need a union at all.  A voxel is a START if it opens a row run of its tile: its tile column is 0 or its left
 // neighbour carries another value.  With v a voxel, n = v + (dd, dh, dw) of the same value:
@@ -110,7 +97,7 @@ __global__ __launch_bounds__(BLK) void tile_kernel(const T* __restrict__ lab, Vo
 #pragma unroll
     for (int q = 0; q < ROWS / NW; q++) {
         const int r = wave + q * NW, d = d0 + r / TH, h = h0 + r % TH;
-        mine[q] = d < vol.D && h < vol.H && w < vol.W ? label_value(lab, d * vol.sd + h * vol.sh + w * vol.sw) : 0;
+        mine[q] = d < vol.D && h < vol.H && w < vol.W ? label_value(lab, vol.offset(d, h, w)) : 0;
     }
 #pragma unroll
     for (int q = 0; q < ROWS / NW; q++) {
@@ -222,7 +209,8 @@ __global__ __launch_bounds__(BLK) void seam_kernel(Vol vol, int conn, int32_t* _
     const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (i >= V) return;
     parent += blockIdx.y * V, cls += blockIdx.y * V;
-    const int w = (int)(i % vol.W), h = (int)(i / vol.W % vol.H), d = (int)(i / ((int64_t)vol.W * vol.H));
+    int d, h, w;
+    vol.split(i, d, h, w);
     const int cw = w % TW, ch = h % TH, cd = d % TD;
     if (cd > 0 && ch > 0 && ch < TH - 1 && cw > 0 && cw < TW - 1) return;          // every neighbour in the same tile
     const int v = cls[i];
@@ -284,7 +272,7 @@ __global__ __launch_bounds__(BLK) void flatten_kernel(Vol vol, const int32_t* __
 // of the atomics.  Slots only grow: a key below slot k - 1 can never enter and is dropped after one look.  A workgroup first keeps
 // its own k best per class in LDS by the same insertion (they include whatever it can contribute to the sample's k best) and counts
 // components and voxels there; at its end it offers those keys and adds the counts, once.
-__device__ __forceinline__ int keep_count(const Listed& cl, int c) {          // cl.k[c] without indexing the kernel's arguments
+__device__ __forceinline__ int keep_count(const KeepClasses& cl, int c) {          // cl.k[c] without indexing the kernel's arguments
     int k = 0;
 #pragma unroll
     for (int j = 0; j < MAXC; j++)
@@ -298,7 +286,7 @@ __device__ __forceinline__ void offer(u64* slot, int k, u64 key) {
         key = old < key ? old : key;
     }
 }
-__global__ __launch_bounds__(BLK) void select_kernel(Vol vol, Listed cl, const int32_t* __restrict__ root, const int32_t* __restrict__ size,
+__global__ __launch_bounds__(BLK) void select_kernel(Vol vol, KeepClasses cl, const int32_t* __restrict__ root, const int32_t* __restrict__ size,
                                                      const uint8_t* __restrict__ cls, u64* __restrict__ stats) {
     __shared__ unsigned comps[MAXC], voxels[MAXC];
     __shared__ u64 best[MAXC][MAXK];
@@ -310,10 +298,8 @@ __global__ __launch_bounds__(BLK) void select_kernel(Vol vol, Listed cl, const i
     for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < V; i += (int64_t)gridDim.x * BLK) {
         if (root[blockIdx.y * V + i] != (int)i) continue;
         const int v = cls[blockIdx.y * V + i];
-        int c = -1, k = 0;
-#pragma unroll
-        for (int j = 0; j < MAXC; j++)
-            if (j < cl.n && cl.value[j] == v) c = j, k = cl.k[j];
+        int k;
+        const int c = class_index(cl, v, k);
         if (c >= 0) {
             const unsigned sz = (unsigned)size[blockIdx.y * V + i];
             atomicAdd(&comps[c], 1u);
@@ -335,7 +321,7 @@ __global__ __launch_bounds__(BLK) void select_kernel(Vol vol, Listed cl, const i
 
 // keys -> the table of mi3d.h: a component is kept iff its rank is below k and its size is at least min_size; sizes fall with the
 // rank, so the kept ones are a prefix.  One thread per (sample, class).
-__global__ __launch_bounds__(BLK) void finish_kernel(int rows, Listed cl, int64_t min_size, int64_t* __restrict__ stats) {
+__global__ __launch_bounds__(BLK) void finish_kernel(int rows, KeepClasses cl, int64_t min_size, int64_t* __restrict__ stats) {
     const int t = blockIdx.x * BLK + threadIdx.x;
     if (t >= rows) return;
     int64_t* s = stats + (int64_t)t * STATS;
@@ -355,7 +341,7 @@ __global__ __launch_bounds__(BLK) void finish_kernel(int rows, Listed cl, int64_
 // ---- apply ------------------------------------------------------------------------------------------------------------------------
 // One thread per voxel, which reads its own label and writes its own output: out may be lab.
 template <typename T>
-__global__ __launch_bounds__(BLK) void apply_kernel(const T* lab, T* out, Vol vol, Listed cl, int fill,
+__global__ __launch_bounds__(BLK) void apply_kernel(const T* lab, T* out, Vol vol, KeepClasses cl, int fill,
                                                     const int32_t* __restrict__ root, const uint8_t* __restrict__ cls,
                                                     const int64_t* __restrict__ stats) {
     __shared__ int kept[MAXC][MAXK];
@@ -366,16 +352,14 @@ __global__ __launch_bounds__(BLK) void apply_kernel(const T* lab, T* out, Vol vo
     __syncthreads();
     const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (i >= V) return;
-    const int w = (int)(i % vol.W), h = (int)(i / vol.W % vol.H), d = (int)(i / ((int64_t)vol.W * vol.H));
-    const int64_t off = blockIdx.y * vol.sn + d * vol.sd + h * vol.sh + w * vol.sw;
+    int d, h, w;
+    vol.split(i, d, h, w);
+    const int64_t off = blockIdx.y * vol.sn + vol.offset(d, h, w);
     T l = lab[off];
     const int v = cls[blockIdx.y * V + i];
     if (v) {
         const int r = root[blockIdx.y * V + i];
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < MAXC; j++)
-            if (j < cl.n && cl.value[j] == v) c = j;
+        const int c = class_index(cl, v, 0);
         bool keep = false;
 #pragma unroll
         for (int j = 0; j < MAXK; j++) keep = keep || kept[c][j] == r;
@@ -385,40 +369,24 @@ __global__ __launch_bounds__(BLK) void apply_kernel(const T* lab, T* out, Vol vo
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-struct Workspace {
+struct Workspace {          // the layout, once: mi3d_components_workspace_bytes counts it over a null base
     int32_t *parent, *root, *size;
     uint8_t* cls;
+    size_t bytes;
+    Workspace(void* base, int64_t NV) {
+        Arena a{static_cast<char*>(base)};
+        parent = a.take<int32_t>(NV), root = a.take<int32_t>(NV), size = a.take<int32_t>(NV), cls = a.take<uint8_t>(NV);
+        bytes = a.used;
+    }
 };
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// total voxels, or 0 where the sizes are outside the library's range
-int64_t total_voxels(int N, int D, int H, int W) {
-    if (N < 1 || N > 65535 || D < 1 || H < 1 || W < 1) return 0;
-    const int64_t V = (int64_t)D * H * W;
-    if ((int64_t)D * H >= ((int64_t)1 << 31) || V >= ((int64_t)1 << 31)) return 0;
-    return N * V;          // < 2^47
-}
-size_t workspace_bytes(int64_t NV) { return 3 * align256((size_t)NV * 4) + align256((size_t)NV); }
 
 int check_common(const char* name, const void* labels, int label_dtype, int N, int D, int H, int W, int64_t sn, int64_t sd, int64_t sh,
                  int64_t sw, int connectivity, const int32_t* status_out, const void* workspace, size_t workspace_bytes_given) {
-    MI3D_CHECK_ARG(labels && status_out && workspace, "%s: null pointer", name);
-    MI3D_CHECK_ARG(label_dtype == MI3D_SRC_U8 || label_dtype == MI3D_SRC_I64, "%s: labels are uint8 or int64, not dtype code %d", name,
-                   label_dtype);
-    const int64_t NV = total_voxels(N, D, H, W);
-    MI3D_CHECK_ARG(NV > 0, "%s: N in [1, 65535], sides >= 1 and D * H * W < 2^31 expected, got %d x (%d, %d, %d)", name, N, D, H, W);
-    MI3D_CHECK_ARG(sn >= 1 && sd >= 1 && sh >= 1 && sw >= 1, "%s: strides must be positive element counts", name);
-    MI3D_CHECK_ARG(connectivity >= 1 && connectivity <= 3, "%s: connectivity %d is not 1, 2 or 3", name, connectivity);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", name);
-    MI3D_CHECK_ARG(workspace_bytes_given >= workspace_bytes(NV), "%s: workspace of %zu bytes, %zu needed", name, workspace_bytes_given,
-                   workspace_bytes(NV));
-    return 0;
-}
-
-Workspace carve(void* workspace, int64_t NV) {
-    char* p = static_cast<char*>(workspace);
-    const size_t words = align256((size_t)NV * 4);
-    return Workspace{(int32_t*)p, (int32_t*)(p + words), (int32_t*)(p + 2 * words), (uint8_t*)(p + 3 * words)};
+    MI3D_TRY(check_map(name, "labels", labels, label_dtype, sn, sd, sh, sw));
+    MI3D_TRY(check_sizes(name, N, D, H, W));
+    MI3D_TRY(check_connectivity(name, connectivity));
+    MI3D_CHECK_ARG(status_out, "%s: null pointer (status_out)", name);
+    return check_workspace(name, workspace, workspace_bytes_given, Workspace(nullptr, total_voxels(N, D, H, W)).bytes);
 }
 
 // status = 0, then tile pass, seam pass, flatten into `root` (and the sizes where size != NULL)
@@ -427,11 +395,10 @@ int label_launch(const void* labels, int label_dtype, const Vol& vol, const Sele
     MI3D_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
     const int tilesW = cdiv(vol.W, TW), tilesH = cdiv(vol.H, TH), tilesD = cdiv(vol.D, TD);
     const int64_t tiles = (int64_t)tilesW * tilesH * tilesD;          // <= V < 2^31
-    dim3 tgrid((unsigned)tiles, (unsigned)vol.N), vgrid((unsigned)((vol.V() + BLK - 1) / BLK), (unsigned)vol.N);
-    if (label_dtype == MI3D_SRC_U8)
-        tile_kernel<uint8_t><<<tgrid, BLK, 0, stream>>>((const uint8_t*)labels, vol, sel, conn, tilesW, tilesH, ws.parent, ws.cls, size, status);
-    else
-        tile_kernel<int64_t><<<tgrid, BLK, 0, stream>>>((const int64_t*)labels, vol, sel, conn, tilesW, tilesH, ws.parent, ws.cls, size, status);
+    dim3 tgrid((unsigned)tiles, (unsigned)vol.N), vgrid((unsigned)voxel_blocks(vol.V()), (unsigned)vol.N);
+    dispatch_src(label_dtype, LabelTypes(), [&](auto tag) {
+        tile_kernel<<<tgrid, BLK, 0, stream>>>((const decltype(tag)*)labels, vol, sel, conn, tilesW, tilesH, ws.parent, ws.cls, size, status);
+    });
     MI3D_LAUNCH_CHECK();
     if (tiles > 1) {
         seam_kernel<<<vgrid, BLK, 0, stream>>>(vol, conn, ws.parent, ws.cls, status);
@@ -451,7 +418,7 @@ size_t mi3d_components_workspace_bytes(int N, int D, int H, int W) {
         mi3d_set_error("mi3d_components_workspace_bytes: N in [1, 65535], sides >= 1 and D * H * W < 2^31 expected");
         return 0;
     }
-    return workspace_bytes(NV);
+    return Workspace(nullptr, NV).bytes;
 }
 
 int mi3d_component_roots(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d,
@@ -466,7 +433,7 @@ int mi3d_component_roots(const void* labels, int label_dtype, int N, int D, int 
     for (int v = 1; v < 256; v++)
         if (class_select[v]) sel.m[v >> 6] |= 1ull << (v & 63);
     const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
-    return label_launch(labels, label_dtype, vol, sel, connectivity, carve(workspace, (int64_t)N * vol.V()), roots_out, nullptr, status_out,
+    return label_launch(labels, label_dtype, vol, sel, connectivity, Workspace(workspace, (int64_t)N * vol.V()), roots_out, nullptr, status_out,
                         (hipStream_t)stream);
 }
 
@@ -479,35 +446,33 @@ int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int 
                           workspace, workspace_bytes));
     MI3D_CHECK_ARG(class_values && keep_k && labels_out && stats_out, "%s: null pointer", name);
     MI3D_CHECK_ARG(((uintptr_t)stats_out & 7) == 0, "%s: stats_out must be 8-byte aligned", name);
-    MI3D_CHECK_ARG(n_classes >= 1 && n_classes <= MAXC, "%s: 1 to %d classes, got %d", name, MAXC, n_classes);
     MI3D_CHECK_ARG(min_size >= 1, "%s: min_size must be at least 1", name);
     MI3D_CHECK_ARG(fill >= 0 && fill <= 255, "%s: fill %d outside 0..255", name, fill);
     Select sel{};
-    Listed cl{};
-    cl.n = n_classes;
+    KeepClasses cl{};
+    MI3D_TRY(check_classes(name, n_classes, class_values, cl));
     for (int j = 0; j < n_classes; j++) {
         const int v = class_values[j], k = keep_k[j];
         MI3D_CHECK_ARG(v >= 1 && v <= 255, "%s: class value %d outside 1..255", name, v);
         MI3D_CHECK_ARG(k >= 1 && k <= MAXK, "%s: keep count %d of class %d outside 1..%d", name, k, v, MAXK);
-        MI3D_CHECK_ARG(!((sel.m[v >> 6] >> (v & 63)) & 1), "%s: class value %d listed twice", name, v);
         sel.m[v >> 6] |= 1ull << (v & 63);
-        cl.value[j] = v, cl.k[j] = k;
+        cl.k[j] = k;
     }
     const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
-    const Workspace ws = carve(workspace, (int64_t)N * vol.V());
+    const Workspace ws(workspace, (int64_t)N * vol.V());
     hipStream_t s = (hipStream_t)stream;
     MI3D_HIP(hipMemsetAsync(stats_out, 0, (size_t)N * n_classes * STATS * sizeof(int64_t), s));
     MI3D_TRY(label_launch(labels, label_dtype, vol, sel, connectivity, ws, ws.root, ws.size, status_out, s));
-    dim3 vgrid((unsigned)((vol.V() + BLK - 1) / BLK), (unsigned)N);
+    dim3 vgrid((unsigned)voxel_blocks(vol.V()), (unsigned)N);
     dim3 sgrid(vgrid.x < SELECT_BLOCKS ? vgrid.x : SELECT_BLOCKS, (unsigned)N);
     select_kernel<<<sgrid, BLK, 0, s>>>(vol, cl, ws.root, ws.size, ws.cls, (u64*)stats_out);
     MI3D_LAUNCH_CHECK();
     finish_kernel<<<cdiv(N * n_classes, BLK), BLK, 0, s>>>(N * n_classes, cl, min_size, stats_out);
     MI3D_LAUNCH_CHECK();
-    if (label_dtype == MI3D_SRC_U8)
-        apply_kernel<uint8_t><<<vgrid, BLK, 0, s>>>((const uint8_t*)labels, (uint8_t*)labels_out, vol, cl, fill, ws.root, ws.cls, stats_out);
-    else
-        apply_kernel<int64_t><<<vgrid, BLK, 0, s>>>((const int64_t*)labels, (int64_t*)labels_out, vol, cl, fill, ws.root, ws.cls, stats_out);
+    dispatch_src(label_dtype, LabelTypes(), [&](auto tag) {
+        using T = decltype(tag);
+        apply_kernel<T><<<vgrid, BLK, 0, s>>>((const T*)labels, (T*)labels_out, vol, cl, fill, ws.root, ws.cls, stats_out);
+    });
     MI3D_LAUNCH_CHECK();
     return 0;
 }

@@ -14,25 +14,20 @@
 #include <type_traits>
 #include <utility>
 
-#include "ops.h"
-#include "../../include/mi3d.h"
+#include "volume.h"
 
 namespace {
 constexpr int BLK = 256, NW = BLK / 64;
-constexpr int MAX_SIDE = 65535;      // a slice index rides in gridDim.y
 constexpr int TARGET_BLOCKS = 1024;  // four workgroups per CU: where a launcher may choose, it makes about this many
 typedef unsigned long long u64;
 
 struct Dims {
     int n[3];
-    bool ok() const { return n[0] >= 1 && n[1] >= 1 && n[2] >= 1 && n[0] <= MAX_SIDE && n[1] <= MAX_SIDE && n[2] <= MAX_SIDE; }
+    bool ok() const { return sides_ok(n[0], n[1], n[2]); }          // a slice index rides in gridDim.y
 };
 struct Strides {
     int64_t s[3];
-    bool ok() const {
-        const int64_t lim = (int64_t)1 << 44;
-        return s[0] >= 1 && s[1] >= 1 && s[2] >= 1 && s[0] < lim && s[1] < lim && s[2] < lim;
-    }
+    bool ok() const { return strides_ok(s[0], s[1], s[2]); }
 };
 
 // the three axes by increasing stride, an axis of one element last among equals: o[0] = F, o[1] = M, o[2] = S
@@ -440,8 +435,6 @@ View view_of(int axis, Dims n, Strides st, int rot90) {
     return View{st.s[axis], 0, st.s[a], st.s[b]};
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // the launcher of mi3d_slice_minmax
 int slice_minmax_launch(const char* name, const void* image, int image_dtype, int D, int H, int W, int64_t stride_d,
                         int64_t stride_h, int64_t stride_w, int axis, int mode, const int32_t* index, int k, uint32_t* keys,
@@ -519,17 +512,11 @@ int mi3d_foreground_profiles(const void* label, int label_dtype, int D, int H, i
                                                                   (nS + MAX_SG - 1) / MAX_SG));
     const int SG = (int)((nS + groups - 1) / groups);
     dim3 grid((unsigned)(fChunks * mTiles), (unsigned)((nS + SG - 1) / SG));
-    auto launch = [&](auto kernel, auto tag) {
-        kernel<<<grid, BLK, 0, (hipStream_t)stream>>>((const decltype(tag)*)label, c[S], c[M], c[F], nS, nM, nF, sS, sM, sF, lgLF, fChunks,
-                                                      SG);
-    };
-    if (label_dtype == MI3D_SRC_U8) {
-        if (vec) launch(foreground_profiles_kernel<uint8_t, 16>, uint8_t());
-        else launch(foreground_profiles_kernel<uint8_t, 1>, uint8_t());
-    } else {
-        if (vec) launch(foreground_profiles_kernel<int64_t, 2>, int64_t());
-        else launch(foreground_profiles_kernel<int64_t, 1>, int64_t());
-    }
+    dispatch_src(label_dtype, LabelTypes(), [&](auto tag) {
+        using T = decltype(tag);
+        auto kernel = vec ? foreground_profiles_kernel<T, 16 / (int)sizeof(T)> : foreground_profiles_kernel<T, 1>;
+        kernel<<<grid, BLK, 0, (hipStream_t)stream>>>((const T*)label, c[S], c[M], c[F], nS, nM, nF, sS, sM, sF, lgLF, fChunks, SG);
+    });
     MI3D_LAUNCH_CHECK();
     return 0;
 }

@@ -16,8 +16,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "ops.h"
-#include "../../include/mi3d.h"
+#include "volume.h"
 
 namespace {
 constexpr int BLK = 256;
@@ -244,23 +243,19 @@ __global__ __launch_bounds__(BLK) void restore_labels3_kernel(const uint8_t* __r
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-constexpr int MAX_SIDE = 65535;      // od rides in gridDim.y; in-plane indices stay far inside int32
 struct Dims {
     int d, h, w;
-    bool ok() const { return d >= 1 && h >= 1 && w >= 1 && d <= MAX_SIDE && h <= MAX_SIDE && w <= MAX_SIDE; }
+    bool ok() const { return sides_ok(d, h, w); }          // od rides in gridDim.y
 };
 
 // The argument check of every entry; `ptrs` is the entry's own null / alias test.  rows: the tables' row counts, which must be
-// the sides of `out`.  st: a stored scan's strides, positive (any value where the side is 1) and the last element's offset
-// inside int64 with room to spare: 65535^3 < 2^48 elements, a dense tensor's largest stride is < 2^32 (that the offset lies
-// inside the caller's buffer is the caller's to guarantee: include/mi3d.h).  tabs16: three tables that must be 16-byte aligned.
+// the sides of `out`.  st: a stored scan's strides (strides_ok; that the offset lies inside the caller's buffer is the caller's to
+// guarantee: include/mi3d.h).  tabs16: three tables that must be 16-byte aligned.
 int check_args(const char* name, bool ptrs, Dims in, Dims out, const int* rows, const SrcStrides* st = nullptr,
                const void* const* tabs16 = nullptr) {
     MI3D_CHECK_ARG(ptrs, "%s: null or aliased pointers", name);
     MI3D_CHECK_ARG(in.ok() && out.ok(), "%s: sides must be in [1, %d]", name, MAX_SIDE);
-    const int64_t lim = (int64_t)1 << 44;
-    MI3D_CHECK_ARG(!st || (st->d >= 1 && st->h >= 1 && st->w >= 1 && st->d < lim && st->h < lim && st->w < lim),
-                   "%s: strides must be positive element counts", name);
+    MI3D_CHECK_ARG(!st || strides_ok(st->d, st->h, st->w), "%s: strides must be positive element counts", name);
     MI3D_CHECK_ARG(!rows || (rows[0] == out.d && rows[1] == out.h && rows[2] == out.w),
                    "%s: tables have (%d, %d, %d) rows, the output is (%d, %d, %d)", name, rows ? rows[0] : 0, rows ? rows[1] : 0,
                    rows ? rows[2] : 0, out.d, out.h, out.w);
@@ -279,20 +274,8 @@ int row_grid(const char* name, Dims o, int NV, const void* out, RowGrid& g) {
     g.WQ = (o.w + NV - 1) / NV;
     MI3D_CHECK_ARG((int64_t)o.h * g.WQ < (int64_t)1 << 31, "%s: output plane too large", name);
     g.grid = dim3((unsigned)(((int64_t)o.h * g.WQ + BLK - 1) / BLK), (unsigned)o.d);
-    g.vec = o.w % NV == 0 && ((uintptr_t)out & 15) == 0;
+    g.vec = o.w % NV == 0 && aligned16(out);
     return 0;
-}
-
-// Source-dtype dispatch: f(S()) for the one type S of the list whose MI3D_SRC_* code is `code`; false where none is
-template <typename S> constexpr int src_code = -1;
-template <> constexpr int src_code<uint8_t> = MI3D_SRC_U8;
-template <> constexpr int src_code<int16_t> = MI3D_SRC_I16;
-template <> constexpr int src_code<float> = MI3D_SRC_F32;
-template <> constexpr int src_code<int64_t> = MI3D_SRC_I64;
-template <typename... S> struct Types {};
-template <typename... S, typename F>
-bool dispatch_src(int code, Types<S...>, F&& f) {
-    return ((code == src_code<S> && (f(S()), true)) || ...);
 }
 
 // every axis with more than one element has the stride of a contiguous (D, H, W) volume

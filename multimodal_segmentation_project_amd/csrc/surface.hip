@@ -21,10 +21,8 @@
 // through fixed slots and one fixed-order reduce: every output has the same bits on every run.  No workgroup waits on another and
 // no loop is unbounded, so there is no status word.  Every launch is on the caller's stream, every buffer the caller's.
 #include <cmath>
-#include <cstdint>
 
-#include "ops.h"
-#include "../../include/mi3d.h"
+#include "volume.h"
 
 #pragma clang fp contract(off)          // hipcc would fuse a product into the add that follows it
 
@@ -34,14 +32,6 @@ constexpr int MAXC = MI3D_COMPONENTS_MAX_CLASSES, MAXT = MI3D_SURFACE_MAX_TOLERA
 constexpr int COUNTS = MI3D_SURFACE_COUNT_COLUMNS, TABLE = MI3D_SURFACE_TABLE_COLUMNS;
 typedef unsigned long long u64;
 
-struct Vol {
-    int N, D, H, W;
-    int64_t sn, sd, sh, sw;          // element strides of a label map
-    MI3D_HD int64_t V() const { return (int64_t)D * H * W; }
-};
-struct Listed {                      // the listed classes: any distinct int32 values
-    int n, value[MAXC];
-};
 struct Tol {                         // fl(tau * tau) of every tolerance
     int n;
     double sq[MAXT];
@@ -59,7 +49,7 @@ __device__ __forceinline__ double min_nonneg(double a, double b) { return b < a 
 // One thread per voxel.  out (N, V) bytes: j + 1 at a surface voxel of listed class j, else 0.  counts (may be NULL): the column of
 // this map in the counts table, one integer atomic per (workgroup, class).  grid: x over voxels, y = sample.
 template <typename T>
-__global__ __launch_bounds__(BLK) void surface_kernel(const T* __restrict__ lab, Vol vol, Listed cl, int conn, uint8_t* __restrict__ out,
+__global__ __launch_bounds__(BLK) void surface_kernel(const T* __restrict__ lab, Vol vol, Classes cl, int conn, uint8_t* __restrict__ out,
                                                       u64* __restrict__ counts) {
     __shared__ unsigned found[MAXC];
     if (threadIdx.x < MAXC) found[threadIdx.x] = 0;
@@ -67,22 +57,20 @@ __global__ __launch_bounds__(BLK) void surface_kernel(const T* __restrict__ lab,
     const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (i < V) {
         lab += blockIdx.y * vol.sn;
-        const int w = (int)(i % vol.W), h = (int)(i / vol.W % vol.H), d = (int)(i / ((int64_t)vol.W * vol.H));
-        const int64_t v = (int64_t)lab[d * vol.sd + h * vol.sh + w * vol.sw];
-        int c = -1;
-#pragma unroll
-        for (int j = 0; j < MAXC; j++)
-            if (j < cl.n && (int64_t)cl.value[j] == v) c = j;
+        int d, h, w;
+        vol.split(i, d, h, w);
+        const int64_t v = (int64_t)lab[vol.offset(d, h, w)];
+        const int c = class_index(cl, v);
         bool edge = false;
         if (c >= 0) {
             for (int o = 0; o < 27 && !edge; o++) {
-                const int dd = o / 9 - 1, dh = o / 3 % 3 - 1, dw = o % 3 - 1, nz = (dd != 0) + (dh != 0) + (dw != 0);
+                const int dd = o / 9 - 1, dh = o / 3 % 3 - 1, dw = o % 3 - 1, nz = nonzeros(dd, dh, dw);
                 if (nz == 0 || nz > conn) continue;
                 const int nd = d + dd, nh = h + dh, nw = w + dw;
                 if (nd < 0 || nd >= vol.D || nh < 0 || nh >= vol.H || nw < 0 || nw >= vol.W)
                     edge = true;          // border_value = 0: outside the volume is outside the class
                 else
-                    edge = (int64_t)lab[nd * vol.sd + nh * vol.sh + nw * vol.sw] != v;
+                    edge = (int64_t)lab[vol.offset(nd, nh, nw)] != v;
             }
             if (edge) atomicAdd(&found[c], 1u);
         }
@@ -98,8 +86,9 @@ template <typename T>
 __global__ __launch_bounds__(BLK) void nonzero_kernel(const T* __restrict__ mask, Vol vol, uint8_t* __restrict__ out) {
     const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (i >= V) return;
-    const int w = (int)(i % vol.W), h = (int)(i / vol.W % vol.H), d = (int)(i / ((int64_t)vol.W * vol.H));
-    out[blockIdx.y * V + i] = (uint8_t)(mask[blockIdx.y * vol.sn + d * vol.sd + h * vol.sh + w * vol.sw] != 0);
+    int d, h, w;
+    vol.split(i, d, h, w);
+    out[blockIdx.y * V + i] = (uint8_t)(mask[blockIdx.y * vol.sn + vol.offset(d, h, w)] != 0);
 }
 
 // ---- w pass -----------------------------------------------------------------------------------------------------------------------
@@ -187,13 +176,10 @@ __global__ __launch_bounds__(BLK) void query_kernel(const double* __restrict__ i
             if (t < tol.n && g <= tol.sq[t]) atomicAdd(&within[t], 1u);
         root = sqrt(g);
     }
-    for (int off = 32; off > 0; off >>= 1) root = root + __shfl_down(root, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = root;
+    block_sum_fixed_put(root, wave_sum);
     __syncthreads();
     if (threadIdx.x == 0) {
-        double sum = wave_sum[0];
-        for (int v = 1; v < NW; v++) sum = sum + wave_sum[v];
-        partial[job * gridDim.x + blockIdx.x] = sum;
+        partial[job * gridDim.x + blockIdx.x] = block_sum_fixed_get(wave_sum);
         if (top) atomicMax(state + 2 * job + 1, top);
     }
     if (threadIdx.x < tol.n && within[threadIdx.x])
@@ -218,8 +204,7 @@ __global__ __launch_bounds__(BLK) void select_kernel(const u64* __restrict__ lis
     double* row = table + blockIdx.y * row_stride + blockIdx.z * 4;
     double sum = 0.0;
     for (int64_t b = threadIdx.x; b < blocks; b += BLK) sum = sum + partial[job * blocks + b];
-    for (int off = 32; off > 0; off >>= 1) sum = sum + __shfl_down(sum, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = sum;
+    block_sum_fixed_put(sum, wave_sum);
     if (threadIdx.x == 0) above = ~0ull;
     __syncthreads();
     if (n == 0) {          // an empty direction
@@ -228,10 +213,8 @@ __global__ __launch_bounds__(BLK) void select_kernel(const u64* __restrict__ lis
         return;
     }
     if (threadIdx.x == 0) {
-        double total = wave_sum[0];
-        for (int v = 1; v < NW; v++) total = total + wave_sum[v];
         row[0] = __longlong_as_double((long long)state[2 * job + 1]);
-        row[3] = total;
+        row[3] = block_sum_fixed_get(wave_sum);
     }
     list += job * V;
     const double at = (double)(n - 1) * q;
@@ -279,72 +262,30 @@ __global__ __launch_bounds__(BLK) void select_kernel(const u64* __restrict__ lis
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// total voxels, or 0 where the sizes are outside the library's range
-int64_t total_voxels(int N, int D, int H, int W) {
-    if (N < 1 || N > 65535 || D < 1 || H < 1 || W < 1) return 0;
-    const int64_t V = (int64_t)D * H * W;
-    if ((int64_t)D * H >= ((int64_t)1 << 31) || V >= ((int64_t)1 << 31)) return 0;
-    return N * V;          // < 2^47
-}
-int64_t voxel_blocks(int64_t V) { return (V + BLK - 1) / BLK; }
-
-// the two surface bytemaps, two buffers of (sample, direction, voxel) doubles, the partial sums and the state words
+// the two surface bytemaps, two buffers of (sample, direction, voxel) doubles, the partial sums, the state words: the layout, once
 struct Workspace {
     uint8_t *pred, *target;
     double *a, *b, *partial;
     u64* state;
+    size_t bytes;
+    Workspace(void* base, int N, int64_t V) {
+        Arena ar{static_cast<char*>(base)};
+        pred = ar.take<uint8_t>((size_t)N * V), target = ar.take<uint8_t>((size_t)N * V);
+        a = ar.take<double>((size_t)N * V * 2), b = ar.take<double>((size_t)N * V * 2);
+        partial = ar.take<double>((size_t)(2 * N * voxel_blocks(V))), state = ar.take<u64>((size_t)N * 4);
+        bytes = ar.used;
+    }
 };
-struct Parts {          // byte sizes of the workspace's parts for N samples of V voxels
-    size_t maps, lines, partial, state;
-    Parts(int N, int64_t V)
-        : maps(align256((size_t)N * V)), lines(align256((size_t)N * V * 16)), partial(align256((size_t)(2 * N * voxel_blocks(V)) * 8)),
-          state(align256((size_t)N * 4 * 8)) {}
-    size_t total() const { return 2 * maps + 2 * lines + partial + state; }
-};
-Workspace carve(void* workspace, const Parts& parts) {
-    char* p = static_cast<char*>(workspace);
-    Workspace ws;
-    ws.pred = (uint8_t*)p, ws.target = (uint8_t*)(p + parts.maps);
-    p += 2 * parts.maps;
-    ws.a = (double*)p, ws.b = (double*)(p + parts.lines);
-    p += 2 * parts.lines;
-    ws.partial = (double*)p;
-    ws.state = (u64*)(p + parts.partial);
-    return ws;
-}
 
-int check_map(const char* name, const char* which, const void* labels, int dtype, int64_t sn, int64_t sd, int64_t sh, int64_t sw) {
-    MI3D_CHECK_ARG(labels, "%s: null pointer (%s)", name, which);
-    MI3D_CHECK_ARG(dtype == MI3D_SRC_U8 || dtype == MI3D_SRC_I64, "%s: %s is uint8 or int64, not dtype code %d", name, which, dtype);
-    MI3D_CHECK_ARG(sn >= 1 && sd >= 1 && sh >= 1 && sw >= 1, "%s: the strides of %s must be positive element counts", name, which);
-    return 0;
-}
-int check_sizes(const char* name, int N, int D, int H, int W) {
-    MI3D_CHECK_ARG(total_voxels(N, D, H, W) > 0, "%s: N in [1, 65535], sides >= 1 and D * H * W < 2^31 expected, got %d x (%d, %d, %d)", name, N, D,
-                   H, W);
-    return 0;
-}
 int check_spacing(const char* name, const double* spacing) {
     MI3D_CHECK_ARG(spacing, "%s: null pointer (spacing)", name);
     for (int a = 0; a < 3; a++)
         MI3D_CHECK_ARG(std::isfinite(spacing[a]) && spacing[a] > 0.0, "%s: spacing %g of axis %d is not a positive finite number", name, spacing[a], a);
     return 0;
 }
-int check_workspace(const char* name, const void* workspace, size_t given, const Parts& parts) {
-    MI3D_CHECK_ARG(workspace, "%s: null pointer (workspace)", name);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", name);
-    MI3D_CHECK_ARG(given >= parts.total(), "%s: workspace of %zu bytes, %zu needed", name, given, parts.total());
-    return 0;
-}
-
-int surface_launch(const void* labels, int dtype, const Vol& vol, const Listed& cl, int conn, uint8_t* out, u64* counts, hipStream_t s) {
+int surface_launch(const void* labels, int dtype, const Vol& vol, const Classes& cl, int conn, uint8_t* out, u64* counts, hipStream_t s) {
     dim3 grid((unsigned)voxel_blocks(vol.V()), (unsigned)vol.N);
-    if (dtype == MI3D_SRC_U8)
-        surface_kernel<uint8_t><<<grid, BLK, 0, s>>>((const uint8_t*)labels, vol, cl, conn, out, counts);
-    else
-        surface_kernel<int64_t><<<grid, BLK, 0, s>>>((const int64_t*)labels, vol, cl, conn, out, counts);
+    dispatch_src(dtype, LabelTypes(), [&](auto tag) { surface_kernel<<<grid, BLK, 0, s>>>((const decltype(tag)*)labels, vol, cl, conn, out, counts); });
     MI3D_LAUNCH_CHECK();
     return 0;
 }
@@ -358,7 +299,7 @@ size_t mi3d_surface_workspace_bytes(int N, int D, int H, int W, int n_classes) {
         mi3d_set_error("mi3d_surface_workspace_bytes: N in [1, 65535], sides >= 1, D * H * W < 2^31 and 1 to %d classes expected", MAXC);
         return 0;
     }
-    return Parts(N, NV / N).total();
+    return Workspace(nullptr, N, NV / N).bytes;
 }
 
 int mi3d_distance_transform(const void* mask, int mask_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
@@ -371,15 +312,11 @@ int mi3d_distance_transform(const void* mask, int mask_dtype, int N, int D, int 
     MI3D_CHECK_ARG(dist2_out && ((uintptr_t)dist2_out & 7) == 0, "%s: dist2_out must be a non-null, 8-byte aligned pointer", name);
     const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
     const int64_t V = vol.V();
-    const Parts parts(N, V);
-    MI3D_TRY(check_workspace(name, workspace, workspace_bytes, parts));
-    const Workspace ws = carve(workspace, parts);
+    const Workspace ws(workspace, N, V);
+    MI3D_TRY(check_workspace(name, workspace, workspace_bytes, ws.bytes));
     hipStream_t s = (hipStream_t)stream;
     dim3 vgrid((unsigned)voxel_blocks(V), (unsigned)N), rgrid((unsigned)cdiv((int64_t)D * H, NW), (unsigned)N);
-    if (mask_dtype == MI3D_SRC_U8)
-        nonzero_kernel<uint8_t><<<vgrid, BLK, 0, s>>>((const uint8_t*)mask, vol, ws.pred);
-    else
-        nonzero_kernel<int64_t><<<vgrid, BLK, 0, s>>>((const int64_t*)mask, vol, ws.pred);
+    dispatch_src(mask_dtype, LabelTypes(), [&](auto tag) { nonzero_kernel<<<vgrid, BLK, 0, s>>>((const decltype(tag)*)mask, vol, ws.pred); });
     MI3D_LAUNCH_CHECK();
     w_kernel<<<rgrid, BLK, 0, s>>>(ws.pred, ws.pred, 1, (int64_t)D * H, W, spacing[2], dist2_out);
     MI3D_LAUNCH_CHECK();
@@ -395,9 +332,9 @@ int mi3d_surface_mask(const void* labels, int label_dtype, int N, int D, int H, 
     const char* name = "mi3d_surface_mask";
     MI3D_TRY(check_map(name, "labels", labels, label_dtype, stride_n, stride_d, stride_h, stride_w));
     MI3D_TRY(check_sizes(name, N, D, H, W));
-    MI3D_CHECK_ARG(connectivity >= 1 && connectivity <= 3, "%s: connectivity %d is not 1, 2 or 3", name, connectivity);
+    MI3D_TRY(check_connectivity(name, connectivity));
     MI3D_CHECK_ARG(surface_out, "%s: null pointer (surface_out)", name);
-    Listed cl{};
+    Classes cl{};
     cl.n = 1, cl.value[0] = class_value;
     const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
     return surface_launch(labels, label_dtype, vol, cl, connectivity, surface_out, nullptr, (hipStream_t)stream);
@@ -412,15 +349,9 @@ int mi3d_surface_distances(const void* pred, int pred_dtype, int64_t pred_stride
     MI3D_TRY(check_map(name, "pred", pred, pred_dtype, pred_stride_n, pred_stride_d, pred_stride_h, pred_stride_w));
     MI3D_TRY(check_map(name, "target", target, target_dtype, target_stride_n, target_stride_d, target_stride_h, target_stride_w));
     MI3D_TRY(check_sizes(name, N, D, H, W));
-    MI3D_CHECK_ARG(connectivity >= 1 && connectivity <= 3, "%s: connectivity %d is not 1, 2 or 3", name, connectivity);
-    MI3D_CHECK_ARG(n_classes >= 1 && n_classes <= MAXC, "%s: 1 to %d classes, got %d", name, MAXC, n_classes);
-    MI3D_CHECK_ARG(class_values, "%s: null pointer (class_values)", name);
-    Listed cl{};
-    cl.n = n_classes;
-    for (int j = 0; j < n_classes; j++) {
-        for (int k = 0; k < j; k++) MI3D_CHECK_ARG(class_values[k] != class_values[j], "%s: class value %d listed twice", name, class_values[j]);
-        cl.value[j] = class_values[j];
-    }
+    MI3D_TRY(check_connectivity(name, connectivity));
+    Classes cl{};
+    MI3D_TRY(check_classes(name, n_classes, class_values, cl));
     MI3D_TRY(check_spacing(name, spacing));
     MI3D_CHECK_ARG(q >= 0.0 && q <= 1.0, "%s: q = %g is outside [0, 1]", name, q);
     MI3D_CHECK_ARG(n_tol >= 0 && n_tol <= MAXT, "%s: 0 to %d tolerances, got %d", name, MAXT, n_tol);
@@ -436,9 +367,8 @@ int mi3d_surface_distances(const void* pred, int pred_dtype, int64_t pred_stride
     const Vol pv{N, D, H, W, pred_stride_n, pred_stride_d, pred_stride_h, pred_stride_w};
     const Vol tv{N, D, H, W, target_stride_n, target_stride_d, target_stride_h, target_stride_w};
     const int64_t V = pv.V(), blocks = voxel_blocks(V);
-    const Parts parts(N, V);
-    MI3D_TRY(check_workspace(name, workspace, workspace_bytes, parts));
-    const Workspace ws = carve(workspace, parts);
+    const Workspace ws(workspace, N, V);
+    MI3D_TRY(check_workspace(name, workspace, workspace_bytes, ws.bytes));
     hipStream_t s = (hipStream_t)stream;
     u64* counts = (u64*)counts_out;
     MI3D_HIP(hipMemsetAsync(counts_out, 0, (size_t)N * n_classes * COUNTS * sizeof(int64_t), s));

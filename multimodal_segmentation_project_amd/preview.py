@@ -18,27 +18,12 @@ import operator
 
 import torch
 
-from . import _lib, orientation
+from . import _lib
 from ._lib import Mi3dError, call, ptr, stream_ptr
+from ._volume import _IMAGE, _LABEL, _strides, _volume3
 
 VIEW_AXES = (2, 0, 1)          # figure rows: axial, sagittal, coronal (test_model.py:94-96)
-_IMAGE = {torch.float32: _lib.SRC_F32, torch.int16: _lib.SRC_I16}
-_LABEL = {torch.uint8: _lib.SRC_U8, torch.int64: _lib.SRC_I64}
 _OUT = {torch.float64: _lib.OVERLAY_F64, torch.float32: _lib.OVERLAY_F32, torch.uint8: _lib.OVERLAY_U8}
-
-
-def _volume(t, codes, kind, what):
-    """The 3-D view of a volume argument and its dtype code; every check that needs no device."""
-    if not isinstance(t, torch.Tensor):
-        raise Mi3dError(f"{what}: the {kind} is a torch tensor, got {type(t).__name__}")
-    while t.dim() > 3 and t.shape[0] == 1:
-        t = t[0]
-    if t.dim() != 3 or min(t.shape) < 1:
-        raise Mi3dError(f"{what}: one 3-D {kind} volume (leading singleton dims aside) expected, got {tuple(t.shape)}")
-    if t.dtype not in codes:
-        raise Mi3dError(f"{what}: the {kind} is {' or '.join(str(d) for d in codes)}, got {t.dtype}")
-    orientation.check_dense(t.shape, t.stride(), what)
-    return t, codes[t.dtype]
 
 
 def _same(what, first, *others):
@@ -49,10 +34,6 @@ def _same(what, first, *others):
         _lib.require_cuda(t, what)
         if t.device != first.device:
             raise Mi3dError(f"{what}: tensors on {first.device} and {t.device}")
-
-
-def _strides(t):
-    return [max(int(s), 1) for s in t.stride()]          # the stride of a one-element axis is never used
 
 
 def _stride_array(t):
@@ -88,7 +69,7 @@ def foreground_profiles(labels):
     """[np.sum(labels > 0, axis=(1, 2)), np.sum(labels > 0, axis=(0, 2)), np.sum(labels > 0, axis=(0, 1))] as int64 device tensors
     (find_best_slice, test_model.py:77-82): exact, one read of the volume, the same bits every run."""
     what = "foreground_profiles"
-    labels, code = _volume(labels, _LABEL, "label", what)
+    labels, code = _volume3(labels, _LABEL, "label", what)
     _same(what, labels)
     d, h, _ = labels.shape
     counts = _profiles(labels, code)
@@ -106,7 +87,7 @@ def best_slices(labels):
     """find_best_slice (test_model.py:75-91) for axes 0, 1, 2 as an int32 (3,) device tensor: the first slice with the most voxels
     > 0, the middle slice n // 2 where there is none."""
     what = "best_slices"
-    labels, code = _volume(labels, _LABEL, "label", what)
+    labels, code = _volume3(labels, _LABEL, "label", what)
     _same(what, labels)
     return _best(labels, code)
 
@@ -127,8 +108,8 @@ def overlay_slice(image, labels, axis, index, rot90=False, dtype=torch.float64):
     one-element integer device tensor such as best_slices(labels)[axis], read on the device and clamped to the axis.
     dtype: float64 the reference's bits, float32 one rounding of them, uint8 (255 * overlay).astype(np.uint8) with NaN as 0."""
     what = "overlay_slice"
-    image, icode = _volume(image, _IMAGE, "image", what)
-    labels, lcode = _volume(labels, _LABEL, "label", what)
+    image, icode = _volume3(image, _IMAGE, "image", what)
+    labels, lcode = _volume3(labels, _LABEL, "label", what)
     axis, ocode = _axis(axis, what), _out_code(dtype, what)
     k = 0
     if isinstance(index, torch.Tensor):
@@ -155,8 +136,8 @@ def overlay_stack(image, labels, axis=2, dtype=torch.uint8):
     """create_overlay of EVERY slice of `axis`, each normalised by its own minimum and maximum: (n, A, B, 3), the slider of
     visualize_nifti.py:54-73 for all positions at once (not rotated, as there).  Two launches: the per-slice min / max, the render."""
     what = "overlay_stack"
-    image, icode = _volume(image, _IMAGE, "image", what)
-    labels, lcode = _volume(labels, _LABEL, "label", what)
+    image, icode = _volume3(image, _IMAGE, "image", what)
+    labels, lcode = _volume3(labels, _LABEL, "label", what)
     axis, ocode = _axis(axis, what), _out_code(dtype, what)
     _same(what, image, labels)
     n = image.shape[axis]
@@ -171,9 +152,9 @@ def prediction_panels(image, label, pred, dtype=torch.float64):
     dtype and strides (an int64 target, the uint8 map of segment.predict_labels).  Four kernel launches (profiles, best slices,
     three min / max pairs, nine panels) behind the one zero fill of their workspace; no host synchronisation."""
     what = "prediction_panels"
-    image, icode = _volume(image, _IMAGE, "image", what)
-    label, lcode = _volume(label, _LABEL, "label", what)
-    pred, pcode = _volume(pred, _LABEL, "prediction", what)
+    image, icode = _volume3(image, _IMAGE, "image", what)
+    label, lcode = _volume3(label, _LABEL, "label", what)
+    pred, pcode = _volume3(pred, _LABEL, "prediction", what)
     ocode = _out_code(dtype, what)
     _same(what, image, label, pred)
     lib, dev, (d, h, w) = _lib.lib(), image.device, image.shape

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib, orientation
 from ._lib import Mi3dError, call, ptr, stream_ptr
-from .components import _connectivity, _integer, _strides, _volume
+from ._volume import _connectivity, _integer, _samples, _strides, _workspace
 
 MAX_CLASSES, MAX_TOLERANCES = _lib.COMPONENTS_MAX_CLASSES, _lib.SURFACE_MAX_TOLERANCES
 COUNT_COLUMNS, TABLE_COLUMNS = _lib.SURFACE_COUNT_COLUMNS, _lib.SURFACE_TABLE_COLUMNS
@@ -54,14 +54,6 @@ def _spacing(spacing, affine, what):
     return s
 
 
-def _workspace(t, n_classes, what):
-    n, d, h, w = t.shape
-    nbytes = _lib.lib().mi3d_surface_workspace_bytes(n, d, h, w, n_classes)
-    if nbytes == 0:
-        raise Mi3dError(f"{what}: {tuple(t.shape)} with {n_classes} classes is outside the library's range")
-    return nbytes
-
-
 def distance_to(mask, spacing=(1, 1, 1), squared=False):
     """The distance in mm of every voxel to the nearest non-zero voxel of `mask` (bool, uint8 or int64; (D, H, W) or (N, D, H, W)):
     float64, C-contiguous, shape of `mask`; +inf throughout a sample whose mask is empty.  Equals
@@ -70,10 +62,10 @@ def distance_to(mask, spacing=(1, 1, 1), squared=False):
     what = "distance_to"
     if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
-    t, code, _ = _volume(mask, what)
+    t, code, _ = _samples(mask, what)
     s = _spacing(spacing, None, what)
     _lib.require_cuda(t, what)
-    nbytes = _workspace(t, 1, what)
+    nbytes = _workspace("mi3d_surface_workspace_bytes", t, what, 1)
     # everything is checked: allocate and launch
     ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
     out = torch.empty(mask.shape, dtype=torch.float64, device=t.device)
@@ -86,7 +78,7 @@ def surface_mask(labels, cls, connectivity=1):
     neighbours) of another value or outside the volume.  Equals M & ~scipy.ndimage.binary_erosion(M,
     scipy.ndimage.generate_binary_structure(3, connectivity)) of M = (labels == cls)."""
     what = "surface_mask"
-    t, code, _ = _volume(labels, what)
+    t, code, _ = _samples(labels, what)
     cls = _class(cls, what)
     connectivity = _connectivity(connectivity, what)
     _lib.require_cuda(t, what)
@@ -113,8 +105,8 @@ def surface_distances(pred, target, classes=(1, 2, 3), spacing=None, affine=None
     what = "surface_distances"
     if isinstance(target, torch.Tensor) and isinstance(pred, torch.Tensor) and target.dim() == 5 and target.shape[1] == 1 and pred.dim() == 4:
         target = target[:, 0]
-    p, pcode, single = _volume(pred, what)
-    t, tcode, _ = _volume(target, what)
+    p, pcode, single = _samples(pred, what)
+    t, tcode, _ = _samples(target, what)
     if pred.shape != target.shape:
         raise Mi3dError(f"{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
     try:
@@ -142,7 +134,7 @@ def surface_distances(pred, target, classes=(1, 2, 3), spacing=None, affine=None
     if p.device != t.device:
         raise Mi3dError(f"{what}: pred is on {p.device}, target on {t.device}")
     nc = len(classes)
-    nbytes = _workspace(p, nc, what)
+    nbytes = _workspace("mi3d_surface_workspace_bytes", p, what, nc)
     # everything is checked: allocate and launch
     n = p.shape[0]
     ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
