@@ -245,6 +245,29 @@ int mi3d_head_labels(int dtype, const void* z, int zcs, int Cin, const float* w,
                      uint8_t* labels_out, const int64_t* target, int64_t* counts, void* workspace, void* stream);
 int mi3d_unet_head_labels(const mi3d_unet_desc* d, const void* const* params, const int64_t* target, uint8_t* labels_out,
                           int64_t* counts, void* head_workspace, void* workspace, size_t workspace_bytes, void* stream);
+/* Flip and model ensembles (test-time mirroring over the axes random_flip trains with, utils/dataloader.py:207-213, and the same
+ * average over several checkpoints): ONE VIEW per call, the 1x1x1 head, its softmax and the add into a vote volume in one pass
+ * over the decoder output, so the logits and the probabilities of a view are never written.  A view is (a model, a flip code):
+ * bit 0 of `flip` mirrors W, bit 1 H, bit 2 D.  z is the decoder output of model(torch.flip(x, those dims)); operands as for
+ * mi3d_head_labels, the volume given as D, H, W (D * H * W < 2^31).  For view = 0 .. views - 1, in that order:
+ *     p      = softmax over the classes, in float32, of the logits mi3d_conv1_forward gives (bit for bit), flipped back
+ *     votes  float (N,Cout,D,H,W): view 0 stores p (the volume needs no clearing), a later view adds p: float32 adds in view order
+ *     last view: the total stays in registers; labels_out uint8 (N,D,H,W) = its first maximum (strict `>` scan from class 0);
+ *            confidence float (N,D,H,W), optional = total[label] / (float)views (IEEE division); target / counts / workspace
+ *            as for mi3d_head_labels (workspace: mi3d_head_votes_workspace_bytes(N, Cout)); the total is written to `votes`
+ *            only with MI3D_VOTES_KEEP in `flags`.
+ * views = 1 is first and last at once; `votes` may then be NULL unless it is kept.  labels_out, confidence, target and counts
+ * must be NULL on every view but the last.  One thread owns a voxel and nothing is atomic: the same inputs give the same bits.
+ * Every argument is checked before anything is launched.  mi3d_unet_head_votes runs a view on the decoder output that the
+ * last mi3d_unet_infer with logits = NULL left in `workspace` (the sibling of mi3d_unet_head_labels). */
+#define MI3D_VOTES_KEEP 1
+size_t mi3d_head_votes_workspace_bytes(int N, int Cout);
+int mi3d_head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int D, int H,
+                    int W, int flip, int view, int views, int flags, float* votes, uint8_t* labels_out, float* confidence,
+                    const int64_t* target, int64_t* counts, void* workspace, void* stream);
+int mi3d_unet_head_votes(const mi3d_unet_desc* d, const void* const* params, int flip, int view, int views, int flags, float* votes,
+                         uint8_t* labels_out, float* confidence, const int64_t* target, int64_t* counts, void* head_workspace,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DANN head.  Replaces train_dann.py:34-49 (DomainDiscriminator MLP 256-256-128-64-2, ReLU, Dropout 0.2) and

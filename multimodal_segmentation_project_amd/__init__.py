@@ -6,7 +6,7 @@ from .unet import DoubleConv, UNet3D  # noqa: F401
 from .dann import DomainDiscriminator, GradientReversal, grad_reverse  # noqa: F401
 from .metrics import (calculate_accuracy, calculate_dice, calculate_iou, combined_ce_tversky_loss,  # noqa: F401
                       combined_loss, distillation_loss, get_loss_fn, per_class_dice_iou, tversky_loss)
-from .segment import per_sample_dice_iou, predict_labels, segment_scan  # noqa: F401
+from .segment import FLIPS8, NO_FLIP, per_sample_dice_iou, predict_labels, predict_labels_ensemble, segment_scan  # noqa: F401
 from .surface import distance_to, surface_distances, surface_mask, surface_metrics  # noqa: F401
 from .preview import best_slices, foreground_profiles, overlay_slice, overlay_stack, prediction_panels  # noqa: F401
 

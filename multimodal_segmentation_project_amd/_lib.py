@@ -56,6 +56,7 @@ class Conv3BnRoute(C.Structure):                   # mi3d_conv3_bn_route
 
 
 CONV3_BN_KEEP_TICKETS = 1
+VOTES_KEEP = 1                                     # MI3D_VOTES_KEEP
 
 
 class Conv3InferRoute(C.Structure):                # mi3d_conv3_infer_route
@@ -129,6 +130,9 @@ _SIGS = {
     "mi3d_head_labels_workspace_bytes": (sz, [i32, i32]),
     "mi3d_head_labels": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
     "mi3d_unet_head_labels": (i32, [_DP, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi3d_head_votes_workspace_bytes": (sz, [i32, i32]),
+    "mi3d_head_votes": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mi3d_unet_head_votes": (i32, [_DP, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi3d_linear_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mi3d_linear_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp]),
     "mi3d_scale": (i32, [vp, vp, i64, f32, vp, vp]),

@@ -90,6 +90,15 @@ int mi3d_head_labels(int dtype, const void* z, int zcs, int Cin, const float* w,
     MI3D_CHECK_ARG(dtype == MI3D_F32 || dtype == MI3D_BF16, "mi3d_head_labels: bad dtype %d", dtype);
     return head_labels(dtype, z, zcs, Cin, w, bias, Cout, N, V, labels_out, target, counts, workspace, (hipStream_t)stream);
 }
+size_t mi3d_head_votes_workspace_bytes(int N, int Cout) { return head_labels_ws_bytes(N, Cout); }
+int mi3d_head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int D, int H, int W,
+                    int flip, int view, int views, int flags, float* votes, uint8_t* labels_out, float* confidence,
+                    const int64_t* target, int64_t* counts, void* workspace, void* stream) {
+    MI3D_CHECK_ARG(z && w, "mi3d_head_votes: null pointer");
+    MI3D_CHECK_ARG(dtype == MI3D_F32 || dtype == MI3D_BF16, "mi3d_head_votes: bad dtype %d", dtype);
+    return head_votes(dtype, z, zcs, Cin, w, bias, Cout, N, D, H, W, flip, view, views, flags, votes, labels_out, confidence, target,
+                      counts, workspace, (hipStream_t)stream);
+}
 
 int mi3d_linear_forward(const float* x, const float* w, const float* b, float* y, int M, int K, int Nout, int relu,
                         const float* drop, void* stream) {

@@ -12,6 +12,7 @@
 //   g_c = w_reg/(C-1) * (A_c [t=c] + B_c),  A_c, B_c = dR_c/dI_c-ish coefficients computed once from the sums.
 #include <type_traits>
 
+#include "../../include/mi3d.h"
 #include "mfma_tile.h"
 #include "ops.h"
 
@@ -1041,6 +1042,113 @@ __global__ __launch_bounds__(BLK) void head_labels_kernel(const T* __restrict__ 
     if constexpr (TARGET) cnt.store_block_row(C, counts + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (3 * C + 1));
 }
 
+// ------------------------------------------------------------------ head + softmax + vote of one view (flip / model ensembles)
+// One view of an ensemble: z is the decoder output of model(flip(x)), and the view's probabilities are added into the planar
+// float32 vote volume (N, C, D, H, W) AT THE UN-FLIPPED VOXEL.  The kernel walks the OUTPUT voxels linearly and gathers the
+// channel row of z at the mirrored index (flip bit 0: W, 1: H, 2: D): the gather sits on the side with the widest unit (a whole
+// 2 Cin-byte channel row per voxel stays contiguous, and a W flip only reverses the order in which a wave touches the same rows),
+// and the C vote planes and the label bytes, which are 4- and 1-byte units, stay linear.
+//   MODE & VOTE_FIRST   the votes are not read: votes = p (no memset)
+//   neither             votes = votes + p
+//   MODE & VOTE_LAST    total = votes + p stays in registers: first_argmax -> uint8 label (+ counts with TARGET); confidence, if
+//                       asked for, total[label] / views (IEEE division); the total is written back only with `keep`
+// p = softmax_c of conv1_voxel's logits; the adds are float32 adds in view order (__fadd_rn: never contracted with the
+// product inside softmax_c), one thread owns a voxel, no atomics: the same bits on every run.
+// HBM-bound: per voxel Cin * sizeof(T) bytes of z, and of votes 4 C written (FIRST), 8 C (neither), 4 C read + 1 label byte (LAST).
+// A thread owns VV consecutive output voxels, as in conv1_fwd_kernel and seg_metrics_kernel: with VV = 4 (V % 4 == 0, aligned
+// planes) every plane access is 16 bytes and the labels are one 4-byte store.  The other candidate, head_labels_kernel's
+// lane-per-voxel rounds with an LDS label tile, was built and timed against a 4-voxel kernel in one process at 192^3, bf16,
+// 4 classes, all three axes mirrored (same bits): FIRST 75 us against 96, MIDDLE 136 against 112, LAST 110 against 97 -- 1.00 ms
+// against 0.86 ms for the eight passes of a flip ensemble (profiles/votes_timing.txt): the vote planes are most of the traffic
+// and decide, not the z rows, so the 4-voxel walk is the one kept.
+// (d, h, w): the group's first voxel is decoded with two 32-bit divisions, the others step from it with a carry; V < 2^31 is
+// the launcher's check.
+constexpr int VOTE_FIRST = 1, VOTE_LAST = 2;
+template <typename T, bool VEC, int NC, int VV, int MODE, bool TARGET>
+__global__ __launch_bounds__(BLK) void head_votes_kernel(const T* __restrict__ z, int zcs, int Cin, const float* __restrict__ w,
+                                                         const float* __restrict__ bias, int C, int D, int H, int W, int flip,
+                                                         float views, int keep, float* __restrict__ votes,
+                                                         uint8_t* __restrict__ labels, float* __restrict__ confidence,
+                                                         const int64_t* __restrict__ target, unsigned long long* __restrict__ counts) {
+    constexpr bool FIRST = (MODE & VOTE_FIRST) != 0, LAST = (MODE & VOTE_LAST) != 0;
+    const int n = blockIdx.y;
+    const unsigned V = (unsigned)D * (unsigned)H * (unsigned)W;
+    const T* zn = z + (int64_t)n * V * zcs;
+    float* vn = votes ? votes + (int64_t)n * C * V : nullptr;
+    uint8_t* ln = LAST ? labels + (int64_t)n * V : nullptr;
+    float* cn = (LAST && confidence) ? confidence + (int64_t)n * V : nullptr;
+    const int64_t* tn = TARGET ? target + (int64_t)n * V : nullptr;
+    const bool fw = flip & 1, fh = flip & 2, fd = flip & 4;
+    VoxelCounts<NC> cnt;
+    // ONE: the whole channel row is one block (the network's head: Cin = 16), as in head_labels_kernel: a constant single trip
+    auto groups = [&](auto ONE) {
+        const int cin = decltype(ONE)::value ? CINB : Cin;
+        for (unsigned grp = blockIdx.x * BLK + threadIdx.x; grp < V / VV; grp += gridDim.x * BLK) {
+            const unsigned v0 = grp * VV, row = v0 / (unsigned)W;
+            unsigned xw = v0 - row * (unsigned)W, xd = row / (unsigned)H, xh = row - xd * (unsigned)H;
+            float p[VV][NC];
+#pragma unroll
+            for (int k = 0; k < VV; k++) {
+                const unsigned sw = fw ? W - 1 - xw : xw, sh = fh ? H - 1 - xh : xh, sd = fd ? D - 1 - xd : xd;
+                float acc[NC], lse;
+                conv1_voxel<T, VEC, NC>(zn + (((int64_t)sd * H + sh) * W + sw) * zcs, cin, w, bias, 0, C, acc);
+                softmax_c<NC>(acc, C, 1.f, p[k], lse);
+                if (++xw == (unsigned)W) {                   // the next voxel of the group
+                    xw = 0;
+                    if (++xh == (unsigned)H) { xh = 0; xd++; }
+                }
+            }
+            if constexpr (!FIRST) {
+                float t[VV][NC];
+                load_planes<NC, VV>(vn, C, V, v0, t);
+#pragma unroll
+                for (int k = 0; k < VV; k++) {
+#pragma unroll
+                    for (int c = 0; c < NC; c++) p[k][c] = __fadd_rn(t[k][c], p[k][c]);
+                }
+            }
+            if (!LAST || keep) {
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    if (c < C) {
+                        if constexpr (VV == 4) *reinterpret_cast<float4*>(vn + (int64_t)c * V + v0) = float4{p[0][c], p[1][c], p[2][c], p[3][c]};
+                        else vn[(int64_t)c * V + v0] = p[0][c];
+                    }
+                }
+            }
+            if constexpr (LAST) {
+                int best[VV];
+                float cf[VV];
+#pragma unroll
+                for (int k = 0; k < VV; k++) {
+                    best[k] = first_argmax<NC>(p[k], C);
+                    float top = p[k][0];
+#pragma unroll
+                    for (int c = 1; c < NC; c++) top = best[k] == c ? p[k][c] : top;
+                    cf[k] = __fdiv_rn(top, views);
+                }
+                if constexpr (TARGET) {
+#pragma unroll
+                    for (int k = 0; k < VV; k++) {
+                        const int64_t tv = tn[v0 + k];
+                        cnt.add(best[k], (tv >= 0 && tv < C) ? (int)tv : -1);
+                    }
+                }
+                if constexpr (VV == 4) {
+                    *reinterpret_cast<unsigned*>(ln + v0) = (unsigned)best[0] | (unsigned)best[1] << 8 | (unsigned)best[2] << 16 | (unsigned)best[3] << 24;
+                    if (cn) *reinterpret_cast<float4*>(cn + v0) = float4{cf[0], cf[1], cf[2], cf[3]};
+                } else {
+                    ln[v0] = (uint8_t)best[0];
+                    if (cn) cn[v0] = cf[0];
+                }
+            }
+        }
+    };
+    if (VEC && Cin == CINB) groups(std::integral_constant<bool, VEC>{});
+    else groups(std::false_type{});
+    if constexpr (TARGET) cnt.store_block_row(C, counts + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (3 * C + 1));
+}
+
 __device__ __forceinline__ void count_row_sum(const unsigned long long* part, int nblk, int C, int q, int lane, unsigned long long* counts);
 __device__ __forceinline__ void metric_scalars(const unsigned long long* counts, int N, int C, int D, int64_t V, float* out);
 // Q1: the reference's class loop is range(1, pred.size(1)) AFTER argmax -> bound = first spatial dim D
@@ -1322,6 +1430,66 @@ int head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, cons
     });
 #undef HLAB
     if (target) {
+        seg_counts_finalize_kernel<<<N, 1024, 0, s>>>(rows, (int)grid.x, Cout, (long long*)counts);
+        MI3D_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// ---- head + softmax + vote of one view (+ argmax, counts, confidence on the last)
+int head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int D, int H, int W,
+               int flip, int view, int views, int flags, float* votes, uint8_t* labels, float* confidence, const int64_t* target,
+               int64_t* counts, void* ws, hipStream_t s) {
+    MI3D_CHECK_ARG(Cin >= 1 && zcs >= Cin, "head_votes: bad channels (Cin %d, stride %d)", Cin, zcs);
+    MI3D_CHECK_ARG(Cout >= 1 && Cout <= MAXC, "head_votes: %d classes unsupported (max %d)", Cout, MAXC);
+    MI3D_CHECK_ARG(N >= 1 && N <= 65535 && D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < (1ll << 31),
+                   "head_votes: bad batch %d or volume %d x %d x %d (below 2^31 voxels per sample)", N, D, H, W);
+    MI3D_CHECK_ARG(flip >= 0 && flip < 8, "head_votes: flip code %d outside [0, 8)", flip);
+    MI3D_CHECK_ARG(views >= 1 && view >= 0 && view < views, "head_votes: view %d outside [0, %d)", view, views);
+    MI3D_CHECK_ARG((flags & ~MI3D_VOTES_KEEP) == 0, "head_votes: unknown flags 0x%x", flags);
+    const bool first = view == 0, last = view == views - 1, keep = (flags & MI3D_VOTES_KEEP) != 0;
+    if (!last) {
+        MI3D_CHECK_ARG(!labels && !confidence && !target && !counts,
+                       "head_votes: labels, confidence, target and counts belong to the last view (view %d of %d)", view, views);
+    } else {
+        MI3D_CHECK_ARG(labels, "head_votes: the last view needs labels_out");
+        MI3D_CHECK_ARG(!target == !counts, "head_votes: target and counts come together");
+        MI3D_CHECK_ARG(!target || ws, "head_votes: counts need the workspace");
+    }
+    MI3D_CHECK_ARG(votes || (views == 1 && !keep), "head_votes: the vote volume is NULL (only a single view that does not keep it may)");
+    const int64_t V = (int64_t)D * H * W;
+    // a thread owns 4 consecutive voxels where every plane, label and confidence access of a group is aligned
+    const bool v4 = V % 4 == 0 && al16(votes) && (uintptr_t)labels % 4 == 0 && al16(confidence);
+    const int64_t want = (V / (v4 ? 4 : 1) + BLK - 1) / BLK, cap = HEAD_LABEL_BLOCKS / N < 1 ? 1 : HEAD_LABEL_BLOCKS / N;
+    dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)N);
+    unsigned long long* rows = (unsigned long long*)ws;
+    const bool vec = Cin % CINB == 0 && zcs % 8 == 0 && al16(z);      // as conv1_fwd
+#define HVOTE(VEC_, NC_, VV_, MODE_, TGT_)                                                                                                \
+    head_votes_kernel<T, VEC_, NC_, VV_, MODE_, TGT_><<<grid, BLK, 0, s>>>((const T*)z, zcs, Cin, w, bias, Cout, D, H, W, flip, (float)views, \
+                                                                           keep ? 1 : 0, votes, labels, confidence, target, rows)
+#define HVOTE_MODE(VEC_, NC_, VV_)                                                                                                        \
+    do {                                                                                                                                   \
+        if (last && target) { if (first) HVOTE(VEC_, NC_, VV_, VOTE_FIRST | VOTE_LAST, true); else HVOTE(VEC_, NC_, VV_, VOTE_LAST, true); }   \
+        else if (last) { if (first) HVOTE(VEC_, NC_, VV_, VOTE_FIRST | VOTE_LAST, false); else HVOTE(VEC_, NC_, VV_, VOTE_LAST, false); }      \
+        else if (first) HVOTE(VEC_, NC_, VV_, VOTE_FIRST, false);                                                                          \
+        else HVOTE(VEC_, NC_, VV_, 0, false);                                                                                              \
+    } while (0)
+#define HVOTE_VV(VEC_, NC_)                  \
+    do {                                     \
+        if (v4) HVOTE_MODE(VEC_, NC_, 4);    \
+        else HVOTE_MODE(VEC_, NC_, 1);       \
+    } while (0)
+    DISPATCH_T(dtype, T, {
+        if (vec && Cout <= 4) HVOTE_VV(true, 4);
+        else if (vec) HVOTE_VV(true, MAXC);
+        else if (Cout <= 4) HVOTE_VV(false, 4);
+        else HVOTE_VV(false, MAXC);
+        MI3D_LAUNCH_CHECK();
+    });
+#undef HVOTE_VV
+#undef HVOTE_MODE
+#undef HVOTE
+    if (last && target) {
         seg_counts_finalize_kernel<<<N, 1024, 0, s>>>(rows, (int)grid.x, Cout, (long long*)counts);
         MI3D_LAUNCH_CHECK();
     }

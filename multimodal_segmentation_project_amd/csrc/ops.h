@@ -409,6 +409,11 @@ int seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D,
 size_t head_labels_ws_bytes(int N, int Cout);
 int head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int64_t V,
                 uint8_t* labels, const int64_t* target, int64_t* counts, void* ws, hipStream_t s);
+// one view of a flip / model ensemble: votes (N,Cout,D,H,W) float += softmax of that head at the voxel mirrored by `flip`; the
+// last view ends in the argmax of the total (contract: include/mi3d.h mi3d_head_votes).  ws: head_labels_ws_bytes(N, Cout)
+int head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int D, int H, int W,
+               int flip, int view, int views, int flags, float* votes, uint8_t* labels, float* confidence, const int64_t* target,
+               int64_t* counts, void* ws, hipStream_t s);
 
 // ---- spatial augmentation: flip + in-plane rotation of one (C, D, H, W) sample ------------- spatial.hip
 // Reference: random_flip / random_rotate, utils/dataloader.py:207-221.  Contract and arithmetic: include/mi3d.h mi3d_plane_affine.

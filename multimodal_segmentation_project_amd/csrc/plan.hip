@@ -852,6 +852,17 @@ int mi3d_unet_head_labels(const mi3d_unet_desc* d, const void* const* params, co
                        p.geo[0].V(), labels_out, target, counts, head_workspace, c.s);
 }
 
+// head + softmax + vote of one view of a flip / model ensemble on that same decoder output (mi3d_head_votes)
+int mi3d_unet_head_votes(const mi3d_unet_desc* d, const void* const* params, int flip, int view, int views, int flags, float* votes,
+                         uint8_t* labels_out, float* confidence, const int64_t* target, int64_t* counts, void* head_workspace,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    Plan p;
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_head_votes", true, params, workspace, workspace_bytes, stream));
+    return head_votes(p.dt, c.at(p.zd[p.L - 1]), p.C[0], p.C[0], c.P(p.final_pidx()), c.P(p.final_pidx() + 1), d->out_channels, d->N,
+                      p.geo[0].D, p.geo[0].H, p.geo[0].W, flip, view, views, flags, votes, labels_out, confidence, target, counts, head_workspace, c.s);
+}
+
 int mi3d_unet_forward(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
                       const float* drop_scales, int training, float* logits, float* gap_out, void* workspace,
                       size_t workspace_bytes, void* stream) {

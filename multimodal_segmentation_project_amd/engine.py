@@ -106,6 +106,9 @@ BN_PUBLISH = 2          # batch statistics, the update deferred: (mean, unbiased
 THIN_CONSUMERS = 4      # or-ed to either: another forward runs beside this one, the BatchNorm apply passes stay thin
 
 
+HEAD_VOTES = "mi3d_unet_head_votes"      # Plan.head_votes' entry; its argument order is written down there and nowhere else
+
+
 class LossGroup:
     """What the loss calls share: the configuration, metrics = {loss, iou, dice, acc, ...} (device float[n_metrics]; the loss
     is written to [0], the three metrics to [1:4]), the 20 loss coefficients the backward reads, and the two workspaces."""
@@ -202,6 +205,12 @@ class Plan:
     def head_labels(self, *, labels=None, out, counts=None, head_ws=None, stream):
         call("mi3d_unet_head_labels", self.d, self.ptab, ptr(labels), ptr(out), ptr(counts), ptr(head_ws), self.ws_ptr,
              self.ws_bytes, stream)
+
+    def head_votes(self, *, flip, view, views, flags=0, votes=None, out=None, confidence=None, labels=None, counts=None, head_ws=None,
+                   stream):
+        """One view of a flip / model ensemble on the decoder output the last infer() left (mi3d_unet_head_votes)."""
+        call(HEAD_VOTES, self.d, self.ptab, flip, view, views, flags, ptr(votes), ptr(out), ptr(confidence), ptr(labels),
+             ptr(counts), ptr(head_ws), self.ws_ptr, self.ws_bytes, stream)
 
     def bn_apply_deferred(self, side, *, stream):
         """side: the Plan whose buffer table holds the side buffers a BN_PUBLISH forward filled."""
