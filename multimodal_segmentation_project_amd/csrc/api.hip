@@ -4,7 +4,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "ops.h"
+#include "scratch.h"
 
 static_assert(MI3D_LOSS_COEF_FLOATS >= 2 * MI3D_MAX_CLASSES + 4, "coef buffer too small");
 
@@ -145,24 +148,69 @@ int mi3d_dropout_scales(float* out, int64_t n, float p, uint64_t* state_dev, voi
 // ---- per-operator entry points ------------------------------------------------------------------
 }  // extern "C"
 
-// mi3d_conv3_bn_backward / mi3d_conv3_backward: the plan's scratch areas of one layer's backward in a workspace of its own
+// What the per-operator conv entries share: argument checks, the single-job pack launch, and the three workspace layouts: the areas
+// one layer touches in the plan's workspace, in the plan's order, in a workspace of its own, sized by the layer's ConvScratch (scratch.h)
 namespace {
-struct ConvBnBwdWs {
-    size_t wpf, wpd, bnws, wgws, wgws_floats, skws, total;
-};
-ConvBnBwdWs conv_bn_bwd_ws(bool mfma, int Cin, int Cout, Geo g) {
-    ConvBnBwdWs L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    L.wpf = take(mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cin, Cout) * sizeof(float));
-    L.wpd = take(mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cout, Cin) * sizeof(float));
-    L.bnws = take(bn_ws_floats(Cout) * sizeof(float));
-    L.wgws_floats = conv3_direct_wgrad_ws_floats(Cin, Cout, g);
-    if ((mfma || (Cin == 1 && Cout % 16 == 0)) && conv3_mfma_wgrad_ws_floats(Cin, Cout, g) > L.wgws_floats)
-        L.wgws_floats = conv3_mfma_wgrad_ws_floats(Cin, Cout, g);
-    L.wgws = take(L.wgws_floats * sizeof(float));
-    L.skws = take((mfma ? conv3_mfma_splitk_floats(Cout, Cin, g) : 0) * sizeof(float) + 16);      // the input gradient's split-K partials
-    L.total = off;
+// x_halves / ocs: the input arrives as planar halves (16-channel blocks) / channel stride of the entry's output-side tensor
+int conv_entry_check(const char* fn, int in_dtype, int dtype, int Cin, int Cout, int xcs, bool x_halves, int ocs, Geo g) {
+    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
+                   "%s: bad dtypes %d -> %d", fn, in_dtype, dtype);
+    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= (x_halves ? 16 : Cin) && ocs >= Cout && g.N >= 1 && g.D >= 1 && g.H >= 1 && g.W >= 1,
+                   "%s: bad shape", fn);
+    return 0;
+}
+int workspace_check(const char* fn, const void* workspace, size_t have, size_t need) {
+    MI3D_CHECK_ARG(have >= need, "%s: workspace too small: %zu < %zu", fn, have, need);
+    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    return 0;
+}
+inline bool geo_ok(int Cin, int Cout, int N, int D, int H, int W) { return Cin >= 1 && Cout >= 1 && N >= 1 && D >= 1 && H >= 1 && W >= 1; }
+// the plan's pack launch with one job.  scale: BatchNorm scale folded into the forward image; zero: ticket counters block 0 clears
+int pack_one_conv3(const float* w, int Cin, int Cout, void* wpf, void* wpd, Geo g, hipStream_t s, const float* scale = nullptr, int* zero = nullptr) {
+    PackJobs J;
+    J.n = 0; J.nblocks = 0;
+    if (zero) { J.zero = zero; J.nzero = CONV3_TK_COUNTERS; }
+    MI3D_TRY(pack_all_add_conv3(J, w, Cin, Cout, wpf, wpd, g, scale));
+    return pack_all_launch(J, s);
+}
+
+struct ConvBnWs { size_t statpart, tkcount, bnws, wpf, wpd, skws, total; };       // mi3d_conv3_bn_forward
+ConvBnWs conv_bn_ws(const ConvScratch& S, int Cout) {
+    ConvBnWs L; Arena A;
+    L.statpart = A.take((size_t)S.stat_rows * 2 * Cout * sizeof(float));
+    L.tkcount = A.take((size_t)CONV3_TK_COUNTERS * sizeof(int));
+    L.bnws = A.take(bn_ws_floats(Cout) * sizeof(float));
+    L.wpf = A.take(S.wpf_bytes);
+    L.wpd = A.take(S.wpd_bytes);
+    L.skws = A.take(S.splitk_fwd_floats * sizeof(float) + 16);
+    L.total = A.off;
+    return L;
+}
+struct ConvInferWs { size_t fold, wpf, wpd, skws, total; };                       // mi3d_conv3_infer_forward
+ConvInferWs conv_infer_ws(const ConvScratch& S, int Cout) {
+    ConvInferWs L; Arena A;
+    L.fold = A.take((size_t)2 * Cout * sizeof(float));      // scale, then the folded bias: the plan's stat[0..2C) of an inference call
+    L.wpf = A.take(S.wpf_bytes);
+    L.wpd = A.take(S.mfma ? S.wpd_bytes : 0);               // the pack launch writes both images; the direct pack only the forward one
+    L.skws = A.take(S.splitk_fwd_floats * sizeof(float) + 16);
+    L.total = A.off;
+    return L;
+}
+// mi3d_conv3_bn_backward / mi3d_conv3_backward.  S: the kernels the call runs -- the layer's class, or the direct description where
+// mi3d_conv3_backward routes a class-MFMA layer down because of the caller's strides
+struct ConvBnBwdWs { size_t wpf, wpd, bnws, wgws, wgws_floats, skws, total; };
+ConvBnBwdWs conv_bn_bwd_ws(const ConvScratch& S, int Cin, int Cout, Geo g) {
+    ConvBnBwdWs L; Arena A;
+    L.wpf = A.take(S.wpf_bytes);
+    L.wpd = A.take(S.wpd_bytes);
+    L.bnws = A.take(bn_ws_floats(Cout) * sizeof(float));
+    // a class that runs on the matrix cores may still land on the direct weight gradient at the call: room for the larger of the two.
+    // A one-channel layer has always reserved the first-layer kernel's slabs whatever its dtype: dx_offset and the size query keep that
+    const ConvScratch Dk = conv3_scratch_direct(Cin, Cout, g), F = conv3_scratch(MI3D_BF16, Cin, Cout, g);
+    L.wgws_floats = std::max({S.wgrad_floats, Dk.wgrad_floats, F.c1 ? F.wgrad_floats : (size_t)0});
+    L.wgws = A.take(L.wgws_floats * sizeof(float));
+    L.skws = A.take(S.splitk_bwd_floats * sizeof(float) + 16);      // the input gradient's split-K partials
+    L.total = A.off;
     return L;
 }
 static_assert(sizeof(mi3d_pending_sum) == sizeof(SlabJob) && alignof(mi3d_pending_sum) == alignof(SlabJob), "mi3d_pending_sum holds a SlabJob");
@@ -175,14 +223,8 @@ struct ConvBwdCall {
 };
 // the plan's pack launch, then conv3_bn_half_backward with a Pending of the caller's riders; the layer's own sum is handed out or launched
 int conv_bn_bwd_run(const ConvBwdCall& k, const ConvBnBwdWs& L, hipStream_t s) {
-    if (k.mfma) {
-        PackJobs J;
-        J.n = 0; J.nblocks = 0;
-        MI3D_TRY(pack_all_add_conv3(J, k.w, k.Cin, k.Cout, k.ws + L.wpf, k.ws + L.wpd, k.g));
-        MI3D_TRY(pack_all_launch(J, s));
-    } else if (k.dx) {
-        MI3D_TRY(conv3_direct_pack(k.w, k.Cin, k.Cout, (float*)(k.ws + L.wpf), (float*)(k.ws + L.wpd), s));
-    }
+    if (k.mfma) MI3D_TRY(pack_one_conv3(k.w, k.Cin, k.Cout, k.ws + L.wpf, k.ws + L.wpd, k.g, s));
+    else if (k.dx) MI3D_TRY(conv3_direct_pack(k.w, k.Cin, k.Cout, (float*)(k.ws + L.wpf), (float*)(k.ws + L.wpd), s));
     Pending pending;
     if (k.riders) {
         memcpy(&pending.pend, &k.riders[0], sizeof(SlabJob));
@@ -216,15 +258,14 @@ int conv_bn_bwd_run(const ConvBwdCall& k, const ConvBnBwdWs& L, hipStream_t s) {
 extern "C" {
 
 size_t mi3d_conv3_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W) {
-    Geo g{N, D, H, W};
-    size_t wg = conv3_direct_wgrad_ws_floats(Cin, Cout, g);
-    if ((conv3_mfma_supported(Cin, Cout, 16, 16) || (Cin == 1 && Cout % 16 == 0)) && conv3_mfma_wgrad_ws_floats(Cin, Cout, g) > wg)
-        wg = conv3_mfma_wgrad_ws_floats(Cin, Cout, g);
-    size_t fwd = (conv3_direct_pack_floats(Cin, Cout) + conv3_direct_pack_floats(Cout, Cin) + wg + 64) * sizeof(float);
+    // no dtype argument: room for the layer's bf16 class and for the direct kernels, whichever the call runs.  The forward: the two
+    // direct images (the MFMA ones are smaller) in front of a slab region
+    const Geo g{N, D, H, W};
+    const ConvScratch S = conv3_scratch(MI3D_BF16, Cin, Cout, g), Dk = conv3_scratch_direct(Cin, Cout, g);
+    const size_t fwd = Dk.wpf_bytes + Dk.wpd_bytes + (std::max(S.wgrad_floats, Dk.wgrad_floats) + 64) * sizeof(float);
     // the backward's areas (mi3d_conv3_backward aligns the workspace itself: + 256)
-    size_t bwd = conv_bn_bwd_ws(false, Cin, Cout, g).total;
-    if (conv3_mfma_supported(Cin, Cout, 16, 16) && conv_bn_bwd_ws(true, Cin, Cout, g).total > bwd) bwd = conv_bn_bwd_ws(true, Cin, Cout, g).total;
-    return (fwd > bwd ? fwd : bwd) + 256;
+    const size_t bwd = std::max(conv_bn_bwd_ws(S, Cin, Cout, g).total, conv_bn_bwd_ws(Dk, Cin, Cout, g).total);
+    return std::max(fwd, bwd) + 256;
 }
 int mi3d_conv3_forward(int in_dtype, int out_dtype, const void* x, int xcs, int Cin, const float* w, const float* bias,
                        void* y, int ycs, int Cout, int N, int D, int H, int W, void* workspace, size_t workspace_bytes,
@@ -232,7 +273,7 @@ int mi3d_conv3_forward(int in_dtype, int out_dtype, const void* x, int xcs, int 
     MI3D_CHECK_ARG(x && w && y && workspace, "mi3d_conv3_forward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_conv3_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_conv3_forward: workspace too small");
     float* wpf = (float*)workspace;
-    float* wpd = wpf + conv3_direct_pack_floats(Cin, Cout);
+    float* wpd = (float*)((char*)workspace + conv3_scratch_direct(Cin, Cout, Geo{N, D, H, W}).wpf_bytes);
     hipStream_t s = (hipStream_t)stream;
     if (use_mfma(in_dtype, out_dtype, Cin, Cout, xcs, ycs)) {       // bf16 implicit GEMM on the matrix cores
         MI3D_TRY(conv3_mfma_pack(w, Cin, Cout, wpf, wpd, Geo{N, D, H, W}, s));
@@ -249,12 +290,12 @@ int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int C
     MI3D_CHECK_ARG(x && w && dy && workspace, "mi3d_conv3_backward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_conv3_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_conv3_backward: workspace too small");
     Geo g{N, D, H, W};
-    bool mfma, c1;
-    conv3_layer_class(dy_dtype, Cin, Cout, mfma, c1);
-    mfma = mfma && x_dtype == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, xcs, dycs) && dycs % 8 == 0 &&
-           (!dx || conv3_mfma_supported(Cout, Cin, dycs, dxcs));
-    c1 = c1 && x_dtype == MI3D_F32 && xcs == 1 && dycs % 8 == 0 && !dx;
-    const ConvBnBwdWs L = conv_bn_bwd_ws(mfma, Cin, Cout, g);
+    const ConvScratch S = conv3_scratch(dy_dtype, Cin, Cout, g);
+    const bool mfma = S.mfma && x_dtype == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, xcs, dycs) && dycs % 8 == 0 &&
+                      (!dx || conv3_mfma_supported(Cout, Cin, dycs, dxcs));
+    const bool c1 = S.c1 && x_dtype == MI3D_F32 && xcs == 1 && dycs % 8 == 0 && !dx;
+    // strides that rule the MFMA kernels out: the direct kernels' areas (the layout keeps slab room for either weight gradient)
+    const ConvBnBwdWs L = conv_bn_bwd_ws(S.mfma && !mfma ? conv3_scratch_direct(Cin, Cout, g) : S, Cin, Cout, g);
     char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     ConvBwdCall k{x_dtype, dy_dtype, x, xcs, Halves(), Cin, w, nullptr, nullptr, nullptr, const_cast<void*>(dy), dycs, nullptr, 0, nullptr,
                   dx, dxcs, Halves(), dW, db, nullptr, nullptr, accumulate, nullptr, nullptr, 0, nullptr, Cout, g, mfma, c1, ws};
@@ -262,10 +303,8 @@ int mi3d_conv3_backward(int x_dtype, int dy_dtype, const void* x, int xcs, int C
 }
 
 size_t mi3d_conv3_bn_bwd_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W) {
-    if (Cin < 1 || Cout < 1 || N < 1 || D < 1 || H < 1 || W < 1) return 0;
-    bool mfma, c1;
-    conv3_layer_class(dtype, Cin, Cout, mfma, c1);
-    return conv_bn_bwd_ws(mfma, Cin, Cout, Geo{N, D, H, W}).total;
+    const Geo g{N, D, H, W};
+    return geo_ok(Cin, Cout, N, D, H, W) ? conv_bn_bwd_ws(conv3_scratch(dtype, Cin, Cout, g), Cin, Cout, g).total : 0;
 }
 int mi3d_conv3_bn_backward(int in_dtype, int dtype, const void* x, int xcs, int x_split, int64_t x_delta, int Cin, const float* w,
                            const void* y, const float* stat, const float* drop, void* dz, int dzcs, const float* dz_partials,
@@ -277,30 +316,23 @@ int mi3d_conv3_bn_backward(int in_dtype, int dtype, const void* x, int xcs, int 
     MI3D_CHECK_ARG(x && w && dz && workspace, "%s: null pointer", fn);
     MI3D_CHECK_ARG(!stat || (y && dy), "%s: the BatchNorm backward needs y and dy", fn);
     MI3D_CHECK_ARG(stat || (!dz_partials && !riders), "%s: dz partials and riders need the BatchNorm backward", fn);
-    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
-                   "%s: bad dtypes %d -> %d", fn, in_dtype, dtype);
-    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= (x_delta ? 16 : Cin) && dzcs >= Cout && N >= 1 && D >= 1 && H >= 1 && W >= 1,
-                   "%s: bad shape", fn);
+    const Geo g{N, D, H, W};
+    MI3D_TRY(conv_entry_check(fn, in_dtype, dtype, Cin, Cout, xcs, x_delta != 0, dzcs, g));
     MI3D_CHECK_ARG(!dz_partials || dz_ks >= 1, "%s: dz_ks=%d", fn, dz_ks);
     MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_LEAVE_PENDING) || pending_out, "%s: LEAVE_PENDING needs pending_out", fn);
     MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_DEFER) || !(flags & MI3D_CONV3_BN_BWD_LEAVE_PENDING), "%s: DEFER launches its own sum", fn);
-    const Geo g{N, D, H, W};
-    bool mfma, c1;
-    conv3_layer_class(dtype, Cin, Cout, mfma, c1);
-    MI3D_CHECK_ARG(!mfma || (xcs % 8 == 0 && dzcs % 8 == 0 && (!dx || dxcs % 4 == 0)), "%s: channel strides %d / %d / %d", fn, xcs, dzcs, dxcs);
-    MI3D_CHECK_ARG(!c1 || (in_dtype == MI3D_F32 && !dx), "%s: the first-layer kernel reads an fp32 image and has no input gradient", fn);
+    const ConvScratch S = conv3_scratch(dtype, Cin, Cout, g);
+    MI3D_CHECK_ARG(!S.mfma || (xcs % 8 == 0 && dzcs % 8 == 0 && (!dx || dxcs % 4 == 0)), "%s: channel strides %d / %d / %d", fn, xcs, dzcs, dxcs);
+    MI3D_CHECK_ARG(!S.c1 || (in_dtype == MI3D_F32 && !dx), "%s: the first-layer kernel reads an fp32 image and has no input gradient", fn);
     MI3D_CHECK_ARG(!dx || dxcs >= (dx_delta ? 16 : Cin), "%s: dx stride %d", fn, dxcs);
-    MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_DEFER) || (mfma && (dW || db)), "%s: only MFMA layers with a weight gradient defer it", fn);
-    MI3D_CHECK_ARG((!x_delta && !dx_delta) || (mfma && conv3_mfma_halves_ok(Cout, Cin, g)),
+    MI3D_CHECK_ARG(!(flags & MI3D_CONV3_BN_BWD_DEFER) || (S.mfma && (dW || db)), "%s: only MFMA layers with a weight gradient defer it", fn);
+    MI3D_CHECK_ARG((!x_delta && !dx_delta) || (S.mfma && conv3_mfma_halves_ok(Cout, Cin, g)),
                    "%s: planar halves need the full-resolution kernels", fn);
-    const ConvBnBwdWs L = conv_bn_bwd_ws(mfma, Cin, Cout, g);
-    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
-    Halves xh, dxh;
-    if (x_delta) { xh.split = x_split; xh.delta = x_delta; }
-    if (dx_delta) { dxh.split = dx_split; dxh.delta = dx_delta; }
-    ConvBwdCall k{in_dtype, dtype, x, xcs, xh, Cin, w, y, stat, drop, dz, dzcs, dz_partials, dz_ks, dy, dx, dxcs, dxh, dW, db, dgamma, dbeta,
-                  accumulate, riders, pending_out, flags, route_out, Cout, g, mfma, c1, (char*)workspace};
+    const ConvBnBwdWs L = conv_bn_bwd_ws(S, Cin, Cout, g);
+    MI3D_TRY(workspace_check(fn, workspace, workspace_bytes, L.total));
+    ConvBwdCall k{in_dtype, dtype, x, xcs, halves_at(x_split, x_delta), Cin, w, y, stat, drop, dz, dzcs, dz_partials, dz_ks, dy, dx, dxcs,
+                  halves_at(dx_split, dx_delta), dW, db, dgamma, dbeta, accumulate, riders, pending_out, flags, route_out, Cout, g, S.mfma, S.c1,
+                  (char*)workspace};
     return conv_bn_bwd_run(k, L, (hipStream_t)stream);
 }
 int mi3d_pending_sum_launch(const mi3d_pending_sum* job, void* stream) {
@@ -310,68 +342,32 @@ int mi3d_pending_sum_launch(const mi3d_pending_sum* job, void* stream) {
     return slab_job_launch(q, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
-// mi3d_conv3_bn_forward: the layer's route class as build_plan assigns it, and the plan's scratch areas in a workspace of its own
-namespace {
-struct ConvBnWs {
-    bool mfma, c1;
-    size_t statpart, tkcount, bnws, wpf, wpd, skws, total;
-};
-ConvBnWs conv_bn_ws(int dtype, int Cin, int Cout, Geo g) {
-    ConvBnWs L;
-    conv3_layer_class(dtype, Cin, Cout, L.mfma, L.c1);      // in_dtype is checked against the class by the entry
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    int rows = L.mfma ? conv3_mfma_stat_blocks(Cin, Cout, g) : L.c1 ? conv3_c1_fwd_stat_blocks(g) : 1;
-    L.statpart = take((size_t)rows * 2 * Cout * sizeof(float));
-    L.tkcount = take((size_t)CONV3_TK_COUNTERS * sizeof(int));
-    L.bnws = take(bn_ws_floats(Cout) * sizeof(float));
-    L.wpf = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cin, Cout) * sizeof(float));
-    L.wpd = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cout, Cin) * sizeof(float));
-    L.skws = take((L.mfma ? conv3_mfma_splitk_floats(Cin, Cout, g) : 0) * sizeof(float) + 16);
-    L.total = off;
-    return L;
-}
-}  // namespace
-
-extern "C" {
-
 size_t mi3d_conv3_bn_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W) {
-    if (Cin < 1 || Cout < 1 || N < 1 || D < 1 || H < 1 || W < 1) return 0;
-    return conv_bn_ws(dtype, Cin, Cout, Geo{N, D, H, W}).total;
+    return geo_ok(Cin, Cout, N, D, H, W) ? conv_bn_ws(conv3_scratch(dtype, Cin, Cout, Geo{N, D, H, W}), Cout).total : 0;
 }
 int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias,
                           const float* gamma, const float* beta, float* running_mean, float* running_var,
                           int64_t* num_batches_tracked, float momentum, float eps, const float* drop, void* y, void* z, int zcs,
                           void* pooled, int pcs, float* stat, int flags, mi3d_conv3_bn_route* route_out, int Cout, int N, int D,
                           int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
-    MI3D_CHECK_ARG(x && w && bias && gamma && beta && y && z && stat && workspace, "mi3d_conv3_bn_forward: null pointer");
-    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
-                   "mi3d_conv3_bn_forward: bad dtypes %d -> %d", in_dtype, dtype);
-    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= Cin && zcs >= Cout && N >= 1 && D >= 1 && H >= 1 && W >= 1,
-                   "mi3d_conv3_bn_forward: bad shape");
-    MI3D_CHECK_ARG(!pooled || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && pcs >= Cout && (int64_t)N * D * H * W * Cout < (1ll << 31)),
-                   "mi3d_conv3_bn_forward: pooled needs even sides and fewer than 2^31 elements");
+    const char* fn = "mi3d_conv3_bn_forward";
+    MI3D_CHECK_ARG(x && w && bias && gamma && beta && y && z && stat && workspace, "%s: null pointer", fn);
     const Geo g{N, D, H, W};
-    const ConvBnWs L = conv_bn_ws(dtype, Cin, Cout, g);
-    MI3D_CHECK_ARG(!L.mfma || xcs % 8 == 0, "mi3d_conv3_bn_forward: input channel stride %d", xcs);
-    MI3D_CHECK_ARG(!L.c1 || in_dtype == MI3D_F32, "mi3d_conv3_bn_forward: the first-layer kernel reads an fp32 image");
-    MI3D_CHECK_ARG(workspace_bytes >= L.total, "mi3d_conv3_bn_forward: workspace too small: %zu < %zu", workspace_bytes, L.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "mi3d_conv3_bn_forward: workspace must be 256-byte aligned");
+    MI3D_TRY(conv_entry_check(fn, in_dtype, dtype, Cin, Cout, xcs, false, zcs, g));
+    MI3D_CHECK_ARG(!pooled || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && pcs >= Cout && (int64_t)N * D * H * W * Cout < (1ll << 31)),
+                   "%s: pooled needs even sides and fewer than 2^31 elements", fn);
+    const ConvScratch S = conv3_scratch(dtype, Cin, Cout, g);      // the route class as build_plan assigns it
+    const ConvBnWs L = conv_bn_ws(S, Cout);
+    MI3D_CHECK_ARG(!S.mfma || xcs % 8 == 0, "%s: input channel stride %d", fn, xcs);
+    MI3D_CHECK_ARG(!S.c1 || in_dtype == MI3D_F32, "%s: the first-layer kernel reads an fp32 image", fn);
+    MI3D_TRY(workspace_check(fn, workspace, workspace_bytes, L.total));
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    bool tk_zeroed = false;
-    if (L.mfma) {      // the plan's pack launch: the weight images, and block 0 clears the ticket counters
-        PackJobs J;
-        J.n = 0; J.nblocks = 0;
-        if (!(flags & MI3D_CONV3_BN_KEEP_TICKETS)) { J.zero = (int*)(ws + L.tkcount); J.nzero = CONV3_TK_COUNTERS; }
-        MI3D_TRY(pack_all_add_conv3(J, w, Cin, Cout, ws + L.wpf, ws + L.wpd, g));
-        MI3D_TRY(pack_all_launch(J, s));
-        tk_zeroed = true;
-    }
-    ConvBnHalf a{Cin, Cout, g, dtype, L.mfma, L.c1, x, xcs, in_dtype, Halves(), w, bias, gamma, beta, ws + L.wpf, ws + L.wpd,
-                 y, stat, running_mean, running_var, num_batches_tracked, momentum, eps, 1, tk_zeroed, false,
+    if (S.mfma)      // the plan's pack launch: the weight images, and block 0 clears the ticket counters
+        MI3D_TRY(pack_one_conv3(w, Cin, Cout, ws + L.wpf, ws + L.wpd, g, s, nullptr,
+                                (flags & MI3D_CONV3_BN_KEEP_TICKETS) ? nullptr : (int*)(ws + L.tkcount)));
+    ConvBnHalf a{Cin, Cout, g, dtype, S.mfma, S.c1, x, xcs, in_dtype, Halves(), w, bias, gamma, beta, ws + L.wpf, ws + L.wpd,
+                 y, stat, running_mean, running_var, num_batches_tracked, momentum, eps, 1, /*tk_zeroed*/ S.mfma, false,
                  (float*)(ws + L.statpart), (float*)(ws + L.skws), (int*)(ws + L.tkcount), (float*)(ws + L.bnws),
                  drop, z, zcs, pooled, pcs};
     MI3D_TRY(conv3_bn_half_forward(a, s, route_out));
@@ -379,33 +375,8 @@ int mi3d_conv3_bn_forward(int in_dtype, int dtype, const void* x, int xcs, int C
     return 0;
 }
 
-}  // extern "C"
-
-// mi3d_conv3_infer_forward: the areas of the plan's workspace an inference layer touches, in a workspace of its own
-namespace {
-struct ConvInferWs {
-    bool mfma, c1;
-    size_t fold, wpf, wpd, skws, total;
-};
-ConvInferWs conv_infer_ws(int dtype, int Cin, int Cout, Geo g) {
-    ConvInferWs L;
-    conv3_layer_class(dtype, Cin, Cout, L.mfma, L.c1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    L.fold = take((size_t)2 * Cout * sizeof(float));      // scale, then the folded bias: the plan's stat[0..2C) of an inference call
-    L.wpf = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : conv3_direct_pack_floats(Cin, Cout) * sizeof(float));
-    L.wpd = take(L.mfma ? conv3_mfma_pack_elems(Cin, Cout) * 2 : 0);      // the pack launch writes both images
-    L.skws = take((L.mfma ? conv3_mfma_splitk_floats(Cin, Cout, g) : 0) * sizeof(float) + 16);
-    L.total = off;
-    return L;
-}
-}  // namespace
-
-extern "C" {
-
 size_t mi3d_conv3_infer_workspace_bytes(int in_dtype, int dtype, int Cin, int Cout, int N, int D, int H, int W) {
-    if (Cin < 1 || Cout < 1 || N < 1 || D < 1 || H < 1 || W < 1) return 0;
-    return conv_infer_ws(dtype, Cin, Cout, Geo{N, D, H, W}).total;
+    return geo_ok(Cin, Cout, N, D, H, W) ? conv_infer_ws(conv3_scratch(dtype, Cin, Cout, Geo{N, D, H, W}), Cout).total : 0;
 }
 int mi3d_conv3_infer_forward(int in_dtype, int dtype, const void* x, int xcs, int x_split, int64_t x_delta, int Cin,
                              const float* w, const float* bias, const float* gamma, const float* beta,
@@ -414,19 +385,16 @@ int mi3d_conv3_infer_forward(int in_dtype, int dtype, const void* x, int xcs, in
                              size_t workspace_bytes, void* stream) {
     const char* fn = "mi3d_conv3_infer_forward";
     MI3D_CHECK_ARG(x && w && gamma && beta && running_mean && running_var && z && workspace, "%s: null pointer", fn);
-    MI3D_CHECK_ARG((dtype == MI3D_F32 || dtype == MI3D_BF16) && (in_dtype == dtype || (in_dtype == MI3D_F32 && Cin == 1 && xcs == 1)),
-                   "%s: bad dtypes %d -> %d", fn, in_dtype, dtype);
-    MI3D_CHECK_ARG(Cin >= 1 && Cout >= 1 && Cout <= 256 && xcs >= (x_delta ? 16 : Cin) && zcs >= Cout && N >= 1 && D >= 1 && H >= 1 && W >= 1,
-                   "%s: bad shape", fn);
     const Geo g{N, D, H, W};
-    const ConvInferWs L = conv_infer_ws(dtype, Cin, Cout, g);
-    MI3D_CHECK_ARG(!L.mfma || (xcs % 8 == 0 && zcs % 4 == 0 && ((uintptr_t)x % 16) == 0), "%s: channel strides %d / %d", fn, xcs, zcs);
-    MI3D_CHECK_ARG(!L.c1 || (in_dtype == MI3D_F32 && zcs % 4 == 0), "%s: the first-layer kernel reads an fp32 image", fn);
-    MI3D_CHECK_ARG(!(L.mfma || L.c1) || ((uintptr_t)z % 8) == 0, "%s: misaligned output", fn);
-    MI3D_CHECK_ARG(!L.mfma || ((uintptr_t)w % 16) == 0, "%s: the weight tensor must be 16-byte aligned", fn);
-    MI3D_CHECK_ARG(!x_delta || (L.mfma && conv3_mfma_halves_ok(Cin, Cout, g)), "%s: planar halves need the full-resolution kernels", fn);
-    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    MI3D_TRY(conv_entry_check(fn, in_dtype, dtype, Cin, Cout, xcs, x_delta != 0, zcs, g));
+    const ConvScratch S = conv3_scratch(dtype, Cin, Cout, g);
+    const ConvInferWs L = conv_infer_ws(S, Cout);
+    MI3D_CHECK_ARG(!S.mfma || (xcs % 8 == 0 && zcs % 4 == 0 && ((uintptr_t)x % 16) == 0), "%s: channel strides %d / %d", fn, xcs, zcs);
+    MI3D_CHECK_ARG(!S.c1 || (in_dtype == MI3D_F32 && zcs % 4 == 0), "%s: the first-layer kernel reads an fp32 image", fn);
+    MI3D_CHECK_ARG(!(S.mfma || S.c1) || ((uintptr_t)z % 8) == 0, "%s: misaligned output", fn);
+    MI3D_CHECK_ARG(!S.mfma || ((uintptr_t)w % 16) == 0, "%s: the weight tensor must be 16-byte aligned", fn);
+    MI3D_CHECK_ARG(!x_delta || (S.mfma && conv3_mfma_halves_ok(Cin, Cout, g)), "%s: planar halves need the full-resolution kernels", fn);
+    MI3D_TRY(workspace_check(fn, workspace, workspace_bytes, L.total));
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
     float* scale = (float*)(ws + L.fold);
@@ -434,15 +402,9 @@ int mi3d_conv3_infer_forward(int in_dtype, int dtype, const void* x, int xcs, in
     F.n = 1; F.eps = eps;
     F.j[0] = BnFoldJob{gamma, beta, running_mean, running_var, bias, scale, scale + Cout, Cout};
     MI3D_TRY(bn_fold_all(F, s));
-    if (L.mfma) {      // launch 2: the weight images, BatchNorm scale multiplied into the forward one
-        PackJobs J;
-        J.n = 0; J.nblocks = 0;
-        MI3D_TRY(pack_all_add_conv3(J, w, Cin, Cout, ws + L.wpf, ws + L.wpd, g, scale));
-        MI3D_TRY(pack_all_launch(J, s));
-    }
-    Halves xh;
-    if (x_delta) { xh.split = x_split; xh.delta = x_delta; }
-    ConvBnHalfInfer a{Cin, Cout, g, dtype, L.mfma, L.c1, x, xcs, in_dtype, xh, w, ws + L.wpf, scale, scale + Cout, z, zcs,
+    if (S.mfma)      // launch 2: the weight images, BatchNorm scale multiplied into the forward one
+        MI3D_TRY(pack_one_conv3(w, Cin, Cout, ws + L.wpf, ws + L.wpd, g, s, scale));
+    ConvBnHalfInfer a{Cin, Cout, g, dtype, S.mfma, S.c1, x, xcs, in_dtype, halves_at(x_split, x_delta), w, ws + L.wpf, scale, scale + Cout, z, zcs,
                       (float*)(ws + L.skws)};
     MI3D_TRY(conv3_bn_half_infer(a, s, route_out));
     if (fold_out) MI3D_HIP(hipMemcpyAsync(fold_out, scale, (size_t)2 * Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -543,25 +505,24 @@ int mi3d_maxpool2_backward_partials(int dtype, const float* dp_partials, int ks,
 // mi3d_up_forward / mi3d_up_backward: the route class of a decoder up step and its scratch areas in a workspace of its own
 namespace {
 struct UpWs { size_t wp, wp_bytes, tmp, tmp_bytes, wgws, wgws2, wg_floats, total; };
-size_t up_wg_floats(int Cin, int Cout, Geo g) {
-    size_t wsf = upconv2_bwd_ws_floats(Cin, Cout, g);
-    if (upconv2_mfma_supported(Cin, Cout, 8, 8) && upconv2_mfma_bwd_ws_floats(Cin, Cout, g) > wsf) wsf = upconv2_mfma_bwd_ws_floats(Cin, Cout, g);
-    return wsf;
-}
+// The plan knows a level's route when it lays the level out and reserves the class's images and slabs.  An entry learns its route
+// from the caller's strides at the call, and its size queries from less still (mi3d_upconv2_workspace_bytes has no dtype): it
+// reserves the direct images, which are never smaller than the MFMA ones, and the larger of the two slab sizes, for either route
 UpWs up_ws(int dtype, int Cin, int Cout, Geo g) {
-    UpWs L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    L.wp_bytes = upconv2_pack_floats(Cin, Cout) * sizeof(float);       // >= the MFMA images (2 * Cin * Cout * 8 bf16)
-    L.wp = take(L.wp_bytes);
+    const UpScratch S = upconv2_scratch(MI3D_BF16, Cin, Cout, g);
+    UpWs L; Arena A;
+    L.wp_bytes = S.direct_pack_bytes;
+    L.wp = A.take(L.wp_bytes);
     L.tmp_bytes = (size_t)g.M() * 8 * Cout * (dtype == MI3D_BF16 ? 2 : 4);
-    L.tmp = take(L.tmp_bytes);
-    L.wg_floats = up_wg_floats(Cin, Cout, g);
-    L.wgws = take(L.wg_floats * sizeof(float));
-    L.wgws2 = take(L.wg_floats * sizeof(float));
-    L.total = off;
+    L.tmp = A.take(L.tmp_bytes);
+    L.wg_floats = std::max(S.wgrad_floats, S.direct_wgrad_floats);
+    L.wgws = A.take(L.wg_floats * sizeof(float));
+    L.wgws2 = A.take(L.wg_floats * sizeof(float));
+    L.total = A.off;
     return L;
 }
+// the route of a call: the MFMA kernels where dtype and the caller's strides allow them
+inline bool up_mfma_route(int dtype, int Cin, int Cout, int xcs, int ycs) { return dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, ycs); }
 // the direct kernels' two weight images inside the packed-weights area
 inline float* up_wpb(void* wp, int Cin, int Cout) { return (float*)wp + (size_t)cdiv(Cout, 8) * Cin * 64; }
 inline bool up_args_ok(int dtype, int Cin, int Cout, int N, int D, int H, int W, int Do, int Ho, int Wo) {
@@ -573,14 +534,15 @@ inline bool up_args_ok(int dtype, int Cin, int Cout, int N, int D, int H, int W,
 extern "C" {
 
 size_t mi3d_upconv2_workspace_bytes(int Cin, int Cout, int N, int D, int H, int W) {
-    return (upconv2_pack_floats(Cin, Cout) + up_wg_floats(Cin, Cout, Geo{N, D, H, W})) * sizeof(float);
+    const UpWs L = up_ws(MI3D_F32, Cin, Cout, Geo{N, D, H, W});      // the two areas the wrappers use, back to back
+    return L.wp_bytes + L.wg_floats * sizeof(float);
 }
 // thin wrappers: the up step without a resize, the weight images at the start of the workspace and one slab region behind them
 int mi3d_upconv2_forward(int dtype, const void* x, int xcs, int Cin, const float* w, const float* bias, void* y, int ycs,
                          int Cout, int N, int D, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
     MI3D_CHECK_ARG(x && w && y && workspace, "mi3d_upconv2_forward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_upconv2_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_upconv2_forward: workspace too small");
-    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, ycs);
+    const bool mfma = up_mfma_route(dtype, Cin, Cout, xcs, ycs);
     if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, (hipStream_t)stream));
     UpHalf a{Cin, Cout, Geo{N, D, H, W}, dtype, mfma, x, xcs, w, bias, workspace, up_wpb(workspace, Cin, Cout), y, ycs,
              Geo{N, 2 * D, 2 * H, 2 * W}, nullptr};
@@ -591,16 +553,16 @@ int mi3d_upconv2_backward(int dtype, const void* x, int xcs, int Cin, const floa
                           void* workspace, size_t workspace_bytes, void* stream) {
     MI3D_CHECK_ARG(x && w && gy && workspace, "mi3d_upconv2_backward: null pointer");
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_upconv2_workspace_bytes(Cin, Cout, N, D, H, W), "mi3d_upconv2_backward: workspace too small");
-    Geo g{N, D, H, W};
+    const Geo g{N, D, H, W};
+    const UpWs L = up_ws(dtype, Cin, Cout, g);
     hipStream_t s = (hipStream_t)stream;
     float* wb = up_wpb(workspace, Cin, Cout);
-    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, gycs) && (!dx || dxcs % 4 == 0);
+    const bool mfma = up_mfma_route(dtype, Cin, Cout, xcs, gycs) && (!dx || dxcs % 4 == 0);
     if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, workspace, s));
     else MI3D_TRY(upconv2_pack(w, Cin, Cout, (float*)workspace, wb, s));
     Pending pending;
     UpHalfBwd a{Cin, Cout, g, dtype, mfma, x, xcs, workspace, wb, gy, gycs, Geo{N, 2 * D, 2 * H, 2 * W}, nullptr, dx, dxcs, dW, db,
-                accumulate, (float*)workspace + upconv2_pack_floats(Cin, Cout), nullptr,
-                mfma ? upconv2_mfma_bwd_ws_floats(Cin, Cout, g) : upconv2_bwd_ws_floats(Cin, Cout, g), false};
+                accumulate, (float*)((char*)workspace + L.wp_bytes), nullptr, L.wg_floats, false};
     return up_half_backward(a, pending, s);
 }
 
@@ -623,12 +585,11 @@ int mi3d_up_forward(int dtype, const void* x, int xcs, int Cin, const float* w, 
     MI3D_CHECK_ARG(up_args_ok(dtype, Cin, Cout, N, D, H, W, Do, Ho, Wo) && xcs >= Cin && ucs >= Cout, "%s: bad shape or dtype", fn);
     const Geo g{N, D, H, W}, go{N, Do, Ho, Wo};
     const UpWs L = up_ws(dtype, Cin, Cout, g);
-    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    MI3D_TRY(workspace_check(fn, workspace, workspace_bytes, L.total));
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
     const bool rs = Do != 2 * D || Ho != 2 * H || Wo != 2 * W;
-    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, rs ? Cout : ucs);
+    const bool mfma = up_mfma_route(dtype, Cin, Cout, xcs, rs ? Cout : ucs);
     if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, ws + L.wp, s));
     UpHalf a{Cin, Cout, g, dtype, mfma, x, xcs, w, bias, ws + L.wp, up_wpb(ws + L.wp, Cin, Cout), up, ucs, go, ws + L.tmp};
     return up_half_forward(a, s, route_out);
@@ -644,12 +605,11 @@ int mi3d_up_backward(int dtype, const void* x, int xcs, int Cin, const float* w,
     MI3D_CHECK_ARG(!leave || pending_out, "%s: LEAVE_PENDING needs pending_out", fn);
     const Geo g{N, D, H, W}, go{N, Do, Ho, Wo};
     const UpWs L = up_ws(dtype, Cin, Cout, g);
-    MI3D_CHECK_ARG(workspace_bytes >= L.total, "%s: workspace too small: %zu < %zu", fn, workspace_bytes, L.total);
-    MI3D_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+    MI3D_TRY(workspace_check(fn, workspace, workspace_bytes, L.total));
     char* ws = (char*)workspace;
     hipStream_t s = (hipStream_t)stream;
     const bool rs = Do != 2 * D || Ho != 2 * H || Wo != 2 * W;
-    const bool mfma = dtype == MI3D_BF16 && upconv2_mfma_supported(Cin, Cout, xcs, rs ? Cout : gucs) && (!dx || dxcs % 4 == 0);
+    const bool mfma = up_mfma_route(dtype, Cin, Cout, xcs, rs ? Cout : gucs) && (!dx || dxcs % 4 == 0);
     MI3D_CHECK_ARG(!second || (mfma && !mi3d_routes().no_upbwd_carry), "%s: only the MFMA route with the carry has a second slab workspace", fn);
     float* wb = up_wpb(ws + L.wp, Cin, Cout);
     if (mfma) MI3D_TRY(upconv2_mfma_pack(w, Cin, Cout, ws + L.wp, s));

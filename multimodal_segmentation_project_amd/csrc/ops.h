@@ -49,6 +49,11 @@ bool conv3_mfma_fuses_stats(int Cin, int Cout, Geo g);        // false -> caller
 // 16-channel block b >= split is found `delta` elements further than the single-plane address would say.
 // Default = ordinary single-plane tensor.  Only the persistent full-resolution kernels and wgrad honour it.
 struct Halves { int split = 1 << 30; int64_t delta = 0; bool on() const { return delta != 0; } };
+inline Halves halves_at(int split, int64_t delta) {      // delta == 0: the single-plane default, whatever split says
+    Halves h;
+    if (delta) { h.split = split; h.delta = delta; }
+    return h;
+}
 bool conv3_mfma_halves_ok(int Cin, int Cout, Geo g);          // forward (Cin,Cout) launch can take Halves x / y
 // The split-K forward launch of this layer can finish itself: the LAST of the ks workgroups of an (output tile, channel group) to
 // arrive (one atomic ticket per workgroup on a counter only those ks workgroups touch) sums the ks fp32 partials in k order, adds

@@ -11,8 +11,10 @@
 //   gradients           : gz[l], gcat[l], gp[l] per level + two max-size scratch tensors
 #include "../../include/mi3d.h"
 #include <stdlib.h>
+#include <algorithm>
 
 #include "ops.h"
+#include "scratch.h"
 
 // One half of a DoubleConv block, forward (ops.h ConvBnHalf): conv -> BatchNorm statistics -> apply (-> MaxPool3d).  Every route
 // decision of the forward is made here and only here.  a.pooled != NULL (second half of an encoder block on an even volume): the
@@ -21,7 +23,7 @@ int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_rout
     const Geo g = a.g;
     const int training = a.training;
     bool fused_stats = false;
-    int ksd = 0, c1_blocks = 0;
+    int ksd = 0;
     Conv3Launch ln;
     bool tk = false;
     if (a.mfma) {
@@ -39,7 +41,7 @@ int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_rout
         // BN partial sums fused like the other convs
         MI3D_TRY(conv3_c1_fwd_mfma((const float*)a.in, a.w, a.bias, a.y, a.Cout, a.Cout, g,
                                    training ? a.statpart : nullptr, s));
-        if (training) { fused_stats = true; c1_blocks = conv3_c1_fwd_stat_blocks(g); }
+        fused_stats = training != 0;
         ln.kind = 1;
     } else {
         MI3D_TRY(conv3_direct_pack(a.w, a.Cin, a.Cout, (float*)a.wpf, (float*)a.wpd, s));
@@ -52,7 +54,7 @@ int conv3_bn_half_forward(const ConvBnHalf& a, hipStream_t s, mi3d_conv3_bn_rout
     if (fused_stats) {
         // round 4: the apply pass finishes the conv epilogue's partial rows itself (bn.hip, wide consumer); the pooled pass only
         // in its two-threads-per-window form
-        rows = c1_blocks ? c1_blocks : conv3_mfma_stat_blocks(a.Cin, a.Cout, g);
+        rows = conv3_scratch(a.dt, a.Cin, a.Cout, g).stat_rows;
         const bool pool_pass = a.pooled != nullptr;
         if (a.dt == MI3D_BF16 && bn_rows_route_ok(a.Cout, g.M(), rows) && !(pool_pass && mi3d_routes().no_pool_pair) &&
             !(a.beside && !bn_small_ok(a.Cout, g.M(), rows))) {
@@ -333,11 +335,7 @@ struct Plan {
     Geo up_geo(int l) const { return Geo{geo[l + 1].N, 2 * geo[l + 1].D, 2 * geo[l + 1].H, 2 * geo[l + 1].W}; }
     int catcs(int l) const { return planar[l] ? C[l] : 2 * C[l]; }
     size_t half_off(int l) const { return (planar[l] ? (size_t)geo[l].M() * C[l] : (size_t)C[l]) * esz; }   // bytes to the up half
-    Halves halves(int l) const {
-        Halves h;
-        if (planar[l]) { h.split = C[l] / 16; h.delta = geo[l].M() * C[l] - C[l]; }
-        return h;
-    }
+    Halves halves(int l) const { return halves_at(C[l] / 16, planar[l] ? geo[l].M() * C[l] - C[l] : 0); }
     size_t gz[MAXL + 1], gcat[MAXL], gp[MAXL], sB, sB2, sC;
     size_t bnws, wgws, wgws2, wgws3, statpart, skws, tkcount;
     // (block, half) after whose BatchNorm backward the pending deferred weight gradients of group 1 / 2 go to the aux stream
@@ -347,8 +345,6 @@ struct Plan {
     int up_pidx(int i) const { return 8 * (L + 1) + 2 * i; }
     int final_pidx() const { return 8 * (L + 1) + 2 * L + 8 * L; }
 };
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int build_plan(const mi3d_unet_desc* d, Plan& p) {
     MI3D_CHECK_ARG(d != nullptr, "null descriptor");
@@ -383,8 +379,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
     for (int l = 0; l < p.L; l++)
         p.planar[l] = p.dt == MI3D_BF16 && p.C[l] % 16 == 0 && conv3_mfma_halves_ok(2 * p.C[l], p.C[l], p.geo[l]) &&
                       conv3_mfma_halves_ok(p.C[l], 2 * p.C[l], p.geo[l]) && !mi3d_routes().no_planar;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
+    Arena A;
     int64_t drop_off = 0;
     size_t wg_floats = 0, maxCM = 0, statpart_floats = 1, skws_floats = 1;
     int maxC = 1;
@@ -401,74 +396,61 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             HalfP& H = B.h[h];
             H.Cin = h == 0 ? cin : cout;
             H.Cout = cout;
-            H.y = take((size_t)g.M() * cout * p.esz);
-            H.stat = take((size_t)4 * cout * sizeof(float));
-            conv3_layer_class(p.dt, H.Cin, H.Cout, H.mfma, H.c1);
-            if (H.mfma) {
-                H.wpf = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
-                H.wpd = take(conv3_mfma_pack_elems(H.Cin, H.Cout) * 2);
-                size_t sp = (size_t)conv3_mfma_stat_blocks(H.Cin, H.Cout, g) * 2 * cout;
-                if (sp > statpart_floats) statpart_floats = sp;
-                size_t sk = conv3_mfma_splitk_floats(H.Cin, H.Cout, g), sk2 = conv3_mfma_splitk_floats(H.Cout, H.Cin, g);
-                if (sk > skws_floats) skws_floats = sk;
-                if (sk2 > skws_floats) skws_floats = sk2;
-            } else {
-                H.wpf = take(conv3_direct_pack_floats(H.Cin, H.Cout) * sizeof(float));
-                H.wpd = take(conv3_direct_pack_floats(H.Cout, H.Cin) * sizeof(float));
-            }
+            H.y = A.take((size_t)g.M() * cout * p.esz);
+            H.stat = A.take((size_t)4 * cout * sizeof(float));
+            // the shared areas (statistics rows, split-K partials, slabs) hold the largest layer's
+            const ConvScratch S = conv3_scratch(p.dt, H.Cin, H.Cout, g);
+            H.mfma = S.mfma; H.c1 = S.c1;
+            H.wpf = A.take(S.wpf_bytes);
+            H.wpd = A.take(S.wpd_bytes);
+            if (S.mfma || S.c1) statpart_floats = std::max(statpart_floats, (size_t)S.stat_rows * 2 * cout);      // the direct kernels write no rows
+            skws_floats = std::max(skws_floats, std::max(S.splitk_fwd_floats, S.splitk_bwd_floats));
+            wg_floats = std::max(wg_floats, S.wgrad_floats);
             H.pidx = pbase + 4 * h;
             H.bidx = 6 * b + 3 * h;
             H.drop_off = drop_off;
             drop_off += (int64_t)d->N * cout;
-            if (H.c1) {
-                size_t sp = (size_t)conv3_c1_fwd_stat_blocks(g) * 2 * cout;
-                if (sp > statpart_floats) statpart_floats = sp;
-            }
-            size_t wf = (H.mfma || H.c1) ? conv3_mfma_wgrad_ws_floats(H.Cin, H.Cout, g) : conv3_direct_wgrad_ws_floats(H.Cin, H.Cout, g);
-            if (wf > wg_floats) wg_floats = wf;
             // the dy buffers are part of the layout whatever the route says (a route changed between the workspace query and a
             // launch must not move anything)
             H.defer = !H.mfma ? 0 : !conv3_mfma_big_geo(g) ? 2 : (b > p.L ? 1 : 0);
-            H.dyk = H.defer ? take((size_t)g.M() * cout * p.esz) : 0;
+            H.dyk = H.defer ? A.take((size_t)g.M() * cout * p.esz) : 0;
         }
-        B.z1 = take((size_t)g.M() * cout * p.esz);
+        B.z1 = A.take((size_t)g.M() * cout * p.esz);
         if ((size_t)g.M() * cout > maxCM) maxCM = (size_t)g.M() * cout;
         if (cout > maxC) maxC = cout;
     }
     for (int l = 0; l < p.L; l++) {
-        p.cat[l] = take((size_t)p.geo[l].M() * 2 * p.C[l] * p.esz);
-        p.pool[l] = take((size_t)p.geo[l + 1].M() * p.C[l] * p.esz);
-        p.gcat[l] = take((size_t)p.geo[l].M() * 2 * p.C[l] * p.esz);
-        p.gp[l] = take((size_t)p.geo[l + 1].M() * p.C[l] * p.esz);
-        p.gz[l] = take((size_t)p.geo[l].M() * p.C[l] * p.esz);
+        p.cat[l] = A.take((size_t)p.geo[l].M() * 2 * p.C[l] * p.esz);
+        p.pool[l] = A.take((size_t)p.geo[l + 1].M() * p.C[l] * p.esz);
+        p.gcat[l] = A.take((size_t)p.geo[l].M() * 2 * p.C[l] * p.esz);
+        p.gp[l] = A.take((size_t)p.geo[l + 1].M() * p.C[l] * p.esz);
+        p.gz[l] = A.take((size_t)p.geo[l].M() * p.C[l] * p.esz);
     }
-    p.gz[p.L] = take((size_t)p.geo[p.L].M() * p.C[p.L] * p.esz);
-    p.zb = take((size_t)p.geo[p.L].M() * p.C[p.L] * p.esz);
+    p.gz[p.L] = A.take((size_t)p.geo[p.L].M() * p.C[p.L] * p.esz);
+    p.zb = A.take((size_t)p.geo[p.L].M() * p.C[p.L] * p.esz);
     for (int i = 0; i < p.L; i++) {
         int l = p.L - 1 - i;
-        p.zd[i] = take((size_t)p.geo[l].M() * p.C[l] * p.esz);
-        p.up_mfma[i] = p.dt == MI3D_BF16 && upconv2_mfma_supported(2 * p.C[l], p.C[l], 2 * p.C[l], 2 * p.C[l]);
-        p.upw[i] = take(p.up_mfma[i] ? upconv2_mfma_pack_elems(2 * p.C[l], p.C[l]) * 2
-                                     : upconv2_pack_floats(2 * p.C[l], p.C[l]) * sizeof(float));
-        size_t wf = p.up_mfma[i] ? upconv2_mfma_bwd_ws_floats(2 * p.C[l], p.C[l], p.geo[l + 1])
-                                 : upconv2_bwd_ws_floats(2 * p.C[l], p.C[l], p.geo[l + 1]);
-        if (wf > wg_floats) wg_floats = wf;
+        p.zd[i] = A.take((size_t)p.geo[l].M() * p.C[l] * p.esz);
+        // a level runs the kernels of its class only: the class's images and slabs
+        const UpScratch U = upconv2_scratch(p.dt, 2 * p.C[l], p.C[l], p.geo[l + 1]);
+        p.up_mfma[i] = U.mfma;
+        p.upw[i] = A.take(U.pack_bytes);
+        wg_floats = std::max(wg_floats, U.wgrad_floats);
     }
-    p.uptmp = up_elems ? take(up_elems * p.esz) : 0;
-    p.xcl = d->in_channels > 1 ? take((size_t)p.geo[0].M() * d->in_channels * p.esz) : 0;
-    size_t c1 = conv1_bwd_ws_floats(p.C[0], d->out_channels);
-    if (c1 > wg_floats) wg_floats = c1;
-    p.sB = take(maxCM * p.esz);
-    p.sB2 = take(maxCM * p.esz);
-    p.sC = take(maxCM * p.esz);
-    p.bnws = take(bn_ws_floats(maxC) * sizeof(float));
-    p.statpart = take(statpart_floats * sizeof(float));
-    p.tkcount = take((size_t)CONV3_TK_COUNTERS * sizeof(int));        // split-K ticket counters (zeroed by the forward's pack launch)
-    p.skws = take(skws_floats * sizeof(float));
+    p.uptmp = up_elems ? A.take(up_elems * p.esz) : 0;
+    p.xcl = d->in_channels > 1 ? A.take((size_t)p.geo[0].M() * d->in_channels * p.esz) : 0;
+    wg_floats = std::max(wg_floats, conv1_bwd_ws_floats(p.C[0], d->out_channels));
+    p.sB = A.take(maxCM * p.esz);
+    p.sB2 = A.take(maxCM * p.esz);
+    p.sC = A.take(maxCM * p.esz);
+    p.bnws = A.take(bn_ws_floats(maxC) * sizeof(float));
+    p.statpart = A.take(statpart_floats * sizeof(float));
+    p.tkcount = A.take((size_t)CONV3_TK_COUNTERS * sizeof(int));        // split-K ticket counters (zeroed by the forward's pack launch)
+    p.skws = A.take(skws_floats * sizeof(float));
     p.wgws_floats = wg_floats;
-    p.wgws = take(wg_floats * sizeof(float));
-    p.wgws2 = take(wg_floats * sizeof(float));
-    p.wgws3 = take(wg_floats * sizeof(float));       // slabs of the weight gradients on the aux stream
+    p.wgws = A.take(wg_floats * sizeof(float));
+    p.wgws2 = A.take(wg_floats * sizeof(float));
+    p.wgws3 = A.take(wg_floats * sizeof(float));       // slabs of the weight gradients on the aux stream
     // backward order of the conv layers: decoder.L-1 .. decoder.0 (level 0 first), bottleneck, encoder.L-1 .. 0; half 1 then 0
     for (int k = 0; k < 2; k++) p.flush_b[k] = p.flush_h[k] = -1;
     for (int q = 0; q < p.nblk; q++) {
@@ -478,7 +460,7 @@ int build_plan(const mi3d_unet_desc* d, Plan& p) {
             if (dfr) { p.flush_b[dfr - 1] = b; p.flush_h[dfr - 1] = h; }
         }
     }
-    p.total = off;
+    p.total = A.off;
     return 0;
 }
 

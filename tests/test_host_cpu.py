@@ -337,3 +337,111 @@ def test_every_route_switch_is_exercised_by_a_gpu_test():
     assert len(names) == 16
     gpu_tests = "\n".join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py"))))
     assert [n for n in names if not re.search(rf"\b{n}\b", gpu_tests)] == []
+
+
+# ---- scratch sizes of the conv and up entries and of the whole-network plan, pinned ------------------------------------------
+_F32, _BF16 = _lib.DTYPE_F32, _lib.DTYPE_BF16
+# (dtype, Cin, Cout): first layer on the matrix cores, full-resolution MFMA, the deep split-K layers in both orientations, direct
+_CONV_LAYERS = [(_BF16, 1, 16), (_BF16, 16, 16), (_BF16, 16, 32), (_BF16, 32, 16), (_BF16, 128, 256), (_BF16, 256, 128),
+                (_F32, 1, 16), (_F32, 3, 5)]
+_CONV_GEOS = [(2, 96, 96, 96), (2, 48, 48, 48), (2, 8, 8, 8), (2, 6, 6, 6), (1, 5, 6, 7)]
+_UP_LAYERS = [(_BF16, 32, 16), (_BF16, 256, 128), (_F32, 6, 3)]
+_UP_GEOS = [(2, 48, 48, 48), (2, 6, 6, 6), (1, 5, 6, 7)]
+_NET_CASES = [((2, 1, 96, 96, 96), torch.bfloat16), ((2, 1, 96, 96, 96), torch.float32), ((2, 1, 32, 32, 32), torch.bfloat16),
+              ((1, 1, 18, 20, 22), torch.bfloat16)]
+
+
+def _scratch_query_values():
+    """Every workspace query of the conv / up entries and of the plan over the tables above, in table order."""
+    lib = _lib.lib()
+    conv, up, net = [], [], []
+    for dt, cin, cout in _CONV_LAYERS:
+        idt = _F32 if cin == 1 else dt
+        for g in _CONV_GEOS:
+            conv.append((lib.mi3d_conv3_workspace_bytes(cin, cout, *g), lib.mi3d_conv3_bn_workspace_bytes(idt, dt, cin, cout, *g),
+                         lib.mi3d_conv3_bn_bwd_workspace_bytes(idt, dt, cin, cout, *g),
+                         lib.mi3d_conv3_infer_workspace_bytes(idt, dt, cin, cout, *g)))
+    for dt, cin, cout in _UP_LAYERS:
+        for g in _UP_GEOS:
+            row = [lib.mi3d_upconv2_workspace_bytes(cin, cout, *g), lib.mi3d_up_workspace_bytes(dt, cin, cout, *g)]
+            for which in range(4):
+                n = C.c_size_t(0)
+                row += [lib.mi3d_up_workspace_region(dt, cin, cout, *g, which, C.byref(n)), n.value]
+            up.append(tuple(row))
+    m = mi.UNet3D(in_channels=1, out_channels=4)
+    for shape, dt in _NET_CASES:
+        net.append(lib.mi3d_unet_workspace_bytes(C.byref(engine.build_desc(m, torch.zeros(shape), dt))))
+    return conv, up, net
+
+
+# Recorded from a build of the parent commit of the change that gave plan and entries one scratch description (same table order
+# as _scratch_query_values); that build and this one both return them.  Conv rows: mi3d_conv3_workspace_bytes, _bn_, _bn_bwd_,
+# _infer_.  Up rows: mi3d_upconv2_workspace_bytes, mi3d_up_workspace_bytes, then (offset, bytes) of regions 0..3.
+_CONV_PINS = [
+    (1996288, 308480, 1996032, 2304),
+    (1078784, 232704, 1078528, 2304),
+    (175616, 177920, 175360, 2304),
+    (175616, 177920, 175360, 2304),
+    (168448, 177664, 168192, 2304),
+    (14375680, 242176, 14348800, 29184),
+    (14375680, 231936, 14348800, 29184),
+    (408832, 177152, 381952, 29184),
+    (408832, 177152, 381952, 29184),
+    (297984, 176896, 271104, 29184),
+    (28750848, 467712, 28697344, 57856),
+    (28750848, 447232, 28697344, 57856),
+    (894976, 337664, 894720, 57856),
+    (819200, 337664, 818944, 57856),
+    (595456, 337152, 568832, 57856),
+    (28586752, 270848, 28533248, 57856),
+    (28586752, 260608, 28533248, 57856),
+    (685312, 336896, 631808, 188928),
+    (685312, 261120, 631808, 113152),
+    (463872, 232448, 410368, 84736),
+    (65818112, 12864768, 62409984, 3672320),
+    (65818112, 6671616, 62409984, 3672320),
+    (38284800, 9989376, 38284544, 7866624),
+    (37498368, 7564544, 35859712, 5441792),
+    (23338496, 7511296, 21650688, 5392640),
+    (64759808, 8275712, 61351680, 3671296),
+    (64759808, 5179136, 61351680, 3671296),
+    (37230592, 8935168, 37230336, 7865600),
+    (36444160, 6510336, 34805504, 5440768),
+    (22286336, 6459136, 20598528, 5391616),
+    (1996288, 177664, 1996032, 2304),
+    (1078784, 177664, 1078528, 2304),
+    (175616, 177664, 175360, 2304),
+    (175616, 177664, 175360, 2304),
+    (168448, 177664, 168192, 2304),
+    (895488, 72192, 895232, 5888),
+    (895488, 72192, 895232, 5888),
+    (69120, 72192, 68864, 5888),
+    (69120, 72192, 68864, 5888),
+    (62464, 72192, 62208, 5888),
+]
+_UP_PINS = [
+    (8454144, 73498624, 0, 32768, 32768, 56623104, 56655872, 8421376, 65077248, 8421376),
+    (263040, 604160, 0, 32768, 32768, 110592, 143360, 230272, 373760, 230272),
+    (147904, 316928, 0, 32768, 32768, 53760, 86528, 115136, 201728, 115136),
+    (18882560, 488652800, 0, 2097152, 2097152, 452984832, 455081984, 16785408, 471867392, 16785408),
+    (16784384, 32356352, 0, 2097152, 2097152, 884736, 2981888, 14687232, 17669120, 14687232),
+    (9440768, 17214464, 0, 2097152, 2097152, 430080, 2527232, 7343616, 9870848, 7343616),
+    (303360, 21838080, 0, 2304, 2304, 21233664, 21235968, 301056, 21537024, 301056),
+    (10536, 60672, 0, 2304, 2304, 41472, 43776, 8232, 52224, 8232),
+    (6420, 31232, 0, 2304, 2304, 20160, 22528, 4116, 26880, 4116),
+]
+_NET_PINS = [1327185664, 2401791232, 119624448, 53729792]
+
+
+def test_scratch_queries_return_the_pinned_sizes():
+    """The scratch a conv layer or an up step needs is described once (csrc/scratch.h) and laid out by the plan and by each
+    per-operator entry; a size or an offset that leaves the library through a query must not move when that code is rearranged.
+    Every route class at workload and at small sizes, literal numbers."""
+    conv, up, net = _scratch_query_values()
+    assert len(conv) == len(_CONV_PINS) == len(_CONV_LAYERS) * len(_CONV_GEOS)
+    assert len(up) == len(_UP_PINS) == len(_UP_LAYERS) * len(_UP_GEOS)
+    for i, (got, want) in enumerate(zip(conv, _CONV_PINS)):
+        assert got == want, (_CONV_LAYERS[i // len(_CONV_GEOS)], _CONV_GEOS[i % len(_CONV_GEOS)])
+    for i, (got, want) in enumerate(zip(up, _UP_PINS)):
+        assert got == want, (_UP_LAYERS[i // len(_UP_GEOS)], _UP_GEOS[i % len(_UP_GEOS)])
+    assert net == _NET_PINS
