@@ -389,6 +389,32 @@ int mi3d_merge_masks3(const mi3d_mask_list* masks, int src_dtype, int64_t stride
 int mi3d_restore_labels3(const uint8_t* grid, int Dg, int Hg, int Wg, uint8_t* out, int D, int H, int W, int64_t stride_d,
                          int64_t stride_h, int64_t stride_w, const int32_t* index_d, const int32_t* index_h, const int32_t* index_w,
                          void* stream);
+/* The soft way back: the float32 vote volume (C, Dg, Hg, Wg, contiguous; mi3d_head_votes with MI3D_VOTES_KEEP) zoomed linearly onto
+ * the scan as stored and the argmax taken THERE, in one gather: scipy.ndimage.zoom(votes[k], ras_shape / grid_shape, order=1,
+ * mode='nearest', prefilter=False) per class, restated so that the bits are fixed.  Per axis, for RAS index i of n onto a grid of
+ * n_grid: z = (n_grid - 1) / (n - 1) (1.0 for n = 1), c = i * z in float64, f = floor(c), t = c - f; table row, 24 bytes:
+ *   { int32_t idx[2]; double w[2]; }   taps clip(f, 0, n_grid - 1) and clip(f + 1, 0, n_grid - 1); weights 1.0 - t and t
+ * (resample.py axis_table(n_grid, n, 1), D / H / W rows; built in RAS order and, for a flipped axis, read backwards as index_* of
+ * mi3d_restore_labels3).  The value of class k at (d, h, w) is the nested interpolation, W innermost, then H, then D, in float64,
+ * every product and every sum rounded on its own (no fused multiply-add):
+ *   r(a, b) = p[k][d_a][h_b][w_0] * ww0 + p[k][d_a][h_b][w_1] * ww1          a, b in {0, 1}
+ *   s(a)    = r(a, 0) * wh0 + r(a, 1) * wh1
+ *   v_k     = s(0) * wd0 + s(1) * wd1
+ * out (uint8) = the first maximum of v_0 .. v_{C-1} (strict `>` scan from class 0, the rule of mi3d_head_votes); confidence (float,
+ * may be NULL) = (float)v_label, the one rounding to float32.  Both are the stored tensor seen in RAS order (sides D, H, W, element
+ * strides as for mi3d_restore_labels3) and are written in its memory order for every orientation: the lanes of a wave run along the
+ * destination axis that is the grid's W, the only contiguous axis of the votes (consecutive bytes per lane where that is the stored-
+ * fastest axis, a 16-byte piece of its own row per lane, cut at aligned addresses, where it is not).  The order of operations
+ * does not depend on the layout, so a float64 numpy model of the lines above gives the same bits, ties included.  Finite votes are
+ * the contract (a NaN never wins a comparison).  C in [2, 8]; sides and strides as for mi3d_restore_labels3; out and confidence
+ * must differ from votes and from each other.  Every argument is checked before anything is launched. */
+typedef struct {
+    int32_t idx[2];
+    double w[2];
+} mi3d_lerp_row;
+int mi3d_restore_votes3(const float* votes, int C, int Dg, int Hg, int Wg, uint8_t* out, float* confidence, int D, int H, int W,
+                        int64_t stride_d, int64_t stride_h, int64_t stride_w, const mi3d_lerp_row* rows_d, const mi3d_lerp_row* rows_h,
+                        const mi3d_lerp_row* rows_w, void* stream);
 
 /* The preview figure of the reference's test loop (visualize_prediction, test_model.py:66-193, called at :299-305 on whole host
  * copies of the image, the label and the prediction) and the slider of visualize_nifti.py:29-52, computed where the volumes are.

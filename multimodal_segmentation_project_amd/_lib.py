@@ -152,6 +152,7 @@ _SIGS = {
     "mi3d_zoom3_nearest_src": (i32, [vp, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_merge_masks3": (i32, [_MP, i32, i64, i64, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp]),
     "mi3d_restore_labels3": (i32, [vp, i32, i32, i32, vp, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp]),
+    "mi3d_restore_votes3": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp]),
     "mi3d_preview_workspace_bytes": (sz, [i32, i32, i32]),
     "mi3d_foreground_profiles": (i32, [vp, i32, i32, i32, i32, i64, i64, i64, vp, vp]),
     "mi3d_best_slices": (i32, [vp, i32, i32, i32, vp, vp]),

@@ -242,6 +242,152 @@ __global__ __launch_bounds__(BLK) void restore_labels3_kernel(const uint8_t* __r
     }
 }
 
+// The soft way back: float32 votes (C, Dg, Hg, Wg) on the training grid -> the label of the trilinearly zoomed votes on the scan as
+// stored (contract: include/mi3d.h mi3d_restore_votes3).  F / M / S are the destination's axes by stride, as in
+// restore_labels3_kernel, and the output is written in memory order whatever the orientation.  FA / MA say which grid axis (0 = D,
+// 1 = H, 2 = W) F and M are: they decide which table a row comes from and which way the lanes run (below), never the arithmetic,
+// which is always in grid-axis order, W innermost, then H, then D, so the layout cannot move a bit.
+struct LerpRow {           // one destination index of one axis; layout shared with resample.py (_ROW1) and mi3d_lerp_row
+    int32_t idx[2];        // grid indices of the two taps floor(c), floor(c) + 1, each clamped to [0, n_grid - 1]
+    double w[2];           // 1 - t and t
+};
+static_assert(sizeof(LerpRow) == 24 && sizeof(mi3d_lerp_row) == 24, "table row layout");
+
+struct Tap {               // a row with its indices turned into element offsets along its grid axis
+    int64_t o0, o1;
+    double w0, w1;
+};
+__device__ __forceinline__ Tap tap_of(const LerpRow& r, int64_t gs) { return Tap{r.idx[0] * gs, r.idx[1] * gs, r.w[0], r.w[1]}; }
+
+// v_k of one output voxel: eight taps through L1 / L2, fp64.  Contraction is switched off with the pragma (not the __dmul_rn /
+// __dadd_rn intrinsics): every product and every sum below is rounded on its own, no fused multiply-add, as the numpy model does.
+__device__ __forceinline__ double lerp3(const float* __restrict__ p, const Tap& d, const Tap& h, const Tap& w) {
+#pragma clang fp contract(off)
+    const float* p00 = p + (d.o0 + h.o0);
+    const float* p01 = p + (d.o0 + h.o1);
+    const float* p10 = p + (d.o1 + h.o0);
+    const float* p11 = p + (d.o1 + h.o1);
+    const double r00 = (double)p00[w.o0] * w.w0 + (double)p00[w.o1] * w.w1;
+    const double r01 = (double)p01[w.o0] * w.w0 + (double)p01[w.o1] * w.w1;
+    const double r10 = (double)p10[w.o0] * w.w0 + (double)p10[w.o1] * w.w1;
+    const double r11 = (double)p11[w.o0] * w.w0 + (double)p11[w.o1] * w.w1;
+    const double s0 = r00 * h.w0 + r01 * h.w1;
+    const double s1 = r10 * h.w0 + r11 * h.w1;
+    return s0 * d.w0 + s1 * d.w1;
+}
+// the tap of grid axis A among those of the destination's S, M and F axes
+template <int A, int FA, int MA>
+__device__ __forceinline__ const Tap& axis_tap(const Tap& s, const Tap& m, const Tap& f) {
+    if constexpr (A == FA) return f;
+    else if constexpr (A == MA) return m;
+    else return s;
+}
+template <int FA, int MA>
+__device__ __forceinline__ double vote_at(const float* __restrict__ p, const Tap& s, const Tap& m, const Tap& f) {
+    return lerp3(p, axis_tap<0, FA, MA>(s, m, f), axis_tap<1, FA, MA>(s, m, f), axis_tap<2, FA, MA>(s, m, f));
+}
+
+// A group is VG = 4 outputs of one thread.  The classes are outermost: one running (best value, best label) per output, so the
+// first maximum under a strict `>` from class 0 falls out and the register count does not depend on C; 32 independent taps are in
+// flight.  With 16 outputs in one class loop the compiler keeps 16 rows and 128 taps live: 256 VGPRs + 136 to 256 AGPRs, one wave
+// per SIMD, and over 1 KB of scratch per lane when bounded to 128 registers; in groups of four it is 128 to 156 VGPRs, no scratch.
+constexpr int VG = 4;
+template <int FA, int MA>
+__device__ __forceinline__ void vote_group(const float* __restrict__ votes, int C, int64_t cs, const Tap& ts, const Tap& tm,
+                                           const Tap (&tf)[VG], double (&best)[VG], int (&lab)[VG]) {
+#pragma unroll
+    for (int j = 0; j < VG; j++) best[j] = vote_at<FA, MA>(votes, ts, tm, tf[j]), lab[j] = 0;
+    for (int k = 1; k < C; k++) {
+        const float* p = votes + k * cs;
+#pragma unroll
+        for (int j = 0; j < VG; j++) {
+            const double v = vote_at<FA, MA>(p, ts, tm, tf[j]);
+            if (v > best[j]) best[j] = v, lab[j] = k;
+        }
+    }
+}
+
+// Which thread does what.  Only the grid's W axis is contiguous in the votes, so the lanes of a wave run along the destination axis
+// that IS the grid's W, whichever of F, M, S that is (LA): neighbouring lanes then read neighbouring taps.
+//   F is W (LA = 0): x over (m, t), y = s; a row along F is cut in VG quarters of Q = ceil(nF / VG) and thread t owns f = t + j * Q,
+//                    j = 0 .. 3: consecutive lanes store consecutive bytes (and floats of the confidence), no head and no tail
+//   M is W (LA = 1): x over (piece, m), y = s, lanes along m; every lane owns a 16-byte piece of its own row, cut as the order-0
+//                    kernel cuts it (head to the first aligned byte, whole pieces in one store each, scalar tail)
+//   S is W (LA = 2): x over (piece, s), y = m, lanes along s; pieces as for LA = 1
+// Measured on 4 x 192^3 -> 512 x 512 x 100 with lanes along 16-byte pieces of F in EVERY layout, as the order-0 kernel has them:
+// 0.88 ms C-ordered, 2.05 ms F-ordered (every lane of a load in a line of its own), against 0.61 / 0.74 ms for interpolate + argmax
+// in torch.  That form is not in the tree, so those figures cannot be measured again from it; the rows of the form built are in
+// profiles/restore_soft_timing.txt.  A fastest axis that is not dense (oF != 1 with nF > 1) is stored an element at a time; it can
+// come through the C entry only, resample.py admits dense layouts.
+constexpr int votes_lane_axis(int FA, int MA) { return FA == 2 ? 0 : MA == 2 ? 1 : 2; }
+template <int FA, int MA, bool CONF>
+__global__ __launch_bounds__(BLK) void restore_votes3_kernel(const float* __restrict__ votes, int C, int64_t cs, uint8_t* __restrict__ out,
+                                                             float* __restrict__ conf, int nI, int nO, int nF,
+                                                             const LerpRow* __restrict__ tS, const LerpRow* __restrict__ tM,
+                                                             const LerpRow* __restrict__ tF, int64_t gS, int64_t gM, int64_t gF,
+                                                             int64_t oS, int64_t oM, int64_t oF) {
+    constexpr int LA = votes_lane_axis(FA, MA);
+    const int q = blockIdx.x * BLK + threadIdx.x;
+    if (q >= nI * nO) return;
+    const int ou = q / nI, in = q - ou * nI, y = blockIdx.y;
+    const int m = LA == 0 ? ou : LA == 1 ? in : y, s = LA == 2 ? in : y;
+    const int64_t orow = s * oS + m * oM;
+    uint8_t* o = out + orow;
+    const Tap ts = tap_of(tS[s], gS), tm = tap_of(tM[m], gM);
+    Tap tf[VG];
+    double best[VG];
+    int lab[VG];
+    if constexpr (LA == 0) {
+#pragma unroll
+        for (int j = 0; j < VG; j++) tf[j] = tap_of(tF[min(in + j * nI, nF - 1)], gF);          // past the end: the last row, never stored
+        vote_group<FA, MA>(votes, C, cs, ts, tm, tf, best, lab);
+#pragma unroll
+        for (int j = 0; j < VG; j++) {
+            const int f = in + j * nI;
+            if (f < nF) {
+                o[f * oF] = (uint8_t)lab[j];
+                if constexpr (CONF) conf[orow + f * oF] = (float)best[j];          // (float): the one rounding to fp32
+            }
+        }
+    } else {
+        const int piece = ou;
+        const int head = oF == 1 ? (int)((RW - (reinterpret_cast<uintptr_t>(o) & (RW - 1))) & (RW - 1)) : 0;
+        const int f0 = piece == 0 ? 0 : head + (piece - 1) * RW;
+        const int f1 = min(piece == 0 ? head : f0 + RW, nF);
+        if (f0 >= f1) return;
+        const bool whole = f1 - f0 == RW && oF == 1;
+        float* c = CONF ? conf + (orow + f0) : nullptr;
+        const bool cvec = whole && (reinterpret_cast<uintptr_t>(c) & 15) == 0;
+        uint32_t a[RW / VG];
+#pragma unroll
+        for (int g = 0; g < RW / VG; g++) {
+            if (f0 + VG * g >= f1) break;
+#pragma unroll
+            for (int j = 0; j < VG; j++) tf[j] = tap_of(tF[min(f0 + VG * g + j, nF - 1)], gF);
+            vote_group<FA, MA>(votes, C, cs, ts, tm, tf, best, lab);
+            a[g] = (uint32_t)lab[0] | (uint32_t)lab[1] << 8 | (uint32_t)lab[2] << 16 | (uint32_t)lab[3] << 24;
+            if (!whole) {
+#pragma unroll
+                for (int j = 0; j < VG; j++) {
+                    const int f = f0 + VG * g + j;
+                    if (f < f1) {
+                        o[f * oF] = (uint8_t)lab[j];
+                        if constexpr (CONF) conf[orow + f * oF] = (float)best[j];
+                    }
+                }
+            } else if constexpr (CONF) {
+                if (cvec) {
+                    reinterpret_cast<float4*>(c)[g] = float4{(float)best[0], (float)best[1], (float)best[2], (float)best[3]};
+                } else {
+#pragma unroll
+                    for (int j = 0; j < VG; j++) c[VG * g + j] = (float)best[j];
+                }
+            }
+        }
+        if (whole) *reinterpret_cast<uint4*>(o + f0) = uint4{a[0], a[1], a[2], a[3]};
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 struct Dims {
     int d, h, w;
@@ -348,6 +494,29 @@ int reorient3_launch(const S* in, T* out, Dims n, SrcStrides st, int flips, hipS
     MI3D_LAUNCH_CHECK();
     return 0;
 }
+
+// The walk of the two restore kernels over a destination seen in RAS order: its axes by increasing stride, an axis of one element
+// last among equals: a[0] = F, a[1] = M, a[2] = S; each with its side, destination stride, the grid's stride along it, its table
+// and which grid axis it is (0 = D, 1 = H, 2 = W).  pieces(): the 16-byte pieces of a row along F, the head included.
+template <typename T>
+struct RestoreWalk {
+    struct Axis { int n; int64_t os, gs; const T* t; int ga; };
+    Axis a[3];
+    int pieces() const { return 1 + (a[0].n + RW - 1) / RW; }
+    RestoreWalk(Dims g, Dims n, SrcStrides st, const T* td, const T* th, const T* tw)
+        : a{{n.d, st.d, (int64_t)g.h * g.w, td, 0}, {n.h, st.h, (int64_t)g.w, th, 1}, {n.w, st.w, 1, tw, 2}} {
+        auto before = [](const Axis& x, const Axis& y) { return (x.n > 1) != (y.n > 1) ? x.n > 1 : x.os < y.os; };
+        if (before(a[1], a[0])) std::swap(a[0], a[1]);
+        if (before(a[2], a[1])) std::swap(a[1], a[2]);
+        if (before(a[1], a[0])) std::swap(a[0], a[1]);
+    }
+};
+// the launch shape: x over nO * nI threads, the lanes along the nI axis, y the third axis
+int walk_grid(const char* name, int nI, int nO, int ny, dim3& grid) {
+    MI3D_CHECK_ARG((int64_t)nI * nO < (int64_t)1 << 31, "%s: output plane too large", name);
+    grid = dim3((unsigned)(((int64_t)nI * nO + BLK - 1) / BLK), (unsigned)ny);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -439,19 +608,50 @@ int mi3d_restore_labels3(const uint8_t* grid, int Dg, int Hg, int Wg, uint8_t* o
     const SrcStrides st{stride_d, stride_h, stride_w};
     MI3D_TRY(check_args("mi3d_restore_labels3", grid && out && grid != out && index_d && index_h && index_w, {Dg, Hg, Wg}, {D, H, W},
                         nullptr, &st));
-    // the destination's axes by increasing stride, an axis of one element last among equals: a[0] = F, a[1] = M, a[2] = S
-    struct Axis { int n; int64_t os, gs; const int32_t* t; };
-    Axis a[3] = {{D, stride_d, (int64_t)Hg * Wg, index_d}, {H, stride_h, (int64_t)Wg, index_h}, {W, stride_w, 1, index_w}};
-    auto before = [](const Axis& x, const Axis& y) { return (x.n > 1) != (y.n > 1) ? x.n > 1 : x.os < y.os; };
-    if (before(a[1], a[0])) std::swap(a[0], a[1]);
-    if (before(a[2], a[1])) std::swap(a[1], a[2]);
-    if (before(a[1], a[0])) std::swap(a[0], a[1]);
-    const Axis &F = a[0], &M = a[1], &S = a[2];
-    const int FQ = 1 + (F.n + RW - 1) / RW;
-    MI3D_CHECK_ARG((int64_t)M.n * FQ < (int64_t)1 << 31, "mi3d_restore_labels3: output plane too large");
-    dim3 grd((unsigned)(((int64_t)M.n * FQ + BLK - 1) / BLK), (unsigned)S.n);
-    restore_labels3_kernel<<<grd, BLK, 0, (hipStream_t)stream>>>(grid, out, M.n, F.n, FQ, S.t, M.t, F.t, S.gs, M.gs, F.gs, S.os, M.os,
+    const RestoreWalk<int32_t> k({Dg, Hg, Wg}, {D, H, W}, st, index_d, index_h, index_w);
+    const auto &F = k.a[0], &M = k.a[1], &S = k.a[2];
+    dim3 grd;
+    MI3D_TRY(walk_grid("mi3d_restore_labels3", k.pieces(), M.n, S.n, grd));
+    restore_labels3_kernel<<<grd, BLK, 0, (hipStream_t)stream>>>(grid, out, M.n, F.n, k.pieces(), S.t, M.t, F.t, S.gs, M.gs, F.gs, S.os, M.os,
                                                                  F.n > 1 ? F.os : 1);
+    MI3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int mi3d_restore_votes3(const float* votes, int C, int Dg, int Hg, int Wg, uint8_t* out, float* confidence, int D, int H, int W,
+                        int64_t stride_d, int64_t stride_h, int64_t stride_w, const mi3d_lerp_row* rows_d, const mi3d_lerp_row* rows_h,
+                        const mi3d_lerp_row* rows_w, void* stream) {
+    const char* name = "mi3d_restore_votes3";
+    const SrcStrides st{stride_d, stride_h, stride_w};
+    const void *v = votes, *o = out, *c = confidence;
+    MI3D_TRY(check_args(name, v && o && v != o && v != c && o != c && rows_d && rows_h && rows_w, {Dg, Hg, Wg}, {D, H, W}, nullptr, &st));
+    MI3D_CHECK_ARG(C >= 2 && C <= 8, "%s: %d classes, 2 to 8 are supported (the range of the head kernels)", name, C);
+    const RestoreWalk<LerpRow> k({Dg, Hg, Wg}, {D, H, W}, st, (const LerpRow*)rows_d, (const LerpRow*)rows_h, (const LerpRow*)rows_w);
+    const auto &F = k.a[0], &M = k.a[1], &S = k.a[2];
+    const int lane = votes_lane_axis(F.ga, M.ga);
+    const int nI = lane == 0 ? (F.n + VG - 1) / VG : lane == 1 ? M.n : S.n, nO = lane == 0 ? M.n : k.pieces();
+    dim3 grd;
+    MI3D_TRY(walk_grid(name, nI, nO, lane == 2 ? M.n : S.n, grd));
+    const int64_t cs = (int64_t)Dg * Hg * Wg;
+    auto launch = [&](auto kernel) {
+        kernel<<<grd, BLK, 0, (hipStream_t)stream>>>(votes, C, cs, out, confidence, nI, nO, F.n, S.t, M.t, F.t, S.gs, M.gs, F.gs, S.os,
+                                                        M.os, F.n > 1 ? F.os : 1);
+    };
+    auto pick = [&](auto fa, auto ma) {
+        constexpr int FA = decltype(fa)::value, MA = decltype(ma)::value;
+        launch(confidence ? restore_votes3_kernel<FA, MA, true> : restore_votes3_kernel<FA, MA, false>);
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    switch (F.ga * 3 + M.ga) {
+        case 1: pick(I0(), I1()); break;
+        case 2: pick(I0(), I2()); break;
+        case 3: pick(I1(), I0()); break;
+        case 5: pick(I1(), I2()); break;
+        case 6: pick(I2(), I0()); break;
+        default: pick(I2(), I1()); break;
+    }
     MI3D_LAUNCH_CHECK();
     return 0;
 }

@@ -14,6 +14,8 @@ scaling) stays outside: callers pass the decoded array as it is stored, and its 
   resample_scan(image, affine, ...)        the whole per-scan body: (image on the grid, label or None, output affine)
   merge_masks_to_grid(masks, affine, ...)  the label of resample_scan(masks=...) alone
   restore_labels(labels, affine, stored)   the way back: uint8 labels on the grid put onto the scan as stored (one order-0 gather)
+  restore_labels_soft(votes, affine, stored)  the soft way back: float32 class votes on the grid zoomed linearly (order 1) onto
+                                           the scan as stored and the argmax taken there, in one gather
 
 A stored scan is any dense 3-D device tensor: a permutation of a contiguous array, such as the tensor made from nibabel's
 Fortran-ordered array without a host copy; int16 / uint8 / float32 images, uint8 / int16 / int64 labels, uint8 / float32 masks.
@@ -35,6 +37,9 @@ from ._lib import Mi3dError, call, ptr, stream_ptr
 # one row of a cubic table as the kernel reads it (csrc/resample.hip CubicRow, include/mi3d.h)
 _ROW = np.dtype([("idx", "<i4", (4,)), ("w", "<f8", (4,))])
 assert _ROW.itemsize == 48
+# one row of a linear table (csrc/resample.hip LerpRow, include/mi3d.h mi3d_lerp_row)
+_ROW1 = np.dtype([("idx", "<i4", (2,)), ("w", "<f8", (2,))])
+assert _ROW1.itemsize == 24
 
 TABLE_CACHE_SIZE = 256     # device tables kept (least recently used first out); one chain with labels uses at most 9
 _device_tables = collections.OrderedDict()     # (n_in, order or kind, output side(s), device, flipped) -> device tensor
@@ -71,6 +76,7 @@ def axis_table(n_in, n_out, order, flip=False):
     """Host tables of one axis, one row per output index.
     order 0: int32 (n_out,) input index floor(c + 0.5), clamped.
     order 3: (int32 (n_out, 4) tap indices floor(c) - 1 .. floor(c) + 2, each clamped; float64 (n_out, 4) B-spline weights).
+    order 1: (int32 (n_out, 2) tap indices floor(c), floor(c) + 1, each clamped; float64 (n_out, 2) weights 1 - t, t).
     flip: the axis is stored reversed: the finished indices i become n_in - 1 - i, the weights stay."""
     n_in, n_out = int(n_in), int(n_out)
     if n_in < 1 or n_out < 1:
@@ -78,10 +84,13 @@ def axis_table(n_in, n_out, order, flip=False):
     cc = _coords(n_in, n_out)
     if order == 0:
         return _flipped(np.clip(np.floor(cc + 0.5), 0, n_in - 1).astype(np.int32), n_in, flip)
-    if order != 3:
-        raise Mi3dError(f"axis_table: order {order} is not supported (3 = cubic B-spline, 0 = nearest)")
+    if order not in (1, 3):
+        raise Mi3dError(f"axis_table: order {order} is not supported (3 = cubic B-spline, 1 = linear, 0 = nearest)")
     f = np.floor(cc)
     t = cc - f
+    if order == 1:
+        idx = np.clip(f[:, None] + np.arange(0.0, 2.0)[None, :], 0, n_in - 1).astype(np.int32)
+        return _flipped(idx, n_in, flip), np.stack([1.0 - t, t], axis=1)
     idx = np.clip(f[:, None] + np.arange(-1.0, 3.0)[None, :], 0, n_in - 1).astype(np.int32)
     w = np.stack([(1.0 - t) ** 3 / 6.0,
                   (3.0 * t ** 3 - 6.0 * t ** 2 + 4.0) / 6.0,
@@ -117,6 +126,13 @@ def cubic_rows(n_in, n_out, flip=False):
     return rows
 
 
+def linear_rows(n_in, n_out, flip=False):
+    """The order-1 table of one axis in the kernel's row format."""
+    rows = np.zeros(int(n_out), dtype=_ROW1)
+    rows["idx"], rows["w"] = axis_table(n_in, n_out, 1, flip)
+    return rows
+
+
 def composed_index_table(n_in, n_mid, n_out, flip=False):
     """Two order-0 zooms along one axis as ONE gather: table1[table2]; both built in RAS order, the result remapped for a flip."""
     return _flipped(compose_index_tables(axis_table(n_in, n_mid, 0), axis_table(n_mid, n_out, 0)), n_in, flip)
@@ -127,12 +143,15 @@ def _host_table(n_in, sides, order, flip):
         return cubic_rows(n_in, *sides, flip)
     if order == "restore":
         return _restore_table(n_in, *sides, flip)
+    if order == "restore1":
+        return _restore_table(n_in, *sides, flip, linear_rows)
     return composed_index_table(n_in, *sides, flip) if len(sides) == 2 else axis_table(n_in, *sides, 0, flip)
 
 
 def _device_table(n_in, n_out, order, device, flip=False):
     """The device table of one axis, through the cache.  order 3: cubic rows; order 0: nearest indices, or for n_out =
-    (n_mid, n_out) the composed ones; order "restore": restore_labels' table from a grid of n_in onto n_out."""
+    (n_mid, n_out) the composed ones; order "restore": restore_labels' table from a grid of n_in onto n_out; "restore1":
+    restore_labels_soft's linear rows."""
     sides = n_out if isinstance(n_out, tuple) else (int(n_out),)
     return _cached((int(n_in), order, *sides, device, bool(flip)), lambda: _host_table(n_in, sides, order, flip), device)
 
@@ -484,9 +503,14 @@ def resample_scan(image, affine, label=None, masks=None, target_spacing=(1.0, 1.
 
 
 # ---- labels from the grid back onto the scan as stored -------------------------------------------------------------------------
-def _restore_table(n_grid, n_ras, flip):
-    """Not _flipped: here the flipped axis is the OUTPUT's, so the table is read backwards and its values (grid indices) stay."""
-    t = axis_table(n_grid, n_ras, 0)
+def _nearest_rows(n_grid, n_ras):
+    return axis_table(n_grid, n_ras, 0)
+
+
+def _restore_table(n_grid, n_ras, flip, rows=_nearest_rows):
+    """Not _flipped: here the flipped axis is the OUTPUT's, so the table is read backwards and its values (grid indices, and the
+    weights of linear_rows) stay."""
+    t = rows(n_grid, n_ras)
     return np.ascontiguousarray(t[::-1]) if flip else t
 
 
@@ -501,6 +525,19 @@ def restore_tables(grid_shape, affine, shape, strides, what="restore_labels"):
     return dst.shape, dst.strides, [_restore_table(g, n, f) for g, n, f in zip(grid_shape, dst.shape, dst.flips)]
 
 
+def _stored_layout(stored, source, what, kind):
+    """(shape, strides) of `stored`: the stored tensor (which must be on the device of `source`, the `kind` on the grid) or a pair."""
+    if isinstance(stored, torch.Tensor):
+        if stored.device != source.device:
+            raise Mi3dError(f"{what}: the stored scan is on {stored.device}, the {kind} on {source.device}")
+        return tuple(stored.shape), tuple(stored.stride())
+    try:
+        shape, strides = (tuple(int(v) for v in part) for part in stored)
+    except (TypeError, ValueError):
+        raise Mi3dError(f"{what}: `stored` is the stored tensor or a (shape, strides) pair, got {stored!r}") from None
+    return shape, strides
+
+
 def restore_labels(labels, affine, stored):
     """A uint8 (Dg, Hg, Wg) label map on the training grid put back onto the scan as stored: scipy.ndimage.zoom(labels,
     ras_shape / grid_shape, order=0, mode='nearest', prefilter=False) (one zoom: the intermediate shape of the inbound chain
@@ -513,15 +550,7 @@ def restore_labels(labels, affine, stored):
         raise Mi3dError(f"{what}: one 3-D label map (Dg, Hg, Wg) expected, got {tuple(getattr(labels, 'shape', ()))}")
     if labels.dtype != torch.uint8:
         raise Mi3dError(f"{what}: the label map is uint8 (segment.predict_labels' output), got {labels.dtype}")
-    if isinstance(stored, torch.Tensor):
-        shape, strides = tuple(stored.shape), tuple(stored.stride())
-        if stored.device != labels.device:
-            raise Mi3dError(f"{what}: the stored scan is on {stored.device}, the labels on {labels.device}")
-    else:
-        try:
-            shape, strides = (tuple(int(v) for v in part) for part in stored)
-        except (TypeError, ValueError):
-            raise Mi3dError(f"{what}: `stored` is the stored tensor or a (shape, strides) pair, got {stored!r}") from None
+    shape, strides = _stored_layout(stored, labels, what, "labels")
     dst = _Stored.of_layout(shape, strides, affine, what)
     _lib.require_cuda(labels, what)
     # everything is checked: launch
@@ -532,3 +561,38 @@ def restore_labels(labels, affine, stored):
     call("mi3d_restore_labels3", ptr(grid), *grid.shape, ptr(out), *dst.shape, *dst.strides, ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]),
          stream_ptr())
     return out
+
+
+MIN_CLASSES, MAX_CLASSES = 2, 8      # what the head kernels and mi3d_restore_votes3 accept
+
+
+def restore_labels_soft(votes, affine, stored, confidence=False):
+    """A float32 (C, Dg, Hg, Wg) vote volume on the training grid (segment.predict_labels_ensemble(..., votes=True); a leading
+    batch axis of 1 is dropped) put back onto the scan as stored: per class scipy.ndimage.zoom(votes[k], ras_shape / grid_shape,
+    order=1, mode='nearest', prefilter=False), the first maximum over the classes on the DESTINATION grid, then the inverse of
+    reorient_to_ras, as ONE gather that writes the stored layout in memory order.  The interpolation is nested, W innermost,
+    then H, then D, in float64 with every product and sum rounded on its own (include/mi3d.h mi3d_restore_votes3), so the bits
+    do not depend on the orientation or the layout.  `stored` and `affine` as for restore_labels.  Returns a uint8 tensor with the
+    stored shape and strides; with confidence=True also the float32 tensor of that layout holding the winning class's
+    interpolated vote.  Every check runs before the first launch."""
+    what = "restore_labels_soft"
+    if isinstance(votes, torch.Tensor) and votes.dim() == 5 and votes.shape[0] == 1:
+        votes = votes[0]
+    if not isinstance(votes, torch.Tensor) or votes.dim() != 4 or min(votes.shape) < 1:
+        raise Mi3dError(f"{what}: one 4-D vote volume (C, Dg, Hg, Wg) expected, got {tuple(getattr(votes, 'shape', ()))}")
+    if votes.dtype != torch.float32:
+        raise Mi3dError(f"{what}: the vote volume is float32 (segment.predict_labels_ensemble's votes), got {votes.dtype}")
+    if not MIN_CLASSES <= votes.shape[0] <= MAX_CLASSES:
+        raise Mi3dError(f"{what}: {votes.shape[0]} classes, {MIN_CLASSES} to {MAX_CLASSES} are supported (the range of the head kernels)")
+    shape, strides = _stored_layout(stored, votes, what, "votes")
+    dst = _Stored.of_layout(shape, strides, affine, what)
+    _lib.require_cuda(votes, what)
+    # everything is checked: launch
+    vol = votes.contiguous()
+    dev = vol.device
+    tabs = [_device_table(g, n, "restore1", dev, f) for g, n, f in zip(vol.shape[1:], dst.shape, dst.flips)]
+    out = torch.empty_strided(shape, strides, dtype=torch.uint8, device=dev)
+    conf = torch.empty_strided(shape, strides, dtype=torch.float32, device=dev) if confidence else None
+    call("mi3d_restore_votes3", ptr(vol), *vol.shape, ptr(out), ptr(conf), *dst.shape, *dst.strides, ptr(tabs[0]), ptr(tabs[1]),
+         ptr(tabs[2]), stream_ptr())
+    return (out, conf) if confidence else out

@@ -4,7 +4,9 @@ test_model.py:242-309 (model(image), torch.argmax(outputs, dim=1), the per-sampl
   predict_labels(model, x, target=None)         uint8 (N, D, H, W) label map, and with a target the exact per-sample counts
   predict_labels_ensemble(models, x, flips)     the label map of the softmax average over mirrored views and / or several models
   per_sample_dice_iou(counts, classes)          [{class: (dice, iou)}] per sample from those counts (test_model.py:265-276)
-  segment_scan(model, image, affine, dataset)   a scan as stored -> its label map as stored: resample, predict, restore
+  segment_scan(model, image, affine, dataset)   a scan as stored -> its label map as stored: resample, predict, restore; the restore
+                                                is the order-0 gather of the label map ("nearest") or, from the votes, the order-1
+                                                zoom per class with the argmax on the stored grid ("linear", restore_labels_soft)
 
 The logits never reach memory: the network runs with logits = NULL (mi3d_unet_infer) and the 1x1x1 head, the argmax and the counts
 are one pass over the decoder output (mi3d_unet_head_labels), which writes 1 byte per voxel where the logits route writes 16 and
@@ -13,7 +15,8 @@ are preview.prediction_panels' work, on the device as well.  Test-time flips (th
 and model ensembles vote in the same place: per view one pass over the decoder output does head -> softmax -> add into a
 float32 vote volume at the mirrored voxel (mi3d_unet_head_votes), and the last view's pass ends in the argmax, so neither the
 logits nor the probabilities of a view are ever written.  File reading / writing, drawing (matplotlib) and sliding windows
-(every scan is squeezed onto the training grid, so there is no window to slide) stay outside.
+(every scan is squeezed onto the training grid, so there is no window to slide) stay outside.  So do, for the soft restore:
+several scans per call, per-class counts against a ground truth on the stored grid, and zoom orders other than 1 and 0.
 """
 import torch
 
@@ -153,8 +156,11 @@ def per_sample_dice_iou(counts, classes=(1, 2, 3)):
     return [metrics.dice_iou_from_counts(r, len(r) // 3, classes) for r in rows]
 
 
+RESTORE_MODES = ("nearest", "linear")
+
+
 def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192), keep_largest=None,
-                 connectivity=1, flips=None, models=None):
+                 connectivity=1, flips=None, models=None, restore="nearest"):
     """A decoded scan AS STORED and its 4x4 affine -> (uint8 labels with the scan's shape and strides, uint8 labels on the
     training grid, affine of the grid).  A composition only: resample.resample_scan (CT window fused into the last store for
     '_ct' names, preprocess.preprocess_mri afterwards otherwise: the dispatch of preprocess.preprocess), predict_labels,
@@ -162,12 +168,28 @@ def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1
     cleaned by components.keep_largest (with `connectivity`) before it is restored, the second element is the cleaned grid map
     and a fourth, the Cleaned record (stats, status), is appended.  None: no cleaning, three elements.
     flips / models: with either, the grid map is predict_labels_ensemble's over `models` (default: the model) and `flips` (default
-    NO_FLIP), e.g. flips=FLIPS8 for mirroring on all three axes; with both None it is predict_labels', bit for bit as before."""
+    NO_FLIP), e.g. flips=FLIPS8 for mirroring on all three axes; with both None it is predict_labels', bit for bit as before.
+    restore: "nearest" (the default) is the route above.  "linear" restores from the probabilities: the grid prediction is
+    predict_labels_ensemble(models or the model, flips or NO_FLIP, votes=True) and the stored map is
+    resample.restore_labels_soft of its votes (order-1 zoom per class, argmax on the stored grid), so organ boundaries are not the
+    staircase of an upsampled label map.  keep_largest then cleans the STORED map, after the restore: the first element is the
+    cleaned stored map, the second the UNCLEANED grid map, and the Cleaned record describes the stored map.  Any other value
+    raises before anything is launched."""
+    if restore not in RESTORE_MODES:
+        raise Mi3dError(f"segment_scan: restore is one of {RESTORE_MODES}, got {restore!r}")
     ct = dataset_name.lower().endswith("_ct")
     grid, _, grid_affine = resample.resample_scan(image, affine, target_spacing=target_spacing, target_shape=target_shape,
                                                   ct_window=CT_WINDOW if ct else None)
     if not ct:
         grid = preprocess.preprocess_mri(grid)
+    if restore == "linear":
+        on_grid, votes = predict_labels_ensemble(model if models is None else models, grid[None, None],
+                                                 flips=NO_FLIP if flips is None else flips, votes=True)
+        stored = resample.restore_labels_soft(votes, affine, image)
+        if keep_largest is None:
+            return stored, on_grid[0], grid_affine
+        cleaned = components.keep_largest(stored, keep=keep_largest, connectivity=connectivity)
+        return cleaned.labels, on_grid[0], grid_affine, cleaned
     if flips is None and models is None:
         on_grid = predict_labels(model, grid[None, None])[0]
     else:

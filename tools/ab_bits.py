@@ -399,6 +399,13 @@ def battery(only=None):
                         put(f"{tag}/reorient{shape}/{order}/{np.dtype(sdt).name}", got)
                 grid = torch.from_numpy(rng.integers(0, 16, targets[0], dtype=np.uint8)).to(dev)
                 put(f"{tag}/restore/{order}", resample.restore_labels(grid, aff, store(image, order)))
+                if "mi3d_restore_votes3" in _lib._SIGS:          # the soft restore of 4-class votes on that grid; a build without it has no rows
+                    lg = np.random.default_rng(5).standard_normal((4,) + targets[0]) * 2.0
+                    e = np.exp(lg - lg.max(axis=0, keepdims=True))
+                    votes = torch.from_numpy((e / e.sum(axis=0, keepdims=True)).astype(np.float32)).to(dev)
+                    soft, conf = resample.restore_labels_soft(votes, aff, store(image, order), confidence=True)
+                    put(f"{tag}/restore_soft/{order}/labels", soft)
+                    put(f"{tag}/restore_soft/{order}/confidence", conf)
 
     resample_ops()
     labelmap_ops()
