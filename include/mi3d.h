@@ -575,6 +575,51 @@ int mi3d_surface_distances(const void* pred, int pred_dtype, int64_t pred_stride
 int mi3d_plane_affine(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W,
                       int ax0, int ax1, const double* matrix, const double* offset, int flip_mask, void* stream);
 
+/* Affine + elastic spatial augmentation of ONE sample: the MONAI RandAffined / Rand3DElasticd block that combined_transform() lists
+ * and leaves commented out (utils/dataloader.py:227-248), as one smoothed random displacement field and one gather that reads image
+ * and label through the same coordinates (spatial.py draws the parameters).
+ *
+ * mi3d_elastic_field writes the float32 field u (3, D, H, W); component a displaces along axis a of (D, H, W).  V = D*H*W, idx the
+ * C-order voxel index:
+ *   noise   r = mix64a(mix64a(seed) ^ (uint64)(a*V + idx)), k = r >> 40, noise = (float)((int)k - 2^23) * 2^-23: an exact dyadic in
+ *           [-1, 1), never stored
+ *   taps    a HOST table of 2*radius + 1 doubles, taps[j + radius] = g[j], read before the call returns; radius <=
+ *           MI3D_ELASTIC_MAX_RADIUS.  (MONAI's GaussianFilter(sigma, truncated=3.0, approx="erf") table: spatial.gaussian_taps)
+ *   smooth  three separable passes in the order W, H, D, zeros beyond the volume: out[i] = sum over j of g[j] * (double)src[i + j]
+ *           (scipy.ndimage.correlate1d(mode='constant', cval=0)), a float64 sum in ascending j, every product and sum rounded on its
+ *           own (no FMA), taps beyond the volume skipped; each pass rounds once to float32
+ * workspace: mi3d_elastic_workspace_bytes(D, H, W), 16-byte aligned, not the field.  Negative return: null pointers, non-positive
+ * sizes, more than 2^31 - 1 field values, radius outside 0..MI3D_ELASTIC_MAX_RADIUS, workspace too small.
+ *
+ * mi3d_warp3 gathers img_out (C, Do, Ho, Wo) float32 and lab_out (C, Do, Ho, Wo) int64 from img_in / lab_in (C, D, H, W), all
+ * contiguous; either pair may be NULL; in != out.  matrix (3x3, row-major) and translate (3) are HOST doubles, read before the call
+ * returns; field is NULL or a device (3, Do, Ho, Wo) float32 field on the OUTPUT grid.  Per output voxel o, with n = (D, H, W) and
+ * no = (Do, Ho, Wo), in IEEE double, every operation rounded on its own (no FMA), in this order:
+ *   c_a = (double)o_a - (no_a - 1)/2
+ *   p_a = c_a + magnitude * (double)u_a[o]                  (field NULL: p_a = c_a)
+ *   s_a = ((M[a][0]*p_0 + M[a][1]*p_1) + M[a][2]*p_2) + ((n_a - 1)/2 + t_a)
+ * M maps output coordinates to sampling coordinates (a pull), both voxel-centred about the middle of their grid.
+ *   outside  any s_a that is not 0 <= s_a <= n_a - 1 (so a NaN coordinate is outside), decided first; then every s_a is clamped to
+ *            [0, n_a - 1], a NaN to 0
+ *   image    f_a = floor(s_a), t_a = s_a - f_a, upper tap min(f_a + 1, n_a - 1); the W level lo*(1 - t) + hi*t on the four (d, h) rows,
+ *            then H, then D, in double; one rounding to float32   (scipy.ndimage.map_coordinates(order=1))
+ *   label    the voxel floor(s_a + 0.5) per axis, value copied         (order=0)
+ *   padding  MI3D_PAD_BORDER: as above (scipy mode='nearest'); MI3D_PAD_ZEROS: 0 where outside, as above elsewhere (mode='constant',
+ *            cval=0); one mode each for image and label
+ * Every channel uses the same coordinates.  No index outside the input is formed: a NaN coordinate reads voxel 0 under
+ * MI3D_PAD_BORDER and gives 0 under MI3D_PAD_ZEROS.  Allocates nothing,
+ * does not synchronise.  Negative return: null matrix / translate, a pair with only one of in / out, aliased in / out, non-positive
+ * sizes, more than 2^31 - 1 voxels in a volume, an unknown padding mode. */
+#define MI3D_ELASTIC_MAX_RADIUS 32      /* covers sigma <= 10.5 of the truncated=3.0 table */
+#define MI3D_PAD_BORDER 0
+#define MI3D_PAD_ZEROS 1
+size_t mi3d_elastic_workspace_bytes(int D, int H, int W);
+int mi3d_elastic_field(float* field, int D, int H, int W, uint64_t seed, const double* taps, int radius, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int mi3d_warp3(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do, int Ho,
+               int Wo, const double* matrix, const double* translate, const float* field, double magnitude, int image_padding,
+               int label_padding, void* stream);
+
 /* Training-set augmentation, combined_transform() (utils/dataloader.py:223-262, used at train_unet.py:361): the
  * arithmetic of MONAI's RandBiasField -> RandGaussianNoise -> RandAdjustContrast -> RandHistogramShift ->
  * RandCoarseDropout on one (C, D, H, W) float volume, with the random parameters already drawn by the host

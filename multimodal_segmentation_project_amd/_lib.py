@@ -45,6 +45,8 @@ PREVIEW_STACK, PREVIEW_ONE, PREVIEW_THREE = 0, 1, 2      # mi3d_slice_minmax / m
 OVERLAY_F64, OVERLAY_F32, OVERLAY_U8 = 0, 1, 2
 COMPONENTS_TILE, COMPONENTS_MAX_CLASSES, COMPONENTS_MAX_KEEP = 8, 8, 8      # MI3D_COMPONENTS_*
 SURFACE_MAX_TOLERANCES, SURFACE_COUNT_COLUMNS, SURFACE_TABLE_COLUMNS = 4, 10, 8      # MI3D_SURFACE_*
+ELASTIC_MAX_RADIUS = 32                            # MI3D_ELASTIC_MAX_RADIUS
+PAD_BORDER, PAD_ZEROS = 0, 1                       # MI3D_PAD_*
 
 
 class MaskList(C.Structure):                       # mi3d_mask_list
@@ -169,6 +171,10 @@ _SIGS = {
     "mi3d_surface_distances": (i32, [vp, i32, i64, i64, i64, i64, vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double, i32, C.POINTER(C.c_double), vp, vp, vp, sz, vp]),
     "mi3d_plane_affine": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp]),
+    "mi3d_elastic_workspace_bytes": (sz, [i32, i32, i32]),
+    "mi3d_elastic_field": (i32, [vp, i32, i32, i32, C.c_uint64, C.POINTER(C.c_double), i32, vp, sz, vp]),
+    "mi3d_warp3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp,
+                         C.c_double, i32, i32, vp]),
     "mi3d_augment_workspace_bytes": (sz, []),
     "mi3d_augment": (i32, [vp, vp, vp, i32, i32, i32, i32, _AP, vp, sz, vp]),
     "mi3d_fill_boxes_i64": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64, vp]),

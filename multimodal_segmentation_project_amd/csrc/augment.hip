@@ -9,6 +9,7 @@
 // prologue (deterministic, no atomics, no finalize launch).  Only when the first active transform is contrast / hist
 // does a read-only min/max pass run first.  Worst case (all five drawn): 3 reads + 3 writes of the volume.
 #include "ops.h"
+#include "rng.h"
 #include "../../include/mi3d.h"
 
 namespace {
@@ -18,12 +19,6 @@ constexpr int MAXBLK = 2048;
 struct VolGeo { int C, D, H, W; int64_t n; };
 struct Stage { int bias, noise, contrast, hist, holes, write, emit, stats_in, uniform_cp; };
 
-__device__ __forceinline__ uint64_t mix64a(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ float wave_minf(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
