@@ -268,6 +268,42 @@ int mi3d_head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, 
 int mi3d_unet_head_votes(const mi3d_unet_desc* d, const void* const* params, int flip, int view, int views, int flags, float* votes,
                          uint8_t* labels_out, float* confidence, const int64_t* target, int64_t* counts, void* head_workspace,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* Sliding-window inference (the network sees windows of the size it was trained on; overlapping predictions are blended with an
+ * importance map): the vote pass of mi3d_head_votes for N WINDOW samples of sides d x h x w, each added, weighted, into a sub-box of
+ * ONE accumulator acc float (Cout,D,H,W), contiguous, D * H * W < 2^31.  Operands z, zcs, Cin, w, bias, Cout, dtype as for
+ * mi3d_head_votes (z holds the N samples one after another).  Host arrays, read at call time: flips (N codes; bit 0 mirrors W,
+ * bit 1 H, bit 2 D, WITHIN the window) and origins (N x 3 ints {od, oh, ow}).  Device float tables g_d (d), g_h (h), g_w (w).
+ * For sample n = 0 .. N - 1 in that order, for every window voxel x = (xd, xh, xw):
+ *     p        = softmax over the classes, in float32, of the logits mi3d_conv1_forward gives (bit for bit), flipped back
+ *     weight   = (g_d[xd] * g_h[xh]) * g_w[xw]                      float32, each product rounded on its own
+ *     acc[c][o + x] = acc[c][o + x] + weight * p[c]                 the product rounded, then the sum: never contracted
+ * The samples of a call may overlap in acc; the result is that of one call per sample in sample order (one launch per sample on
+ * the stream).  One thread owns a voxel and nothing is atomic: the same inputs give the same bits.  The caller clears acc
+ * (0 + x is exact).  16-byte plane accesses are taken where W, w and the origin's ow are multiples of 4, the one-voxel route
+ * elsewhere; both give the same bits.  Every argument is checked before anything is launched (every origin + window inside the
+ * volume, Cout <= 8, non-NULL tables, D * H * W < 2^31, flip codes in [0, 8)): a bad call leaves acc untouched.
+ * mi3d_unet_head_votes_window runs it on the decoder output that the last mi3d_unet_infer with logits = NULL left in `workspace`:
+ * N and the window are the descriptor's.
+ *
+ * mi3d_votes_finish turns the weighted totals into the outputs of mi3d_head_votes' last view.  n_d (D), n_h (H), n_w (W): device
+ * float tables, n_axis[i] = the float32 rounding of the float64 sum of that axis's importance-table entries over the windows that
+ * cover index i (the windows form a tensor grid, so the weight sum of a voxel factorises).  Per voxel (xd, xh, xw):
+ *     labels_out uint8 (D,H,W) = the first maximum of acc over the classes (strict `>` scan from class 0)
+ *     norm       = ((n_d[xd] * n_h[xh]) * n_w[xw]) * (float)views_per_window        float32, each product rounded on its own
+ *     confidence float (D,H,W), optional = acc[label] / norm                        IEEE division
+ *     with MI3D_VOTES_NORMALIZE in `flags`: acc[c] = acc[c] / norm in place, the mean probabilities (IEEE division)
+ *     target int64 (D*H*W) / counts int64 (3*Cout + 1) / workspace (mi3d_head_votes_workspace_bytes(1, Cout)) as for mi3d_head_votes
+ * Every argument is checked before anything is launched. */
+#define MI3D_VOTES_NORMALIZE 1
+int mi3d_head_votes_window(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int d, int h,
+                           int wd, const int* flips, const float* g_d, const float* g_h, const float* g_w, const int* origins, float* acc,
+                           int D, int H, int W, void* stream);
+int mi3d_unet_head_votes_window(const mi3d_unet_desc* d, const void* const* params, const int* flips, const float* g_d, const float* g_h,
+                                const float* g_w, const int* origins, float* acc, int D, int H, int W, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int mi3d_votes_finish(float* acc, int Cout, int D, int H, int W, const float* n_d, const float* n_h, const float* n_w,
+                      int views_per_window, int flags, uint8_t* labels_out, float* confidence, const int64_t* target, int64_t* counts,
+                      void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DANN head.  Replaces train_dann.py:34-49 (DomainDiscriminator MLP 256-256-128-64-2, ReLU, Dropout 0.2) and

@@ -59,6 +59,7 @@ class Conv3BnRoute(C.Structure):                   # mi3d_conv3_bn_route
 
 CONV3_BN_KEEP_TICKETS = 1
 VOTES_KEEP = 1                                     # MI3D_VOTES_KEEP
+VOTES_NORMALIZE = 1                                # MI3D_VOTES_NORMALIZE (mi3d_votes_finish)
 
 
 class Conv3InferRoute(C.Structure):                # mi3d_conv3_infer_route
@@ -85,6 +86,7 @@ class UpRoute(C.Structure):                        # mi3d_up_route
 UP_BWD_LEAVE_PENDING, UP_BWD_SECOND_WORKSPACE = 1, 2
 
 _DP, _LP, _AP, _MP = C.POINTER(UNetDesc), C.POINTER(LossCfg), C.POINTER(AugParams), C.POINTER(MaskList)
+_IP = C.POINTER(C.c_int32)                         # a host array of ints read at call time (int_table)
 
 # name -> (restype, argtypes); one line per symbol declared in include/mi3d.h
 _SIGS = {
@@ -135,6 +137,9 @@ _SIGS = {
     "mi3d_head_votes_workspace_bytes": (sz, [i32, i32]),
     "mi3d_head_votes": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "mi3d_unet_head_votes": (i32, [_DP, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi3d_head_votes_window": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, _IP, vp, vp, vp, _IP, vp, i32, i32, i32, vp]),
+    "mi3d_unet_head_votes_window": (i32, [_DP, vp, _IP, vp, vp, vp, _IP, vp, i32, i32, i32, vp, sz, vp]),
+    "mi3d_votes_finish": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mi3d_linear_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "mi3d_linear_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp]),
     "mi3d_scale": (i32, [vp, vp, i64, f32, vp, vp]),
@@ -316,6 +321,11 @@ def ptr_table(ptrs):
     """Host array of device pointers (void* const*)."""
     arr = (C.c_void_p * len(ptrs))(*[p if p else None for p in ptrs])
     return arr
+
+
+def int_table(values):
+    """Host array of C ints (const int*), e.g. the flip codes and the flattened origins of mi3d_head_votes_window."""
+    return (C.c_int32 * len(values))(*[int(v) for v in values])
 
 
 def dtype_code(dt):

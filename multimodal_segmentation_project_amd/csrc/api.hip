@@ -102,6 +102,20 @@ int mi3d_head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, 
     return head_votes(dtype, z, zcs, Cin, w, bias, Cout, N, D, H, W, flip, view, views, flags, votes, labels_out, confidence, target,
                       counts, workspace, (hipStream_t)stream);
 }
+int mi3d_head_votes_window(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int d, int h,
+                           int wd, const int* flips, const float* g_d, const float* g_h, const float* g_w, const int* origins, float* acc,
+                           int D, int H, int W, void* stream) {
+    MI3D_CHECK_ARG(z && w, "mi3d_head_votes_window: null pointer");
+    MI3D_CHECK_ARG(dtype == MI3D_F32 || dtype == MI3D_BF16, "mi3d_head_votes_window: bad dtype %d", dtype);
+    return head_votes_window(dtype, z, zcs, Cin, w, bias, Cout, N, d, h, wd, flips, g_d, g_h, g_w, origins, acc, D, H, W,
+                             (hipStream_t)stream);
+}
+int mi3d_votes_finish(float* acc, int Cout, int D, int H, int W, const float* n_d, const float* n_h, const float* n_w,
+                      int views_per_window, int flags, uint8_t* labels_out, float* confidence, const int64_t* target, int64_t* counts,
+                      void* workspace, void* stream) {
+    return votes_finish(acc, Cout, D, H, W, n_d, n_h, n_w, views_per_window, flags, labels_out, confidence, target, counts, workspace,
+                        (hipStream_t)stream);
+}
 
 int mi3d_linear_forward(const float* x, const float* w, const float* b, float* y, int M, int K, int Nout, int relu,
                         const float* drop, void* stream) {

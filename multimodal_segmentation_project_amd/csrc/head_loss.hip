@@ -1149,6 +1149,113 @@ __global__ __launch_bounds__(BLK) void head_votes_kernel(const T* __restrict__ z
     if constexpr (TARGET) cnt.store_block_row(C, counts + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (3 * C + 1));
 }
 
+// ------------------------------------------------------ head + softmax + WEIGHTED vote of one window (sliding-window inference)
+// One window sample of sides d x h x w at origin (od, oh, ow) of the accumulator acc (C, D, H, W): head_votes_kernel's walk and
+// mirror map, within the window, and
+//     acc[c][o + x] = acc[c][o + x] + ((g_d[xd] * g_h[xh]) * g_w[xw]) * p[c]       __fmul_rn, then __fadd_rn: never contracted
+// Windows overlap in acc, so a launch handles ONE sample and the stream orders the samples: one thread owns a voxel, nothing is
+// atomic, the same bits on every run.  VV = 4 where W, w and ow are multiples of 4 (the launcher's check): a group then stays
+// inside one window row and is 16-byte aligned in every plane; VV = 1 is the same arithmetic per voxel, so both give the same bits.
+// HBM-bound: per window voxel Cin * sizeof(T) bytes of z and 8 C of acc (the three tables stay in cache); v < 2^31 because the
+// window lies inside a volume the launcher holds to that.
+template <typename T, bool VEC, int NC, int VV>
+__global__ __launch_bounds__(BLK) void head_votes_window_kernel(const T* __restrict__ zn, int zcs, int Cin, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, int C, int d, int h, int wd, int flip,
+                                                                const float* __restrict__ gd, const float* __restrict__ gh,
+                                                                const float* __restrict__ gw, int od, int oh, int ow,
+                                                                float* __restrict__ acc, int H, int W, int64_t V) {
+    const unsigned v = (unsigned)d * (unsigned)h * (unsigned)wd;
+    const bool fw = flip & 1, fh = flip & 2, fd = flip & 4;
+    auto groups = [&](auto ONE) {
+        const int cin = decltype(ONE)::value ? CINB : Cin;
+        for (unsigned grp = blockIdx.x * BLK + threadIdx.x; grp < v / VV; grp += gridDim.x * BLK) {
+            const unsigned v0 = grp * VV, row = v0 / (unsigned)wd;
+            const unsigned xw = v0 - row * (unsigned)wd, xd = row / (unsigned)h, xh = row - xd * (unsigned)h;
+            const unsigned sh = fh ? h - 1 - xh : xh, sd = fd ? d - 1 - xd : xd;
+            const float gdh = __fmul_rn(gd[xd], gh[xh]);
+            const int64_t a0 = ((int64_t)(od + (int)xd) * H + (oh + (int)xh)) * W + (ow + (int)xw);
+            float p[VV][NC];
+#pragma unroll
+            for (int k = 0; k < VV; k++) {
+                const unsigned sw = fw ? wd - 1 - (xw + k) : xw + k;
+                float lg[NC], lse;
+                conv1_voxel<T, VEC, NC>(zn + (((int64_t)sd * h + sh) * wd + sw) * zcs, cin, w, bias, 0, C, lg);
+                softmax_c<NC>(lg, C, 1.f, p[k], lse);
+                const float wt = __fmul_rn(gdh, gw[xw + k]);
+#pragma unroll
+                for (int c = 0; c < NC; c++) p[k][c] = __fmul_rn(wt, p[k][c]);
+            }
+            float t[VV][NC];
+            load_planes<NC, VV>(acc, C, V, a0, t);
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if (c < C) {
+                    if constexpr (VV == 4)
+                        *reinterpret_cast<float4*>(acc + (int64_t)c * V + a0) = float4{__fadd_rn(t[0][c], p[0][c]), __fadd_rn(t[1][c], p[1][c]),
+                                                                                       __fadd_rn(t[2][c], p[2][c]), __fadd_rn(t[3][c], p[3][c])};
+                    else acc[(int64_t)c * V + a0] = __fadd_rn(t[0][c], p[0][c]);
+                }
+            }
+        }
+    };
+    if (VEC && Cin == CINB) groups(std::integral_constant<bool, VEC>{});
+    else groups(std::false_type{});
+}
+
+// The finishing pass of the window votes: per voxel of acc (C, D, H, W)
+//     norm = ((n_d[xd] * n_h[xh]) * n_w[xw]) * views         __fmul_rn each
+//     label = first_argmax(acc);  confidence = acc[label] / norm;  with `normalize` acc[c] = acc[c] / norm     (IEEE divisions)
+// and with TARGET the counts of head_votes_kernel's last view.  VV = 4 where W % 4 == 0 and every pointer is aligned.
+// HBM-bound: 4 C bytes read (+ 4 C written with normalize), 1 label byte (+ 4 confidence, + 8 target) per voxel.
+template <int NC, int VV, bool TARGET>
+__global__ __launch_bounds__(BLK) void votes_finish_kernel(float* __restrict__ acc, int C, int D, int H, int W, const float* __restrict__ nd,
+                                                           const float* __restrict__ nh, const float* __restrict__ nw, float views,
+                                                           int normalize, uint8_t* __restrict__ labels, float* __restrict__ confidence,
+                                                           const int64_t* __restrict__ target, unsigned long long* __restrict__ counts) {
+    const unsigned V = (unsigned)D * (unsigned)H * (unsigned)W;
+    VoxelCounts<NC> cnt;
+    for (unsigned grp = blockIdx.x * BLK + threadIdx.x; grp < V / VV; grp += gridDim.x * BLK) {
+        const unsigned v0 = grp * VV, row = v0 / (unsigned)W;
+        const unsigned xw = v0 - row * (unsigned)W, xd = row / (unsigned)H, xh = row - xd * (unsigned)H;
+        const float ndh = __fmul_rn(nd[xd], nh[xh]);
+        float t[VV][NC], norm[VV], cf[VV];
+        int best[VV];
+        load_planes<NC, VV>(acc, C, V, v0, t);
+#pragma unroll
+        for (int k = 0; k < VV; k++) {
+            norm[k] = __fmul_rn(__fmul_rn(ndh, nw[xw + k]), views);
+            best[k] = first_argmax<NC>(t[k], C);
+            float top = t[k][0];
+#pragma unroll
+            for (int c = 1; c < NC; c++) top = best[k] == c ? t[k][c] : top;
+            cf[k] = __fdiv_rn(top, norm[k]);
+            if constexpr (TARGET) {
+                const int64_t tv = target[v0 + k];
+                cnt.add(best[k], (tv >= 0 && tv < C) ? (int)tv : -1);
+            }
+        }
+        if (normalize) {
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if (c < C) {
+                    if constexpr (VV == 4)
+                        *reinterpret_cast<float4*>(acc + (int64_t)c * V + v0) = float4{__fdiv_rn(t[0][c], norm[0]), __fdiv_rn(t[1][c], norm[1]),
+                                                                                       __fdiv_rn(t[2][c], norm[2]), __fdiv_rn(t[3][c], norm[3])};
+                    else acc[(int64_t)c * V + v0] = __fdiv_rn(t[0][c], norm[0]);
+                }
+            }
+        }
+        if constexpr (VV == 4) {
+            *reinterpret_cast<unsigned*>(labels + v0) = (unsigned)best[0] | (unsigned)best[1] << 8 | (unsigned)best[2] << 16 | (unsigned)best[3] << 24;
+            if (confidence) *reinterpret_cast<float4*>(confidence + v0) = float4{cf[0], cf[1], cf[2], cf[3]};
+        } else {
+            labels[v0] = (uint8_t)best[0];
+            if (confidence) confidence[v0] = cf[0];
+        }
+    }
+    if constexpr (TARGET) cnt.store_block_row(C, counts + (int64_t)blockIdx.x * (3 * C + 1));
+}
+
 __device__ __forceinline__ void count_row_sum(const unsigned long long* part, int nblk, int C, int q, int lane, unsigned long long* counts);
 __device__ __forceinline__ void metric_scalars(const unsigned long long* counts, int N, int C, int D, int64_t V, float* out);
 // Q1: the reference's class loop is range(1, pred.size(1)) AFTER argmax -> bound = first spatial dim D
@@ -1491,6 +1598,90 @@ int head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, const
 #undef HVOTE
     if (last && target) {
         seg_counts_finalize_kernel<<<N, 1024, 0, s>>>(rows, (int)grid.x, Cout, (long long*)counts);
+        MI3D_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// ---- head + softmax + weighted vote of N window samples into one accumulator (contract: include/mi3d.h mi3d_head_votes_window)
+int head_votes_window(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int d, int h, int wd,
+                      const int* flips, const float* gd, const float* gh, const float* gw, const int* origins, float* acc, int D, int H,
+                      int W, hipStream_t s) {
+    MI3D_CHECK_ARG(Cin >= 1 && zcs >= Cin, "head_votes_window: bad channels (Cin %d, stride %d)", Cin, zcs);
+    MI3D_CHECK_ARG(Cout >= 1 && Cout <= MAXC, "head_votes_window: %d classes unsupported (max %d)", Cout, MAXC);
+    MI3D_CHECK_ARG(D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < (1ll << 31),
+                   "head_votes_window: bad volume %d x %d x %d (below 2^31 voxels)", D, H, W);
+    MI3D_CHECK_ARG(N >= 1 && N <= 65535 && d >= 1 && h >= 1 && wd >= 1 && d <= D && h <= H && wd <= W,
+                   "head_votes_window: bad batch %d or window %d x %d x %d (inside the volume %d x %d x %d)", N, d, h, wd, D, H, W);
+    MI3D_CHECK_ARG(gd && gh && gw, "head_votes_window: a weight table is NULL");
+    MI3D_CHECK_ARG(flips && origins && acc, "head_votes_window: flips, origins or the accumulator is NULL");
+    for (int n = 0; n < N; n++) {
+        const int* o = origins + 3 * n;
+        MI3D_CHECK_ARG(flips[n] >= 0 && flips[n] < 8, "head_votes_window: flip code %d of sample %d outside [0, 8)", flips[n], n);
+        MI3D_CHECK_ARG(o[0] >= 0 && o[0] <= D - d && o[1] >= 0 && o[1] <= H - h && o[2] >= 0 && o[2] <= W - wd,
+                       "head_votes_window: sample %d at (%d, %d, %d) leaves the window outside the volume", n, o[0], o[1], o[2]);
+    }
+    const int64_t V = (int64_t)D * H * W, v = (int64_t)d * h * wd;
+    const bool vec = Cin % CINB == 0 && zcs % 8 == 0 && al16(z);      // as conv1_fwd; a sample is a whole number of channel rows
+#define HWIN(VEC_, NC_, VV_)                                                                                                           \
+    head_votes_window_kernel<T, VEC_, NC_, VV_><<<grid, BLK, 0, s>>>((const T*)z + (int64_t)n * v * zcs, zcs, Cin, w, bias, Cout, d, h, wd, \
+                                                                     flips[n], gd, gh, gw, o[0], o[1], o[2], acc, H, W, V)
+#define HWIN_VV(VEC_, NC_)             \
+    do {                               \
+        if (v4) HWIN(VEC_, NC_, 4);    \
+        else HWIN(VEC_, NC_, 1);       \
+    } while (0)
+    for (int n = 0; n < N; n++) {          // the samples may overlap in acc: the stream keeps them in sample order
+        const int* o = origins + 3 * n;
+        // a thread owns 4 consecutive voxels where a group stays in one window row and is aligned in every plane
+        const bool v4 = W % 4 == 0 && wd % 4 == 0 && o[2] % 4 == 0 && al16(acc);
+        const int64_t want = (v / (v4 ? 4 : 1) + BLK - 1) / BLK;
+        dim3 grid((unsigned)(want < HEAD_LABEL_BLOCKS ? want : HEAD_LABEL_BLOCKS));
+        DISPATCH_T(dtype, T, {
+            if (vec && Cout <= 4) HWIN_VV(true, 4);
+            else if (vec) HWIN_VV(true, MAXC);
+            else if (Cout <= 4) HWIN_VV(false, 4);
+            else HWIN_VV(false, MAXC);
+            MI3D_LAUNCH_CHECK();
+        });
+    }
+#undef HWIN_VV
+#undef HWIN
+    return 0;
+}
+
+// ---- labels, confidence, mean probabilities and counts from the weighted totals (contract: include/mi3d.h mi3d_votes_finish)
+int votes_finish(float* acc, int Cout, int D, int H, int W, const float* nd, const float* nh, const float* nw, int views, int flags,
+                 uint8_t* labels, float* confidence, const int64_t* target, int64_t* counts, void* ws, hipStream_t s) {
+    MI3D_CHECK_ARG(acc && labels, "votes_finish: the accumulator or labels_out is NULL");
+    MI3D_CHECK_ARG(Cout >= 1 && Cout <= MAXC, "votes_finish: %d classes unsupported (max %d)", Cout, MAXC);
+    MI3D_CHECK_ARG(D >= 1 && H >= 1 && W >= 1 && (int64_t)D * H * W < (1ll << 31),
+                   "votes_finish: bad volume %d x %d x %d (below 2^31 voxels)", D, H, W);
+    MI3D_CHECK_ARG(nd && nh && nw, "votes_finish: a norm table is NULL");
+    MI3D_CHECK_ARG(views >= 1, "votes_finish: %d views per window", views);
+    MI3D_CHECK_ARG((flags & ~MI3D_VOTES_NORMALIZE) == 0, "votes_finish: unknown flags 0x%x", flags);
+    MI3D_CHECK_ARG(!target == !counts, "votes_finish: target and counts come together");
+    MI3D_CHECK_ARG(!target || ws, "votes_finish: counts need the workspace");
+    const int64_t V = (int64_t)D * H * W;
+    const bool v4 = W % 4 == 0 && al16(acc) && (uintptr_t)labels % 4 == 0 && al16(confidence);
+    const int64_t want = (V / (v4 ? 4 : 1) + BLK - 1) / BLK;
+    dim3 grid((unsigned)(want < HEAD_LABEL_BLOCKS ? want : HEAD_LABEL_BLOCKS));
+    unsigned long long* rows = (unsigned long long*)ws;
+    const int normalize = (flags & MI3D_VOTES_NORMALIZE) != 0;
+#define VFIN(NC_, VV_, TGT_) \
+    votes_finish_kernel<NC_, VV_, TGT_><<<grid, BLK, 0, s>>>(acc, Cout, D, H, W, nd, nh, nw, (float)views, normalize, labels, confidence, target, rows)
+#define VFIN_VV(NC_)                                                      \
+    do {                                                                  \
+        if (v4) { if (target) VFIN(NC_, 4, true); else VFIN(NC_, 4, false); } \
+        else { if (target) VFIN(NC_, 1, true); else VFIN(NC_, 1, false); }    \
+    } while (0)
+    if (Cout <= 4) VFIN_VV(4);
+    else VFIN_VV(MAXC);
+    MI3D_LAUNCH_CHECK();
+#undef VFIN_VV
+#undef VFIN
+    if (target) {
+        seg_counts_finalize_kernel<<<1, 1024, 0, s>>>(rows, (int)grid.x, Cout, (long long*)counts);
         MI3D_LAUNCH_CHECK();
     }
     return 0;

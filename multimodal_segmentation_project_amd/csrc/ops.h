@@ -419,6 +419,14 @@ int head_labels(int dtype, const void* z, int zcs, int Cin, const float* w, cons
 int head_votes(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int D, int H, int W,
                int flip, int view, int views, int flags, float* votes, uint8_t* labels, float* confidence, const int64_t* target,
                int64_t* counts, void* ws, hipStream_t s);
+// sliding-window inference: N window samples (d, h, wd) of that head, each weighted by the tables' product and added into
+// acc (Cout,D,H,W) at its origin, in sample order; then the finishing pass over acc (contract: include/mi3d.h
+// mi3d_head_votes_window, mi3d_votes_finish).  flips (N) and origins (N x 3) are host arrays.  ws: head_labels_ws_bytes(1, Cout)
+int head_votes_window(int dtype, const void* z, int zcs, int Cin, const float* w, const float* bias, int Cout, int N, int d, int h, int wd,
+                      const int* flips, const float* gd, const float* gh, const float* gw, const int* origins, float* acc, int D, int H,
+                      int W, hipStream_t s);
+int votes_finish(float* acc, int Cout, int D, int H, int W, const float* nd, const float* nh, const float* nw, int views, int flags,
+                 uint8_t* labels, float* confidence, const int64_t* target, int64_t* counts, void* ws, hipStream_t s);
 
 // ---- spatial augmentation: flip + in-plane rotation of one (C, D, H, W) sample ------------- spatial.hip
 // Reference: random_flip / random_rotate, utils/dataloader.py:207-221.  Contract and arithmetic: include/mi3d.h mi3d_plane_affine.

@@ -845,6 +845,17 @@ int mi3d_unet_head_votes(const mi3d_unet_desc* d, const void* const* params, int
                       p.geo[0].D, p.geo[0].H, p.geo[0].W, flip, view, views, flags, votes, labels_out, confidence, target, counts, head_workspace, c.s);
 }
 
+// head + softmax + weighted vote of the d->N window samples of that same decoder output into one accumulator (mi3d_head_votes_window)
+int mi3d_unet_head_votes_window(const mi3d_unet_desc* d, const void* const* params, const int* flips, const float* g_d, const float* g_h,
+                                const float* g_w, const int* origins, float* acc, int D, int H, int W, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    Plan p;
+    Ctx c{p};
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_head_votes_window", true, params, workspace, workspace_bytes, stream));
+    return head_votes_window(p.dt, c.at(p.zd[p.L - 1]), p.C[0], p.C[0], c.P(p.final_pidx()), c.P(p.final_pidx() + 1), d->out_channels, d->N,
+                             p.geo[0].D, p.geo[0].H, p.geo[0].W, flips, g_d, g_h, g_w, origins, acc, D, H, W, c.s);
+}
+
 int mi3d_unet_forward(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
                       const float* drop_scales, int training, float* logits, float* gap_out, void* workspace,
                       size_t workspace_bytes, void* stream) {

@@ -107,6 +107,7 @@ THIN_CONSUMERS = 4      # or-ed to either: another forward runs beside this one,
 
 
 HEAD_VOTES = "mi3d_unet_head_votes"      # Plan.head_votes' entry; its argument order is written down there and nowhere else
+HEAD_VOTES_WINDOW = "mi3d_unet_head_votes_window"      # Plan.head_votes_window's, likewise
 
 
 class LossGroup:
@@ -211,6 +212,13 @@ class Plan:
         """One view of a flip / model ensemble on the decoder output the last infer() left (mi3d_unet_head_votes)."""
         call(HEAD_VOTES, self.d, self.ptab, flip, view, views, flags, ptr(votes), ptr(out), ptr(confidence), ptr(labels),
              ptr(counts), ptr(head_ws), self.ws_ptr, self.ws_bytes, stream)
+
+    def head_votes_window(self, *, flips, tables, origins, acc, stream):
+        """The window samples of the decoder output the last infer() left, weighted by `tables` (g_d, g_h, g_w) and added into
+        acc (C, D, H, W) at `origins` (mi3d_unet_head_votes_window).  flips, origins: host tables (_lib.int_table), one code and
+        three ints per sample."""
+        call(HEAD_VOTES_WINDOW, self.d, self.ptab, flips, ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), origins, ptr(acc),
+             acc.shape[1], acc.shape[2], acc.shape[3], self.ws_ptr, self.ws_bytes, stream)
 
     def bn_apply_deferred(self, side, *, stream):
         """side: the Plan whose buffer table holds the side buffers a BN_PUBLISH forward filled."""
