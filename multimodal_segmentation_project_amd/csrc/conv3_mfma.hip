@@ -189,52 +189,130 @@ struct LdsP {            // persistent body: halo tile | all weight fragments [N
 };
 
 // staging map of the four- and eight-wave kernels: each of the NTHR threads moves NIT 16-byte pieces (voxel, channel half) per
-// chunk; the voxel -> global offset map is chunk-invariant, so it is computed once.  soff = -1: outside the volume -> zero fill;
-// sdst = element offset of the piece in the padded LDS tile (unused where the pitch is not padded)
-template <class T, int NTHR, int NIT>
-__device__ __forceinline__ void staging_map(int z0, int y0, int x0, int D, int H, int W, int xcs, int (&soff)[NIT], int (&sdst)[NIT]) {
+// chunk.  The map is chunk-invariant and computed once: rel = byte offset of the piece from the tile's halo origin
+// (z0 - 1, y0 - 1, x0 - 1) -- the loads add it to ONE wave-uniform base, which may point in front of the sample and is only
+// dereferenced where the piece is inside; ok = bit it set: piece it exists and lies inside the volume (others: zero fill);
+// sdst = element offset of the piece in the padded LDS tile (unused where the pitch is not padded).
+// The border test runs on the packed halo coordinates ix | iy << 8 | iz << 16 of a piece, all three axes at once: with a guard
+// bit 7 over each field, c + (0x80 - lo) keeps the guard bit where the field is >= lo and (0x80 + hi) - c where it is <= hi
+// (no carry leaves a field: coordinates and bounds are below 128).  lo / hi = first / last halo coordinate inside the volume,
+// wave-uniform; hi is capped at the halo size, so the pieces past the tile that the last round of threads would move
+// (iz >= IZ) fail the same test.
+template <class T, int NTHR>
+struct StagingMap {
+    static constexpr int NIT = T::pieces(NTHR);
+    static_assert((NIT * NTHR) / 2 / (T::IX * T::IY) < 128 && T::IX < 128 && T::IY < 128, "packed coordinate fields");
+    unsigned rel[NIT], ok;
+    int sdst[NIT];
+    __device__ __forceinline__ StagingMap(int z0, int y0, int x0, int D, int H, int W, int xcs) {
+        constexpr unsigned G = 0x808080u;
+        const int zhi = min(T::IZ - 1, D - z0), yhi = min(T::IY - 1, H - y0), xhi = min(T::IX - 1, W - x0);
+        const unsigned klo = G - ((unsigned)(x0 == 0) | (unsigned)(y0 == 0) << 8 | (unsigned)(z0 == 0) << 16);
+        const unsigned khi = G | ((unsigned)xhi | (unsigned)yhi << 8 | (unsigned)zhi << 16);
+        ok = 0;
 #pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        int idx = threadIdx.x + it * NTHR;
-        int vox = idx >> 1, half = idx & 1;
-        int ix = vox % T::IX, t = vox / T::IX, iy = t % T::IY, iz = t / T::IY;
-        sdst[it] = T::IXP == T::IX ? 0 : (t * T::IXP + ix) * 16 + half * 8;
-        int gz = z0 - 1 + iz, gy = y0 - 1 + iy, gx = x0 - 1 + ix;
-        bool inb = idx < T::NVOX * 2 && gz >= 0 && gz < D && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        soff[it] = inb ? ((gz * H + gy) * W + gx) * xcs + half * 8 : -1;
+        for (int it = 0; it < NIT; it++) {
+            int idx = threadIdx.x + it * NTHR;
+            int vox = idx >> 1, half = idx & 1;
+            int ix = vox % T::IX, t = vox / T::IX, iy = t % T::IY, iz = t / T::IY;
+            sdst[it] = T::IXP == T::IX ? 0 : (t * T::IXP + ix) * 16 + half * 8;
+            rel[it] = (unsigned)(((iz * H + iy) * W + ix) * xcs + half * 8) * 2;
+            unsigned c = (unsigned)ix | (unsigned)iy << 8 | (unsigned)iz << 16;
+            if ((((c + klo) & (khi - c)) & G) == G) ok |= 1u << it;
+        }
     }
-}
-template <class T, int NTHR, int NIT>
-__device__ __forceinline__ void staging_store(bf16* xs, const int (&sdst)[NIT], const bf16x8 (&sv)[NIT]) {
+    // the wave-uniform base: channel 0 of the halo origin of the tile at (n, z0, y0, x0)
+    static __device__ __forceinline__ const char* origin(const bf16* x, int xcs, int n, int z0, int y0, int x0, int D, int H, int W) {
+        return reinterpret_cast<const char*>(x) + ((((int64_t)n * D + (z0 - 1)) * H + (y0 - 1)) * W + (x0 - 1)) * xcs * 2;
+    }
+    // (a piece travels as four dwords: the registers of a bf16 vector that is live across a branch get re-packed half by half)
+    // coff = the chunk's byte offset (32 per chunk), added to the lane's 32 bits: the base stays put.  xb + zero-extended
+    // (rel + coff) is an address inside the tensor only for the pieces whose ok bit is set; no other sum is formed into a load.
+    // ZERO: the first chunk's call fills the pieces outside with zeros; ok is chunk-invariant, so later calls leave them alone
+    template <bool ZERO>
+    __device__ __forceinline__ void load(const char* xb, unsigned coff, u32x4 (&sv)[NIT]) const {
 #pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        int idx = threadIdx.x + it * NTHR;
-        if (idx < T::NVOX * 2) *reinterpret_cast<bf16x8*>(xs + (T::IXP == T::IX ? idx * 8 : sdst[it])) = sv[it];
+        for (int it = 0; it < NIT; it++) {
+            if (ZERO) sv[it] = u32x4{0u, 0u, 0u, 0u};
+            if (ok >> it & 1) sv[it] = *reinterpret_cast<const u32x4*>(xb + (rel[it] + coff));
+        }
     }
-}
-// K-step s (taps 2s, 2s + 1; ktap mode 0) -> LDS byte offset of the lane's fragment in M-block 0, and M-block rg -> its offset
+    __device__ __forceinline__ void store(bf16* xs, const u32x4 (&sv)[NIT]) const {
+#pragma unroll
+        for (int it = 0; it < NIT; it++) {
+            int idx = threadIdx.x + it * NTHR;
+            if (it < NIT - 1 || idx < T::NVOX * 2) *reinterpret_cast<u32x4*>(xs + (T::IXP == T::IX ? idx * 8 : sdst[it])) = sv[it];
+        }
+    }
+};
+// K-step s (taps 2s, 2s + 1; ktap mode 0): lane half g >> 1 reads tap 2s + (g >> 1).  tap_off = LDS byte offset of a tap's voxel
+// from the lane's own.  The second tap of a K-step lies at one of four distances from the first -- the next x, the next row,
+// the next slice, or none (the pad tap repeats tap 26) -- so a lane keeps four bases laneOff + (g >> 1) * distance and the
+// fragment of K-step s is at base[kind(s)] + a constant: no select per K-step.  M-block rg adds row_off
 template <class T>
-__device__ __forceinline__ int frag_off(int s, int laneOff, int g) {
-    int t0 = 2 * s, t1 = (2 * s + 1 < 27) ? 2 * s + 1 : 26;
-    int off0 = (((t0 / 9) * T::IY + ((t0 / 3) % 3)) * T::IXP + (t0 % 3)) * 32;
-    int off1 = (((t1 / 9) * T::IY + ((t1 / 3) % 3)) * T::IXP + (t1 % 3)) * 32;
-    return laneOff + ((g >> 1) ? off1 : off0);
-}
+struct FragBase {
+    static constexpr int tap_off(int t) { return (((t / 9) * T::IY + ((t / 3) % 3)) * T::IXP + (t % 3)) * 32; }
+    static constexpr int kind(int s) { return s == 13 ? 3 : (2 * s) % 3 < 2 ? 0 : ((2 * s) / 3) % 3 < 2 ? 1 : 2; }
+    static constexpr int dist(int k) { return k == 0 ? 32 : k == 1 ? (T::IXP - 2) * 32 : k == 2 ? ((T::IY - 2) * T::IXP - 2) * 32 : 0; }
+    static constexpr bool consistent() {
+        for (int s = 0; s < 14; s++)
+            if (tap_off(2 * s + 1 < 27 ? 2 * s + 1 : 26) - tap_off(2 * s) != dist(kind(s))) return false;
+        return true;
+    }
+    static_assert(consistent(), "tap pairs of ktap mode 0");
+    int b[4];
+    __device__ __forceinline__ FragBase(int laneOff, int g) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) b[k] = laneOff + (g >> 1) * dist(k);
+    }
+    __device__ __forceinline__ int off(int s) const { return b[kind(s)] + tap_off(2 * s); }
+    // the same offset by a select per K-step, for the four-wave body: there the four bases bought nothing in the trace and the
+    // scheduler spent the registers they freed on earlier fragment reads (conv3_bwd_fused_kernel<true, false>: 253 VGPRs for 243)
+    static __device__ __forceinline__ int off_select(int s, int laneOff, int g) {
+        return laneOff + ((g >> 1) ? tap_off(2 * s + 1 < 27 ? 2 * s + 1 : 26) : tap_off(2 * s));
+    }
+};
 template <class T>
 __device__ __forceinline__ int row_off(int rg) { return (((rg / T::TXB) * T::BY) * T::IXP + (rg % T::TXB) * T::BX) * 32; }
 
-// One M-block of a wave: block rg of z-slice gz of the tile at (y0, x0); lane (vn, g) = voxel vn of the block, output channels
-// g*4 .. g*4 + 3 of each of the COB 16-channel blocks.  The callers keep the loop over their blocks: (wave, r) in the four-wave
-// body, (zs, hb * MBW + r) in the eight-wave kernel.  (Per block and with the index written out at the call: a helper that loops
-// over the blocks itself, or a hoisted hb * MBW, costs these kernels VGPRs and scratch -- profiles/conv_tile_refactor_resources.txt)
+// Output view of a wave's z-slice gz of the tile at (y0, x0): lane (vn, g) = voxel vn of each 16-voxel M-block, output channels
+// g*4 .. g*4 + 3 of each of the COB 16-channel blocks.  Every address is ONE wave-uniform 64-bit base (element (n, gz, y0, x0),
+// channel ch0; the caller passes a wave-uniform gz) plus a 32-bit byte offset: the lane's, computed once, and a wave-uniform
+// step per M-block.  ry / rx = rows / columns left in the volume from the lane's voxel of M-block 0 (<= 0: outside), so the
+// in-volume test of M-block rg is one compare per block row and block column.  The base of a slice past the volume points past
+// the tensor; nothing is dereferenced where the test fails.  ES = bytes per element (2: bf16 y, 4: fp32 split-K partials)
+template <class T, int ES>
+struct TileOut {
+    char* base;
+    unsigned lane, rowB, colB;
+    int ry, rx;
+    __device__ __forceinline__ TileOut(void* out, int cs, int n, int gz, int y0, int x0, int vn, int g, int D, int H, int W, int ch0) {
+        base = reinterpret_cast<char*>(out) + ((((((int64_t)n * D + gz) * H + y0) * W + x0) * cs + ch0) * ES);
+        lane = (unsigned)(((vn / T::BX) * W + vn % T::BX) * cs + g * 4) * ES;
+        rowB = (unsigned)(T::BY * W * cs) * ES;
+        colB = (unsigned)(T::BX * cs) * ES;
+        ry = gz < D ? H - y0 - vn / T::BX : 0;
+        rx = W - x0 - vn % T::BX;
+    }
+    __device__ __forceinline__ bool ok(int rg) const { return (rg / T::TXB) * T::BY < ry && (rg % T::TXB) * T::BX < rx; }
+    __device__ __forceinline__ char* at(int rg) const { return base + (lane + (rg / T::TXB) * rowB + (rg % T::TXB) * colB); }
+};
+// the lane's bias values, loaded once per tile (no bias: zeros, which the epilogue still adds)
+template <int COB>
+__device__ __forceinline__ void load_bias(const float* __restrict__ bias, int cobBase, int g, float (&bv)[COB][4]) {
+#pragma unroll
+    for (int c = 0; c < COB; c++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) bv[c][j] = bias ? bias[(cobBase + c) * 16 + g * 4 + j] : 0.f;
+}
+// One M-block of a wave.  The callers keep the loop over their blocks: (wave, r) in the four-wave body, (zs, hb * MBW + r) in the
+// eight-wave kernel, with the wave's half hb read into a scalar register.  (Per block: a helper that loops over the blocks
+// itself costs these kernels VGPRs and scratch -- profiles/conv_tile_refactor_resources.txt)
 // split-K: fp32 partial tile pk[voxel][CoutTotal], 4 channels (16 B) per lane
 template <class T, int COB, bool TK>
-__device__ __forceinline__ void splitk_store(const f32x4 (&acc)[COB], float* __restrict__ pk, int n, int gz, int y0, int x0, int rg, int vn,
-                                             int g, int D, int H, int W, int CoutTotal, int cobBase) {
-    int byb = rg / T::TXB, bxb = rg % T::TXB;
-    int gy = y0 + byb * T::BY + vn / T::BX, gx = x0 + bxb * T::BX + vn % T::BX;
-    if (gz < D && gy < H && gx < W) {
-        float* pp = pk + ((((int64_t)n * D + gz) * H + gy) * W + gx) * CoutTotal + cobBase * 16 + g * 4;
+__device__ __forceinline__ void splitk_store(const f32x4 (&acc)[COB], const TileOut<T, 4>& o, int rg) {
+    if (o.ok(rg)) {
+        float* pp = reinterpret_cast<float*>(o.at(rg));
 #pragma unroll
         for (int c = 0; c < COB; c++) {
             if constexpr (TK) {          // write-through (agent-coherent) store: the finishing workgroup sits on another XCD
@@ -246,28 +324,38 @@ __device__ __forceinline__ void splitk_store(const f32x4 (&acc)[COB], float* __r
 }
 // epilogue of the four- and eight-wave kernels: bias, ReLU (inference: BatchNorm folded into weights and bias), bf16 rounding,
 // BatchNorm sums (s1, s2) of the ROUNDED in-volume values, 8-byte store per lane and output block -- or, WIDE and relu bit 1,
-// one 16-byte store
-template <class T, int COB, bool STATS, bool WIDE>
-__device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[COB], const float* __restrict__ bias, bf16* __restrict__ y, int ycs, int relu,
-                                              int n, int gz, int y0, int x0, int rg, int vn, int g, int D, int H, int W, int cobBase,
-                                              float (&s1)[COB][4], float (&s2)[COB][4]) {
-    int byb = rg / T::TXB, bxb = rg % T::TXB;
-    int gy = y0 + byb * T::BY + vn / T::BX, gx = x0 + bxb * T::BX + vn % T::BX;
-    bool ok = gz < D && gy < H && gx < W;
-    bf16* yp = y + ((((int64_t)n * D + gz) * H + gy) * W + gx) * ycs + cobBase * 16 + g * 4;
+// one 16-byte store.  RELU = bit 0 of relu: the callers branch once per tile, not once per value.  g: the lane's channel group,
+// for the wide store.  The sums take an out-of-volume voxel as +0: s + 0 = s, and the square of a bf16 value is exact in fp32,
+// so the fused multiply-add rounds like multiply, then add -- the bits of skipping the voxel
+template <class T, int COB, bool STATS, bool WIDE, bool RELU>
+__device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[COB], const float (&bv)[COB][4], const TileOut<T, 2>& out, int relu, int rg,
+                                              int g, float (&s1)[COB][4], float (&s2)[COB][4]) {
+    const bool ok = out.ok(rg);
     bf16x4 oc[COB];
 #pragma unroll
     for (int c = 0; c < COB; c++) {
-        bf16x4 o;
+        f32x4 v = acc[c] + f32x4{bv[c][0], bv[c][1], bv[c][2], bv[c][3]};
+        if constexpr (RELU) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float v = acc[c][j] + (bias ? bias[(cobBase + c) * 16 + g * 4 + j] : 0.f);
-            if (relu & 1) v = fmaxf(v, 0.f);
-            o[j] = (bf16)v;
-            if (STATS && ok) { float q = (float)o[j]; s1[c][j] += q; s2[c][j] += q * q; }
+            for (int j = 0; j < 4; j++) v[j] = fmaxf(v[j], 0.f);
         }
-        oc[c] = o;
+        oc[c] = __builtin_convertvector(v, bf16x4);
+        if constexpr (STATS) {
+            // the two values of a packed dword as floats, summed as a pair
+            u32x2 m = __builtin_bit_cast(u32x2, oc[c]);
+            if (!ok) m = u32x2{0u, 0u};
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                f32x2 q = {__builtin_bit_cast(float, m[h] << 16), __builtin_bit_cast(float, m[h] & 0xffff0000u)};
+                f32x2 a = {s1[c][2 * h], s1[c][2 * h + 1]}, b = {s2[c][2 * h], s2[c][2 * h + 1]};
+                a += q;
+                b = __builtin_elementwise_fma(q, q, b);
+                s1[c][2 * h] = a[0]; s1[c][2 * h + 1] = a[1];
+                s2[c][2 * h] = b[0]; s2[c][2 * h + 1] = b[1];
+            }
+        }
     }
+    bf16* yp = reinterpret_cast<bf16*>(out.at(rg));
     if constexpr (WIDE && COB == 2) {
         if (relu & 2) {
             // wide store (round 4): the lane's two 4-channel pieces (output blocks 0 and 1 of ONE voxel) trade halves with the
@@ -316,7 +404,27 @@ __device__ __forceinline__ void bn_row_write(float (*red)[COB][16][2], float* __
         part[(blk * 2 + k) * CoutTotal + ch0 + ch] = v;
     }
 }
-// lane sums (s1, s2) -> wave rows (16 voxel lanes per channel, xor shuffles) -> LDS -> the workgroup's partial row
+// The value lane ^ X holds, the partner of __shfl_xor(v, X, 64).  Inside a 16-lane row (X = 8, 2, 1) it is a DPP operand of the
+// add that follows (row_ror:8, quad_perm) and X = 4 two bank-masked row shifts (row_shl:4 into lanes 0-3 and 8-11 of the row,
+// row_shr:4 into the others), instead of an index computation and a ds_bpermute_b32 each; across rows it stays the shuffle
+template <int X>
+__device__ __forceinline__ float lane_xor(float v) {
+    if constexpr (X >= 16) return __shfl_xor(v, X, 64);
+    else {
+        int i = __builtin_bit_cast(int, v), r;
+        if constexpr (X == 8) r = __builtin_amdgcn_update_dpp(0, i, 0x128, 0xf, 0xf, true);
+        else if constexpr (X == 2) r = __builtin_amdgcn_update_dpp(0, i, 0x4e, 0xf, 0xf, true);
+        else if constexpr (X == 1) r = __builtin_amdgcn_update_dpp(0, i, 0xb1, 0xf, 0xf, true);
+        else {
+            static_assert(X == 4, "xor mask");
+            r = __builtin_amdgcn_update_dpp(i, i, 0x104, 0xf, 0x5, false);
+            r = __builtin_amdgcn_update_dpp(r, i, 0x114, 0xf, 0xa, false);
+        }
+        return __builtin_bit_cast(float, r);
+    }
+}
+// lane sums (s1, s2) -> wave rows (16 voxel lanes per channel, partners lane ^ 8, 4, 2, 1 in that order) -> LDS -> the
+// workgroup's partial row
 template <int COB, int NW, bool PAIRWISE>
 __device__ __forceinline__ void bn_rows_reduce(const float (&s1)[COB][4], const float (&s2)[COB][4], float (*red)[COB][16][2], int wave,
                                                int vn, int g, float* __restrict__ part, int64_t blk, int CoutTotal, int ch0) {
@@ -325,8 +433,10 @@ __device__ __forceinline__ void bn_rows_reduce(const float (&s1)[COB][4], const 
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             float a = s1[c][j], b = s2[c][j];
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+            a += lane_xor<8>(a); b += lane_xor<8>(b);
+            a += lane_xor<4>(a); b += lane_xor<4>(b);
+            a += lane_xor<2>(a); b += lane_xor<2>(b);
+            a += lane_xor<1>(a); b += lane_xor<1>(b);
             if (vn == 0) { red[wave][c][g * 4 + j][0] = a; red[wave][c][g * 4 + j][1] = b; }
         }
     __syncthreads();
@@ -380,22 +490,18 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
 #pragma unroll
         for (int c = 0; c < COB; c++) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    constexpr int NIT = T::pieces(BLK);
-    int soff[NIT], sdst[NIT];
-    staging_map<T, BLK>(z0, y0, x0, D, H, W, xcs, soff, sdst);
-    const bf16* xn = x + (int64_t)n * D * H * W * xcs;
+    using SM = StagingMap<T, BLK>;
+    const SM sm(z0, y0, x0, D, H, W, xcs);
     int nchunk = Cin / 16, chunk0 = 0;
     if (SPLITK) {
         int per = nchunk / bid_.gz;
         chunk0 = bid_.z * per;
         nchunk = chunk0 + per;
     }
-    bf16x8 sv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        sv[it] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (soff[it] >= 0) sv[it] = *reinterpret_cast<const bf16x8*>(xn + soff[it] + chunk0 * 16);
-    }
+    __builtin_assume(chunk0 < nchunk);             // whole chunks, at least one per workgroup: the launchers check ksplit
+    const char* xb = SM::origin(x, xcs, n, z0, y0, x0, D, H, W);
+    u32x4 sv[SM::NIT];
+    sm.template load<true>(xb, chunk0 * 32u, sv);
     // weight fragments stream through a register ring PD K-steps deep (L2-resident, 1 KB per wave-load): the load for
     // K-step s+PD is issued while K-step s computes, and the ring keeps running across chunk boundaries
     constexpr int PD = 7;      // must divide the 14 K-steps of a chunk so ring slots line up across chunks
@@ -410,21 +516,17 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
         for (int c = 0; c < COB; c++) wf[s][c] = *wptr(chunk0, s, c);
     for (int chunk = chunk0; chunk < nchunk; chunk++) {
         __syncthreads();
-        staging_store<T, BLK>(xs, sdst, sv);
+        sm.store(xs, sv);
         __syncthreads();
         // async-stage split: the next chunk's global loads are in flight while this chunk's MFMAs run
-        if (chunk + 1 < nchunk) {
-#pragma unroll
-            for (int it = 0; it < NIT; it++)
-                if (soff[it] >= 0) sv[it] = *reinterpret_cast<const bf16x8*>(xn + soff[it] + (chunk + 1) * 16);
-        }
+        if (chunk + 1 < nchunk) sm.template load<false>(xb, (chunk + 1) * 32u, sv);
         // K loop: the weight ring advances once per K-step; LDS fragment reads are software-pipelined FG M-blocks
         // (one sub-step) ahead of the MFMAs that consume them
         constexpr int FG = MB < 4 ? MB : 4;
         constexpr int SUBS = MB / FG, NSUB = 14 * SUBS;
         bf16x8 xf[2][FG];
         {
-            int toff = frag_off<T>(0, laneOff, g);
+            int toff = FragBase<T>::off_select(0, laneOff, g);
 #pragma unroll
             for (int r = 0; r < FG; r++) xf[0][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(r));
         }
@@ -446,7 +548,7 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
             }
             if (u + 1 < NSUB) {
                 int s1 = (u + 1) / SUBS, h1 = (u + 1) % SUBS;
-                int toff = frag_off<T>(s1, laneOff, g);
+                int toff = FragBase<T>::off_select(s1, laneOff, g);
 #pragma unroll
                 for (int r = 0; r < FG; r++)
                     xf[(u + 1) & 1][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(h1 * FG + r));
@@ -458,23 +560,31 @@ __device__ __forceinline__ void conv3_mfma_body(Bid bid_, const bf16* __restrict
         }
     }
 
+    const int waveu = __builtin_amdgcn_readfirstlane(wave);        // the epilogue's row base is wave-uniform: scalar registers
     if constexpr (SPLITK) {
         // part[kz][voxel][CoutTotal]
         int64_t Mtot = (int64_t)(bid_.gx / (tilesZ * tilesY * tilesX)) * D * H * W;
         float* pk = part + (int64_t)bid_.z * Mtot * CoutTotal;
+        const TileOut<T, 4> out(pk, CoutTotal, n, z0 + waveu, y0, x0, vn, g, D, H, W, cobBase * 16);
 #pragma unroll
-        for (int r = 0; r < MB; r++) splitk_store<T, COB, false>(acc[r], pk, n, z0 + wave, y0, x0, r, vn, g, D, H, W, CoutTotal, cobBase);
+        for (int r = 0; r < MB; r++) splitk_store<T, COB, false>(acc[r], out, r);
         return;
     }
     // 8-byte stores only: the 16-byte ones measured slower in this body (see conv3_mfma_bwd_fused)
-    float s1[COB][4], s2[COB][4];
+    float s1[COB][4], s2[COB][4], bv[COB][4];
 #pragma unroll
     for (int c = 0; c < COB; c++)
 #pragma unroll
         for (int j = 0; j < 4; j++) s1[c][j] = s2[c][j] = 0.f;
+    load_bias<COB>(bias, cobBase, g, bv);
+    const TileOut<T, 2> out(y, ycs, n, z0 + waveu, y0, x0, vn, g, D, H, W, cobBase * 16);
+    if (relu & 1) {
 #pragma unroll
-    for (int r = 0; r < MB; r++)
-        conv_epilogue<T, COB, STATS, false>(acc[r], bias, y, ycs, relu, n, z0 + wave, y0, x0, r, vn, g, D, H, W, cobBase, s1, s2);
+        for (int r = 0; r < MB; r++) conv_epilogue<T, COB, STATS, false, true>(acc[r], bv, out, relu, r, g, s1, s2);
+    } else {
+#pragma unroll
+        for (int r = 0; r < MB; r++) conv_epilogue<T, COB, STATS, false, false>(acc[r], bv, out, relu, r, g, s1, s2);
+    }
     if constexpr (STATS) bn_rows_reduce<COB, 4, false>(s1, s2, red, wave, vn, g, part, bid_.x, CoutTotal, cobBase * 16);
 }
 
@@ -534,48 +644,54 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
     for (int r = 0; r < MBW; r++)
 #pragma unroll
         for (int c = 0; c < COB; c++) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr int NIT = T::pieces(NT);
-    int soff[NIT], sdst[NIT];
-    staging_map<T, NT>(z0, y0, x0, D, H, W, xcs, soff, sdst);
-    const bf16* xn = x + (int64_t)n * D * H * W * xcs;
+    using SM = StagingMap<T, NT>;
+    const SM sm(z0, y0, x0, D, H, W, xcs);
+    const FragBase<T> fb(laneOff, g);
     int nchunk = Cin / 16, chunk0 = 0;
     if (SPLITK) {
         int per = nchunk / bid_.gz;
         chunk0 = bid_.z * per;
         nchunk = chunk0 + per;
     }
-    bf16x8 sv[NIT];
+    __builtin_assume(chunk0 < nchunk);             // whole chunks, at least one per workgroup: the launchers check ksplit
+    u32x4 sv[SM::NIT];
+    // the chunk's weight fragments: thread -> (K-step, output block, lane) is chunk-invariant, one 32-bit byte offset per piece
+    // from a wave-uniform base; a chunk adds one chunk image (14 * nCobTotal KB) to it, like the tile's 32 bytes
     constexpr int NWI = (14 * COB * 64 + NT - 1) / NT;
-    bf16x8 wv[NWI];
-    auto load_chunk = [&](int chunk) {
+    u32x4 wv[NWI];
+    unsigned woff[NWI];
 #pragma unroll
-        for (int it = 0; it < NIT; it++) {
-            sv[it] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            if (soff[it] >= 0) sv[it] = *reinterpret_cast<const bf16x8*>(xn + soff[it] + chunk * 16);
-        }
+    for (int i = 0; i < NWI; i++) {
+        int q = threadIdx.x + i * NT;
+        int f = q >> 6, s_ = f / COB, c_ = f - s_ * COB;
+        woff[i] = (unsigned)(s_ * nCobTotal + c_) * 1024 + (q & 63) * 16;
+    }
+    const unsigned wstep = 14u * nCobTotal * 1024;
+    const char* xb = SM::origin(x, xcs, n, z0, y0, x0, D, H, W);
+    const char* wb = reinterpret_cast<const char*>(wp + cobBase * 512);
+    auto load_chunk = [&](int chunk) {
+        if (chunk == chunk0) sm.template load<true>(xb, chunk * 32u, sv);
+        else sm.template load<false>(xb, chunk * 32u, sv);
 #pragma unroll
         for (int i = 0; i < NWI; i++) {
             int q = threadIdx.x + i * NT;
-            if (q < 14 * COB * 64) {
-                int f = q >> 6, s_ = f / COB, c_ = f - s_ * COB;
-                wv[i] = *reinterpret_cast<const bf16x8*>(wp + (((int64_t)chunk * 14 + s_) * nCobTotal + cobBase + c_) * 512 + (q & 63) * 8);
-            }
+            if (i < NWI - 1 || q < 14 * COB * 64) wv[i] = *reinterpret_cast<const u32x4*>(wb + (woff[i] + chunk * wstep));
         }
     };
     load_chunk(chunk0);
     for (int chunk = chunk0; chunk < nchunk; chunk++) {
         __syncthreads();
-        staging_store<T, NT>(xs, sdst, sv);
+        sm.store(xs, sv);
 #pragma unroll
         for (int i = 0; i < NWI; i++) {
             int q = threadIdx.x + i * NT;
-            if (q < 14 * COB * 64) *reinterpret_cast<bf16x8*>(wl + q * 8) = wv[i];
+            if (i < NWI - 1 || q < 14 * COB * 64) *reinterpret_cast<u32x4*>(wl + q * 8) = wv[i];
         }
         __syncthreads();
         if (chunk + 1 < nchunk) load_chunk(chunk + 1);        // in flight under this chunk's K loop
         bf16x8 xq[2][MBW];
         {
-            int toff = frag_off<T>(0, laneOff, g);
+            int toff = fb.off(0);
 #pragma unroll
             for (int r = 0; r < MBW; r++) xq[0][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(hb * MBW + r));
         }
@@ -585,7 +701,7 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
 #pragma unroll
             for (int c = 0; c < COB; c++) wcur[c] = *reinterpret_cast<const bf16x8*>(wl + ((s * COB + c) * 64 + lane) * 8);
             if (s + 1 < 14) {
-                int toff = frag_off<T>(s + 1, laneOff, g);
+                int toff = fb.off(s + 1);
 #pragma unroll
                 for (int r = 0; r < MBW; r++) xq[(s + 1) & 1][r] = *reinterpret_cast<const bf16x8*>(xsb + toff + row_off<T>(hb * MBW + r));
             }
@@ -595,12 +711,14 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
                 for (int c = 0; c < COB; c++) acc[r][c] = mfma16(wcur[c], xq[s & 1][r], acc[r][c]);
         }
     }
+    // the epilogue's row base and block steps are wave-uniform: scalar registers
+    const int zsu = __builtin_amdgcn_readfirstlane(zs), hbu = __builtin_amdgcn_readfirstlane(hb);
     if constexpr (SPLITK) {
         int64_t Mtot = (int64_t)(bid_.gx / (tilesZ * tilesY * tilesX)) * D * H * W;
         float* pk = part + (int64_t)bid_.z * Mtot * CoutTotal;
+        const TileOut<T, 4> out(pk, CoutTotal, n, z0 + zsu, y0, x0, vn, g, D, H, W, cobBase * 16);
 #pragma unroll
-        for (int r = 0; r < MBW; r++)
-            splitk_store<T, COB, TK>(acc[r], pk, n, z0 + zs, y0, x0, hb * MBW + r, vn, g, D, H, W, CoutTotal, cobBase);
+        for (int r = 0; r < MBW; r++) splitk_store<T, COB, TK>(acc[r], out, hbu * MBW + r);
         if constexpr (!TK) return;
         else {
             // ---- split-K ticket: the last of this (tile, output group)'s ks workgroups finishes the tile.  Release the partials
@@ -666,8 +784,12 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
             // lanes of one channel group (lane % G8) -> wave total -> the 8 waves in fixed order
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-#pragma unroll
-                for (int o_ = G8; o_ < 64; o_ <<= 1) { s1[i] += __shfl_xor(s1[i], o_, 64); s2[i] += __shfl_xor(s2[i], o_, 64); }
+                static_assert(G8 == 2 || G8 == 4, "partners lane ^ G8, .., 32 in that order");
+                if constexpr (G8 == 2) { s1[i] += lane_xor<2>(s1[i]); s2[i] += lane_xor<2>(s2[i]); }
+                s1[i] += lane_xor<4>(s1[i]); s2[i] += lane_xor<4>(s2[i]);
+                s1[i] += lane_xor<8>(s1[i]); s2[i] += lane_xor<8>(s2[i]);
+                s1[i] += lane_xor<16>(s1[i]); s2[i] += lane_xor<16>(s2[i]);
+                s1[i] += lane_xor<32>(s1[i]); s2[i] += lane_xor<32>(s2[i]);
             }
             __syncthreads();                                           // (the K loop's LDS reads are long done; red is free)
             if (lane < G8) {
@@ -682,14 +804,20 @@ __global__ __launch_bounds__(512, 4) void conv3_mfma8_kernel(const bf16* __restr
             return;
         }
     }
-    float s1[COB][4], s2[COB][4];
+    float s1[COB][4], s2[COB][4], bv[COB][4];
 #pragma unroll
     for (int c = 0; c < COB; c++)
 #pragma unroll
         for (int j = 0; j < 4; j++) s1[c][j] = s2[c][j] = 0.f;
+    load_bias<COB>(bias, cobBase, g, bv);
+    const TileOut<T, 2> out(y, ycs, n, z0 + zsu, y0, x0, vn, g, D, H, W, cobBase * 16);
+    if (relu & 1) {
 #pragma unroll
-    for (int r = 0; r < MBW; r++)
-        conv_epilogue<T, COB, STATS, true>(acc[r], bias, y, ycs, relu, n, z0 + zs, y0, x0, hb * MBW + r, vn, g, D, H, W, cobBase, s1, s2);
+        for (int r = 0; r < MBW; r++) conv_epilogue<T, COB, STATS, true, true>(acc[r], bv, out, relu, hbu * MBW + r, g, s1, s2);
+    } else {
+#pragma unroll
+        for (int r = 0; r < MBW; r++) conv_epilogue<T, COB, STATS, true, false>(acc[r], bv, out, relu, hbu * MBW + r, g, s1, s2);
+    }
     if constexpr (STATS) bn_rows_reduce<COB, 8, false>(s1, s2, red, wave, vn, g, part, bid_.x, CoutTotal, cobBase * 16);
 }
 
@@ -1039,6 +1167,8 @@ int launch_cfg(const bf16* x, int xcs, int Cin, const bf16* wp, const float* bia
     using T = ConvTile<TZ, TYB, TXB, BX>;
     int tz = cdiv(g.D, TZ), ty = cdiv(g.H, T::TY), tx = cdiv(g.W, T::TX);
     dim3 grid((unsigned)(g.N * tz * ty * tx), (unsigned)(Cout / (16 * COB)), (unsigned)ksplit);
+    // the kernels assume whole chunks and at least one per workgroup
+    MI3D_CHECK_ARG(ksplit >= 1 && ksplit <= Cin / 16 && (Cin / 16) % ksplit == 0, "conv3_mfma: split-K factor %d of %d chunks", ksplit, Cin / 16);
     constexpr size_t lds8 = Lds8<T, COB>::bytes;
     if (tk_rows) {       // split-K launch that finishes itself (ticket per (tile, output group)); eight-wave kernel only
         MI3D_CHECK_ARG(ksplit > 1 && tk_count && mi3d_routes().conv8 != 0 &&
@@ -1997,6 +2127,7 @@ int conv3_mfma_bwd_fused(const void* x, int xcs, int Cin, const void* dy, int dy
     // weight-gradient workgroups of the same launch (scan at 96^3, ms/step: 32: 2.33, 64: 2.294, 96: 2.282, 128: 2.259,
     // 192: 2.260, 256: 2.284)
     int ks = pick_ksplit(Cout, Cin, g, CONV3_BWD_SPLITK_TARGET);   // dgrad: input channels = Cout, output channels = Cin (1 if big)
+    MI3D_CHECK_ARG(ks >= 1 && ks <= Cout / 16 && (Cout / 16) % ks == 0, "conv3_mfma_bwd_fused: split-K factor %d of %d chunks", ks, Cout / 16);
     FusedArgs a;
     a.wx = (const bf16*)x; a.wxcs = xcs; a.wCin = Cin; a.wdy = (const bf16*)dy; a.wdycs = dycs; a.wCout = Cout;
     a.tZ = cdiv(g.D, WTZ); a.tY = cdiv(g.H, WTY); a.tX = cdiv(g.W, WTX); a.slabs = wgws;

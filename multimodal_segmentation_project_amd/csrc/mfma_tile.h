@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 
+typedef float __attribute__((ext_vector_type(2))) f32x2;
 typedef unsigned __attribute__((ext_vector_type(2))) u32x2;
 typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
