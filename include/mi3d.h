@@ -655,6 +655,58 @@ int mi3d_elastic_field(float* field, int D, int H, int W, uint64_t seed, const d
 int mi3d_warp3(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do, int Ho,
                int Wo, const double* matrix, const double* translate, const float* field, double magnitude, int image_padding,
                int label_padding, void* stream);
+/* mi3d_warp3 with the window placed on a start that lives on the device.  start: NULL, or three DEVICE int32 (a row of
+ * mi3d_patch_pick's starts_out), the input voxel under the window's first voxel; read by the kernel, never by the host.  With start
+ * the last line of the contract above becomes
+ *   s_a = ((M[a][0]*p_0 + M[a][1]*p_1) + M[a][2]*p_2) + (((double)start_a + (no_a - 1)/2) + t_a)
+ * so the window's middle sits at start + (no - 1)/2 instead of at the input's middle; any int32 is a valid start (the coordinates
+ * are clamped as above).  With the identity matrix, no field and t = 0, s_a = o_a + start_a exactly: the call then equals
+ * mi3d_patch_crop for a start inside the volume and finite inputs without -0.0.  start == NULL is mi3d_warp3, bit for bit. */
+int mi3d_warp3_at(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do,
+                  int Ho, int Wo, const double* matrix, const double* translate, const float* field, double magnitude,
+                  int image_padding, int label_padding, const int32_t* start, void* stream);
+
+/* Foreground-balanced patch sampling: where MONAI's RandCropByPosNegLabeld / RandCropByLabelClassesd put their windows, found on the
+ * device from random words the host drew without knowing any count (spatial.py draws them), and the windows cut in one launch.
+ * labels: N samples of sides D, H, W seen through element strides (any dense layout per sample), uint8 or int64, the view of
+ * mi3d_keep_components.  A voxel's index is d*H*W + h*W + w over the logical axes; V = D*H*W.
+ *   group_of   a HOST table of 256 bytes read before the call returns: group_of[v] is the group 0..MI3D_COMPONENTS_MAX_CLASSES-1 of
+ *              label value v, or 255 for "in no group".  G = 1 + the largest group named.  An int64 value outside 0..255 is in no
+ *              group; it is tested as it is, never narrowed to a byte first.  (PosNeg: group_of[0] = 0, group_of[v > 0] = 1; per
+ *              class: group_of[v] = v.)
+ *   mulhi64    mulhi64(a, b) = floor(a * b / 2^64) of two unsigned 64-bit words (__umul64hi)
+ * Integer arithmetic only (integer atomics of sums): the same bits on every run.  Nothing allocates or synchronises.
+ * workspace: mi3d_patch_workspace_bytes bytes, 256-byte aligned: int32 [N][8][ceil(V / MI3D_PATCH_BLOCK)], the voxels of every group
+ * in every block of MI3D_PATCH_BLOCK consecutive voxel indices of a sample; 0 (and an error) for N outside [1, 65535], a side < 1 or
+ * V >= 2^31. */
+#define MI3D_PATCH_BLOCK 4096
+size_t mi3d_patch_workspace_bytes(int N, int D, int H, int W);
+/* One pass over labels writes the workspace and counts_out (N, G) int64 (8-byte aligned, device): the voxels of each group per
+ * sample.  Rows along a unit W stride are read in 16-byte loads; any other layout is read strided, one element per load. */
+int mi3d_patch_count(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
+                     int64_t stride_w, const uint8_t* group_of, int64_t* counts_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* K draws (1..65535) as three HOST arrays read before the call returns: sample[k] in [0, N), group[k] in [0, G), rnd[k] any 64-bit
+ * word; labels, group_of and workspace those of the preceding mi3d_patch_count.  For draw k, with c = the voxels of group[k] in
+ * sample[k]:
+ *   c > 0    r = mulhi64(rnd[k], c); the voxel is the r-th voxel (from 0) of that group in ascending index; picked_out[k] = group[k]
+ *   c == 0   the voxel is mulhi64(rnd[k], V), whatever its value; picked_out[k] = -1
+ *   start    with (c_d, c_h, c_w) the voxel's coordinates: start_a = clamp(c_a - size_a / 2, 0, n_a - size_a), integer division
+ *            (MONAI's correct_crop_centers + SpatialCrop, stated here)
+ * size: three HOST ints, 1 <= size_a <= n_a (a larger window is an argument error).  Outputs on the device: starts_out (K, 3),
+ * voxel_out (K), picked_out (K), all int32.  One workgroup per draw; 256 draws per launch ride in the kernel's arguments. */
+int mi3d_patch_pick(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
+                    int64_t stride_w, const uint8_t* group_of, int K, const int32_t* sample, const int32_t* group, const uint64_t* rnd,
+                    const int32_t* size, int32_t* starts_out, int32_t* voxel_out, int32_t* picked_out, const void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* K windows of ONE sample in one launch: img_out (K, C, Do, Ho, Wo) float32 and lab_out (K, C, Do, Ho, Wo) int64 from img_in float32
+ * and lab_in int64, both (C, D, H, W) contiguous; either pair may be NULL; in != out.  starts: (K, 3) int32 in DEVICE memory, read by
+ * the kernel; each start is clamped to [0, n_a - no_a] where it is used, so no index outside the input is formed whatever it holds.
+ *   out[k][c][od][oh][ow] = in[c][start_d + od][start_h + oh][start_w + ow]
+ * A copy: every bit pattern is kept (NaN payloads, -0.0, Inf).  Negative return: a pair with only one of in / out, aliased in / out,
+ * K outside [1, 65535], non-positive sizes, more than 2^31 - 1 input voxels, a window larger than the volume. */
+int mi3d_patch_crop(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int K, int C, int D, int H, int W, int Do,
+                    int Ho, int Wo, const int32_t* starts, void* stream);
 
 /* Training-set augmentation, combined_transform() (utils/dataloader.py:223-262, used at train_unet.py:361): the
  * arithmetic of MONAI's RandBiasField -> RandGaussianNoise -> RandAdjustContrast -> RandHistogramShift ->

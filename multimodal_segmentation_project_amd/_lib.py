@@ -47,6 +47,7 @@ COMPONENTS_TILE, COMPONENTS_MAX_CLASSES, COMPONENTS_MAX_KEEP = 8, 8, 8      # MI
 SURFACE_MAX_TOLERANCES, SURFACE_COUNT_COLUMNS, SURFACE_TABLE_COLUMNS = 4, 10, 8      # MI3D_SURFACE_*
 ELASTIC_MAX_RADIUS = 32                            # MI3D_ELASTIC_MAX_RADIUS
 PAD_BORDER, PAD_ZEROS = 0, 1                       # MI3D_PAD_*
+PATCH_BLOCK = 4096                                 # MI3D_PATCH_BLOCK
 
 
 class MaskList(C.Structure):                       # mi3d_mask_list
@@ -180,6 +181,13 @@ _SIGS = {
     "mi3d_elastic_field": (i32, [vp, i32, i32, i32, C.c_uint64, C.POINTER(C.c_double), i32, vp, sz, vp]),
     "mi3d_warp3": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp,
                          C.c_double, i32, i32, vp]),
+    "mi3d_warp3_at": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp,
+                            C.c_double, i32, i32, vp, vp]),
+    "mi3d_patch_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "mi3d_patch_count": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, C.POINTER(C.c_uint8), vp, vp, sz, vp]),
+    "mi3d_patch_pick": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, C.POINTER(C.c_uint8), i32, _IP, _IP, C.POINTER(C.c_uint64),
+                              _IP, vp, vp, vp, vp, sz, vp]),
+    "mi3d_patch_crop": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "mi3d_augment_workspace_bytes": (sz, []),
     "mi3d_augment": (i32, [vp, vp, vp, i32, i32, i32, i32, _AP, vp, sz, vp]),
     "mi3d_fill_boxes_i64": (i32, [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64, vp]),

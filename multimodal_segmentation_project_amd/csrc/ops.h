@@ -435,13 +435,13 @@ int plane_affine(const float* img_in, float* img_out, const int64_t* lab_in, int
 
 // ---- spatial augmentation: 3-D affine + elastic warp of one (C, D, H, W) sample ---------------- warp.hip
 // Reference: the commented-out RandAffined / Rand3DElasticd block, utils/dataloader.py:227-248.  Contract and arithmetic:
-// include/mi3d.h mi3d_elastic_field / mi3d_warp3.  taps, matrix, translate: HOST arrays.
+// include/mi3d.h mi3d_elastic_field / mi3d_warp3 / mi3d_warp3_at.  taps, matrix, translate: HOST arrays; start: NULL or three DEVICE ints.
 size_t elastic_ws_bytes(int D, int H, int W);
 int elastic_field(float* field, int D, int H, int W, uint64_t seed, const double* taps, int radius, void* ws, size_t ws_bytes,
                   hipStream_t s);
 int warp3(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do, int Ho,
           int Wo, const double* matrix, const double* translate, const float* field, double magnitude, int image_padding,
-          int label_padding, hipStream_t s);
+          int label_padding, const int32_t* start, hipStream_t s);
 
 // ---- misc ---------------------------------------------------------------------------------- misc.hip
 int ncdhw_to_ndhwc(int dtype, const float* src, void* dst, int dcs, int C, int N, int64_t V, hipStream_t s);

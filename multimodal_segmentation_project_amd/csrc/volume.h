@@ -1,4 +1,4 @@
-// volume.h — what the kernels on stored label maps and scans share (components, surface, preview, resample): the strided volume
+// volume.h — what the kernels on stored label maps and scans share (components, surface, preview, resample, patch): the strided volume
 // view, the listed-class table, the workspace arena, the host argument checks and the source-dtype dispatch.  Integer code and plain
 // additions only: nothing here depends on the floating-point contraction mode of the file that includes it.
 #pragma once

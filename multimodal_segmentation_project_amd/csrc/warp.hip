@@ -6,7 +6,7 @@
 //   field_axis_kernel   the H pass and the D pass: lanes along W, every tap read is a coalesced row piece
 //   warp3_kernel        four consecutive output W per thread; one field read and one coordinate computation serve every channel of
 //                       image and label; 16-byte stores (scalar route for Wo % 4 != 0 or unaligned pointers, same bits)
-// Contract and arithmetic: include/mi3d.h mi3d_elastic_field / mi3d_warp3.  All coordinate and interpolation arithmetic is IEEE
+// Contract and arithmetic: include/mi3d.h mi3d_elastic_field / mi3d_warp3 / mi3d_warp3_at.  All coordinate and interpolation arithmetic is IEEE
 // double with contraction OFF, operation by operation as written there.  Every source index is inside the volume by construction:
 // "outside" (not 0 <= s <= n - 1, so a NaN is outside) is decided on the coordinate, then it is clamped to [0, n - 1] (a NaN clamps to 0) and the upper tap is
 // min(f + 1, n - 1); a smoothing tap beyond the volume is skipped, not read.
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(BLK) void field_axis_kernel(const float* __restrict
 }
 
 struct WarpMap {
-    double m[9], off[3], half_o[3], mag;      // off[a] = (n_a - 1) / 2 + t_a;  half_o[a] = (no_a - 1) / 2
+    double m[9], off[3], half_o[3], t[3], mag;      // off[a] = (n_a - 1) / 2 + t_a;  half_o[a] = (no_a - 1) / 2;  t: the translation
     int n[3], no[3];
 };
 
@@ -83,7 +83,8 @@ struct WarpMap {
 // sampling point lies outside the input
 struct Site { int lo[3], hi[3]; double t[3]; int lab; bool outside; };
 
-__device__ __forceinline__ Site site_of(const WarpMap& m, int od, int oh, int ow, float ud, float uh, float uw, bool has_field) {
+__device__ __forceinline__ Site site_of(const WarpMap& m, const double (&off)[3], int od, int oh, int ow, float ud, float uh, float uw,
+                                        bool has_field) {
 #pragma clang fp contract(off)
     double p[3] = {(double)od - m.half_o[0], (double)oh - m.half_o[1], (double)ow - m.half_o[2]};
     if (has_field) {
@@ -96,7 +97,7 @@ __device__ __forceinline__ Site site_of(const WarpMap& m, int od, int oh, int ow
     int lab[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        double s = ((m.m[3 * a] * p[0] + m.m[3 * a + 1] * p[1]) + m.m[3 * a + 2] * p[2]) + m.off[a];
+        double s = ((m.m[3 * a] * p[0] + m.m[3 * a + 1] * p[1]) + m.m[3 * a + 2] * p[2]) + off[a];
         const double top = (double)(m.n[a] - 1);
         st.outside = st.outside || !(s >= 0.0 && s <= top);      // a NaN is outside
         s = fmin(fmax(s, 0.0), top);                      // inside [0, n - 1] from here on, whatever s was
@@ -127,12 +128,13 @@ __device__ __forceinline__ float trilinear(const float* __restrict__ x, const Wa
 }
 
 // One thread: VW consecutive W outputs of output row (od, oh), every channel.  VEC needs Wo % VW == 0 and 16-byte aligned field and
-// output bases.
+// output bases.  start: NULL, or three device ints, the window's first voxel: the offset is then (start_a + (no_a - 1) / 2) + t_a,
+// formed here in that order, instead of the host's (n_a - 1) / 2 + t_a.
 template <bool VEC>
 __global__ __launch_bounds__(BLK) void warp3_kernel(const float* __restrict__ img_in, float* __restrict__ img_out,
                                                     const int64_t* __restrict__ lab_in, int64_t* __restrict__ lab_out,
-                                                    const float* __restrict__ field, int C, WarpMap m, int WQ, int img_zeros,
-                                                    int lab_zeros, int64_t total) {
+                                                    const float* __restrict__ field, const int32_t* __restrict__ start, int C, WarpMap m,
+                                                    int WQ, int img_zeros, int lab_zeros, int64_t total) {
     const int64_t q = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (q >= total) return;
     const int64_t r = q / WQ;
@@ -156,9 +158,15 @@ __global__ __launch_bounds__(BLK) void warp3_kernel(const float* __restrict__ im
             }
         }
     }
+    double off[3] = {m.off[0], m.off[1], m.off[2]};
+    if (start) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int a = 0; a < 3; a++) off[a] = ((double)start[a] + m.half_o[a]) + m.t[a];
+    }
     Site st[VW];
 #pragma unroll
-    for (int j = 0; j < VW; j++) st[j] = site_of(m, od, oh, w0 + j, u[0][j], u[1][j], u[2][j], field != nullptr);
+    for (int j = 0; j < VW; j++) st[j] = site_of(m, off, od, oh, w0 + j, u[0][j], u[1][j], u[2][j], field != nullptr);
     for (int c = 0; c < C; c++) {
         if (lab_in) {
             const int64_t* src = lab_in + c * Vi;
@@ -231,7 +239,7 @@ int elastic_field(float* field, int D, int H, int W, uint64_t seed, const double
 
 int warp3(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do, int Ho,
           int Wo, const double* matrix, const double* translate, const float* field, double magnitude, int image_padding,
-          int label_padding, hipStream_t s) {
+          int label_padding, const int32_t* start, hipStream_t s) {
     MI3D_CHECK_ARG(matrix && translate, "mi3d_warp3: null matrix or translation");
     MI3D_CHECK_ARG(!img_in == !img_out && !lab_in == !lab_out && (img_in || lab_in),
                    "mi3d_warp3: the image pair, the label pair or both, each with its input AND its output");
@@ -250,16 +258,17 @@ int warp3(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* l
         m.no[a] = no[a];
         m.half_o[a] = (double)(no[a] - 1) / 2.0;
         m.off[a] = (double)(n[a] - 1) / 2.0 + translate[a];
+        m.t[a] = translate[a];
     }
     m.mag = magnitude;
     const int WQ = (Wo + VW - 1) / VW;
     const int64_t total = (int64_t)Do * Ho * WQ;
     const bool vec = Wo % VW == 0 && al16(img_out) && al16(lab_out) && al16(field);
     if (vec)
-        warp3_kernel<true><<<blocks_of(total, BLK), BLK, 0, s>>>(img_in, img_out, lab_in, lab_out, field, C, m, WQ,
+        warp3_kernel<true><<<blocks_of(total, BLK), BLK, 0, s>>>(img_in, img_out, lab_in, lab_out, field, start, C, m, WQ,
                                                                   image_padding == MI3D_PAD_ZEROS, label_padding == MI3D_PAD_ZEROS, total);
     else
-        warp3_kernel<false><<<blocks_of(total, BLK), BLK, 0, s>>>(img_in, img_out, lab_in, lab_out, field, C, m, WQ,
+        warp3_kernel<false><<<blocks_of(total, BLK), BLK, 0, s>>>(img_in, img_out, lab_in, lab_out, field, start, C, m, WQ,
                                                                    image_padding == MI3D_PAD_ZEROS, label_padding == MI3D_PAD_ZEROS, total);
     MI3D_LAUNCH_CHECK();
     return 0;
@@ -276,7 +285,14 @@ int mi3d_elastic_field(float* field, int D, int H, int W, uint64_t seed, const d
 int mi3d_warp3(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do, int Ho,
                int Wo, const double* matrix, const double* translate, const float* field, double magnitude, int image_padding,
                int label_padding, void* stream) {
+    return mi3d_warp3_at(img_in, img_out, lab_in, lab_out, C, D, H, W, Do, Ho, Wo, matrix, translate, field, magnitude, image_padding,
+                         label_padding, nullptr, stream);
+}
+
+int mi3d_warp3_at(const float* img_in, float* img_out, const int64_t* lab_in, int64_t* lab_out, int C, int D, int H, int W, int Do,
+                  int Ho, int Wo, const double* matrix, const double* translate, const float* field, double magnitude,
+                  int image_padding, int label_padding, const int32_t* start, void* stream) {
     return warp3(img_in, img_out, lab_in, lab_out, C, D, H, W, Do, Ho, Wo, matrix, translate, field, magnitude, image_padding,
-                 label_padding, (hipStream_t)stream);
+                 label_padding, start, (hipStream_t)stream);
 }
 }  // extern "C"
