@@ -541,6 +541,31 @@ int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int 
                          int64_t stride_h, int64_t stride_w, int connectivity, int n_classes, const int32_t* class_values,
                          const int32_t* keep_k, int64_t min_size, int fill, void* labels_out, int64_t* stats_out, int32_t* status_out,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* Fill the enclosed holes of a label map by their enclosing class: the step after mi3d_keep_components (which turns a wrong-class
+ * island inside an organ into such a hole).  Integers only, the same bits on every run.  labels as above; S =
+ * scipy.ndimage.generate_binary_structure(3, connectivity).
+ *   background component   a component of labels == 0 (an int64 value exactly 0) of one sample under S.
+ *   ring                   the positions that are not in the component but are S-neighbours of one of its voxels, positions outside
+ *                          the volume included.
+ *   enclosed               no ring position lies outside the volume: none of the component's voxels lies on a face of the sample.
+ *   filled with v          enclosed, every ring voxel carries the same value v, v is a listed class (1..255), and the component has
+ *                          at most max_size voxels (max_size = 0: no limit).  Its voxels become v.
+ * Every other voxel is copied: open components, enclosed ones whose ring carries two or more values (MIXED), and ones whose single
+ * ring value is unlisted or an int64 value outside 0..255 (SKIPPED, as is a component above max_size).  All int64 values outside
+ * 0..255 count as ONE ring value, "other": a ring of 300 and -5 alone is skipped, not mixed; the map is the same either way.
+ * The host route this replaces: ids, n = scipy.ndimage.label(labels == 0, S); per component, on a copy padded by one voxel,
+ * ring = binary_dilation(comp, S) & ~comp and np.unique of the padded map on the ring; on a map with the single class c the result is
+ * scipy.ndimage.binary_fill_holes(labels == c, S) * c.  monai.transforms.FillHoles states the same idea (enclosed background, one
+ * enclosing label, applied_labels); this contract is not pinned against MONAI.
+ * labels_out: dtype and strides of labels; may be labels itself.  class_values: a HOST array of n_classes (1..8) distinct values in
+ * 1..255.  stats_out: (N, n_classes, 2) int64, per listed class [0] holes filled [1] voxels filled.  summary_out: (N, 4) int64,
+ * [0] enclosed components [1] filled [2] mixed [3] skipped; [0] = [1] + [2] + [3].  status_out: as above.  workspace:
+ * mi3d_fill_holes_workspace_bytes bytes (23 per voxel, rounded up), 256-byte aligned; the domain of mi3d_components_workspace_bytes.
+ * Every argument is checked before the first launch. */
+size_t mi3d_fill_holes_workspace_bytes(int N, int D, int H, int W);
+int mi3d_fill_holes(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
+                    int64_t stride_w, int connectivity, int n_classes, const int32_t* class_values, int64_t max_size, void* labels_out,
+                    int64_t* stats_out, int64_t* summary_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Surface distances between two label maps: the exact Euclidean distance transform and, from it, the Hausdorff distance, its
  * percentile (HD95), the average symmetric surface distance (ASSD) and the surface Dice (NSD) per (sample, class): what a user does

@@ -171,6 +171,9 @@ _SIGS = {
     "mi3d_component_roots": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, C.POINTER(C.c_uint8), vp, vp, vp, sz, vp]),
     "mi3d_keep_components": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    i64, i32, vp, vp, vp, vp, sz, vp]),
+    "mi3d_fill_holes_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "mi3d_fill_holes": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, C.POINTER(C.c_int32), i64, vp, vp, vp, vp, vp, sz,
+                              vp]),
     "mi3d_surface_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "mi3d_distance_transform": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, C.POINTER(C.c_double), vp, vp, sz, vp]),
     "mi3d_surface_mask": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp, vp]),

@@ -7,6 +7,10 @@
 //   select         every root offers (size << 32 | ~root) to the k slots of its class        -> stats (components, voxels, k keys)
 //   finish         keys -> sizes and roots of the kept components                            -> stats
 //   apply          a voxel of a listed class keeps its label iff its root is kept            -> labels_out, through the strides
+// and the enclosed holes of the map filled by their enclosing class (mi3d_fill_holes): tile, seam and flatten over the BACKGROUND
+// (the tile pass takes a value map and there also leaves a C-ordered volume of label codes), then
+//   ring           a background voxel's non-background neighbours, min and max code          -> lo[root], hi[root]
+//   fill           enclosed (hi below "outside"), one listed value (lo == hi), size in range -> labels_out, stats, summary
 // A voxel's index is d * H * W + h * W + w in its sample, logical axes, whatever the strides.  A union always hangs the larger
 // root under the smaller, so the root of a set is its smallest index, the first voxel in C order: the labelling is canonical, it
 // does not depend on launch order, tile size or strides.  Only integer atomics (min, add, max of unique keys) are used: every
@@ -24,12 +28,30 @@ typedef unsigned long long u64;
 struct Select {                      // bit v: label value v is selected; bit 0 is never set
     u64 m[4];
 };
+// What the tile pass labels is decided by a VALUE MAP, a template parameter of tile_kernel: value(v) is the component value 0..255 of
+// label v (0: in no component), and a map with CODES = true also hands out the code volume that mi3d_fill_holes reads.
+struct KeepSelected {                // components of the selected values 1..255, each under its own value
+    static constexpr bool CODES = false;
+    static constexpr int64_t PADDING = 0;          // the label a tile carries past the volume's edge: one whose value() is 0
+    Select sel;
+    __device__ __forceinline__ int value(int64_t v) const;
+    __device__ __forceinline__ void put_code(int64_t, int64_t) const {}
+};
+constexpr int CODE_OTHER = 256, CODE_OUTSIDE = 257;          // above every label value; a position outside the volume above all
+struct Background {                  // components of the background (label exactly 0) under value 1; code[i]: the label 0..255 of voxel i,
+    static constexpr bool CODES = true;          // CODE_OTHER for every other int64 value
+    static constexpr int64_t PADDING = 1;
+    uint16_t* code;
+    __device__ __forceinline__ int value(int64_t v) const { return v == 0; }
+    __device__ __forceinline__ void put_code(int64_t i, int64_t v) const { code[i] = (uint16_t)(v >= 0 && v <= 255 ? (int)v : CODE_OTHER); }
+};
 
 __device__ __forceinline__ int selected(const Select& s, int64_t v) {
     if (v < 1 || v > 255) return 0;
     const u64 lo = (v & 64) ? s.m[1] : s.m[0], hi = (v & 64) ? s.m[3] : s.m[2];
     return (int)((((v & 128) ? hi : lo) >> (v & 63)) & 1);
 }
+__device__ __forceinline__ int KeepSelected::value(int64_t v) const { return selected(sel, v) ? (int)v : 0; }
 template <typename T> __device__ __forceinline__ int64_t label_value(const T* p, int64_t off) { return (int64_t)p[off]; }
 
 // The preceding half of the 26 neighbours in C order, without the left neighbour (0, 0, -1): dd < 0, or dd == 0 and dh < 0.
@@ -81,8 +103,8 @@ __device__ __forceinline__ bool tile_union(int* par, int a, int b, int budget) {
 }
 
 // One workgroup per tile of TD x TH rows of 64 voxels along w; a wave takes a row at a time, lane = w.  grid: x = tile, y = sample.
-template <typename T>
-__global__ __launch_bounds__(BLK) void tile_kernel(const T* __restrict__ lab, Vol vol, Select sel, int conn, int tilesW, int tilesH,
+template <typename T, typename Map>
+__global__ __launch_bounds__(BLK) void tile_kernel(const T* __restrict__ lab, Vol vol, Map map, int conn, int tilesW, int tilesH,
                                                    int32_t* __restrict__ parent, uint8_t* __restrict__ cls, int32_t* __restrict__ size,
                                                    int32_t* __restrict__ status) {
     __shared__ int par[TILE];
@@ -97,13 +119,13 @@ __global__ __launch_bounds__(BLK) void tile_kernel(const T* __restrict__ lab, Vo
 #pragma unroll
     for (int q = 0; q < ROWS / NW; q++) {
         const int r = wave + q * NW, d = d0 + r / TH, h = h0 + r % TH;
-        mine[q] = d < vol.D && h < vol.H && w < vol.W ? label_value(lab, vol.offset(d, h, w)) : 0;
+        mine[q] = d < vol.D && h < vol.H && w < vol.W ? label_value(lab, vol.offset(d, h, w)) : Map::PADDING;
     }
 #pragma unroll
     for (int q = 0; q < ROWS / NW; q++) {
         const int r = wave + q * NW, d = d0 + r / TH, h = h0 + r % TH;
         const bool in = d < vol.D && h < vol.H && w < vol.W;
-        const int v = selected(sel, mine[q]) ? (int)mine[q] : 0;
+        const int v = map.value(mine[q]);
         const int left = __shfl_up(v, 1, 64);
         const u64 cont = __ballot(lane > 0 && v != 0 && left == v);
         const u64 starts = ~cont & (~0ull >> (63 - lane));          // the starts at or below this lane; lane 0 is one
@@ -114,6 +136,7 @@ __global__ __launch_bounds__(BLK) void tile_kernel(const T* __restrict__ lab, Vo
         if (in) {
             const int64_t i = sample + ((int64_t)d * vol.H + h) * vol.W + w;
             cls[i] = (uint8_t)v;
+            if constexpr (Map::CODES) map.put_code(i, mine[q]);
         }
     }
     __syncthreads();
@@ -368,6 +391,110 @@ __global__ __launch_bounds__(BLK) void apply_kernel(const T* lab, T* out, Vol vo
     out[off] = l;
 }
 
+// ---- hole filling: ring and fill --------------------------------------------------------------------------------------------------
+// The components here are those of the background (tile_kernel<T, Background>), and `code` is the C-ordered volume of label codes
+// the tile pass left: the neighbours are read from it, never through the strides of the input.
+// ring: lo[root] / hi[root] = the minimum / maximum code on the ring of the component, CODE_OUTSIDE for a ring position outside the
+// volume.  The ring carries one value iff lo == hi, and no position outside iff hi < CODE_OUTSIDE: integer min and max, so the
+// order of the atomics cannot matter.  A background voxel forms the min and max over its own non-background neighbours and issues an
+// atomic only where a relaxed load shows it would change the word: the outer component of a real map has hundreds of thousands
+// of ring voxels aimed at two addresses, and all but the first few end as a load.  Even those loads meet at one place, so a wave
+// first combines the lanes that share a root.  One thread per voxel; grid: x over voxels, y = sample.
+__global__ __launch_bounds__(BLK) void ring_kernel(Vol vol, int conn, const uint16_t* __restrict__ code, const int32_t* __restrict__ root,
+                                                   int32_t* __restrict__ lo, int32_t* __restrict__ hi) {
+    const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    code += blockIdx.y * V;
+    int mn = INT32_MAX, mx = 0;          // mx stays 0 where the voxel has nothing to tell: not background, or background all around
+    if (i < V && code[i] == 0) {
+        int d, h, w;
+        vol.split(i, d, h, w);
+        // a voxel on a face has a neighbour of every connectivity outside the volume
+        if (d == 0 || h == 0 || w == 0 || d == vol.D - 1 || h == vol.H - 1 || w == vol.W - 1) mn = mx = CODE_OUTSIDE;
+        for (int j = 0; j < 27; j++) {
+            const int dd = j / 9 - 1, dh = j / 3 % 3 - 1, dw = j % 3 - 1;
+            const int nd = d + dd, nh = h + dh, nw = w + dw;
+            if (j == 13 || nonzeros(dd, dh, dw) > conn || nd < 0 || nd >= vol.D || nh < 0 || nh >= vol.H || nw < 0 || nw >= vol.W) continue;
+            const int c = code[((int64_t)nd * vol.H + nh) * vol.W + nw];
+            if (c == 0) continue;
+            mn = c < mn ? c : mn;
+            mx = c > mx ? c : mx;
+        }
+    }
+    bool has = mx != 0;
+    const int r = has ? root[blockIdx.y * V + i] : -1;
+    lo += blockIdx.y * V, hi += blockIdx.y * V;
+    // The lanes of a wave that report to one root first combine what they have (twice: the outer component and one more), and one
+    // lane speaks for them; every lane of the wave takes part in the shuffles.  The lanes still left report on their own.
+    for (int round = 0; round < 2; round++) {
+        const u64 todo = __ballot(has);
+        if (!todo) break;
+        const int leader = __builtin_ctzll(todo), lr = __shfl(r, leader, 64);
+        const bool same = has && r == lr;
+        int a = same ? mn : INT32_MAX, b = same ? mx : 0;
+        for (int off = 32; off > 0; off >>= 1) {
+            const int a2 = __shfl_xor(a, off, 64), b2 = __shfl_xor(b, off, 64);
+            a = a2 < a ? a2 : a;
+            b = b2 > b ? b2 : b;
+        }
+        if (lane == leader) {
+            if (g_load(lo + lr) > a) atomicMin(lo + lr, a);
+            if (g_load(hi + lr) < b) atomicMax(hi + lr, b);
+        }
+        has = has && !same;
+    }
+    if (has) {
+        if (g_load(lo + r) > mn) atomicMin(lo + r, mn);
+        if (g_load(hi + r) < mx) atomicMax(hi + r, mx);
+    }
+}
+
+// fill: a background voxel of an enclosed component whose ring carries the single listed value v, of at most max_size voxels
+// (0: no limit), becomes v; every other voxel is copied.  A thread reads its own label and writes its own output: out may be lab.
+// The voxel that is its component's root classifies it for the tables: counts per workgroup in LDS, then one integer atomic per
+// workgroup and non-zero word.  summary row: enclosed, filled, mixed, skipped; stats row of class c: holes, voxels.
+template <typename T>
+__global__ __launch_bounds__(BLK) void fill_kernel(const T* lab, T* out, Vol vol, Classes cl, int64_t max_size, const uint16_t* __restrict__ code,
+                                                   const int32_t* __restrict__ root, const int32_t* __restrict__ size,
+                                                   const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, u64* __restrict__ stats,
+                                                   u64* __restrict__ summary) {
+    __shared__ unsigned holes[MAXC], voxels[MAXC], kinds[4];
+    if (threadIdx.x < MAXC) holes[threadIdx.x] = 0, voxels[threadIdx.x] = 0;
+    if (threadIdx.x < 4) kinds[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x, base = blockIdx.y * V;
+    if (i < V) {
+        int d, h, w;
+        vol.split(i, d, h, w);
+        const int64_t off = blockIdx.y * vol.sn + vol.offset(d, h, w);
+        T l = lab[off];
+        if (code[base + i] == 0) {
+            const int r = root[base + i];
+            const int a = lo[base + r], b = hi[base + r], sz = size[base + r];
+            const bool enclosed = b < CODE_OUTSIDE, one = a == b;
+            const int c = one ? class_index(cl, a) : -1;          // a listed class is in 1..255: never CODE_OTHER
+            const bool fill = enclosed && c >= 0 && (max_size == 0 || sz <= max_size);
+            if (fill) l = (T)a;
+            if (r == (int)i && enclosed) {
+                atomicAdd(&kinds[0], 1u);
+                atomicAdd(&kinds[fill ? 1 : one ? 3 : 2], 1u);
+                if (fill) {
+                    atomicAdd(&holes[c], 1u);
+                    atomicAdd(&voxels[c], (unsigned)sz);          // a workgroup's roots own fewer than 2^31 voxels together
+                }
+            }
+        }
+        out[off] = l;
+    }
+    __syncthreads();
+    if (threadIdx.x < cl.n) {
+        u64* row = stats + ((int64_t)blockIdx.y * cl.n + threadIdx.x) * 2;
+        if (holes[threadIdx.x]) atomicAdd(row, (u64)holes[threadIdx.x]);
+        if (voxels[threadIdx.x]) atomicAdd(row + 1, (u64)voxels[threadIdx.x]);
+    }
+    if (threadIdx.x < 4 && kinds[threadIdx.x]) atomicAdd(summary + (int64_t)blockIdx.y * 4 + threadIdx.x, (u64)kinds[threadIdx.x]);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 struct Workspace {          // the layout, once: mi3d_components_workspace_bytes counts it over a null base
     int32_t *parent, *root, *size;
@@ -379,25 +506,36 @@ struct Workspace {          // the layout, once: mi3d_components_workspace_bytes
         bytes = a.used;
     }
 };
+struct FillWorkspace : Workspace {          // mi3d_fill_holes_workspace_bytes: the same, then the code volume and the ring words per root
+    uint16_t* code;
+    int32_t *lo, *hi;
+    FillWorkspace(void* base, int64_t NV) : Workspace(base, NV) {
+        Arena a{static_cast<char*>(base), bytes};
+        code = a.take<uint16_t>(NV), lo = a.take<int32_t>(NV), hi = a.take<int32_t>(NV);
+        bytes = a.used;
+    }
+};
 
 int check_common(const char* name, const void* labels, int label_dtype, int N, int D, int H, int W, int64_t sn, int64_t sd, int64_t sh,
-                 int64_t sw, int connectivity, const int32_t* status_out, const void* workspace, size_t workspace_bytes_given) {
+                 int64_t sw, int connectivity, const int32_t* status_out, const void* workspace, size_t workspace_bytes_given, bool fill = false) {
     MI3D_TRY(check_map(name, "labels", labels, label_dtype, sn, sd, sh, sw));
     MI3D_TRY(check_sizes(name, N, D, H, W));
     MI3D_TRY(check_connectivity(name, connectivity));
     MI3D_CHECK_ARG(status_out, "%s: null pointer (status_out)", name);
-    return check_workspace(name, workspace, workspace_bytes_given, Workspace(nullptr, total_voxels(N, D, H, W)).bytes);
+    const int64_t NV = total_voxels(N, D, H, W);
+    return check_workspace(name, workspace, workspace_bytes_given, fill ? FillWorkspace(nullptr, NV).bytes : Workspace(nullptr, NV).bytes);
 }
 
 // status = 0, then tile pass, seam pass, flatten into `root` (and the sizes where size != NULL)
-int label_launch(const void* labels, int label_dtype, const Vol& vol, const Select& sel, int conn, const Workspace& ws, int32_t* root,
+template <typename Map>
+int label_launch(const void* labels, int label_dtype, const Vol& vol, const Map& map, int conn, const Workspace& ws, int32_t* root,
                  int32_t* size, int32_t* status, hipStream_t stream) {
     MI3D_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
     const int tilesW = cdiv(vol.W, TW), tilesH = cdiv(vol.H, TH), tilesD = cdiv(vol.D, TD);
     const int64_t tiles = (int64_t)tilesW * tilesH * tilesD;          // <= V < 2^31
     dim3 tgrid((unsigned)tiles, (unsigned)vol.N), vgrid((unsigned)voxel_blocks(vol.V()), (unsigned)vol.N);
     dispatch_src(label_dtype, LabelTypes(), [&](auto tag) {
-        tile_kernel<<<tgrid, BLK, 0, stream>>>((const decltype(tag)*)labels, vol, sel, conn, tilesW, tilesH, ws.parent, ws.cls, size, status);
+        tile_kernel<<<tgrid, BLK, 0, stream>>>((const decltype(tag)*)labels, vol, map, conn, tilesW, tilesH, ws.parent, ws.cls, size, status);
     });
     MI3D_LAUNCH_CHECK();
     if (tiles > 1) {
@@ -429,11 +567,12 @@ int mi3d_component_roots(const void* labels, int label_dtype, int N, int D, int 
                           workspace, workspace_bytes));
     MI3D_CHECK_ARG(class_select && roots_out, "%s: null pointer", name);
     MI3D_CHECK_ARG(class_select[0] == 0, "%s: value 0 is the background and cannot be selected", name);
-    Select sel{};
+    KeepSelected keep{};
+    Select& sel = keep.sel;
     for (int v = 1; v < 256; v++)
         if (class_select[v]) sel.m[v >> 6] |= 1ull << (v & 63);
     const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
-    return label_launch(labels, label_dtype, vol, sel, connectivity, Workspace(workspace, (int64_t)N * vol.V()), roots_out, nullptr, status_out,
+    return label_launch(labels, label_dtype, vol, keep, connectivity, Workspace(workspace, (int64_t)N * vol.V()), roots_out, nullptr, status_out,
                         (hipStream_t)stream);
 }
 
@@ -448,7 +587,8 @@ int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int 
     MI3D_CHECK_ARG(((uintptr_t)stats_out & 7) == 0, "%s: stats_out must be 8-byte aligned", name);
     MI3D_CHECK_ARG(min_size >= 1, "%s: min_size must be at least 1", name);
     MI3D_CHECK_ARG(fill >= 0 && fill <= 255, "%s: fill %d outside 0..255", name, fill);
-    Select sel{};
+    KeepSelected keep{};
+    Select& sel = keep.sel;
     KeepClasses cl{};
     MI3D_TRY(check_classes(name, n_classes, class_values, cl));
     for (int j = 0; j < n_classes; j++) {
@@ -462,7 +602,7 @@ int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int 
     const Workspace ws(workspace, (int64_t)N * vol.V());
     hipStream_t s = (hipStream_t)stream;
     MI3D_HIP(hipMemsetAsync(stats_out, 0, (size_t)N * n_classes * STATS * sizeof(int64_t), s));
-    MI3D_TRY(label_launch(labels, label_dtype, vol, sel, connectivity, ws, ws.root, ws.size, status_out, s));
+    MI3D_TRY(label_launch(labels, label_dtype, vol, keep, connectivity, ws, ws.root, ws.size, status_out, s));
     dim3 vgrid((unsigned)voxel_blocks(vol.V()), (unsigned)N);
     dim3 sgrid(vgrid.x < SELECT_BLOCKS ? vgrid.x : SELECT_BLOCKS, (unsigned)N);
     select_kernel<<<sgrid, BLK, 0, s>>>(vol, cl, ws.root, ws.size, ws.cls, (u64*)stats_out);
@@ -472,6 +612,49 @@ int mi3d_keep_components(const void* labels, int label_dtype, int N, int D, int 
     dispatch_src(label_dtype, LabelTypes(), [&](auto tag) {
         using T = decltype(tag);
         apply_kernel<T><<<vgrid, BLK, 0, s>>>((const T*)labels, (T*)labels_out, vol, cl, fill, ws.root, ws.cls, stats_out);
+    });
+    MI3D_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t mi3d_fill_holes_workspace_bytes(int N, int D, int H, int W) {
+    const int64_t NV = total_voxels(N, D, H, W);
+    if (NV == 0) {
+        mi3d_set_error("mi3d_fill_holes_workspace_bytes: N in [1, 65535], sides >= 1 and D * H * W < 2^31 expected");
+        return 0;
+    }
+    return FillWorkspace(nullptr, NV).bytes;
+}
+
+int mi3d_fill_holes(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d, int64_t stride_h,
+                    int64_t stride_w, int connectivity, int n_classes, const int32_t* class_values, int64_t max_size, void* labels_out,
+                    int64_t* stats_out, int64_t* summary_out, int32_t* status_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* name = "mi3d_fill_holes";
+    MI3D_TRY(check_common(name, labels, label_dtype, N, D, H, W, stride_n, stride_d, stride_h, stride_w, connectivity, status_out,
+                          workspace, workspace_bytes, true));
+    MI3D_CHECK_ARG(class_values && labels_out && stats_out && summary_out, "%s: null pointer", name);
+    MI3D_CHECK_ARG((((uintptr_t)stats_out | (uintptr_t)summary_out) & 7) == 0, "%s: stats_out and summary_out must be 8-byte aligned", name);
+    MI3D_CHECK_ARG(max_size >= 0, "%s: max_size must be at least 0 (0: no limit)", name);
+    Classes cl{};
+    MI3D_TRY(check_classes(name, n_classes, class_values, cl));
+    for (int j = 0; j < n_classes; j++)
+        MI3D_CHECK_ARG(cl.value[j] >= 1 && cl.value[j] <= 255, "%s: class value %d outside 1..255", name, cl.value[j]);
+    const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
+    const int64_t NV = (int64_t)N * vol.V();
+    const FillWorkspace ws(workspace, NV);
+    hipStream_t s = (hipStream_t)stream;
+    MI3D_HIP(hipMemsetAsync(stats_out, 0, (size_t)N * n_classes * 2 * sizeof(int64_t), s));
+    MI3D_HIP(hipMemsetAsync(summary_out, 0, (size_t)N * 4 * sizeof(int64_t), s));
+    MI3D_HIP(hipMemsetAsync(ws.lo, 0x7f, (size_t)NV * sizeof(int32_t), s));          // 0x7f7f7f7f: above every code
+    MI3D_HIP(hipMemsetAsync(ws.hi, 0, (size_t)NV * sizeof(int32_t), s));             // below every code of a ring
+    MI3D_TRY(label_launch(labels, label_dtype, vol, Background{ws.code}, connectivity, ws, ws.root, ws.size, status_out, s));
+    dim3 vgrid((unsigned)voxel_blocks(vol.V()), (unsigned)N);
+    ring_kernel<<<vgrid, BLK, 0, s>>>(vol, connectivity, ws.code, ws.root, ws.lo, ws.hi);
+    MI3D_LAUNCH_CHECK();
+    dispatch_src(label_dtype, LabelTypes(), [&](auto tag) {
+        using T = decltype(tag);
+        fill_kernel<T><<<vgrid, BLK, 0, s>>>((const T*)labels, (T*)labels_out, vol, cl, max_size, ws.code, ws.root, ws.size, ws.lo, ws.hi,
+                                             (u64*)stats_out, (u64*)summary_out);
     });
     MI3D_LAUNCH_CHECK();
     return 0;

@@ -310,8 +310,22 @@ def per_sample_dice_iou(counts, classes=(1, 2, 3)):
 RESTORE_MODES = ("nearest", "linear")
 
 
+def _clean(labels, keep_largest, fill_holes, connectivity):
+    """segment_scan's clean-up of one map: components.keep_largest, then components.fill_holes, each where asked for ->
+    (the map, the records of the steps that ran)."""
+    records = []
+    if keep_largest is not None:
+        records.append(components.keep_largest(labels, keep=keep_largest, connectivity=connectivity))
+        labels = records[-1].labels
+    if fill_holes is not None:
+        records.append(components.fill_holes(labels, classes=fill_holes, connectivity=connectivity))
+        labels = records[-1].labels
+    return labels, records
+
+
 def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1.0), target_shape=(192, 192, 192), keep_largest=None,
-                 connectivity=1, flips=None, models=None, restore="nearest", window=None, overlap=0.5, window_mode="gaussian"):
+                 connectivity=1, flips=None, models=None, restore="nearest", window=None, overlap=0.5, window_mode="gaussian",
+                 fill_holes=None):
     """A decoded scan AS STORED and its 4x4 affine -> (uint8 labels with the scan's shape and strides, uint8 labels on the
     training grid, affine of the grid).  A composition only: resample.resample_scan (CT window fused into the last store for
     '_ct' names, preprocess.preprocess_mri afterwards otherwise: the dispatch of preprocess.preprocess), predict_labels,
@@ -329,7 +343,11 @@ def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1
     window: None (the default) leaves every route above bit for bit as it is.  With a window (three ints) the grid prediction is
     predict_labels_sliding's over `models` (default: the model) and `flips` (default NO_FLIP) with `overlap` and mode
     `window_mode`; restore="linear" feeds its normalised mean probabilities to resample.restore_labels_soft; keep_largest
-    composes as above."""
+    composes as above.
+    fill_holes: None (the default) leaves every route above and what it returns as it is.  A tuple of classes: the map that
+    keep_largest cleans (the grid map for restore="nearest", the stored map for restore="linear"), after keep_largest where both
+    are given, has its enclosed holes filled by components.fill_holes(classes=fill_holes, connectivity=connectivity); that element is
+    then the filled map and the Filled record (stats, summary, status) is appended as the last element."""
     if restore not in RESTORE_MODES:
         raise Mi3dError(f"segment_scan: restore is one of {RESTORE_MODES}, got {restore!r}")
     if window is not None and window_mode not in WINDOW_MODES:
@@ -348,15 +366,15 @@ def segment_scan(model, image, affine, dataset_name, target_spacing=(1.0, 1.0, 1
     if restore == "linear":
         on_grid, votes = ensemble(grid[None, None], votes=True)
         stored = resample.restore_labels_soft(votes, affine, image)
-        if keep_largest is None:
+        if keep_largest is None and fill_holes is None:
             return stored, on_grid[0], grid_affine
-        cleaned = components.keep_largest(stored, keep=keep_largest, connectivity=connectivity)
-        return cleaned.labels, on_grid[0], grid_affine, cleaned
+        stored, records = _clean(stored, keep_largest, fill_holes, connectivity)
+        return (stored, on_grid[0], grid_affine, *records)
     if flips is None and models is None and window is None:
         on_grid = predict_labels(model, grid[None, None])[0]
     else:
         on_grid = ensemble(grid[None, None])[0]
-    if keep_largest is None:
+    if keep_largest is None and fill_holes is None:
         return resample.restore_labels(on_grid, affine, image), on_grid, grid_affine
-    cleaned = components.keep_largest(on_grid, keep=keep_largest, connectivity=connectivity)
-    return resample.restore_labels(cleaned.labels, affine, image), cleaned.labels, grid_affine, cleaned
+    on_grid, records = _clean(on_grid, keep_largest, fill_holes, connectivity)
+    return (resample.restore_labels(on_grid, affine, image), on_grid, grid_affine, *records)
