@@ -216,6 +216,65 @@ int mi3d_unet_backward_loss(const mi3d_unet_desc* d, const float* x, const void*
                             const float* coef, const float* grad_scale, const float* dgap, float gap_scale, int accumulate, int seg_begin,
                             int seg_end, void* workspace, size_t workspace_bytes, void* stream, void* aux_stream, void* const* events,
                             int aux_join);
+/* Ignore value: the loss of partly labelled volumes (torch's ignore_index; self-training on pseudo-labels, partial annotations,
+ * padded or warped-in voxels).  Every loss entry above has a `_masked` sibling that takes `int64_t ignore_index` right after
+ * `cfg` and is otherwise the same call; the entry without it is the sibling with no voxel ignored and launches the kernels it
+ * always launched (same bits).  With m_v = [t_v != ignore_index] over all N*V voxels (any value that fits int32, inside [0, C)
+ * or outside; a value beyond int32 is MI3D_EINVAL) and M_valid = sum_v m_v:
+ *   forward   CE_mean = sum_v m_v (lse_v - z_v[t_v]) / M_valid, and 0 when M_valid = 0 (a deviation: torch gives NaN there);
+ *             I_c = sum_v m_v p_c [t = c], P_c = sum_v m_v p_c, T_c = sum_v m_v [t = c]; region terms, A_c and B_c as above on
+ *             those sums.  The distillation term needs no label: it stays over ALL voxels and its divisor stays N*V*C, so a
+ *             teacher still teaches where nothing is labelled.
+ *   coef      the same 20 floats; ce_s = w_ce / M_valid (0 when M_valid = 0), kd_s unchanged.
+ *   backward  a voxel that counts: the unmasked expression.  An ignored voxel: what that expression gives with
+ *             A = B = ce_s = 0, i.e. grad_out * kd[c]; without a teacher a zero (of either sign).
+ *   metrics   n_inter, n_pred, n_label, n_correct leave the ignored voxels out; accuracy = n_correct / M_valid (0 when
+ *             M_valid = 0); the class-loop bound D stays.
+ * M_valid is not counted separately: it is sum_c T_c, the exact integer label histogram over [0, C) that the forward already
+ * takes from wave ballots (and sum_c n_label[c] for the accuracy), so a label that is neither in [0, C) nor ignore_index is
+ * outside the contract, as it is for the unmasked entries.  No float atomics, fixed-order partial rows: the same bits on
+ * every run.  Selecting a term away adds no rounding, so with no voxel ignored every output has the unmasked entry's bits.
+ * mi3d_*_supported answer for the masked entries too. */
+int mi3d_seg_loss_forward_masked(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int64_t V,
+                                 const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out, float* coef, void* workspace,
+                                 void* stream);
+int mi3d_seg_loss_backward_masked(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int64_t V,
+                                  const mi3d_loss_cfg* cfg, int64_t ignore_index, const float* coef, const float* grad_out,
+                                  float* dlogits, void* stream);
+int mi3d_seg_loss_metrics_forward_masked(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int D,
+                                         int64_t V, const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out, float* coef,
+                                         float* metrics_out, void* loss_workspace, void* metrics_workspace, void* stream);
+int mi3d_head_loss_forward_masked(const void* z, int zcs, int Cin, const float* w, const float* bias, const int64_t* labels,
+                                  const float* teacher, int N, int C, int D, int64_t V, const mi3d_loss_cfg* cfg, int64_t ignore_index,
+                                  float* loss_out, float* coef, float* metrics_out, void* loss_workspace, void* metrics_workspace,
+                                  float* logits_opt, void* stream);
+int mi3d_head_loss_backward_masked(const void* z, int zcs, int Cin, const float* w, const float* bias, const int64_t* labels,
+                                   const float* teacher, int N, int C, int64_t V, const mi3d_loss_cfg* cfg, int64_t ignore_index,
+                                   const float* coef, const float* grad_scale, void* dz, int dzcs, float* dW, float* db, int accumulate,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int mi3d_unet_forward_loss_masked(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
+                                  const float* drop_scales, int training, const int64_t* labels, const float* teacher_logits,
+                                  const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out, float* coef, float* metrics_out,
+                                  void* loss_workspace, void* metrics_workspace, float* logits_opt, float* gap_out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int mi3d_unet_head_loss_forward_masked(const mi3d_unet_desc* d, const void* const* params, const int64_t* labels,
+                                       const float* teacher_logits, const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out,
+                                       float* coef, float* metrics_out, void* loss_workspace, void* metrics_workspace, float* logits_opt,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+int mi3d_unet_backward_loss_masked(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* grads,
+                                   const float* drop_scales, const int64_t* labels, const float* teacher_logits,
+                                   const mi3d_loss_cfg* cfg, int64_t ignore_index, const float* coef, const float* grad_scale,
+                                   const float* dgap, float gap_scale, int accumulate, int seg_begin, int seg_end, void* workspace,
+                                   size_t workspace_bytes, void* stream, void* aux_stream, void* const* events, int aux_join);
+/* Pseudo-labels for self-training: from the uint8 label map and the float32 confidence map (both (N, V)) that the ensemble and
+ * sliding-window predictions return,
+ *     target[n][v] = (label < C and conf >= thresholds[label]) ? label : ignore_index          int64, what the masked loss takes
+ * A NaN confidence compares false and is ignored, and so is a label >= C.  thresholds: C <= 8 host floats, one per class.
+ * table: device int64 (N, C + 1), per sample the voxels kept per class and, last, the voxels ignored (integer adds only: exact,
+ * the same on every run).  One streaming pass, 13 bytes per voxel; groups of four voxels with 16-byte accesses where V % 4 == 0,
+ * labels is 4-byte and confidence and target are 16-byte aligned, one voxel at a time otherwise.  Nothing synchronises. */
+int mi3d_pseudo_labels(const uint8_t* labels, const float* confidence, int N, int64_t V, int C, const float* thresholds,
+                       int64_t ignore_index, int64_t* target, int64_t* table, void* stream);
 size_t mi3d_seg_metrics_workspace_bytes(int C);
 /* out: device float[3] = {iou, dice, accuracy}; D = first spatial dim (reference loop bound, metrics.py:74,101) */
 int mi3d_seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out,

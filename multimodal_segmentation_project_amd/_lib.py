@@ -129,6 +129,17 @@ _SIGS = {
     "mi3d_unet_forward_loss": (i32, [_DP, vp, vp, vp, vp, i32, vp, vp, _LP, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi3d_unet_head_loss_forward": (i32, [_DP, vp, vp, vp, _LP, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi3d_unet_backward_loss": (i32, [_DP, vp, vp, vp, vp, vp, vp, _LP, vp, vp, vp, f32, i32, i32, i32, vp, sz, vp, vp, vp, i32]),
+    "mi3d_seg_loss_forward_masked": (i32, [vp, vp, vp, i32, i32, i64, _LP, i64, vp, vp, vp, vp]),
+    "mi3d_seg_loss_backward_masked": (i32, [vp, vp, vp, i32, i32, i64, _LP, i64, vp, vp, vp, vp]),
+    "mi3d_seg_loss_metrics_forward_masked": (i32, [vp, vp, vp, i32, i32, i32, i64, _LP, i64, vp, vp, vp, vp, vp, vp]),
+    "mi3d_head_loss_forward_masked": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i64, _LP, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "mi3d_head_loss_backward_masked": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, i32, i64, _LP, i64, vp, vp, vp, i32, vp, vp, i32, vp, sz,
+                                             vp]),
+    "mi3d_unet_forward_loss_masked": (i32, [_DP, vp, vp, vp, vp, i32, vp, vp, _LP, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi3d_unet_head_loss_forward_masked": (i32, [_DP, vp, vp, vp, _LP, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi3d_unet_backward_loss_masked": (i32, [_DP, vp, vp, vp, vp, vp, vp, _LP, i64, vp, vp, vp, f32, i32, i32, i32, vp, sz, vp, vp, vp,
+                                             i32]),
+    "mi3d_pseudo_labels": (i32, [vp, vp, i32, i64, i32, C.POINTER(C.c_float), i64, vp, vp, vp]),
     "mi3d_seg_metrics_workspace_bytes": (sz, [i32]),
     "mi3d_seg_metrics": (i32, [vp, vp, i32, i32, i32, i64, vp, vp, vp]),
     "mi3d_seg_class_counts": (i32, [vp, vp, i32, i32, i64, vp, vp, vp]),

@@ -48,6 +48,10 @@ static inline LossCfg to_cfg(const mi3d_loss_cfg* c) {
     k.eps = c->eps; k.w_kd = c->w_kd; k.temp = c->temperature > 0.f ? c->temperature : 1.f;
     return k;
 }
+// the loss configuration of a *_masked entry (ops.h loss_cfg_ignore)
+#define MI3D_MASKED_CFG(k, cfg, ignore_index, what) \
+    LossCfg k = to_cfg(cfg);                        \
+    MI3D_CHECK_ARG(loss_cfg_ignore(k, ignore_index), what ": ignore_index %lld does not fit int32", (long long)(ignore_index))
 
 static inline bool use_mfma(int in_dtype, int out_dtype, int Cin, int Cout, int xcs, int ycs) {
     return in_dtype == MI3D_BF16 && out_dtype == MI3D_BF16 && conv3_mfma_supported(Cin, Cout, xcs, ycs);
@@ -74,6 +78,35 @@ int mi3d_seg_loss_backward(const float* logits, const int64_t* labels, const flo
                            void* stream) {
     MI3D_CHECK_ARG(logits && labels && cfg && coef && dlogits, "mi3d_seg_loss_backward: null pointer");
     return seg_loss_bwd(logits, labels, teacher, N, C, V, to_cfg(cfg), coef, grad_out, dlogits, (hipStream_t)stream);
+}
+// the masked siblings: the same launchers, the ignore value in the internal configuration (MASK = true instantiations)
+int mi3d_seg_loss_forward_masked(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int64_t V,
+                                 const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out, float* coef, void* workspace,
+                                 void* stream) {
+    MI3D_CHECK_ARG(logits && labels && cfg && loss_out && coef && workspace, "mi3d_seg_loss_forward_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_seg_loss_forward_masked");
+    return seg_loss_fwd(logits, labels, teacher, N, C, V, k, loss_out, coef, workspace, (hipStream_t)stream);
+}
+int mi3d_seg_loss_metrics_forward_masked(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int D,
+                                         int64_t V, const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out, float* coef,
+                                         float* metrics_out, void* loss_workspace, void* metrics_workspace, void* stream) {
+    MI3D_CHECK_ARG(logits && labels && cfg && loss_out && coef && metrics_out && loss_workspace && metrics_workspace,
+                   "mi3d_seg_loss_metrics_forward_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_seg_loss_metrics_forward_masked");
+    return seg_loss_fwd(logits, labels, teacher, N, C, V, k, loss_out, coef, loss_workspace, (hipStream_t)stream, D, metrics_out,
+                        metrics_workspace);
+}
+int mi3d_seg_loss_backward_masked(const float* logits, const int64_t* labels, const float* teacher, int N, int C, int64_t V,
+                                  const mi3d_loss_cfg* cfg, int64_t ignore_index, const float* coef, const float* grad_out,
+                                  float* dlogits, void* stream) {
+    MI3D_CHECK_ARG(logits && labels && cfg && coef && dlogits, "mi3d_seg_loss_backward_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_seg_loss_backward_masked");
+    return seg_loss_bwd(logits, labels, teacher, N, C, V, k, coef, grad_out, dlogits, (hipStream_t)stream);
+}
+int mi3d_pseudo_labels(const uint8_t* labels, const float* confidence, int N, int64_t V, int C, const float* thresholds,
+                       int64_t ignore_index, int64_t* target, int64_t* table, void* stream) {
+    MI3D_CHECK_ARG(labels && confidence && thresholds && target && table, "mi3d_pseudo_labels: null pointer");
+    return pseudo_labels(labels, confidence, N, V, C, thresholds, ignore_index, target, table, (hipStream_t)stream);
 }
 size_t mi3d_seg_metrics_workspace_bytes(int C) { return seg_metrics_ws_bytes(C); }
 int mi3d_seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out,
@@ -488,6 +521,25 @@ int mi3d_head_loss_backward(const void* z, int zcs, int Cin, const float* w, con
     MI3D_CHECK_ARG(workspace_bytes >= mi3d_conv1_workspace_bytes(Cin, C), "mi3d_head_loss_backward: workspace too small");
     return head_loss_bwd(z, zcs, Cin, w, bias, labels, teacher, C, to_cfg(cfg), coef, grad_scale, dz, dzcs, dW, db, accumulate,
                          (float*)workspace, N, V, (hipStream_t)stream);
+}
+int mi3d_head_loss_forward_masked(const void* z, int zcs, int Cin, const float* w, const float* bias, const int64_t* labels,
+                                  const float* teacher, int N, int C, int D, int64_t V, const mi3d_loss_cfg* cfg, int64_t ignore_index,
+                                  float* loss_out, float* coef, float* metrics_out, void* loss_workspace, void* metrics_workspace,
+                                  float* logits_opt, void* stream) {
+    MI3D_CHECK_ARG(z && w && labels && cfg && loss_out && coef && loss_workspace, "mi3d_head_loss_forward_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_head_loss_forward_masked");
+    return head_loss_fwd(z, zcs, Cin, w, bias, labels, teacher, N, C, V, k, loss_out, coef, loss_workspace, (hipStream_t)stream, D,
+                         metrics_out, metrics_workspace, logits_opt);
+}
+int mi3d_head_loss_backward_masked(const void* z, int zcs, int Cin, const float* w, const float* bias, const int64_t* labels,
+                                   const float* teacher, int N, int C, int64_t V, const mi3d_loss_cfg* cfg, int64_t ignore_index,
+                                   const float* coef, const float* grad_scale, void* dz, int dzcs, float* dW, float* db, int accumulate,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    MI3D_CHECK_ARG(z && w && labels && cfg && coef && dz && workspace, "mi3d_head_loss_backward_masked: null pointer");
+    MI3D_CHECK_ARG(workspace_bytes >= mi3d_conv1_workspace_bytes(Cin, C), "mi3d_head_loss_backward_masked: workspace too small");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_head_loss_backward_masked");
+    return head_loss_bwd(z, zcs, Cin, w, bias, labels, teacher, C, k, coef, grad_scale, dz, dzcs, dW, db, accumulate, (float*)workspace, N,
+                         V, (hipStream_t)stream);
 }
 int mi3d_conv1_backward(int dtype, const void* z, int zcs, int Cin, const float* w, const float* dlogits, int Cout, void* dz,
                         int dzcs, float* dW, float* db, int accumulate, int N, int64_t V, void* workspace,

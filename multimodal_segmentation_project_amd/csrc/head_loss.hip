@@ -340,11 +340,14 @@ constexpr int NQ = 2 + 3 * MAXC;   // ce, kl, I[c], P[c], T[c]
 // EXACT (C == NC) drops every `c < C` predicate, TEACH compiles the distillation term in or out, and the integer counts
 // (label histogram, argmax histogram, intersections) are wave ballots + scalar popcounts — the vector unit only does the
 // compares.  T[c] = sum [t == c] is taken from the exact label histogram instead of a float accumulator.
-template <int NC, int VV, bool METRICS, bool EXACT, bool TEACH>
+// MASK (the *_masked entries, contract: include/mi3d.h): a voxel whose label is `ign` becomes the label -1, which matches no class
+// in the I sums and the ballots, and its CE term, its P terms and its argmax are selected away; the distillation term stays.
+// The selects add no rounding, and the label histogram stays exact, so M_valid = sum_c T[c] reaches loss_scalars as an integer.
+template <int NC, int VV, bool METRICS, bool EXACT, bool TEACH, bool MASK>
 __global__ __launch_bounds__(BLK) void seg_loss_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                            const float* __restrict__ teacher, int C_, int64_t V,
                                                            float inv_t, double* __restrict__ part,
-                                                           unsigned long long* __restrict__ counts) {
+                                                           unsigned long long* __restrict__ counts, int ign) {
     const int C = EXACT ? NC : C_;
     constexpr int NQL = 2 + 3 * NC;
     __shared__ float red[4][NQL];
@@ -372,6 +375,11 @@ __global__ __launch_bounds__(BLK) void seg_loss_fwd_kernel(const float* __restri
         for (int k = 0; k < VV; k++) {
             float p[NC], lse;
             softmax_c<NC>(z[k], C, 1.f, p, lse);
+            bool scored = true;
+            if constexpr (MASK) {
+                scored = t[k] != ign;
+                t[k] = scored ? t[k] : -1;
+            }
             float zt = 0.f;
 #pragma unroll
             for (int c = 0; c < NC; c++) {
@@ -379,16 +387,19 @@ __global__ __launch_bounds__(BLK) void seg_loss_fwd_kernel(const float* __restri
                     bool is = (c == t[k]);
                     zt = is ? z[k][c] : zt;
                     q[2 + c] += is ? p[c] : 0.f;
-                    q[2 + NC + c] += p[c];
+                    if constexpr (MASK) q[2 + NC + c] += scored ? p[c] : 0.f;
+                    else q[2 + NC + c] += p[c];
                 }
             }
-            q[0] += lse - zt;
+            if constexpr (MASK) q[0] += scored ? lse - zt : 0.f;
+            else q[0] += lse - zt;
             {
                 float bvv = z[k][0];
                 int best = 0;
 #pragma unroll
                 for (int c = 1; c < NC; c++)
                     if ((EXACT || c < C) && z[k][c] > bvv) { bvv = z[k][c]; best = c; }
+                if constexpr (MASK) best = scored ? best : -1;
 #pragma unroll
                 for (int c = 0; c < NC; c++) {
                     unsigned long long mt = __ballot(t[k] == c);
@@ -479,6 +490,15 @@ __device__ __forceinline__ void loss_row_sum(const double* __restrict__ part, in
 __device__ __forceinline__ void loss_scalars(const double* sums, int N, int C, int64_t V, LossCfg cfg, float* loss_out, float* coef) {
     {
         double M = (double)N * (double)V;
+        // the divisor of the CE mean: every voxel, or with cfg.mask M_valid = sum_c T_c, the exact label histogram over [0, C)
+        // (integers below 2^53 in doubles).  M_valid = 0: the CE sum is an exact 0 and ce_s is set to 0 (mi3d.h: not torch's NaN)
+        double Mce = M;
+        if (cfg.mask) {
+            Mce = 0.0;
+            for (int c = 0; c < C; c++) Mce += sums[2 + 2 * MAXC + c];
+        }
+        const bool none_valid = cfg.mask && Mce == 0.0;
+        if (none_valid) Mce = 1.0;
         double reg = 0.0;
         double sc = C > 1 ? (double)cfg.w_reg / (double)(C - 1) : 0.0;
         for (int c = 0; c < MAXC; c++) { coef[c] = 0.f; coef[MAXC + c] = 0.f; }
@@ -500,9 +520,9 @@ __device__ __forceinline__ void loss_scalars(const double* sums, int N, int C, i
             coef[MAXC + c] = (float)(B * sc);
         }
         if (C > 1) reg /= (double)(C - 1);
-        double loss = (double)cfg.w_ce * sums[0] / M + (double)cfg.w_reg * reg +
+        double loss = (double)cfg.w_ce * sums[0] / Mce + (double)cfg.w_reg * reg +
                       (double)cfg.w_kd * (double)cfg.temp * (double)cfg.temp * sums[1] / (M * C);
-        coef[2 * MAXC + 0] = (float)((double)cfg.w_ce / M);
+        coef[2 * MAXC + 0] = none_valid ? 0.f : (float)((double)cfg.w_ce / Mce);
         coef[2 * MAXC + 1] = (float)((double)cfg.w_kd * (double)cfg.temp / (M * C));
         coef[2 * MAXC + 2] = (float)loss;
         coef[2 * MAXC + 3] = 0.f;
@@ -549,11 +569,19 @@ __device__ __forceinline__ void dlogits_voxel(const float (&z)[NC], int t, int C
     }
 }
 
-template <int NC, int VV, bool EXACT, bool TEACH>
+// The gradient of a voxel the masked entries ignore: what dlogits_voxel gives with A = B = ce_s = 0, i.e. go * kd[c] (without a
+// teacher a zero).  A select per class behind the unchanged expression: the voxels that count keep dlogits_voxel's bits.
+template <int NC>
+__device__ __forceinline__ void dlogits_ignored(bool ignored, float go, const float (&kd)[NC], float (&o)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) o[c] = ignored ? go * kd[c] : o[c];
+}
+
+template <int NC, int VV, bool EXACT, bool TEACH, bool MASK>
 __global__ __launch_bounds__(BLK) void seg_loss_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                            const float* __restrict__ teacher, int C_, int64_t V,
                                                            float inv_t, const float* __restrict__ coef,
-                                                           const float* __restrict__ grad_out, float* __restrict__ dlogits) {
+                                                           const float* __restrict__ grad_out, float* __restrict__ dlogits, int ign) {
     const int C = EXACT ? NC : C_;
     int n = blockIdx.y;
     const float* lg = logits + (int64_t)n * C * V;
@@ -586,6 +614,7 @@ __global__ __launch_bounds__(BLK) void seg_loss_bwd_kernel(const float* __restri
                 kd_voxel<NC>(ps, pt, kd_s, kd);
             }
             dlogits_voxel<NC>(z[k], t[k], C, A, B, ce_s, go, kd, o[k]);
+            if constexpr (MASK) dlogits_ignored<NC>(t[k] == ign, go, kd, o[k]);
         }
 #pragma unroll
         for (int c = 0; c < NC; c++) {
@@ -625,12 +654,15 @@ __device__ __forceinline__ void head_logits16(const bf16* __restrict__ zrow, int
 // HLW waves per workgroup: the partial rows (one per workgroup) are capped at LOSS_MAXBLK for the single-workgroup finalize, so the
 // waves a streaming pass needs to cover the memory latency come from fat workgroups (1024 threads: 32 waves per CU at 2 per CU)
 constexpr int HLW = 16;
-template <int NC, bool METRICS, bool EXACT, bool TEACH>
+// MASK: an ignored voxel is a lane past V for the CE term, the I / P sums, `best` and the ballots (scored = false, t = -1), and a
+// live one for the distillation term and logits_opt.
+template <int NC, bool METRICS, bool EXACT, bool TEACH, bool MASK>
 __global__ __launch_bounds__(HLW * 64) void head_loss_fwd_kernel(const bf16* __restrict__ zin, int zcs, int Cin, const float* __restrict__ w,
                                                             const float* __restrict__ bias, const int64_t* __restrict__ labels,
                                                             const float* __restrict__ teacher, float inv_t,
                                                             int C_, int64_t V, double* __restrict__ part,
-                                                            unsigned long long* __restrict__ counts, float* __restrict__ logits_opt) {
+                                                            unsigned long long* __restrict__ counts, float* __restrict__ logits_opt,
+                                                            int ign) {
     const int C = EXACT ? NC : C_;
     constexpr int NQL = 2 + 3 * NC;
     __shared__ float red[HLW][NQL];
@@ -674,6 +706,11 @@ __global__ __launch_bounds__(HLW * 64) void head_loss_fwd_kernel(const bf16* __r
             bool live = lv[u];
             float z[NC];
             int t = tt[u];
+            bool scored = live;                          // the voxel counts in the label-dependent sums
+            if constexpr (MASK) {
+                scored = live && t != ign;
+                t = scored ? t : -1;
+            }
             if (Cin == CINB) {
                 __attribute__((aligned(16))) bf16 row[16];
                 *reinterpret_cast<bf16x8*>(row) = zr[u][0];
@@ -699,10 +736,10 @@ __global__ __launch_bounds__(HLW * 64) void head_loss_fwd_kernel(const bf16* __r
                     bool is = (c == t);
                     zt = is ? z[c] : zt;
                     q[2 + c] += is ? p[c] : 0.f;
-                    q[2 + NC + c] += live ? p[c] : 0.f;
+                    q[2 + NC + c] += scored ? p[c] : 0.f;
                 }
             }
-            q[0] += live ? lse - zt : 0.f;
+            q[0] += scored ? lse - zt : 0.f;
             if constexpr (TEACH) {                       // the distillation term of seg_loss_fwd_kernel, teacher logits from memory
                 float ztv[NC];
 #pragma unroll
@@ -721,7 +758,7 @@ __global__ __launch_bounds__(HLW * 64) void head_loss_fwd_kernel(const bf16* __r
 #pragma unroll
             for (int c = 1; c < NC; c++)
                 if ((EXACT || c < C) && z[c] > bvv) { bvv = z[c]; best = c; }
-            if (!live) best = -1;
+            if (!scored) best = -1;
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 unsigned long long mt = __ballot(t == c);
@@ -778,13 +815,15 @@ __global__ __launch_bounds__(HLW * 64) void head_loss_fwd_kernel(const bf16* __r
 // re-derive voxel l's logits from that tile (head_logits16: the forward's bits), turn them into dL/dz with dlogits_voxel and
 // leave them in a wave-private [class][32 voxels] LDS tile, from which both MFMA operands are read where the plain kernel
 // reads the dlogits planes.  Cin = 16 (one input block), Cout <= 4.
-template <bool TEACH>
+// MASK: the ignored voxel's dlogits are selected in registers (dlogits_ignored) before they go into the tile: no LDS access more,
+// the wave-private tile protocol as it is.
+template <bool TEACH, bool MASK>
 __global__ __launch_bounds__(C1W * 64) void head_loss_bwd_mfma_kernel(const bf16* __restrict__ z, int zcs, const float* __restrict__ w,
                                                                       const float* __restrict__ bias, const int64_t* __restrict__ labels,
                                                                       const float* __restrict__ teacher, float inv_t,
                                                                       int Cout, const float* __restrict__ coef,
                                                                       const float* __restrict__ grad_out, bf16* __restrict__ dz, int dzcs,
-                                                                      int64_t V, float* __restrict__ slabs) {
+                                                                      int64_t V, float* __restrict__ slabs, int ign) {
     constexpr int NC = 4, Cin = 16;
     __shared__ __attribute__((aligned(16))) bf16 zt[C1W][2][32 * 16];
     __shared__ __attribute__((aligned(16))) float dlt[C1W][2][NC * 32];
@@ -839,6 +878,7 @@ __global__ __launch_bounds__(C1W * 64) void head_loss_bwd_mfma_kernel(const bf16
                 kd_voxel<NC>(ps, pt, kd_s, kd0);
             }
             dlogits_voxel<NC>(zl, tl, Cout, A, B, ce_s, go, kd0, o);
+            if constexpr (MASK) dlogits_ignored<NC>(tl == ign, go, kd0, o);
 #pragma unroll
             for (int c = 0; c < NC; c++) dlt[wave][hl][c * 32 + (lane & 31)] = (c < Cout && vl < V) ? o[c] : 0.f;
         }
@@ -1257,7 +1297,7 @@ __global__ __launch_bounds__(BLK) void votes_finish_kernel(float* __restrict__ a
 }
 
 __device__ __forceinline__ void count_row_sum(const unsigned long long* part, int nblk, int C, int q, int lane, unsigned long long* counts);
-__device__ __forceinline__ void metric_scalars(const unsigned long long* counts, int N, int C, int D, int64_t V, float* out);
+__device__ __forceinline__ void metric_scalars(const unsigned long long* counts, int N, int C, int D, int64_t V, float* out, int mask = 0);
 // Q1: the reference's class loop is range(1, pred.size(1)) AFTER argmax -> bound = first spatial dim D
 __device__ __forceinline__ void seg_metrics_finalize_body(const unsigned long long* part, int nblk, int N, int C,
                                                           int D, int64_t V, float* out) {
@@ -1280,7 +1320,9 @@ __device__ __forceinline__ void count_row_sum(const unsigned long long* part, in
     if (lane == 0) counts[q == 3 * C ? 3 * MAXC : (q / C) * MAXC + q % C] = s;
 }
 
-__device__ __forceinline__ void metric_scalars(const unsigned long long* counts, int N, int C, int D, int64_t V, float* out) {
+// mask (the masked loss + metrics pass): the counts leave the ignored voxels out, and accuracy divides by M_valid = sum_c n_label[c]
+// (0 when that is 0)
+__device__ __forceinline__ void metric_scalars(const unsigned long long* counts, int N, int C, int D, int64_t V, float* out, int mask) {
     float iou = 0.f, dice = 0.f;
     int valid = 0;
     for (int c = 1; c < D && c < C; c++) {
@@ -1296,6 +1338,12 @@ __device__ __forceinline__ void metric_scalars(const unsigned long long* counts,
     float dv = (float)(valid > 1 ? valid : 1);
     out[0] = iou / dv;
     out[1] = dice / dv;
+    if (mask) {
+        unsigned long long mv = 0;
+        for (int c = 0; c < C; c++) mv += counts[2 * MAXC + c];
+        out[2] = mv ? (float)((double)counts[3 * MAXC] / (double)mv) : 0.f;
+        return;
+    }
     out[2] = (float)((double)counts[3 * MAXC] / ((double)N * (double)V));
 }
 
@@ -1323,7 +1371,7 @@ __global__ __launch_bounds__(1024) void seg_loss_metrics_finalize_kernel(const d
     }
     __syncthreads();
     if (threadIdx.x == 0) loss_scalars(sums, N, C, V, cfg, loss_out, coef);
-    if (threadIdx.x == 64) metric_scalars(counts, N, C, D, V, met_out);
+    if (threadIdx.x == 64) metric_scalars(counts, N, C, D, V, met_out, cfg.mask);
 }
 
 // raw exact counts for the per-class evaluation metrics (test_model.py:242-285): out[0..C) n_inter, [C..2C) n_pred,
@@ -1430,11 +1478,12 @@ int seg_loss_fwd(const float* logits, const int64_t* labels, const float* teache
     float it = 1.f / cfg.temp;
     bool met = metrics_out && metrics_ws;
     unsigned long long* cw = (unsigned long long*)metrics_ws;
-#define SLF3(NC_, VV_, EX_, TE_)                                                                                          \
+#define SLF4(NC_, VV_, EX_, TE_, MA_)                                                                                     \
     do {                                                                                                                   \
-        if (met) seg_loss_fwd_kernel<NC_, VV_, true, EX_, TE_><<<grid, BLK, 0, s>>>(logits, labels, tch, C, V, it, (double*)ws, cw);   \
-        else seg_loss_fwd_kernel<NC_, VV_, false, EX_, TE_><<<grid, BLK, 0, s>>>(logits, labels, tch, C, V, it, (double*)ws, nullptr); \
+        if (met) seg_loss_fwd_kernel<NC_, VV_, true, EX_, TE_, MA_><<<grid, BLK, 0, s>>>(logits, labels, tch, C, V, it, (double*)ws, cw, cfg.ignore);   \
+        else seg_loss_fwd_kernel<NC_, VV_, false, EX_, TE_, MA_><<<grid, BLK, 0, s>>>(logits, labels, tch, C, V, it, (double*)ws, nullptr, cfg.ignore); \
     } while (0)
+#define SLF3(NC_, VV_, EX_, TE_) do { if (cfg.mask) SLF4(NC_, VV_, EX_, TE_, true); else SLF4(NC_, VV_, EX_, TE_, false); } while (0)
 #define SLF(NC_, VV_)                                                                                                      \
     do {                                                                                                                   \
         if (C == NC_ && tch) SLF3(NC_, VV_, true, true);                                                                  \
@@ -1446,6 +1495,7 @@ int seg_loss_fwd(const float* logits, const int64_t* labels, const float* teache
     else if (C <= 4) SLF(4, 1);
     else if (v4) SLF(MAXC, 4);
     else SLF(MAXC, 1);
+#undef SLF4
 #undef SLF3
 #undef SLF
     MI3D_LAUNCH_CHECK();
@@ -1463,7 +1513,8 @@ int seg_loss_bwd(const float* logits, const int64_t* labels, const float* teache
     bool v4 = vv4(V, logits, labels, tch) && al16(dlogits);
     dim3 grid((unsigned)per_sample_blocks(V, v4 ? 4 : 1, N, 4096), (unsigned)N);
     float it = 1.f / cfg.temp;
-#define SLB3(NC_, VV_, EX_, TE_) seg_loss_bwd_kernel<NC_, VV_, EX_, TE_><<<grid, BLK, 0, s>>>(logits, labels, tch, C, V, it, coef, grad_out, dlogits)
+#define SLB4(NC_, VV_, EX_, TE_, MA_) seg_loss_bwd_kernel<NC_, VV_, EX_, TE_, MA_><<<grid, BLK, 0, s>>>(logits, labels, tch, C, V, it, coef, grad_out, dlogits, cfg.ignore)
+#define SLB3(NC_, VV_, EX_, TE_) do { if (cfg.mask) SLB4(NC_, VV_, EX_, TE_, true); else SLB4(NC_, VV_, EX_, TE_, false); } while (0)
 #define SLB(NC_, VV_)                                                         \
     do {                                                                      \
         if (C == NC_ && tch) SLB3(NC_, VV_, true, true);                      \
@@ -1477,6 +1528,7 @@ int seg_loss_bwd(const float* logits, const int64_t* labels, const float* teache
     else SLB(MAXC, 1);
 #undef SLB
 #undef SLB3
+#undef SLB4
     MI3D_LAUNCH_CHECK();
     return 0;
 }
@@ -1709,7 +1761,8 @@ int head_loss_fwd(const void* z, int zcs, int Cin, const float* w, const float* 
     bool met = metrics_out && metrics_ws;
     unsigned long long* cw = (unsigned long long*)metrics_ws;
     const bf16* zp = (const bf16*)z;
-#define HLF3(ME_, EX_, TE_) head_loss_fwd_kernel<4, ME_, EX_, TE_><<<grid, HLW * 64, 0, s>>>(zp, zcs, Cin, w, bias, labels, tch, it, C, V, (double*)ws, cw, logits_opt)
+#define HLF4(ME_, EX_, TE_, MA_) head_loss_fwd_kernel<4, ME_, EX_, TE_, MA_><<<grid, HLW * 64, 0, s>>>(zp, zcs, Cin, w, bias, labels, tch, it, C, V, (double*)ws, cw, logits_opt, cfg.ignore)
+#define HLF3(ME_, EX_, TE_) do { if (cfg.mask) HLF4(ME_, EX_, TE_, true); else HLF4(ME_, EX_, TE_, false); } while (0)
 #define HLF(ME_, EX_) do { if (tch) HLF3(ME_, EX_, true); else HLF3(ME_, EX_, false); } while (0)
     if (met && C == 4) HLF(true, true);
     else if (met) HLF(true, false);
@@ -1717,6 +1770,7 @@ int head_loss_fwd(const void* z, int zcs, int Cin, const float* w, const float* 
     else HLF(false, false);
 #undef HLF
 #undef HLF3
+#undef HLF4
     MI3D_LAUNCH_CHECK();
     if (met) seg_loss_metrics_finalize_kernel<<<1, 1024, 0, s>>>((const double*)ws, cw, bx * N, N, C, D, V, cfg, loss_out, coef, metrics_out);
     else seg_loss_finalize_kernel<<<1, 1024, 0, s>>>((const double*)ws, bx * N, N, C, V, cfg, loss_out, coef);
@@ -1738,8 +1792,12 @@ int head_loss_bwd(const void* z, int zcs, int Cin, const float* w, const float* 
     int bx = capb / N < 1 ? 1 : capb / N;
     if (bx > want) bx = (int)want;
     dim3 grid((unsigned)bx, (unsigned)N, 1);
-    if (tch) head_loss_bwd_mfma_kernel<true><<<grid, C1W * 64, 0, s>>>((const bf16*)z, zcs, w, bias, labels, tch, it, C, coef, grad_out, (bf16*)dz, dzcs, V, ws);
-    else head_loss_bwd_mfma_kernel<false><<<grid, C1W * 64, 0, s>>>((const bf16*)z, zcs, w, bias, labels, nullptr, it, C, coef, grad_out, (bf16*)dz, dzcs, V, ws);
+#define HLB(TE_, MA_) head_loss_bwd_mfma_kernel<TE_, MA_><<<grid, C1W * 64, 0, s>>>((const bf16*)z, zcs, w, bias, labels, tch, it, C, coef, grad_out, (bf16*)dz, dzcs, V, ws, cfg.ignore)
+    if (tch && cfg.mask) HLB(true, true);
+    else if (tch) HLB(true, false);
+    else if (cfg.mask) HLB(false, true);
+    else HLB(false, false);
+#undef HLB
     MI3D_LAUNCH_CHECK();
     if (pend) { *pend = slab_job_make(0, ws, bx * N, nW + C, nW, dW, db, Cin, C, accumulate); return 0; }
     return slab_reduce(ws, bx * N, nW + C, nW, dW, db, accumulate, s);

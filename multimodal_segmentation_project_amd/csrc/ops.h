@@ -385,7 +385,16 @@ struct LossCfg {
     float alpha, beta, eps;
     float w_kd;       // weight of T^2 * mean_{n,c,v} KL(teacher || student)   (0 = no distillation)
     float temp;
+    int mask = 0;     // the *_masked entries: voxels labelled `ignore` are left out of CE, the region sums and the metric counts
+    int ignore = 0;   // (contract: include/mi3d.h, "Ignore value"); mask = 0 is the unmasked kernels, bit for bit
 };
+// cfg with the ignore value of a *_masked entry; false: the value does not fit int32 (the entry answers MI3D_EINVAL)
+inline bool loss_cfg_ignore(LossCfg& k, int64_t ignore_index) {
+    if (ignore_index < INT32_MIN || ignore_index > INT32_MAX) return false;
+    k.mask = 1;
+    k.ignore = (int)ignore_index;
+    return true;
+}
 enum { MI3D_MAX_CLASSES = 8 };
 size_t seg_loss_ws_bytes(int C);
 // loss_out: device float[1]; coef: device float[2*MI3D_MAX_CLASSES + 4] consumed by seg_loss_bwd
@@ -404,6 +413,10 @@ int head_loss_fwd(const void* z, int zcs, int Cin, const float* w, const float* 
 int head_loss_bwd(const void* z, int zcs, int Cin, const float* w, const float* bias, const int64_t* labels, const float* teacher, int C,
                   LossCfg cfg, const float* coef, const float* grad_out, void* dz, int dzcs, float* dW, float* db, int accumulate,
                   float* ws, int N, int64_t V, hipStream_t s, SlabJob* pend = nullptr);
+// pseudo-labels of a prediction for the masked loss (pseudo_labels.hip; contract: include/mi3d.h mi3d_pseudo_labels);
+// thresholds: C host floats, table: device int64 (N, C + 1)
+int pseudo_labels(const uint8_t* labels, const float* conf, int N, int64_t V, int C, const float* thresholds, int64_t ignore_index,
+                  int64_t* target, int64_t* table, hipStream_t s);
 size_t seg_metrics_ws_bytes(int C);
 // out: device float[3] = {iou, dice, acc}; Q1 loop bound = first spatial dim D (utils/metrics.py:74,101)
 int seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out, void* ws,

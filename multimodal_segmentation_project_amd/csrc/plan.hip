@@ -760,6 +760,10 @@ static LossCfg cfg_of(const mi3d_loss_cfg* c) {
     k.w_kd = c->w_kd; k.temp = c->temperature > 0.f ? c->temperature : 1.f;
     return k;
 }
+// the loss configuration of a *_masked entry (ops.h loss_cfg_ignore)
+#define MI3D_MASKED_CFG(k, cfg, ignore_index, what) \
+    LossCfg k = cfg_of(cfg);                        \
+    MI3D_CHECK_ARG(loss_cfg_ignore(k, ignore_index), what ": ignore_index %lld does not fit int32", (long long)(ignore_index))
 
 static int unet_forward_impl(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
                       const float* drop_scales, int training, float* logits, float* gap_out, void* workspace,
@@ -806,22 +810,38 @@ static int unet_forward_impl(const mi3d_unet_desc* d, const float* x, const void
     return 0;
 }
 
-extern "C" {
-
 // head + loss on the decoder output the last mi3d_unet_forward / mi3d_unet_infer (logits = NULL) left in this workspace
-int mi3d_unet_head_loss_forward(const mi3d_unet_desc* d, const void* const* params, const int64_t* labels, const float* teacher_logits,
-                                const mi3d_loss_cfg* cfg, float* loss_out, float* coef, float* metrics_out, void* loss_workspace,
-                                void* metrics_workspace, float* logits_opt, void* workspace, size_t workspace_bytes, void* stream) {
+static int unet_head_loss_forward_impl(const mi3d_unet_desc* d, const void* const* params, const int64_t* labels, const float* teacher_logits,
+                                       LossCfg k, float* loss_out, float* coef, float* metrics_out, void* loss_workspace,
+                                       void* metrics_workspace, float* logits_opt, void* workspace, size_t workspace_bytes, void* stream) {
     Plan p;
     Ctx c{p};
-    MI3D_TRY(enter(c, p, d, "mi3d_unet_head_loss_forward", labels && cfg && loss_out && coef && loss_workspace, params, workspace,
+    MI3D_TRY(enter(c, p, d, "mi3d_unet_head_loss_forward", labels && loss_out && coef && loss_workspace, params, workspace,
                    workspace_bytes, stream));
-    LossCfg k = cfg_of(cfg);
     MI3D_CHECK_ARG(head_loss_ok(p.dt, c.at(p.zd[p.L - 1]), p.C[0], p.C[0], d->out_channels, k),
                    "mi3d_unet_head_loss_forward: no fused head + loss for this configuration (see mi3d_unet_head_loss_supported)");
     return head_loss_fwd(c.at(p.zd[p.L - 1]), p.C[0], p.C[0], c.P(p.final_pidx()), c.P(p.final_pidx() + 1), labels, teacher_logits, d->N,
                          d->out_channels, p.geo[0].V(), k, loss_out, coef, loss_workspace, c.s, d->D, metrics_out, metrics_workspace,
                          logits_opt);
+}
+
+extern "C" {
+
+int mi3d_unet_head_loss_forward(const mi3d_unet_desc* d, const void* const* params, const int64_t* labels, const float* teacher_logits,
+                                const mi3d_loss_cfg* cfg, float* loss_out, float* coef, float* metrics_out, void* loss_workspace,
+                                void* metrics_workspace, float* logits_opt, void* workspace, size_t workspace_bytes, void* stream) {
+    MI3D_CHECK_ARG(cfg, "mi3d_unet_head_loss_forward: null pointer");
+    return unet_head_loss_forward_impl(d, params, labels, teacher_logits, cfg_of(cfg), loss_out, coef, metrics_out, loss_workspace,
+                                       metrics_workspace, logits_opt, workspace, workspace_bytes, stream);
+}
+int mi3d_unet_head_loss_forward_masked(const mi3d_unet_desc* d, const void* const* params, const int64_t* labels,
+                                       const float* teacher_logits, const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out,
+                                       float* coef, float* metrics_out, void* loss_workspace, void* metrics_workspace, float* logits_opt,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    MI3D_CHECK_ARG(cfg, "mi3d_unet_head_loss_forward_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_unet_head_loss_forward_masked");
+    return unet_head_loss_forward_impl(d, params, labels, teacher_logits, k, loss_out, coef, metrics_out, loss_workspace,
+                                       metrics_workspace, logits_opt, workspace, workspace_bytes, stream);
 }
 
 // head + argmax (+ per-sample counts) on that same decoder output: the sibling of mi3d_unet_head_loss_forward for inference
@@ -877,6 +897,16 @@ int mi3d_unet_forward_loss(const mi3d_unet_desc* d, const float* x, const void* 
                            void* stream) {
     MI3D_CHECK_ARG(labels && cfg && loss_out && coef && loss_workspace, "mi3d_unet_forward_loss: null pointer");
     HeadLoss hl{labels, cfg_of(cfg), loss_out, coef, metrics_out, loss_workspace, metrics_workspace, nullptr, teacher_logits};
+    return unet_forward_impl(d, x, params, buffers, drop_scales, training, logits_opt, gap_out, workspace, workspace_bytes, stream, &hl);
+}
+int mi3d_unet_forward_loss_masked(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* buffers,
+                                  const float* drop_scales, int training, const int64_t* labels, const float* teacher_logits,
+                                  const mi3d_loss_cfg* cfg, int64_t ignore_index, float* loss_out, float* coef, float* metrics_out,
+                                  void* loss_workspace, void* metrics_workspace, float* logits_opt, float* gap_out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    MI3D_CHECK_ARG(labels && cfg && loss_out && coef && loss_workspace, "mi3d_unet_forward_loss_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_unet_forward_loss_masked");
+    HeadLoss hl{labels, k, loss_out, coef, metrics_out, loss_workspace, metrics_workspace, nullptr, teacher_logits};
     return unet_forward_impl(d, x, params, buffers, drop_scales, training, logits_opt, gap_out, workspace, workspace_bytes, stream, &hl);
 }
 
@@ -1056,6 +1086,17 @@ int mi3d_unet_backward_loss(const mi3d_unet_desc* d, const float* x, const void*
                             int aux_join) {
     MI3D_CHECK_ARG(labels && cfg && coef, "mi3d_unet_backward_loss: null pointer");
     HeadLoss hl{labels, cfg_of(cfg), nullptr, const_cast<float*>(coef), nullptr, nullptr, nullptr, grad_scale, teacher_logits};
+    return unet_backward_impl(d, x, params, grads, drop_scales, nullptr, dgap, gap_scale, accumulate, seg_begin, seg_end, workspace,
+                              workspace_bytes, stream, aux_stream, events, aux_join, &hl);
+}
+int mi3d_unet_backward_loss_masked(const mi3d_unet_desc* d, const float* x, const void* const* params, void* const* grads,
+                                   const float* drop_scales, const int64_t* labels, const float* teacher_logits,
+                                   const mi3d_loss_cfg* cfg, int64_t ignore_index, const float* coef, const float* grad_scale,
+                                   const float* dgap, float gap_scale, int accumulate, int seg_begin, int seg_end, void* workspace,
+                                   size_t workspace_bytes, void* stream, void* aux_stream, void* const* events, int aux_join) {
+    MI3D_CHECK_ARG(labels && cfg && coef, "mi3d_unet_backward_loss_masked: null pointer");
+    MI3D_MASKED_CFG(k, cfg, ignore_index, "mi3d_unet_backward_loss_masked");
+    HeadLoss hl{labels, k, nullptr, const_cast<float*>(coef), nullptr, nullptr, nullptr, grad_scale, teacher_logits};
     return unet_backward_impl(d, x, params, grads, drop_scales, nullptr, dgap, gap_scale, accumulate, seg_begin, seg_end, workspace,
                               workspace_bytes, stream, aux_stream, events, aux_join, &hl);
 }

@@ -112,29 +112,35 @@ HEAD_VOTES_WINDOW = "mi3d_unet_head_votes_window"      # Plan.head_votes_window'
 
 class LossGroup:
     """What the loss calls share: the configuration, metrics = {loss, iou, dice, acc, ...} (device float[n_metrics]; the loss
-    is written to [0], the three metrics to [1:4]), the 20 loss coefficients the backward reads, and the two workspaces."""
+    is written to [0], the three metrics to [1:4]), the 20 loss coefficients the backward reads, and the two workspaces.
+    ignore_index (None: every voxel counts): the label value the loss and the metrics leave out; the calls then go to the
+    `_masked` entries (include/mi3d.h, "Ignore value"), which take it right after the configuration."""
 
-    def __init__(self, cfg, classes, device, n_metrics=4):
+    def __init__(self, cfg, classes, device, n_metrics=4, ignore_index=None):
         lib = _lib.lib()
         self.cfg = cfg
+        self.ignore_index = ignore_index
+        self.masked = "" if ignore_index is None else "_masked"                      # suffix of every loss entry
+        self.cfg_args = (C.byref(cfg),) if ignore_index is None else (C.byref(cfg), int(ignore_index))
         self.metrics = torch.empty(n_metrics, dtype=torch.float32, device=device)
         self.coef = torch.empty(_lib.LOSS_COEF_FLOATS, dtype=torch.float32, device=device)
         self.loss_ws = torch.empty(lib.mi3d_seg_loss_workspace_bytes(classes), dtype=torch.uint8, device=device)
         self.met_ws = torch.empty(lib.mi3d_seg_metrics_workspace_bytes(classes), dtype=torch.uint8, device=device)
         m = self.metrics.data_ptr()
         self.cfg_ref = C.byref(cfg)
-        self.fwd = (self.cfg_ref, m, ptr(self.coef), m + 4, ptr(self.loss_ws), ptr(self.met_ws))      # as every forward takes them
+        self.fwd = (*self.cfg_args, m, ptr(self.coef), m + 4, ptr(self.loss_ws), ptr(self.met_ws))      # as every forward takes them
 
     def metrics_forward(self, logits, labels, *, teacher=None, stream):
         """Loss + metrics of (N, C, D, H, W) float logits in one pass (mi3d_seg_loss_metrics_forward)."""
         n, c, d = logits.shape[:3]
-        call("mi3d_seg_loss_metrics_forward", ptr(logits), ptr(labels), ptr(teacher), n, c, d, logits.numel() // (n * c), *self.fwd, stream)
+        call("mi3d_seg_loss_metrics_forward" + self.masked, ptr(logits), ptr(labels), ptr(teacher), n, c, d, logits.numel() // (n * c),
+             *self.fwd, stream)
 
     def backward(self, logits, labels, dlogits, *, teacher=None, grad_scale, stream):
         """dlogits = grad_scale[0] * d loss / d logits (mi3d_seg_loss_backward) from the coefficients the forward left."""
         n, c = logits.shape[:2]
-        call("mi3d_seg_loss_backward", ptr(logits), ptr(labels), ptr(teacher), n, c, logits.numel() // (n * c), self.cfg_ref, ptr(self.coef),
-             ptr(grad_scale), ptr(dlogits), stream)
+        call("mi3d_seg_loss_backward" + self.masked, ptr(logits), ptr(labels), ptr(teacher), n, c, logits.numel() // (n * c),
+             *self.cfg_args, ptr(self.coef), ptr(grad_scale), ptr(dlogits), stream)
 
 
 class Plan:
@@ -185,11 +191,11 @@ class Plan:
         call("mi3d_unet_infer", self.d, ptr(x), self.ptab, self.btab, ptr(logits), ptr(gap), self.ws_ptr, self.ws_bytes, stream)
 
     def forward_loss(self, x, loss, *, drop=None, training=TRAIN, labels, teacher=None, logits=None, gap=None, stream):
-        call("mi3d_unet_forward_loss", self.d, ptr(x), self.ptab, self.btab, ptr(drop), training, ptr(labels), ptr(teacher),
+        call("mi3d_unet_forward_loss" + loss.masked, self.d, ptr(x), self.ptab, self.btab, ptr(drop), training, ptr(labels), ptr(teacher),
              *loss.fwd, ptr(logits), ptr(gap), self.ws_ptr, self.ws_bytes, stream)
 
     def head_loss_forward(self, loss, *, labels, teacher=None, logits=None, stream):
-        call("mi3d_unet_head_loss_forward", self.d, self.ptab, ptr(labels), ptr(teacher), *loss.fwd, ptr(logits),
+        call("mi3d_unet_head_loss_forward" + loss.masked, self.d, self.ptab, ptr(labels), ptr(teacher), *loss.fwd, ptr(logits),
              self.ws_ptr, self.ws_bytes, stream)
 
     def backward(self, x, *, drop=None, dlogits=None, dgap=None, gap_scale=1.0, accumulate=0, start, end, stream, aux=None,
@@ -199,7 +205,7 @@ class Plan:
 
     def backward_loss(self, x, loss, *, drop=None, labels, teacher=None, grad_scale, dgap=None, gap_scale=1.0, accumulate=0,
                       start, end, stream, aux=None, events=None, join=1):
-        call("mi3d_unet_backward_loss", self.d, ptr(x), self.ptab, self.gtab, ptr(drop), ptr(labels), ptr(teacher), loss.cfg_ref,
+        call("mi3d_unet_backward_loss" + loss.masked, self.d, ptr(x), self.ptab, self.gtab, ptr(drop), ptr(labels), ptr(teacher), *loss.cfg_args,
              ptr(loss.coef), ptr(grad_scale), ptr(dgap), gap_scale, accumulate, start, end, self.ws_ptr, self.ws_bytes, stream,
              aux, events, join)
 

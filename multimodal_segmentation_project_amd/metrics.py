@@ -10,6 +10,9 @@
 pred (N,C,D,H,W) float, target (N,1,D,H,W) int64 -> 0-dim tensor, differentiable w.r.t. pred.  Each loss is ONE
 streaming forward kernel (+ a tiny finalize) and ONE backward kernel; the three metrics share ONE pass.
 Nothing here synchronises with the host: results stay on the device until the caller reads them.
+ignore_index (the six losses and get_loss_fn; None = every voxel counts, the calls made without it): voxels labelled with it
+are left out of the CE mean (divisor: the voxels that count), of the region sums and of the gradient, torch's ignore_index;
+the distillation term stays over every voxel.  Contract: include/mi3d.h, "Ignore value".
 Deviation (documented): when no foreground class is present the reference returns the Python number 0 / 0.0;
 here a 0-dim tensor holding 0.0 is returned (same value through torch.as_tensor(.) / float(.)).
 """
@@ -50,16 +53,20 @@ def _prep(pred, target):
 
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pred, labels, teacher, cfg, n, c, v):
+    def forward(ctx, pred, labels, teacher, cfg, n, c, v, ignore_index=None):
         p32 = pred.detach().contiguous().float()
         t32 = teacher.detach().contiguous().float() if teacher is not None else None
         dev = pred.device
         loss = torch.empty((), dtype=torch.float32, device=dev)
         coef = torch.empty(_lib.LOSS_COEF_FLOATS, dtype=torch.float32, device=dev)
         ws = torch.empty(_lib.lib().mi3d_seg_loss_workspace_bytes(c), dtype=torch.uint8, device=dev)
-        call("mi3d_seg_loss_forward", ptr(p32), ptr(labels), ptr(t32), n, c, v, C.byref(cfg), ptr(loss), ptr(coef),
-             ptr(ws), stream_ptr())
-        ctx.cfg, ctx.dims, ctx.in_dtype = cfg, (n, c, v), pred.dtype
+        if ignore_index is None:
+            call("mi3d_seg_loss_forward", ptr(p32), ptr(labels), ptr(t32), n, c, v, C.byref(cfg), ptr(loss), ptr(coef),
+                 ptr(ws), stream_ptr())
+        else:
+            call("mi3d_seg_loss_forward_masked", ptr(p32), ptr(labels), ptr(t32), n, c, v, C.byref(cfg), ignore_index, ptr(loss),
+                 ptr(coef), ptr(ws), stream_ptr())
+        ctx.cfg, ctx.dims, ctx.in_dtype, ctx.ignore_index = cfg, (n, c, v), pred.dtype, ignore_index
         ctx.save_for_backward(p32, labels, t32, coef)
         return loss
 
@@ -69,61 +76,78 @@ class _SegLossFn(torch.autograd.Function):
         n, c, v = ctx.dims
         g = g.contiguous().float()
         d = torch.empty_like(p32)
-        call("mi3d_seg_loss_backward", ptr(p32), ptr(labels), ptr(t32), n, c, v, C.byref(ctx.cfg), ptr(coef), ptr(g),
-             ptr(d), stream_ptr())
+        if ctx.ignore_index is None:
+            call("mi3d_seg_loss_backward", ptr(p32), ptr(labels), ptr(t32), n, c, v, C.byref(ctx.cfg), ptr(coef), ptr(g),
+                 ptr(d), stream_ptr())
+        else:
+            call("mi3d_seg_loss_backward_masked", ptr(p32), ptr(labels), ptr(t32), n, c, v, C.byref(ctx.cfg), ctx.ignore_index,
+                 ptr(coef), ptr(g), ptr(d), stream_ptr())
         if ctx.in_dtype != torch.float32:
             d = d.to(ctx.in_dtype)
-        return d, None, None, None, None, None, None
+        return d, None, None, None, None, None, None, None
 
 
-def _seg_loss(pred, target, cfg, teacher=None):
+def check_ignore_index(ignore_index):
+    """None, or the value as a Python int (the library refuses one that does not fit int32)."""
+    if ignore_index is None:
+        return None
+    if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index:
+        raise _lib.Mi3dError(f"ignore_index must be an integer or None, got {ignore_index!r}")
+    return int(ignore_index)
+
+
+def _seg_loss(pred, target, cfg, teacher=None, ignore_index=None):
     n, c, v, labels = _prep(pred, target)
-    return _SegLossFn.apply(pred, labels, teacher, cfg, n, c, v)
+    ignore_index = check_ignore_index(ignore_index)
+    if ignore_index is None:
+        return _SegLossFn.apply(pred, labels, teacher, cfg, n, c, v)
+    return _SegLossFn.apply(pred, labels, teacher, cfg, n, c, v, ignore_index)
 
 
-def combined_loss(pred, target):
+def combined_loss(pred, target, ignore_index=None):
     """CE(mean) + mean_{c>=1}(1 - (2 I_c + 1e-5)/(P_c + T_c + 1e-5))   [utils/metrics.py:14-40]"""
-    return _seg_loss(pred, target, _cfg(*_KINDS["combined"]))
+    return _seg_loss(pred, target, _cfg(*_KINDS["combined"]), ignore_index=ignore_index)
 
 
-def dice_only_loss(pred, target):
+def dice_only_loss(pred, target, ignore_index=None):
     """The 'dice' variant of get_loss_fn [train_unet.py:186-198]."""
-    return _seg_loss(pred, target, _cfg(*_KINDS["dice"]))
+    return _seg_loss(pred, target, _cfg(*_KINDS["dice"]), ignore_index=ignore_index)
 
 
-def tversky_loss(pred, target, alpha=0.5, beta=0.5, epsilon=1e-6):
+def tversky_loss(pred, target, alpha=0.5, beta=0.5, epsilon=1e-6, ignore_index=None):
     """[utils/metrics.py:137-156]"""
-    return _seg_loss(pred, target, _cfg(0.0, 2, 1.0, alpha, beta, epsilon))
+    return _seg_loss(pred, target, _cfg(0.0, 2, 1.0, alpha, beta, epsilon), ignore_index=ignore_index)
 
 
-def combined_ce_tversky_loss(pred, target, alpha=0.7, beta=0.3):
+def combined_ce_tversky_loss(pred, target, alpha=0.7, beta=0.3, ignore_index=None):
     """0.3*CE + 0.7*Tversky(alpha,beta)   [utils/metrics.py:158-167]"""
-    return _seg_loss(pred, target, _cfg(0.3, 2, 0.7, alpha, beta, 1e-6))
+    return _seg_loss(pred, target, _cfg(0.3, 2, 0.7, alpha, beta, 1e-6), ignore_index=ignore_index)
 
 
-def cross_entropy_loss(pred, target):
+def cross_entropy_loss(pred, target, ignore_index=None):
     """Mean CE.  (The reference's get_loss_fn('ce') hands a (B,1,...) target to nn.CrossEntropyLoss and raises —
     SURVEY Q5; here both (B,1,...) and (B,...) targets work.)"""
-    return _seg_loss(pred, target, _cfg(1.0, 0, 0.0, 0.0, 0.0, 1e-6))
+    return _seg_loss(pred, target, _cfg(1.0, 0, 0.0, 0.0, 0.0, 1e-6), ignore_index=ignore_index)
 
 
-def distillation_loss(student_logits, teacher_logits, target, alpha=0.7, temperature=2.0):
+def distillation_loss(student_logits, teacher_logits, target, alpha=0.7, temperature=2.0, ignore_index=None):
     """alpha*(0.3 CE + 0.7 Tversky(0.7,0.3)) + (1-alpha)*T^2*mean_{n,c,v} KL(teacher||student)  [metrics.py:169-190]"""
     cfg = _cfg(0.3 * alpha, 2, 0.7 * alpha, 0.7, 0.3, 1e-6, 1.0 - alpha, temperature)
-    return _seg_loss(student_logits, target, cfg, teacher=teacher_logits)
+    return _seg_loss(student_logits, target, cfg, teacher=teacher_logits, ignore_index=ignore_index)
 
 
-def get_loss_fn(loss_type):
+def get_loss_fn(loss_type, ignore_index=None):
     """Mirror of train_unet.py:178-205."""
+    ig = check_ignore_index(ignore_index)
     if loss_type == "ce":
-        return cross_entropy_loss
+        return cross_entropy_loss if ig is None else (lambda pred, target: cross_entropy_loss(pred, target, ignore_index=ig))
     if loss_type == "tversky":
-        return lambda pred, target: tversky_loss(pred, target, alpha=0.5, beta=0.5)
+        return lambda pred, target: tversky_loss(pred, target, alpha=0.5, beta=0.5, ignore_index=ig)
     if loss_type == "dice":
-        return dice_only_loss
+        return dice_only_loss if ig is None else (lambda pred, target: dice_only_loss(pred, target, ignore_index=ig))
     if loss_type == "ce_tversky":
-        return lambda pred, target: combined_ce_tversky_loss(pred, target, alpha=0.5, beta=0.5)
-    return combined_loss
+        return lambda pred, target: combined_ce_tversky_loss(pred, target, alpha=0.5, beta=0.5, ignore_index=ig)
+    return combined_loss if ig is None else (lambda pred, target: combined_loss(pred, target, ignore_index=ig))
 
 
 # ---- metrics: one pass for all three, shared through a 1-entry cache ---------------------------------------

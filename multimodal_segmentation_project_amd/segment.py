@@ -4,6 +4,8 @@ test_model.py:242-309 (model(image), torch.argmax(outputs, dim=1), the per-sampl
   predict_labels(model, x, target=None)         uint8 (N, D, H, W) label map, and with a target the exact per-sample counts
   predict_labels_ensemble(models, x, flips)     the label map of the softmax average over mirrored views and / or several models
   predict_labels_sliding(models, x, window)     the same outputs from overlapping windows blended with a Gaussian importance map
+  pseudo_labels(models, x, threshold)           the confident voxels of such a prediction as an int64 training target, the rest
+                                                set to an ignore value (self-training: TrainStep(ignore_index=...).step takes it)
   per_sample_dice_iou(counts, classes)          [{class: (dice, iou)}] per sample from those counts (test_model.py:265-276)
   segment_scan(model, image, affine, dataset)   a scan as stored -> its label map as stored: resample, predict, restore; the restore
                                                 is the order-0 gather of the label map ("nearest") or, from the votes, the order-1
@@ -295,6 +297,49 @@ def predict_labels_sliding(models, x, window=(96, 96, 96), overlap=0.5, mode="ga
     if votes:
         result.append(mean)
     return result[0] if len(result) == 1 else tuple(result)
+
+
+def pseudo_labels_from(labels, confidence, n_classes, threshold=0.9, ignore_index=255):
+    """The pseudo-label pass alone (mi3d_pseudo_labels) on a uint8 label map and its float32 confidence map, both (N, D, H, W):
+    target (N, 1, D, H, W) int64 = the label where confidence >= threshold[label], else ignore_index, and the int64 table
+    (N, C + 1) of the voxels kept per class and, last, ignored per sample.  threshold: a float or one float per class.  A NaN
+    confidence is ignored.  Nothing synchronises."""
+    what = "pseudo_labels"
+    _lib.require_cuda(labels, what)
+    _lib.require_cuda(confidence, what)
+    if labels.dtype != torch.uint8 or confidence.dtype != torch.float32 or labels.shape != confidence.shape or labels.dim() < 2:
+        raise Mi3dError(f"{what}: expected a uint8 label map and a float32 confidence map of one shape (N, ...), got "
+                        f"{labels.dtype} {tuple(labels.shape)} and {confidence.dtype} {tuple(confidence.shape)}")
+    c = int(n_classes)
+    thr = [float(threshold)] * c if isinstance(threshold, (int, float)) else [float(t) for t in threshold]
+    if len(thr) != c:
+        raise Mi3dError(f"{what}: {len(thr)} thresholds for {c} classes")
+    ignore_index = metrics.check_ignore_index(ignore_index)
+    if ignore_index is None:
+        raise Mi3dError(f"{what}: ignore_index is required")
+    labels, confidence = labels.contiguous(), confidence.contiguous()
+    n = labels.shape[0]
+    target = torch.empty((n, 1) + tuple(labels.shape[1:]), dtype=torch.int64, device=labels.device)
+    table = torch.empty((n, c + 1), dtype=torch.int64, device=labels.device)
+    _lib.call("mi3d_pseudo_labels", _lib.ptr(labels), _lib.ptr(confidence), n, labels.numel() // n, c, (_lib.f32 * c)(*thr), ignore_index,
+              _lib.ptr(target), _lib.ptr(table), stream_ptr())
+    return target, table
+
+
+def pseudo_labels(models, x, threshold=0.9, ignore_index=255, flips=NO_FLIP, window=None, **sliding_kw):
+    """Self-training targets on an unlabelled batch: predict with predict_labels_ensemble(confidence=True), or with
+    predict_labels_sliding(window=window, **sliding_kw) when a window is given, keep the voxels whose confidence reaches the
+    threshold of their class and set the others to ignore_index (pseudo_labels_from).  Returns (target int64 (N, 1, D, H, W),
+    table int64 (N, C + 1)); the target is what TrainStep(ignore_index=ignore_index).step(x, target) takes.  The models are in
+    eval() mode, as for every prediction here.  Quantile or class-balanced thresholds are not offered."""
+    if window is None:
+        if sliding_kw:
+            raise Mi3dError(f"pseudo_labels: {sorted(sliding_kw)} belong to a sliding-window prediction (give window=...)")
+        labels, conf = predict_labels_ensemble(models, x, flips=flips, confidence=True)
+    else:
+        labels, conf = predict_labels_sliding(models, x, window=window, flips=flips, confidence=True, **sliding_kw)
+    first = models[0] if isinstance(models, (list, tuple)) else models
+    return pseudo_labels_from(labels, conf, first.final_conv.out_channels, threshold, ignore_index)
 
 
 def per_sample_dice_iou(counts, classes=(1, 2, 3)):

@@ -240,7 +240,7 @@ class _StepBase:
         st.L = desc.n_levels
         st.x = torch.empty(shape, dtype=torch.float32, device=dev)
         st.y = torch.empty((desc.N, desc.D * desc.H * desc.W), dtype=torch.int64, device=dev)
-        st.loss = engine.LossGroup(cfg, desc.out_channels, dev, self._n_metrics)
+        st.loss = engine.LossGroup(cfg, desc.out_channels, dev, self._n_metrics, ignore_index=getattr(self, "ignore_index", None))
         st.metrics = st.loss.metrics
         st.logits_shape = (desc.N, desc.out_channels, desc.D, desc.H, desc.W)
         keep = True
@@ -440,7 +440,7 @@ class TrainStep(_StepBase):
     def __init__(self, model, loss="combined", lr=1e-3, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8,
                  grad_accum=1, kd_teacher=None, kd_alpha=0.7, kd_temperature=2.0, process_group=None,
                  compute_dtype=None, use_graph=False, aux_wgrad=None, reference_zero_grad_quirk=False,
-                 force_comm=False, overlap_teacher=True, keep_logits=False):
+                 force_comm=False, overlap_teacher=True, keep_logits=False, ignore_index=None):
         """aux_wgrad: the backward's critical path is the input-gradient chain alone -- the weight gradients of the decoder's
         full-resolution convs and of all deep-level convs run on a second stream (include/mi3d.h, mi3d_unet_backward: aux_stream),
         forked from the chain at most three times and joined in front of the optimizer; bit-identical results.  None (default):
@@ -448,12 +448,16 @@ class TrainStep(_StepBase):
         queues and replays it at half speed (4.4 vs 2.2 ms, profiles/r04_defer_graph_streams.txt), eager launches do not.
         keep_logits: the step folds the 1x1x1 head into the loss and never writes the logits (mi3d_unet_forward_loss); True
         keeps a copy in the static buffer `logits` for callers that read them after step().
+        ignore_index: voxels labelled with this value count neither in the loss (CE mean over the voxels that do, region sums,
+        gradient) nor in the metrics, in step() and evaluate(), on both head routes, eager and under use_graph; with kd_teacher the
+        distillation term stays over every voxel (include/mi3d.h, "Ignore value").  None (default): the step as it always was.
         reference_zero_grad_quirk: train_unet.py:222 / finetune_ct.py:161 call optimizer.zero_grad() INSIDE
         accelerator.accumulate(), where accelerate only really zeroes on the boundary micro-step -> the gradient the
         reference applies is grad(last micro-batch)/accum.  False (default): accumulate all micro-batches
         (what distill_unet.py:114-115 does and what the flag's name promises); True: reproduce the reference's
         train/finetune behaviour bit for bit (non-boundary micro-steps still run forward, BN statistics and metrics)."""
         cfg = _loss_cfg(loss, kd_alpha if kd_teacher is not None else None, kd_temperature)     # validates the name first
+        self.ignore_index = M.check_ignore_index(ignore_index)      # read by _new_state when the loss group is made
         self._init_common(model, lr, weight_decay, betas, eps, grad_accum, process_group, compute_dtype, use_graph,
                           force_comm)
         self.teacher = kd_teacher
