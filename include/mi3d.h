@@ -275,6 +275,30 @@ int mi3d_unet_backward_loss_masked(const mi3d_unet_desc* d, const float* x, cons
  * labels is 4-byte and confidence and target are 16-byte aligned, one voxel at a time otherwise.  Nothing synchronises. */
 int mi3d_pseudo_labels(const uint8_t* labels, const float* confidence, int N, int64_t V, int C, const float* thresholds,
                        int64_t ignore_index, int64_t* target, int64_t* table, void* stream);
+/* The boundary loss of Kervadec et al. (MIDL 2019): a surface term beside the overlap losses above.  logits (N, C, V) float32,
+ * C <= 8; phi (N, K, V) float32, the signed distance maps of the target (mi3d_signed_distance_maps); channels: a HOST array of K
+ * distinct logit channels in [0, C), map k belongs to channel channels[k].  labels (N, V) int64 and ignore_index (a HOST int64,
+ * read before the call returns): both, or both NULL = every voxel counts.  weight: a host float.  grad_scale: device float[1] or
+ * NULL = 1 (the pointer the other backward calls take).  loss_out: device float[1].  dlogits (N, C, V) float32, or NULL for the
+ * value alone.  flags: MI3D_BD_ADD_LOSS adds to *loss_out instead of storing, MI3D_BD_ADD_GRAD adds into dlogits instead of storing.
+ *   p = softmax over the C logits of a voxel
+ *   t(x) = sum_{k<K} p[channels[k]] phi[k]                                   0 at an ignored voxel
+ *   L    = sum_n sum_x t(x) / (N K V)                                        *loss_out (+)= weight L
+ *   dlogits[j](x) (+)= grad_scale weight p_j (phi~_j - t(x)) / (N K V)       phi~_j = phi[k] if j = channels[k], else 0
+ *                      0, or untouched (bit for bit) under MI3D_BD_ADD_GRAD, at an ignored voxel
+ * The divisor is N K V WHETHER OR NOT voxels are ignored: an ignored voxel contributes nothing and the mean stays over the volume.
+ * This is deliberate and unlike the masked CE above, which divides by the voxels that count: the gradient of a voxel then needs
+ * no global count, so value and gradient leave one pass over the logits, which can run behind the loss kernels without touching
+ * them.  The sum is taken in double from the per-voxel float32 terms through fixed slots added in a fixed order by a second tiny
+ * launch: no float atomics, the same bits on every run.  16-byte accesses, four voxels per thread, where V % 4 == 0 and logits, phi,
+ * dlogits and labels are 16-byte aligned; one voxel at a time otherwise.  Every argument is checked before the first launch; nothing
+ * allocates or synchronises.  workspace: mi3d_boundary_loss_workspace_bytes(N, V) bytes, 8-byte aligned. */
+#define MI3D_BD_ADD_LOSS 1
+#define MI3D_BD_ADD_GRAD 2
+size_t mi3d_boundary_loss_workspace_bytes(int N, int64_t V);
+int mi3d_boundary_loss(const float* logits, const float* phi, int N, int C, int K, int64_t V, const int32_t* channels, const int64_t* labels,
+                       const int64_t* ignore_index, float weight, const float* grad_scale, float* loss_out, float* dlogits, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream);
 size_t mi3d_seg_metrics_workspace_bytes(int C);
 /* out: device float[3] = {iou, dice, accuracy}; D = first spatial dim (reference loop bound, metrics.py:74,101) */
 int mi3d_seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out,
@@ -676,6 +700,27 @@ int mi3d_surface_distances(const void* pred, int pred_dtype, int64_t pred_stride
                            int64_t target_stride_h, int64_t target_stride_w, int N, int D, int H, int W, int connectivity, int n_classes,
                            const int32_t* class_values, const double* spacing, double q, int n_tol, const double* tol_mm,
                            int64_t* counts_out, double* table_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Signed distance maps of a target, what the boundary loss (mi3d_boundary_loss) multiplies the probabilities with; replaces the two
+ * scipy.ndimage.distance_transform_edt calls per class and sample of Kervadec's one_hot2dist.  labels: as above (N samples through
+ * element strides, uint8 or int64).  class_values: a HOST array of n_classes (1..8) distinct int32 values; N * n_classes <= 65535.
+ * inner_offset: a HOST double >= 0.  Per sample and listed class c, with M = (labels == c):
+ *   a = sqrt(g3(x, M))       the distance of x to the nearest voxel of the class            (double, correctly rounded)
+ *   b = sqrt(g3(x, ~M))      the distance of x to the nearest voxel outside the class
+ *   phi[x] = (float)a                            x outside M
+ *   phi[x] = (float)(0 - (b - inner_offset))     x inside M      (a zero is +0)
+ *   phi[x] = 0                                   wherever the distance it needs is +inf: an absent class and a class that fills its
+ *                                                sample both give an all-zero map (scipy measures to a phantom voxel there)
+ * one rounding of the double to float32.  Off those two cases this is one_hot2dist with `sampling`,
+ * edt(~M) * ~M - (edt(M) - 1) * M, when inner_offset = 1; at another spacing the smallest of the three spacings is the largest
+ * offset that keeps phi <= 0 inside the class.  phi_out: float32, contiguous (N, n_classes, D, H, W).  One sweep of the w and h
+ * passes over N * n_classes * 2 jobs; the last pass takes the d pass of the one direction a voxel needs.  The same bits on every run
+ * and for every dense layout of the same map; nothing allocates or synchronises; every argument is checked before the first launch.
+ * workspace: mi3d_signed_distance_workspace_bytes bytes (34 per voxel and map, rounded up), 256-byte aligned; 0 (and an error)
+ * outside the domain above. */
+size_t mi3d_signed_distance_workspace_bytes(int N, int D, int H, int W, int n_classes);
+int mi3d_signed_distance_maps(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d,
+                              int64_t stride_h, int64_t stride_w, int n_classes, const int32_t* class_values, const double* spacing,
+                              double inner_offset, float* phi_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Spatial augmentation of ONE (C, D, H, W) sample: random_flip (np.flip over axes 1, 2, 3, utils/dataloader.py:207-213) and
  * random_rotate (scipy.ndimage.rotate(reshape=False, mode='nearest') in one plane, order=1 image / order=0 label, :215-221)

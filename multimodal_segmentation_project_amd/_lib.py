@@ -45,6 +45,7 @@ PREVIEW_STACK, PREVIEW_ONE, PREVIEW_THREE = 0, 1, 2      # mi3d_slice_minmax / m
 OVERLAY_F64, OVERLAY_F32, OVERLAY_U8 = 0, 1, 2
 COMPONENTS_TILE, COMPONENTS_MAX_CLASSES, COMPONENTS_MAX_KEEP = 8, 8, 8      # MI3D_COMPONENTS_*
 SURFACE_MAX_TOLERANCES, SURFACE_COUNT_COLUMNS, SURFACE_TABLE_COLUMNS = 4, 10, 8      # MI3D_SURFACE_*
+BD_ADD_LOSS, BD_ADD_GRAD = 1, 2                    # MI3D_BD_* (mi3d_boundary_loss flags)
 ELASTIC_MAX_RADIUS = 32                            # MI3D_ELASTIC_MAX_RADIUS
 PAD_BORDER, PAD_ZEROS = 0, 1                       # MI3D_PAD_*
 PATCH_BLOCK = 4096                                 # MI3D_PATCH_BLOCK
@@ -140,6 +141,8 @@ _SIGS = {
     "mi3d_unet_backward_loss_masked": (i32, [_DP, vp, vp, vp, vp, vp, vp, _LP, i64, vp, vp, vp, f32, i32, i32, i32, vp, sz, vp, vp, vp,
                                              i32]),
     "mi3d_pseudo_labels": (i32, [vp, vp, i32, i64, i32, C.POINTER(C.c_float), i64, vp, vp, vp]),
+    "mi3d_boundary_loss_workspace_bytes": (sz, [i32, i64]),
+    "mi3d_boundary_loss": (i32, [vp, vp, i32, i32, i32, i64, _IP, vp, C.POINTER(C.c_int64), f32, vp, vp, vp, i32, vp, sz, vp]),
     "mi3d_seg_metrics_workspace_bytes": (sz, [i32]),
     "mi3d_seg_metrics": (i32, [vp, vp, i32, i32, i32, i64, vp, vp, vp]),
     "mi3d_seg_class_counts": (i32, [vp, vp, i32, i32, i64, vp, vp, vp]),
@@ -190,6 +193,9 @@ _SIGS = {
     "mi3d_surface_mask": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, vp, vp]),
     "mi3d_surface_distances": (i32, [vp, i32, i64, i64, i64, i64, vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32,
                                      C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double, i32, C.POINTER(C.c_double), vp, vp, vp, sz, vp]),
+    "mi3d_signed_distance_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "mi3d_signed_distance_maps": (i32, [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                        C.c_double, vp, vp, sz, vp]),
     "mi3d_plane_affine": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp]),
     "mi3d_elastic_workspace_bytes": (sz, [i32, i32, i32]),
     "mi3d_elastic_field": (i32, [vp, i32, i32, i32, C.c_uint64, C.POINTER(C.c_double), i32, vp, sz, vp]),

@@ -11,6 +11,9 @@
 //                  each tolerance and per-workgroup sums of sqrt(g3) in fixed slots                      partial sums
 //   select         one workgroup per (sample, direction): the partial sums in a fixed order, and a    -> table
 //                  radix select (8 digits of 8 bits, histogram in LDS) of the two order statistics
+//   signed maps    mi3d_signed_distance_maps: per (sample, listed class) the class mask and its inverse as the     -> phi, float32
+//                  features of ONE sweep of the w and h passes (maps x 2 jobs); the last pass takes the d pass of
+//                  the one direction a voxel needs, the root, the sign and the offset, and rounds to float32 once
 // Everything in g is IEEE double with every operation rounded on its own (contraction is off in this file).  g3 is the
 // minimum of the candidate expressions themselves, not the parabola a real-valued envelope picks: the outward walk of the h and d
 // passes evaluates every candidate that can be smaller and stops at offset k only when fl((s k)^2) >= best; rounding is monotone
@@ -186,6 +189,40 @@ __global__ __launch_bounds__(BLK) void query_kernel(const double* __restrict__ i
         atomicAdd(counts + blockIdx.y * row_stride + 2 + blockIdx.z * MAXT + threadIdx.x, (u64)within[threadIdx.x]);
 }
 
+// ---- signed distance maps -----------------------------------------------------------------------------------------------------------
+// The features of mi3d_signed_distance_maps, one thread per voxel: per (sample, listed class j) the class mask (inside) and its
+// inverse (outside), each (N * n_classes, V) bytes, the feat0 / feat1 of the w pass with `match` 1.  grid: x over voxels, y = sample.
+template <typename T>
+__global__ __launch_bounds__(BLK) void class_masks_kernel(const T* __restrict__ lab, Vol vol, Classes cl, uint8_t* __restrict__ inside,
+                                                          uint8_t* __restrict__ outside) {
+    const int64_t V = vol.V(), i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (i >= V) return;
+    int d, h, w;
+    vol.split(i, d, h, w);
+    const int c = class_index(cl, (int64_t)lab[blockIdx.y * vol.sn + vol.offset(d, h, w)]);
+#pragma unroll
+    for (int j = 0; j < MAXC; j++)
+        if (j < cl.n) {
+            const int64_t at = ((int64_t)blockIdx.y * cl.n + j) * V + i;
+            inside[at] = (uint8_t)(j == c), outside[at] = (uint8_t)(j != c);
+        }
+}
+
+// The last pass of mi3d_signed_distance_maps: the d pass of the ONE direction a voxel needs (inside the class the distance to the
+// outside, job 2 m + 1; outside it the distance to the class, job 2 m), its root, the sign and the offset, one rounding to float32.
+// A distance of +inf (the class, or its complement, is empty in the sample) gives 0.  grid: x over voxels, y = map m = sample *
+// n_classes + class.  in (2 maps, V), phi (maps, V).
+__global__ __launch_bounds__(BLK) void signed_kernel(const double* __restrict__ in, const uint8_t* __restrict__ inside, int64_t V, int64_t stride,
+                                                     int L, double s, double inner_offset, float* __restrict__ phi) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x, m = blockIdx.y;
+    if (i >= V) return;
+    const bool in_class = inside[m * V + i] != 0;
+    const double g = line_min(in + (2 * m + (in_class ? 1 : 0)) * V, i, stride, (int)(i / stride % L), L, s);
+    const double root = sqrt(g);
+    const double v = g == inf() ? 0.0 : in_class ? 0.0 - (root - inner_offset) : root;          // 0 - x: a zero is +0
+    phi[m * V + i] = (float)v;
+}
+
 // ---- select -----------------------------------------------------------------------------------------------------------------------
 // One workgroup per (sample, direction).  The sum: thread t adds the partials t, t + 256, ... in that order, then the fixed tree.
 // The order statistics of n values at lo = floor((n - 1) q) and hi = ceil((n - 1) q): eight passes over the list, most significant
@@ -273,6 +310,19 @@ struct Workspace {
         pred = ar.take<uint8_t>((size_t)N * V), target = ar.take<uint8_t>((size_t)N * V);
         a = ar.take<double>((size_t)N * V * 2), b = ar.take<double>((size_t)N * V * 2);
         partial = ar.take<double>((size_t)(2 * N * voxel_blocks(V))), state = ar.take<u64>((size_t)N * 4);
+        bytes = ar.used;
+    }
+};
+
+// mi3d_signed_distance_maps: the two feature bytemaps and two buffers of doubles, each per (map, direction, voxel)
+struct SignedWorkspace {
+    uint8_t *inside, *outside;
+    double *a, *b;
+    size_t bytes;
+    SignedWorkspace(void* base, int64_t maps, int64_t V) {
+        Arena ar{static_cast<char*>(base)};
+        inside = ar.take<uint8_t>((size_t)maps * V), outside = ar.take<uint8_t>((size_t)maps * V);
+        a = ar.take<double>((size_t)maps * V * 2), b = ar.take<double>((size_t)maps * V * 2);
         bytes = ar.used;
     }
 };
@@ -388,6 +438,49 @@ int mi3d_surface_distances(const void* pred, int pred_dtype, int64_t pred_stride
                                             (int64_t)n_classes * TABLE);
         MI3D_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+size_t mi3d_signed_distance_workspace_bytes(int N, int D, int H, int W, int n_classes) {
+    const int64_t NV = total_voxels(N, D, H, W);
+    if (NV == 0 || n_classes < 1 || n_classes > MAXC || (int64_t)N * n_classes > 65535) {
+        mi3d_set_error("mi3d_signed_distance_workspace_bytes: N >= 1, sides >= 1, D * H * W < 2^31, 1 to %d classes and N * n_classes <= 65535 "
+                       "expected", MAXC);
+        return 0;
+    }
+    return SignedWorkspace(nullptr, (int64_t)N * n_classes, NV / N).bytes;
+}
+
+int mi3d_signed_distance_maps(const void* labels, int label_dtype, int N, int D, int H, int W, int64_t stride_n, int64_t stride_d,
+                              int64_t stride_h, int64_t stride_w, int n_classes, const int32_t* class_values, const double* spacing,
+                              double inner_offset, float* phi_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* name = "mi3d_signed_distance_maps";
+    MI3D_TRY(check_map(name, "labels", labels, label_dtype, stride_n, stride_d, stride_h, stride_w));
+    MI3D_TRY(check_sizes(name, N, D, H, W));
+    Classes cl{};
+    MI3D_TRY(check_classes(name, n_classes, class_values, cl));
+    MI3D_CHECK_ARG((int64_t)N * n_classes <= 65535, "%s: N * n_classes = %lld maps, at most 65535", name, (long long)N * n_classes);
+    MI3D_TRY(check_spacing(name, spacing));
+    MI3D_CHECK_ARG(std::isfinite(inner_offset) && inner_offset >= 0.0, "%s: inner_offset %g is not a finite number >= 0", name, inner_offset);
+    MI3D_CHECK_ARG(phi_out && ((uintptr_t)phi_out & 3) == 0, "%s: phi_out must be a non-null, 4-byte aligned pointer", name);
+    const Vol vol{N, D, H, W, stride_n, stride_d, stride_h, stride_w};
+    const int64_t V = vol.V(), maps = (int64_t)N * n_classes;
+    const SignedWorkspace ws(workspace, maps, V);
+    MI3D_TRY(check_workspace(name, workspace, workspace_bytes, ws.bytes));
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)voxel_blocks(V);
+    dim3 lgrid(blocks, (unsigned)N), vgrid(blocks, (unsigned)maps, 2), rgrid((unsigned)cdiv((int64_t)D * H, NW), (unsigned)maps, 2),
+        sgrid(blocks, (unsigned)maps);
+    dispatch_src(label_dtype, LabelTypes(),
+                 [&](auto tag) { class_masks_kernel<<<lgrid, BLK, 0, s>>>((const decltype(tag)*)labels, vol, cl, ws.inside, ws.outside); });
+    MI3D_LAUNCH_CHECK();
+    // one sweep over maps x 2 jobs: job 2 m the distance to the class (features: inside), job 2 m + 1 to its complement
+    w_kernel<<<rgrid, BLK, 0, s>>>(ws.inside, ws.outside, 1, (int64_t)D * H, W, spacing[2], ws.a);
+    MI3D_LAUNCH_CHECK();
+    line_kernel<<<vgrid, BLK, 0, s>>>(ws.a, ws.b, V, W, H, spacing[1]);
+    MI3D_LAUNCH_CHECK();
+    signed_kernel<<<sgrid, BLK, 0, s>>>(ws.b, ws.inside, V, (int64_t)H * W, D, spacing[0], inner_offset, phi_out);
+    MI3D_LAUNCH_CHECK();
     return 0;
 }
 

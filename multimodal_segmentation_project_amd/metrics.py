@@ -6,6 +6,7 @@
   distillation_loss(student, teacher, target, a, T)    :169-190
   calculate_iou / calculate_dice / calculate_accuracy  :65-129  (incl. the reference's class-loop bound)
   get_loss_fn(loss_type)                               train_unet.py:178-205
+  boundary_loss(pred, dist, classes, ...)              not in the reference: Kervadec et al., MIDL 2019 (include/mi3d.h)
 
 pred (N,C,D,H,W) float, target (N,1,D,H,W) int64 -> 0-dim tensor, differentiable w.r.t. pred.  Each loss is ONE
 streaming forward kernel (+ a tiny finalize) and ONE backward kernel; the three metrics share ONE pass.
@@ -148,6 +149,84 @@ def get_loss_fn(loss_type, ignore_index=None):
     if loss_type == "ce_tversky":
         return lambda pred, target: combined_ce_tversky_loss(pred, target, alpha=0.5, beta=0.5, ignore_index=ig)
     return combined_loss if ig is None else (lambda pred, target: combined_loss(pred, target, ignore_index=ig))
+
+
+# ---- boundary loss (Kervadec et al., MIDL 2019): a surface term beside the overlap losses ---------------------------------
+def check_channels(classes, c, what):
+    """The listed logit channels as a tuple of distinct ints inside [0, c)."""
+    try:
+        ch = tuple(int(k) for k in classes)
+    except (TypeError, ValueError):
+        raise _lib.Mi3dError(f"{what}: classes {classes!r} is not a sequence of integers") from None
+    if not ch or any(isinstance(k, bool) or int(k) != k for k in classes):
+        raise _lib.Mi3dError(f"{what}: classes {classes!r} is not a non-empty sequence of integers")
+    if len(set(ch)) != len(ch) or not all(0 <= k < c for k in ch):
+        raise _lib.Mi3dError(f"{what}: classes {ch} are distinct logit channels in [0, {c})")
+    return ch
+
+
+def boundary_term(logits, dist, channels, *, labels=None, ignore_index=None, weight=1.0, grad_scale=None, loss_out, dlogits=None, flags=0,
+                  workspace, stream):
+    """One mi3d_boundary_loss call on float32 (N, C, ...) logits and (N, K, ...) maps: the argument order of include/mi3d.h."""
+    n, c = logits.shape[:2]
+    k = len(channels)
+    ig = None if ignore_index is None else C.byref(C.c_int64(int(ignore_index)))
+    call("mi3d_boundary_loss", ptr(logits), ptr(dist), n, c, k, logits.numel() // (n * c), _lib.int_table(channels), ptr(labels), ig,
+         float(weight), ptr(grad_scale), ptr(loss_out), ptr(dlogits), flags, ptr(workspace), workspace.numel(), stream)
+
+
+def boundary_workspace(n, v, device):
+    nbytes = _lib.lib().mi3d_boundary_loss_workspace_bytes(n, v)
+    if nbytes == 0:
+        _lib.check(-1, "mi3d_boundary_loss_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+class _BoundaryLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, dist, channels, labels, ignore_index):
+        p32 = pred.detach().contiguous().float()
+        n, c = p32.shape[:2]
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        grad = torch.empty_like(p32) if ctx.needs_input_grad[0] else None         # value and gradient leave one pass
+        ws = boundary_workspace(n, p32.numel() // (n * c), pred.device)
+        boundary_term(p32, dist, channels, labels=labels, ignore_index=ignore_index, loss_out=loss, dlogits=grad, workspace=ws,
+                      stream=stream_ptr())
+        ctx.grad, ctx.in_dtype = grad, pred.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d = ctx.grad * g.float()
+        if ctx.in_dtype != torch.float32:
+            d = d.to(ctx.in_dtype)
+        return d, None, None, None, None
+
+
+def boundary_loss(pred, dist, classes=(1, 2, 3), target=None, ignore_index=None):
+    """mean over n, k, voxels of softmax(pred)[:, classes[k]] * dist[:, k]: the boundary loss, to be added to an overlap loss with a
+    weight that is raised over the epochs, `combined_loss(pred, y) + alpha * boundary_loss(pred, dist)`.  pred (N, C, D, H, W)
+    float, C <= 8; dist float32 (N, K, D, H, W), what surface.signed_distance_maps returned for the same `classes`; constant (no
+    gradient flows to it).  target and ignore_index, both or neither: voxels labelled ignore_index add nothing to the sum and get no
+    gradient; the mean stays over all N K V terms (include/mi3d.h, mi3d_boundary_loss).  One pass gives value and gradient."""
+    what = "boundary_loss"
+    _lib.require_cuda(pred, what)
+    if pred.dim() < 3:
+        raise _lib.Mi3dError(f"{what}: pred must be (N, C, spatial...), got {tuple(pred.shape)}")
+    n, c = pred.shape[:2]
+    ch = check_channels(classes, c, what)
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.device != pred.device:
+        raise _lib.Mi3dError(f"{what}: dist is a float32 tensor on {pred.device} (surface.signed_distance_maps)")
+    if tuple(dist.shape) != (n, len(ch)) + tuple(pred.shape[2:]):
+        raise _lib.Mi3dError(f"{what}: dist {tuple(dist.shape)} does not fit pred {tuple(pred.shape)} with {len(ch)} classes")
+    ignore_index = check_ignore_index(ignore_index)
+    if (target is None) != (ignore_index is None):
+        raise _lib.Mi3dError(f"{what}: target and ignore_index come together or not at all")
+    labels = None
+    if target is not None:
+        _lib.require_cuda(target, what)
+        labels = _prep(pred, target)[3]
+    return _BoundaryLossFn.apply(pred, dist.detach().contiguous(), ch, labels, ignore_index)
 
 
 # ---- metrics: one pass for all three, shared through a 1-entry cache ---------------------------------------

@@ -9,6 +9,7 @@ M = (labels == c), and distances from scipy.ndimage.distance_transform_edt(~surf
   surface_mask(labels, cls, connectivity=1)                   uint8, 1 on the surface of labels == cls
   surface_distances(pred, target, classes=(1, 2, 3), ...)     SurfaceStats(counts, table, classes, percentile, tolerances)
   surface_metrics(stats)                                      per sample {class: {"hd", "hd95", "assd", "nsd", "n_pred", "n_target"}}
+  signed_distance_maps(labels, classes=(1, 2, 3), ...)        float32 (..., K, D, H, W): the maps of the boundary loss
 
 A map is (D, H, W) or (N, D, H, W), N independent samples, uint8 (segment.predict_labels' output) or int64 (a target), dense with
 any strides per sample; spacing is (sd, sh, sw) in mm per voxel.  The squared distance is defined separably in float64 (g1, g2, g3
@@ -109,14 +110,7 @@ def surface_distances(pred, target, classes=(1, 2, 3), spacing=None, affine=None
     t, tcode, _ = _samples(target, what)
     if pred.shape != target.shape:
         raise Mi3dError(f"{what}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
-    try:
-        classes = tuple(_class(c, what) for c in classes)
-    except TypeError:
-        raise Mi3dError(f"{what}: classes {classes!r} is not a sequence of integers") from None
-    if not 1 <= len(classes) <= MAX_CLASSES:
-        raise Mi3dError(f"{what}: 1 to {MAX_CLASSES} classes can be listed, got {len(classes)}")
-    if len(set(classes)) != len(classes):
-        raise Mi3dError(f"{what}: a class is listed twice in {classes!r}")
+    classes = _classes(classes, what)
     s = _spacing(spacing, affine, what)
     connectivity = _connectivity(connectivity, what)
     try:
@@ -144,6 +138,56 @@ def surface_distances(pred, target, classes=(1, 2, 3), spacing=None, affine=None
          (C.c_int32 * nc)(*classes), (C.c_double * 3)(*s), percentile / 100.0, len(tolerances), (C.c_double * max(len(tolerances), 1))(*tolerances),
          ptr(counts), ptr(table), ptr(ws), nbytes, stream_ptr())
     return SurfaceStats(counts[0] if single else counts, table[0] if single else table, classes, percentile, tolerances)
+
+
+def _classes(classes, what):
+    try:
+        classes = tuple(_class(c, what) for c in classes)
+    except TypeError:
+        raise Mi3dError(f"{what}: classes {classes!r} is not a sequence of integers") from None
+    if not 1 <= len(classes) <= MAX_CLASSES:
+        raise Mi3dError(f"{what}: 1 to {MAX_CLASSES} classes can be listed, got {len(classes)}")
+    if len(set(classes)) != len(classes):
+        raise Mi3dError(f"{what}: a class is listed twice in {classes!r}")
+    return classes
+
+
+def signed_distance_maps(labels, classes=(1, 2, 3), spacing=None, affine=None, inner_offset=None):
+    """The signed distance map of every listed class of a target, what metrics.boundary_loss and TrainStep(boundary_weight=...)
+    multiply the probabilities with (Kervadec et al., MIDL 2019): float32 (..., K, D, H, W) for labels (D, H, W), (N, D, H, W) or
+    (N, 1, D, H, W), uint8 or int64 with any dense strides per sample.  Per class, with M = (labels == c): outside M the distance in
+    mm to the nearest voxel of the class, inside M minus (the distance to the nearest voxel outside it - inner_offset); an absent
+    class and a class that fills its sample give an all-zero map (include/mi3d.h, mi3d_signed_distance_maps).  Off those two cases
+    this is one_hot2dist's edt(~M, sampling) * ~M - (edt(M, sampling) - 1) * M when inner_offset is 1.  inner_offset=None: the
+    smallest of the three spacings, which is 1 at unit spacing and at any other the largest offset with phi <= 0 inside the class
+    (a literal 1 at 0.75 mm gives +0.25 there).  spacing / affine: as surface_distances.  Every argument is checked before the
+    first launch; nothing synchronises; the same bits on every run and for every layout of the same map."""
+    what = "signed_distance_maps"
+    five = isinstance(labels, torch.Tensor) and labels.dim() == 5
+    if five:
+        if labels.shape[1] != 1:
+            raise Mi3dError(f"{what}: labels {tuple(labels.shape)}: a 5-D map is (N, 1, D, H, W)")
+        labels = labels[:, 0]
+    t, code, single = _samples(labels, what)
+    classes = _classes(classes, what)
+    s = _spacing(spacing, affine, what)
+    if inner_offset is None:
+        inner_offset = min(s)
+    try:
+        inner_offset = float(inner_offset)
+    except (TypeError, ValueError):
+        raise Mi3dError(f"{what}: inner_offset {inner_offset!r} is not a number") from None
+    if not (math.isfinite(inner_offset) and inner_offset >= 0.0):
+        raise Mi3dError(f"{what}: inner_offset {inner_offset} is not a finite number >= 0")
+    _lib.require_cuda(t, what)
+    nc = len(classes)
+    nbytes = _workspace("mi3d_signed_distance_workspace_bytes", t, what, nc)
+    # everything is checked: allocate and launch
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+    out = torch.empty((t.shape[0], nc) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
+    call("mi3d_signed_distance_maps", ptr(t), code, *t.shape, *_strides(t), nc, (C.c_int32 * nc)(*classes), (C.c_double * 3)(*s), inner_offset,
+         ptr(out), ptr(ws), nbytes, stream_ptr())
+    return out[0] if single else out
 
 
 def _directed(n, table, q):

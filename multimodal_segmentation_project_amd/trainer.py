@@ -24,12 +24,13 @@ Design (MI355X-first, not a DDP translation):
   * no host synchronisation inside step(); results are device tensors.
 """
 import ctypes as C
+import math
 import os
 
 import torch
 import torch.distributed as dist
 
-from . import _lib, engine
+from . import _lib, engine, surface
 from ._lib import Mi3dError, call, ptr, ptr_table, stream_ptr
 from .engine import BN_PUBLISH, THIN_CONSUMERS, TRAIN
 from . import metrics as M
@@ -48,6 +49,16 @@ def _loss_cfg(kind, kd_alpha=None, temperature=2.0):
     if kind not in _LOSS_TABLE:
         raise Mi3dError(f"unknown loss {kind!r}: one of {sorted(_LOSS_TABLE)} (train_unet.py:538 --loss choices)")
     return M._cfg(*_LOSS_TABLE[kind])
+
+
+def _finite_weight(value):
+    try:
+        value = float(value)
+    except (TypeError, ValueError):
+        raise Mi3dError(f"boundary_weight {value!r} is not a number") from None
+    if not math.isfinite(value):
+        raise Mi3dError(f"boundary_weight {value} is not finite")
+    return value
 
 
 def _priority_stream(device, cls):
@@ -440,7 +451,8 @@ class TrainStep(_StepBase):
     def __init__(self, model, loss="combined", lr=1e-3, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8,
                  grad_accum=1, kd_teacher=None, kd_alpha=0.7, kd_temperature=2.0, process_group=None,
                  compute_dtype=None, use_graph=False, aux_wgrad=None, reference_zero_grad_quirk=False,
-                 force_comm=False, overlap_teacher=True, keep_logits=False, ignore_index=None):
+                 force_comm=False, overlap_teacher=True, keep_logits=False, ignore_index=None, boundary_weight=None,
+                 boundary_classes=(1, 2, 3), boundary_spacing=(1, 1, 1)):
         """aux_wgrad: the backward's critical path is the input-gradient chain alone -- the weight gradients of the decoder's
         full-resolution convs and of all deep-level convs run on a second stream (include/mi3d.h, mi3d_unet_backward: aux_stream),
         forked from the chain at most three times and joined in front of the optimizer; bit-identical results.  None (default):
@@ -451,6 +463,16 @@ class TrainStep(_StepBase):
         ignore_index: voxels labelled with this value count neither in the loss (CE mean over the voxels that do, region sums,
         gradient) nor in the metrics, in step() and evaluate(), on both head routes, eager and under use_graph; with kd_teacher the
         distillation term stays over every voxel (include/mi3d.h, "Ignore value").  None (default): the step as it always was.
+        boundary_weight: a float (0.0 included) adds boundary_weight * the boundary loss of Kervadec et al. (include/mi3d.h,
+        mi3d_boundary_loss) over the logit channels boundary_classes to the loss and its gradient to the logits' gradient, one
+        pass directly behind the loss backward.  The step then keeps head and loss apart (fused_head is False: the logits have to
+        exist).  The signed distance maps are the static buffer `dist`: given to step() / load_batch() as dist=, or computed
+        from the labels at boundary_spacing (mm per voxel; surface.signed_distance_maps) right after the load, outside any
+        captured graph.  The property boundary_weight may be raised between epochs; like lr it is a kernel argument, so a
+        captured graph is captured again.  The returned loss is overlap + boundary_weight * L, undivided by the accumulation
+        count like the rest; ignored voxels add nothing to L, the distillation term is untouched.  Out of scope: evaluate()
+        keeps reporting the overlap loss alone, DannStep has no such term, and the term is not folded into the fused head +
+        loss pass.  None (default): no new buffer, no new launch, the step as it always was.
         reference_zero_grad_quirk: train_unet.py:222 / finetune_ct.py:161 call optimizer.zero_grad() INSIDE
         accelerator.accumulate(), where accelerate only really zeroes on the boundary micro-step -> the gradient the
         reference applies is grad(last micro-batch)/accum.  False (default): accumulate all micro-batches
@@ -458,6 +480,11 @@ class TrainStep(_StepBase):
         train/finetune behaviour bit for bit (non-boundary micro-steps still run forward, BN statistics and metrics)."""
         cfg = _loss_cfg(loss, kd_alpha if kd_teacher is not None else None, kd_temperature)     # validates the name first
         self.ignore_index = M.check_ignore_index(ignore_index)      # read by _new_state when the loss group is made
+        self._boundary_weight, self.boundary_classes, self.boundary_spacing = None, None, None
+        if boundary_weight is not None:
+            self._boundary_weight = _finite_weight(boundary_weight)
+            self.boundary_classes = M.check_channels(boundary_classes, 8, "TrainStep")      # against the head's channels in _extend
+            self.boundary_spacing = surface._spacing(boundary_spacing, None, "TrainStep")
         self._init_common(model, lr, weight_decay, betas, eps, grad_accum, process_group, compute_dtype, use_graph,
                           force_comm)
         self.teacher = kd_teacher
@@ -521,11 +548,39 @@ class TrainStep(_StepBase):
         self._statics = {}
         self._static = None
 
+    @property
+    def boundary_weight(self):
+        return self._boundary_weight
+
+    @boundary_weight.setter
+    def boundary_weight(self, value):
+        """The weight of the boundary term; only a step built with one has the term (and the buffers) to weigh."""
+        if self._boundary_weight is None:
+            raise Mi3dError("TrainStep was built without boundary_weight: the step has no boundary term to weigh")
+        self._boundary_weight = _finite_weight(value)
+
+    def _hyper(self):
+        return super()._hyper() + (self._boundary_weight,)
+
+    def _new_state(self, key, cfg):
+        st = super()._new_state(key, cfg)
+        if key[3] == "train" and self._boundary_weight is not None and st.fused_head:
+            # the term reads the logits and adds into their gradient: head and loss stay apart
+            st.fused_head = False
+            st.logits = torch.empty(st.logits_shape, dtype=torch.float32, device=self.device)
+            st.dlogits = torch.empty(st.logits_shape, dtype=torch.float32, device=self.device)
+        return st
+
     # ---- TrainStep's part of a static state: the segment and exchange schedule, the teacher
     def _extend(self, st):
         if st.mode != "train":
             return
         desc, trainable, dev = st.desc, st.trainable, self.device
+        if self._boundary_weight is not None:
+            if max(self.boundary_classes) >= desc.out_channels:
+                raise Mi3dError(f"TrainStep: boundary_classes {self.boundary_classes} are logit channels below {desc.out_channels}")
+            st.dist = torch.zeros((desc.N, len(self.boundary_classes), desc.D, desc.H, desc.W), dtype=torch.float32, device=dev)
+            st.bd_ws = M.boundary_workspace(desc.N, desc.D * desc.H * desc.W, dev)
         st.opt_ranges = self._trainable_ranges(self.arena, trainable)
         last = -1
         r = (C.c_int * 4)()
@@ -569,7 +624,7 @@ class TrainStep(_StepBase):
         drop, t_logits = self._forward_loss(st, s)
         self._backward_exchange(st, s, comm, drop, t_logits, accumulate, boundary, run_backward)
         if boundary:
-            self._adamw(self.arena, st.opt_ranges, self._hyper(), s)
+            self._adamw(self.arena, st.opt_ranges, self._hyper()[:5], s)
 
     def _forward_loss(self, st, s):
         """Dropout scales, the teacher's forward, the student's forward with loss and metrics.  Returns (drop, t_logits)."""
@@ -628,6 +683,7 @@ class TrainStep(_StepBase):
         if run_backward:
             if not st.fused_head:
                 st.loss.backward(st.logits, st.y, st.dlogits, teacher=t_logits, grad_scale=self.inv_accum, stream=s)
+            self._boundary_term(st, s, True)
             nseg = st.nseg_run
             due = st.comm_after if (self.do_comm and boundary) else {}
             aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
@@ -673,21 +729,47 @@ class TrainStep(_StepBase):
                     comm(exchange(buckets))
             if aux_open:       # the last call may have had nothing for the aux stream: join what earlier calls left there
                 torch.cuda.current_stream().wait_stream(self.aux_stream)
+        else:
+            self._boundary_term(st, s, False)
         if met_pending:
             comm(lambda: self._on_comm_stream(lambda: self.comm.average_(met)))
         if self.do_comm and not joined:
             comm(self._join_comm)
 
-    def load_batch(self, images, labels):
-        """Copy a batch into the static buffers (then step_static() runs on it)."""
-        self._load(self._prepare(images), False, x=images, y=labels)
+    def _boundary_term(self, st, s, with_grad):
+        """loss += boundary_weight * L and, with_grad, dlogits += its gradient (mi3d_boundary_loss): one pass directly behind the
+        loss backward, in front of any exchange, so the metrics' all-reduce carries it.  Nothing without boundary_weight."""
+        if self._boundary_weight is None:
+            return
+        masked = self.ignore_index is not None
+        M.boundary_term(st.logits, st.dist, self.boundary_classes, labels=st.y if masked else None, ignore_index=self.ignore_index,
+                        weight=self._boundary_weight, grad_scale=self.inv_accum, loss_out=st.metrics, dlogits=st.dlogits if with_grad else None,
+                        flags=_lib.BD_ADD_LOSS | (_lib.BD_ADD_GRAD if with_grad else 0), workspace=st.bd_ws, stream=s)
 
-    def step(self, images, labels, last_batch=False):
+    def _load_batch(self, images, labels, dist, non_blocking):
+        st = self._prepare(images)
+        if self._boundary_weight is None:
+            if dist is not None:
+                raise Mi3dError("TrainStep was built without boundary_weight: it has no use for dist")
+            self._load(st, non_blocking, x=images, y=labels)
+        elif dist is not None:
+            self._load(st, non_blocking, x=images, y=labels, dist=dist)
+        else:
+            self._load(st, non_blocking, x=images, y=labels)
+            d = st.desc
+            st.dist.copy_(surface.signed_distance_maps(st.y.view(d.N, d.D, d.H, d.W), self.boundary_classes, spacing=self.boundary_spacing))
+
+    def load_batch(self, images, labels, dist=None):
+        """Copy a batch into the static buffers (then step_static() runs on it).  dist: TrainStep(boundary_weight=...)."""
+        self._load_batch(images, labels, dist, False)
+
+    def step(self, images, labels, last_batch=False, dist=None):
         """One micro-step on (images (N,Cin,D,H,W) float, labels (N,1,D,H,W) int64).  Returns a device float32[4]
         tensor {loss, iou, dice, acc} (already averaged over ranks when world > 1).
         last_batch=True on the final batch of an epoch: the optimizer steps there even inside an accumulation window and
-        the next epoch starts a new window, as accelerate does for the reference's prepared loaders (see _run)."""
-        self._load(self._prepare(images), True, x=images, y=labels)
+        the next epoch starts a new window, as accelerate does for the reference's prepared loaders (see _run).
+        dist: the signed distance maps (N, K, D, H, W) float32 of a step built with boundary_weight; None computes them."""
+        self._load_batch(images, labels, dist, True)
         return self.step_static(last_batch=last_batch)
 
     @torch.no_grad()
