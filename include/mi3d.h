@@ -299,6 +299,34 @@ size_t mi3d_boundary_loss_workspace_bytes(int N, int64_t V);
 int mi3d_boundary_loss(const float* logits, const float* phi, int N, int C, int K, int64_t V, const int32_t* channels, const int64_t* labels,
                        const int64_t* ignore_index, float weight, const float* grad_scale, float* loss_out, float* dlogits, int flags,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* Entropy minimisation (MinEnt of ADVENT, Vu et al., CVPR 2019): the unsupervised term that makes the network confident where nothing
+ * is labelled.  logits (N, C, V) float32, 2 <= C <= 8 (C = 1 has ln C = 0 and is refused).  mode selects the voxels:
+ *   MI3D_ENT_ALL      every voxel; labels and ignore_index may be NULL (given, they are not read)
+ *   MI3D_ENT_COUNTED  the voxels with labels != ignore_index         MI3D_ENT_IGNORED  the voxels with labels == ignore_index
+ * labels (N, V) int64 and ignore_index (a HOST int64, read before the call returns): both or neither; both label modes require them.
+ * weight: a host float.  grad_scale: device float[1] or NULL = 1.  loss_out: device float[1].  dlogits (N, C, V) float32, or NULL for
+ * the value alone.  flags: MI3D_ENT_ADD_LOSS adds to *loss_out instead of storing, MI3D_ENT_ADD_GRAD adds into dlogits instead of
+ * storing (what the MI3D_BD_* pair means).  Per voxel, in the log-sum-exp form, which never forms p log p (a saturated voxel gives
+ * exactly 0 and no NaN):
+ *   d_j = z_j - max_j z_j,  e_j = exp(d_j),  se = sum_j e_j,  p_j = e_j / se,  H = log(se) - sum_j p_j d_j
+ *   *loss_out (+)= weight sum_{selected voxels} H / (N V ln C)                                in [0, weight], as in ADVENT
+ *   dlogits[k](x) (+)= grad_scale weight p_k (log(se) - d_k - H) / (N V ln C)                 at a selected voxel
+ *                      0, or untouched (bit for bit) under MI3D_ENT_ADD_GRAD, at an unselected voxel
+ * The divisor is N V ln C WHATEVER is selected, for the boundary term's reason: the gradient of a voxel then needs nothing but the
+ * voxel (no global count), so value and gradient leave ONE pass over the logits.  The sum is float32 per voxel and double from the
+ * thread's accumulator on, through fixed slots added in a fixed order by a second tiny launch: no float atomics, the same bits on
+ * every run.  16-byte accesses, four voxels per thread, where V % 4 == 0 and logits, dlogits and the labels that are read are 16-byte
+ * aligned; one voxel at a time otherwise.  Every argument is checked before the first launch; nothing allocates or synchronises.
+ * workspace: mi3d_entropy_loss_workspace_bytes(N, V) bytes, 8-byte aligned. */
+#define MI3D_ENT_ALL 0
+#define MI3D_ENT_COUNTED 1
+#define MI3D_ENT_IGNORED 2
+#define MI3D_ENT_ADD_LOSS 1
+#define MI3D_ENT_ADD_GRAD 2
+size_t mi3d_entropy_loss_workspace_bytes(int N, int64_t V);
+int mi3d_entropy_loss(const float* logits, int N, int C, int64_t V, const int64_t* labels, const int64_t* ignore_index, int mode,
+                      float weight, const float* grad_scale, float* loss_out, float* dlogits, int flags,
+                      void* workspace, size_t workspace_bytes, void* stream);
 size_t mi3d_seg_metrics_workspace_bytes(int C);
 /* out: device float[3] = {iou, dice, accuracy}; D = first spatial dim (reference loop bound, metrics.py:74,101) */
 int mi3d_seg_metrics(const float* logits, const int64_t* labels, int N, int C, int D, int64_t V, float* out,

@@ -46,6 +46,8 @@ OVERLAY_F64, OVERLAY_F32, OVERLAY_U8 = 0, 1, 2
 COMPONENTS_TILE, COMPONENTS_MAX_CLASSES, COMPONENTS_MAX_KEEP = 8, 8, 8      # MI3D_COMPONENTS_*
 SURFACE_MAX_TOLERANCES, SURFACE_COUNT_COLUMNS, SURFACE_TABLE_COLUMNS = 4, 10, 8      # MI3D_SURFACE_*
 BD_ADD_LOSS, BD_ADD_GRAD = 1, 2                    # MI3D_BD_* (mi3d_boundary_loss flags)
+ENT_ALL, ENT_COUNTED, ENT_IGNORED = 0, 1, 2        # MI3D_ENT_* (mi3d_entropy_loss modes)
+ENT_ADD_LOSS, ENT_ADD_GRAD = 1, 2                  # MI3D_ENT_ADD_* (mi3d_entropy_loss flags)
 ELASTIC_MAX_RADIUS = 32                            # MI3D_ELASTIC_MAX_RADIUS
 PAD_BORDER, PAD_ZEROS = 0, 1                       # MI3D_PAD_*
 PATCH_BLOCK = 4096                                 # MI3D_PATCH_BLOCK
@@ -143,6 +145,8 @@ _SIGS = {
     "mi3d_pseudo_labels": (i32, [vp, vp, i32, i64, i32, C.POINTER(C.c_float), i64, vp, vp, vp]),
     "mi3d_boundary_loss_workspace_bytes": (sz, [i32, i64]),
     "mi3d_boundary_loss": (i32, [vp, vp, i32, i32, i32, i64, _IP, vp, C.POINTER(C.c_int64), f32, vp, vp, vp, i32, vp, sz, vp]),
+    "mi3d_entropy_loss_workspace_bytes": (sz, [i32, i64]),
+    "mi3d_entropy_loss": (i32, [vp, i32, i32, i64, vp, C.POINTER(C.c_int64), i32, f32, vp, vp, vp, i32, vp, sz, vp]),
     "mi3d_seg_metrics_workspace_bytes": (sz, [i32]),
     "mi3d_seg_metrics": (i32, [vp, vp, i32, i32, i32, i64, vp, vp, vp]),
     "mi3d_seg_class_counts": (i32, [vp, vp, i32, i32, i64, vp, vp, vp]),

@@ -7,6 +7,7 @@
   calculate_iou / calculate_dice / calculate_accuracy  :65-129  (incl. the reference's class-loop bound)
   get_loss_fn(loss_type)                               train_unet.py:178-205
   boundary_loss(pred, dist, classes, ...)              not in the reference: Kervadec et al., MIDL 2019 (include/mi3d.h)
+  entropy_loss(pred, target, ignore_index, on)         not in the reference: MinEnt of ADVENT, Vu et al., CVPR 2019 (include/mi3d.h)
 
 pred (N,C,D,H,W) float, target (N,1,D,H,W) int64 -> 0-dim tensor, differentiable w.r.t. pred.  Each loss is ONE
 streaming forward kernel (+ a tiny finalize) and ONE backward kernel; the three metrics share ONE pass.
@@ -227,6 +228,77 @@ def boundary_loss(pred, dist, classes=(1, 2, 3), target=None, ignore_index=None)
         _lib.require_cuda(target, what)
         labels = _prep(pred, target)[3]
     return _BoundaryLossFn.apply(pred, dist.detach().contiguous(), ch, labels, ignore_index)
+
+
+# ---- entropy minimisation (MinEnt of ADVENT, Vu et al., CVPR 2019): the term on voxels without a label ---------------------
+ENTROPY_MODES = {"all": _lib.ENT_ALL, "counted": _lib.ENT_COUNTED, "ignored": _lib.ENT_IGNORED}
+
+
+def entropy_mode(on, what):
+    """The MI3D_ENT_* mode of on = "all" | "counted" | "ignored"."""
+    if on not in ENTROPY_MODES:
+        raise _lib.Mi3dError(f"{what}: on={on!r} is not one of {tuple(ENTROPY_MODES)}")
+    return ENTROPY_MODES[on]
+
+
+def entropy_term(logits, *, labels=None, ignore_index=None, mode=_lib.ENT_ALL, weight=1.0, grad_scale=None, loss_out, dlogits=None, flags=0,
+                 workspace, stream):
+    """One mi3d_entropy_loss call on float32 (N, C, ...) logits: the argument order of include/mi3d.h."""
+    n, c = logits.shape[:2]
+    ig = None if ignore_index is None else C.byref(C.c_int64(int(ignore_index)))
+    call("mi3d_entropy_loss", ptr(logits), n, c, logits.numel() // (n * c), ptr(labels), ig, mode, float(weight), ptr(grad_scale),
+         ptr(loss_out), ptr(dlogits), flags, ptr(workspace), workspace.numel(), stream)
+
+
+def entropy_workspace(n, v, device):
+    nbytes = _lib.lib().mi3d_entropy_loss_workspace_bytes(n, v)
+    if nbytes == 0:
+        _lib.check(-1, "mi3d_entropy_loss_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+class _EntropyLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, labels, ignore_index, mode):
+        p32 = pred.detach().contiguous().float()
+        n, c = p32.shape[:2]
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        grad = torch.empty_like(p32) if ctx.needs_input_grad[0] else None         # value and gradient leave one pass
+        ws = entropy_workspace(n, p32.numel() // (n * c), pred.device)
+        entropy_term(p32, labels=labels, ignore_index=ignore_index, mode=mode, loss_out=loss, dlogits=grad, workspace=ws, stream=stream_ptr())
+        ctx.grad, ctx.in_dtype = grad, pred.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d = ctx.grad * g.float()
+        if ctx.in_dtype != torch.float32:
+            d = d.to(ctx.in_dtype)
+        return d, None, None, None
+
+
+def entropy_loss(pred, target=None, ignore_index=None, on="all"):
+    """mean over n and voxels of the entropy of softmax(pred) in units of ln C (a value in [0, 1]): entropy minimisation, to be added
+    to a supervised loss with a small weight, `combined_loss(pred, y, ignore_index=255) + w * entropy_loss(pred, y, 255, on="ignored")`,
+    or alone on a batch without labels.  pred (N, C, D, H, W) float, 2 <= C <= 8.  on: "all" = every voxel, "counted" = the voxels
+    whose label is not ignore_index, "ignored" = those whose label is; both label modes need target and ignore_index.  Unselected
+    voxels add nothing and get no gradient; the mean stays over all N V voxels (include/mi3d.h, mi3d_entropy_loss).  One pass gives
+    value and gradient."""
+    what = "entropy_loss"
+    _lib.require_cuda(pred, what)
+    if pred.dim() < 3:
+        raise _lib.Mi3dError(f"{what}: pred must be (N, C, spatial...), got {tuple(pred.shape)}")
+    mode = entropy_mode(on, what)
+    ignore_index = check_ignore_index(ignore_index)
+    if (target is None) != (ignore_index is None):
+        raise _lib.Mi3dError(f"{what}: target and ignore_index come together or not at all")
+    if mode != _lib.ENT_ALL and target is None:
+        raise _lib.Mi3dError(f"{what}: on={on!r} selects voxels by their label: target and ignore_index are required")
+    labels = None
+    if target is not None:
+        _lib.require_cuda(target, what)
+        labels = _prep(pred, target)[3]
+    return _EntropyLossFn.apply(pred, labels, ignore_index, mode)
 
 
 # ---- metrics: one pass for all three, shared through a 1-entry cache ---------------------------------------

@@ -51,13 +51,13 @@ def _loss_cfg(kind, kd_alpha=None, temperature=2.0):
     return M._cfg(*_LOSS_TABLE[kind])
 
 
-def _finite_weight(value):
+def _finite_weight(value, name="boundary_weight"):
     try:
         value = float(value)
     except (TypeError, ValueError):
-        raise Mi3dError(f"boundary_weight {value!r} is not a number") from None
+        raise Mi3dError(f"{name} {value!r} is not a number") from None
     if not math.isfinite(value):
-        raise Mi3dError(f"boundary_weight {value} is not finite")
+        raise Mi3dError(f"{name} {value} is not finite")
     return value
 
 
@@ -452,7 +452,7 @@ class TrainStep(_StepBase):
                  grad_accum=1, kd_teacher=None, kd_alpha=0.7, kd_temperature=2.0, process_group=None,
                  compute_dtype=None, use_graph=False, aux_wgrad=None, reference_zero_grad_quirk=False,
                  force_comm=False, overlap_teacher=True, keep_logits=False, ignore_index=None, boundary_weight=None,
-                 boundary_classes=(1, 2, 3), boundary_spacing=(1, 1, 1)):
+                 boundary_classes=(1, 2, 3), boundary_spacing=(1, 1, 1), entropy_weight=None, entropy_on="ignored"):
         """aux_wgrad: the backward's critical path is the input-gradient chain alone -- the weight gradients of the decoder's
         full-resolution convs and of all deep-level convs run on a second stream (include/mi3d.h, mi3d_unet_backward: aux_stream),
         forked from the chain at most three times and joined in front of the optimizer; bit-identical results.  None (default):
@@ -473,6 +473,13 @@ class TrainStep(_StepBase):
         count like the rest; ignored voxels add nothing to L, the distillation term is untouched.  Out of scope: evaluate()
         keeps reporting the overlap loss alone, DannStep has no such term, and the term is not folded into the fused head +
         loss pass.  None (default): no new buffer, no new launch, the step as it always was.
+        entropy_weight: a float (0.0 included) adds entropy_weight * the entropy of the prediction (MinEnt of ADVENT, Vu et al.;
+        include/mi3d.h, mi3d_entropy_loss) over the voxels entropy_on selects to the loss and its gradient to the logits' gradient:
+        one pass directly behind the loss backward (behind the boundary pass when both are set), in front of any exchange.
+        entropy_on: "ignored" (default) = the voxels labelled ignore_index, where the loss is otherwise silent (needs ignore_index);
+        "counted" = the others; "all" = every voxel.  Like boundary_weight the keyword keeps head and loss apart, the property
+        entropy_weight may be set between steps (a captured graph is captured again), and the returned loss is overlap (+ boundary)
+        + entropy_weight * L, undivided by the accumulation count.  evaluate() is untouched.  None (default): no buffer, no launch.
         reference_zero_grad_quirk: train_unet.py:222 / finetune_ct.py:161 call optimizer.zero_grad() INSIDE
         accelerator.accumulate(), where accelerate only really zeroes on the boundary micro-step -> the gradient the
         reference applies is grad(last micro-batch)/accum.  False (default): accumulate all micro-batches
@@ -485,6 +492,13 @@ class TrainStep(_StepBase):
             self._boundary_weight = _finite_weight(boundary_weight)
             self.boundary_classes = M.check_channels(boundary_classes, 8, "TrainStep")      # against the head's channels in _extend
             self.boundary_spacing = surface._spacing(boundary_spacing, None, "TrainStep")
+        self._entropy_weight, self.entropy_on = None, None
+        if entropy_weight is not None:
+            self._entropy_weight = _finite_weight(entropy_weight, "entropy_weight")
+            M.entropy_mode(entropy_on, "TrainStep")
+            if entropy_on == "ignored" and self.ignore_index is None:
+                raise Mi3dError('TrainStep: entropy_on="ignored" selects the voxels labelled ignore_index, and none was given')
+            self.entropy_on = entropy_on
         self._init_common(model, lr, weight_decay, betas, eps, grad_accum, process_group, compute_dtype, use_graph,
                           force_comm)
         self.teacher = kd_teacher
@@ -559,13 +573,25 @@ class TrainStep(_StepBase):
             raise Mi3dError("TrainStep was built without boundary_weight: the step has no boundary term to weigh")
         self._boundary_weight = _finite_weight(value)
 
+    @property
+    def entropy_weight(self):
+        return self._entropy_weight
+
+    @entropy_weight.setter
+    def entropy_weight(self, value):
+        """The weight of the entropy term; only a step built with one has the term (and the workspace) to weigh."""
+        if self._entropy_weight is None:
+            raise Mi3dError("TrainStep was built without entropy_weight: the step has no entropy term to weigh")
+        self._entropy_weight = _finite_weight(value, "entropy_weight")
+
     def _hyper(self):
-        return super()._hyper() + (self._boundary_weight,)
+        return super()._hyper() + (self._boundary_weight, self._entropy_weight)
 
     def _new_state(self, key, cfg):
         st = super()._new_state(key, cfg)
-        if key[3] == "train" and self._boundary_weight is not None and st.fused_head:
-            # the term reads the logits and adds into their gradient: head and loss stay apart
+        extra = self._boundary_weight is not None or self._entropy_weight is not None
+        if key[3] == "train" and extra and st.fused_head:
+            # a term on the logits reads them and adds into their gradient: head and loss stay apart
             st.fused_head = False
             st.logits = torch.empty(st.logits_shape, dtype=torch.float32, device=self.device)
             st.dlogits = torch.empty(st.logits_shape, dtype=torch.float32, device=self.device)
@@ -581,6 +607,10 @@ class TrainStep(_StepBase):
                 raise Mi3dError(f"TrainStep: boundary_classes {self.boundary_classes} are logit channels below {desc.out_channels}")
             st.dist = torch.zeros((desc.N, len(self.boundary_classes), desc.D, desc.H, desc.W), dtype=torch.float32, device=dev)
             st.bd_ws = M.boundary_workspace(desc.N, desc.D * desc.H * desc.W, dev)
+        if self._entropy_weight is not None:
+            if not 2 <= desc.out_channels <= 8:
+                raise Mi3dError(f"TrainStep: the entropy term takes 2 to 8 logit channels, the head has {desc.out_channels}")
+            st.ent_ws = M.entropy_workspace(desc.N, desc.D * desc.H * desc.W, dev)
         st.opt_ranges = self._trainable_ranges(self.arena, trainable)
         last = -1
         r = (C.c_int * 4)()
@@ -683,7 +713,7 @@ class TrainStep(_StepBase):
         if run_backward:
             if not st.fused_head:
                 st.loss.backward(st.logits, st.y, st.dlogits, teacher=t_logits, grad_scale=self.inv_accum, stream=s)
-            self._boundary_term(st, s, True)
+            self._logit_terms(st, s, True)
             nseg = st.nseg_run
             due = st.comm_after if (self.do_comm and boundary) else {}
             aux = self.aux_stream.cuda_stream if self.aux_stream is not None else None
@@ -730,21 +760,28 @@ class TrainStep(_StepBase):
             if aux_open:       # the last call may have had nothing for the aux stream: join what earlier calls left there
                 torch.cuda.current_stream().wait_stream(self.aux_stream)
         else:
-            self._boundary_term(st, s, False)
+            self._logit_terms(st, s, False)
         if met_pending:
             comm(lambda: self._on_comm_stream(lambda: self.comm.average_(met)))
         if self.do_comm and not joined:
             comm(self._join_comm)
 
-    def _boundary_term(self, st, s, with_grad):
-        """loss += boundary_weight * L and, with_grad, dlogits += its gradient (mi3d_boundary_loss): one pass directly behind the
-        loss backward, in front of any exchange, so the metrics' all-reduce carries it.  Nothing without boundary_weight."""
-        if self._boundary_weight is None:
-            return
+    def _logit_terms(self, st, s, with_grad):
+        """The terms on the logits beside the overlap loss, each loss += weight * L and, with_grad, dlogits += its gradient: one
+        pass each directly behind the loss backward, the boundary term (mi3d_boundary_loss) then the entropy term
+        (mi3d_entropy_loss), in front of any exchange, so the metrics' all-reduce carries them.  Nothing without their keywords."""
         masked = self.ignore_index is not None
-        M.boundary_term(st.logits, st.dist, self.boundary_classes, labels=st.y if masked else None, ignore_index=self.ignore_index,
-                        weight=self._boundary_weight, grad_scale=self.inv_accum, loss_out=st.metrics, dlogits=st.dlogits if with_grad else None,
-                        flags=_lib.BD_ADD_LOSS | (_lib.BD_ADD_GRAD if with_grad else 0), workspace=st.bd_ws, stream=s)
+        dlogits = st.dlogits if with_grad else None
+        if self._boundary_weight is not None:
+            M.boundary_term(st.logits, st.dist, self.boundary_classes, labels=st.y if masked else None, ignore_index=self.ignore_index,
+                            weight=self._boundary_weight, grad_scale=self.inv_accum, loss_out=st.metrics, dlogits=dlogits,
+                            flags=_lib.BD_ADD_LOSS | (_lib.BD_ADD_GRAD if with_grad else 0), workspace=st.bd_ws, stream=s)
+        if self._entropy_weight is not None:
+            # without an ignore value every voxel counts: "counted" is "all"
+            M.entropy_term(st.logits, labels=st.y if masked else None, ignore_index=self.ignore_index,
+                           mode=M.ENTROPY_MODES[self.entropy_on] if masked else _lib.ENT_ALL, weight=self._entropy_weight,
+                           grad_scale=self.inv_accum, loss_out=st.metrics, dlogits=dlogits,
+                           flags=_lib.ENT_ADD_LOSS | (_lib.ENT_ADD_GRAD if with_grad else 0), workspace=st.ent_ws, stream=s)
 
     def _load_batch(self, images, labels, dist, non_blocking):
         st = self._prepare(images)
@@ -808,12 +845,25 @@ class DannStep(_StepBase):
     backward of the source graph (dlogits and dgap, gap_scale = -lambda = the gradient reversal, so the encoder sees
     -lambda^2 dL_dom/df, Q3) interleaved segment by segment with the backward of the target graph (dgap only:
     bottleneck + encoder, accumulating into the same gradient arena) ; two arena AdamW updates.
-    Under DP the discriminator arena is one more bucket, in flight under the whole U-Net backward."""
+    Under DP the discriminator arena is one more bucket, in flight under the whole U-Net backward.
+
+    entropy_weight: a float (0.0 included) adds entropy minimisation on the target batch (MinEnt of ADVENT, Vu et al.; include/mi3d.h,
+    mi3d_entropy_loss), the companion of the adversarial loss and the only way the target batch reaches the decoder and the head:
+    total = task + lambda * domain + entropy_weight * L_ent.  The target forward then writes its logits (static `t_logits`), one pass
+    over them in mode ALL stores the gradient (static `t_dlogits`, scaled by 1 / grad_accum) and the weighted value (a sixth
+    metrics slot), and the target graph's backward runs EVERY segment, decoder included, with dlogits and dgap: the target's decoder
+    backward is real extra work.  step() then returns float32[6]; task_loss stays the reference's figure.  The property
+    entropy_weight may be set between steps; like lr it is a kernel argument, so a captured graph is captured again.  None
+    (default): five values and the kernels the step always launched."""
     _n_metrics = 5
 
     def __init__(self, seg_model, disc_model, loss="ce_tversky", lambda_domain=0.1, lr=1e-3, weight_decay=0.01,
                  betas=(0.9, 0.999), eps=1e-8, grad_accum=1, process_group=None, compute_dtype=None, use_graph=False,
-                 force_comm=False, overlap_forwards=True):
+                 force_comm=False, overlap_forwards=True, entropy_weight=None):
+        self._entropy_weight = None
+        if entropy_weight is not None:
+            self._entropy_weight = _finite_weight(entropy_weight, "entropy_weight")
+            self._n_metrics = 6          # per instance: task, iou, dice, acc, domain, weighted target entropy
         self._init_common(seg_model, lr, weight_decay, betas, eps, grad_accum, process_group, compute_dtype, use_graph,
                           force_comm)
         # The target forward does not depend on the source forward (train_dann.py:268-272): it runs on its own stream beside it.
@@ -839,7 +889,18 @@ class DannStep(_StepBase):
     def _hyper(self):
         g = self.disc_optimizer.param_groups[0]
         return super()._hyper() + (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                   float(g["weight_decay"]))
+                                   float(g["weight_decay"]), self._entropy_weight)
+
+    @property
+    def entropy_weight(self):
+        return self._entropy_weight
+
+    @entropy_weight.setter
+    def entropy_weight(self, value):
+        """The weight of the target entropy term; only a step built with one has the term (and the buffers) to weigh."""
+        if self._entropy_weight is None:
+            raise Mi3dError("DannStep was built without entropy_weight: the step has no entropy term to weigh")
+        self._entropy_weight = _finite_weight(value, "entropy_weight")
 
     def _mutable_state(self):
         d = self.disc_arena
@@ -877,7 +938,14 @@ class DannStep(_StepBase):
         st.feat = torch.empty((2 * n, F), dtype=torch.float32, device=dev)
         st.dfeat = torch.empty((2 * n, F), dtype=torch.float32, device=dev)
         st.gap, st.dgap = (st.feat[:n], st.feat[n:]), (st.dfeat[:n], st.dfeat[n:])       # (source rows, target rows)
-        st.domain_loss = st.metrics[4:]                   # metrics = task, iou, dice, acc, domain
+        st.domain_loss = st.metrics[4:5]                  # metrics = task, iou, dice, acc, domain (, weighted target entropy)
+        if self._entropy_weight is not None:
+            if not 2 <= desc.out_channels <= 8:
+                raise Mi3dError(f"DannStep: the entropy term takes 2 to 8 logit channels, the head has {desc.out_channels}")
+            st.t_logits = torch.empty(st.logits_shape, dtype=torch.float32, device=dev)
+            st.t_dlogits = torch.empty(st.logits_shape, dtype=torch.float32, device=dev)
+            st.entropy_loss = st.metrics[5:6]
+            st.ent_ws = M.entropy_workspace(n, desc.D * desc.H * desc.W, dev)
         widths = [l.out_features for l in self.lins]
         st.acts = [torch.empty((2 * n, w), dtype=torch.float32, device=dev) for w in widths]
         st.gacts = [torch.empty((2 * n, w), dtype=torch.float32, device=dev) for w in widths]
@@ -910,10 +978,12 @@ class DannStep(_StepBase):
         drop_s = engine.fill_drop_scales(st.drop, p, rng, injected[0], s)
         drop_t = engine.fill_drop_scales(st.drop_t, p, rng, injected[1], s)
         (gap_s, gap_t), fs = st.gap, self.fwd_stream
+        ent = self._entropy_weight is not None
+        t_logits = st.t_logits if ent else None      # without the entropy term the target logits are never read: the head is not run
         if fs is not None:
             fs.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(fs):
-                tgt.forward(st.xt, drop=drop_t, training=BN_PUBLISH | THIN_CONSUMERS, gap=gap_t, stream=fs.cuda_stream)
+                tgt.forward(st.xt, drop=drop_t, training=BN_PUBLISH | THIN_CONSUMERS, logits=t_logits, gap=gap_t, stream=fs.cuda_stream)
         fused = st.fused_head
         beside = TRAIN | THIN_CONSUMERS      # two forwards side by side; also in the serial order, so that both orders run the
         #                                      same kernels and stay bitwise equal
@@ -925,10 +995,14 @@ class DannStep(_StepBase):
             torch.cuda.current_stream().wait_stream(fs)
             src.bn_apply_deferred(tgt, stream=s)
         else:
-            tgt.forward(st.xt, drop=drop_t, training=beside, gap=gap_t, stream=s)      # the target logits are never read
+            tgt.forward(st.xt, drop=drop_t, training=beside, logits=t_logits, gap=gap_t, stream=s)
         if not fused:
             loss.metrics_forward(st.logits, st.y, stream=s)
             loss.backward(st.logits, st.y, st.dlogits, grad_scale=self.inv_accum, stream=s)
+        if ent:
+            # entropy minimisation on every target voxel: the weighted value to its metrics slot, the gradient STORED to t_dlogits
+            M.entropy_term(st.t_logits, mode=_lib.ENT_ALL, weight=self._entropy_weight, grad_scale=self.inv_accum,
+                           loss_out=st.entropy_loss, dlogits=st.t_dlogits, workspace=st.ent_ws, stream=s)
         # ---- discriminator on the 2N feature rows (train_dann.py:34-49,276-283)
         dinj = getattr(disc, "_mi3d_injected_drop_scales", None) or (None, None)      # tests: [mask after net.1, mask after net.4]
         dd = [engine.fill_drop_scales(st.ddrop[i], self.disc_p[i], self._disc_rng, dinj[i], s) for i in (0, 1)] + [None, None]
@@ -966,9 +1040,11 @@ class DannStep(_StepBase):
                 src.backward_loss(st.x, loss, labels=st.y, grad_scale=self.inv_accum, **kw)
             else:
                 src.backward(st.x, dlogits=st.dlogits, **kw)
-            t0 = max(start, L + 1)            # the target graph has no decoder part
+            # without the entropy term the target graph has no decoder part; with it every segment runs, head and decoder included
+            t0 = start if ent else max(start, L + 1)
             if end > t0:
-                tgt.backward(st.xt, drop=drop_t, dgap=st.dgap[1], gap_scale=-lam, accumulate=1, start=t0, end=end, stream=s)
+                tgt.backward(st.xt, drop=drop_t, dlogits=st.t_dlogits if ent else None, dgap=st.dgap[1], gap_scale=-lam, accumulate=1,
+                             start=t0, end=end, stream=s)
             for k in buckets:
                 comm(lambda k=k: self._on_comm_stream(lambda: self.comm.reduce_bucket(k)))
         if self.do_comm:
@@ -976,14 +1052,15 @@ class DannStep(_StepBase):
         if boundary:
             h = self._hyper()
             self._adamw(self.arena, st.opt_ranges, h[:5], s)
-            self._adamw(self.disc_arena, [(0, self.disc_arena.numel)], h[5:], s)
+            self._adamw(self.disc_arena, [(0, self.disc_arena.numel)], h[5:10], s)
 
     def load_batch(self, source_images, source_labels, target_images):
         self._load(self._prepare(source_images, target_images), False, x=source_images, xt=target_images, y=source_labels)
 
     def step(self, source_images, source_labels, target_images, last_batch=False):
         """One micro-step.  Returns device float32[5] = {task_loss, iou, dice, acc, domain_loss} (source-domain metrics,
-        train_dann.py:291-299; losses un-divided by the accumulation count like the reference's running sums).
+        train_dann.py:291-299; losses un-divided by the accumulation count like the reference's running sums); built with
+        entropy_weight, float32[6]: entropy_weight * the target batch's entropy term comes last (task_loss stays the reference's).
         last_batch: train_dann.py:287 also steps on the final batch of an epoch."""
         self._load(self._prepare(source_images, target_images), True, x=source_images, xt=target_images, y=source_labels)
         return self.step_static(last_batch=last_batch)
