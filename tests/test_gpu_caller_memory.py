@@ -85,12 +85,15 @@ def tdtype(dtype):
 
 
 class Op:
-    """One entry on one case.  outs: name -> dict(shape, dtype[, align, strides]); call(ws_ptr, ws_bytes, {name: ptr}) -> status;
-    check({name: numpy}) asserts the reference; init: name -> the content an output starts with where it is an input too."""
+    """One entry (or one sequence of entries) on one case.  outs: name -> dict(shape, dtype[, align, strides]);
+    call(ws_ptr, ws_bytes, {name: ptr}) -> status; check({name: numpy}) asserts the reference; init: name -> the content an output
+    starts with where it is an input too; side: name -> (bytes, align) of further workspaces of the call (the loss workspaces beside
+    the network's arena), filled like the workspace, between bands of their own, their pointers in the same dict as the outputs'."""
 
-    def __init__(self, name, ws_bytes, ws_align, outs, call, check, init=None, keep=()):
+    def __init__(self, name, ws_bytes, ws_align, outs, call, check, init=None, keep=(), side=None):
         self.name, self.ws_bytes, self.ws_align, self.outs, self.call, self.check, self.init = name, ws_bytes, ws_align, outs, call, check, init or {}
         self.keep = keep          # the device inputs, alive as long as the op
+        self.side = side or {}
 
 
 def exact(want):
@@ -106,20 +109,30 @@ def exact(want):
     return check
 
 
-def launch(op, ws, k, ws_ptr=None, ws_bytes=None):
-    """Fresh outputs with the k-th prefill, one call.  Returns (status, outputs)."""
+def side_workspaces(op, fill):
+    return {n: G.Guarded(nbytes, align=align, fill=fill, device=DEV) for n, (nbytes, align) in op.side.items()}
+
+
+def launch(op, ws, k, ws_ptr=None, ws_bytes=None, sides=None):
+    """Fresh outputs with the k-th prefill (and, unless given, fresh side workspaces with the workspace's fill), one call.
+    Returns (status, outputs, side workspaces)."""
     outs = {n: G.GuardedOut(prefill=G.PREFILLS[spec["dtype"]][k], device=DEV, **spec) for n, spec in op.outs.items()}
     for n, a in op.init.items():
         outs[n].set(a)
-    rc = op.call(ws.ptr if ws_ptr is None else ws_ptr, ws.nbytes if ws_bytes is None else ws_bytes, {n: o.ptr for n, o in outs.items()})
-    return rc, outs
+    sides = side_workspaces(op, ws.fill) if sides is None else sides
+    ptrs = {n: o.ptr for n, o in outs.items()}
+    ptrs.update({n: sides[n].ptr for n in op.side})
+    rc = op.call(ws.ptr if ws_ptr is None else ws_ptr, ws.nbytes if ws_bytes is None else ws_bytes, ptrs)
+    return rc, outs, sides
 
 
-def run(op, ws, k=0):
+def run(op, ws, k=0, sides=None):
     """One good call: status 0, every band intact.  Returns the outputs on the host."""
-    rc, outs = launch(op, ws, k)
+    rc, outs, sides = launch(op, ws, k, sides=sides)
     assert rc == 0, (op.name, rc, lib().mi3d_last_error())
     ws.check(op.name + " workspace")
+    for n in op.side:
+        sides[n].check(f"{op.name} {n}")
     for n, o in outs.items():
         o.check(f"{op.name} {n}")
     return {n: o.host() for n, o in outs.items()}
@@ -139,29 +152,32 @@ def poisoned(op):
 
 
 def reused(a, b):
-    """Stale reuse: a, b, a in one workspace that is never refilled, each against its run alone."""
+    """Stale reuse: a, b, a in one workspace (and one set of side workspaces) that is never refilled, each against its run alone."""
     assert a.ws_align == b.ws_align
     alone = [run(op, workspace(op)) for op in (a, b)]
     ws = workspace(a, nbytes=max(a.ws_bytes, b.ws_bytes))
+    both = dict(b.side, **a.side)
+    sizes = {n: max(op.side[n][0] for op in (a, b) if n in op.side) for n in both}
+    sides = {n: G.Guarded(sizes[n], align=both[n][1], fill=ws.fill, device=DEV) for n in both}
     for k, (op, want) in enumerate(((a, alone[0]), (b, alone[1]), (a, alone[0]))):
-        got = run(op, ws, 1 + k % 2)
+        got = run(op, ws, 1 + k % 2, sides=sides)
         for n in op.outs:
             G.same_bits([want[n], got[n]], f"{op.name} {n}, call {k} in the shared workspace")
     a.check(alone[0])
     b.check(alone[1])
 
 
-def refused(op, misalign=0):
-    """One byte short (misalign = 0) or a workspace of the right size `misalign` bytes off its alignment: a negative status, a
-    message about the workspace, the bands intact, and every output and workspace byte as it was."""
-    assert op.ws_bytes > 0 and 0 <= misalign < op.ws_align
+def refused(op, misalign=0, null=False, needle=b"workspace"):
+    """One byte short (misalign = 0), a workspace of the right size `misalign` bytes off its alignment, or (null) no workspace
+    at all: a negative status, a message with `needle` in it, the bands intact, and every output and workspace byte as it was."""
+    assert op.ws_bytes > 0 and 0 <= misalign < op.ws_align and not (null and misalign)
     ws = workspace(op, nbytes=op.ws_bytes + misalign)
-    rc, outs = launch(op, ws, 0, ws.ptr + misalign, op.ws_bytes - (0 if misalign else 1))
+    rc, outs, sides = launch(op, ws, 0, 0 if null else ws.ptr + misalign, op.ws_bytes - (0 if misalign or null else 1))
     message = lib().mi3d_last_error()
-    assert rc < 0 and message and b"workspace" in message, (op.name, rc, message)
+    assert rc < 0 and message and needle in message, (op.name, rc, message)
     ws.check(op.name + " workspace")
     assert ws.untouched(), op.name
-    for n, o in outs.items():
+    for n, o in list(outs.items()) + list(sides.items()):
         o.check(f"{op.name} {n}")
         assert o.untouched(), (op.name, n)
 

@@ -186,6 +186,13 @@ def test_loss_metrics_vs_oracle_large(orc):
 
 
 # ------------------------------------------------------------------------------------------------ whole net
+# test_small_unet_golden_fp32's rule for "equals the golden fixture" on the fp32 path
+SMALL_LOGITS_TOL = dict(rtol=1e-3, atol=2e-4)
+SMALL_LOSS_RTOL = 1e-5
+SMALL_GRAD_ZERO, SMALL_GRAD_ZERO_TOL, SMALL_GRAD_TOL = 1e-5, 1e-4, 2e-3      # a gradient that is analytically zero / any other, norm-relative
+SMALL_BN_TOL = dict(rtol=1e-4, atol=1e-5)
+
+
 def test_small_unet_golden_fp32(golden):
     """Complete fixture: every weight, every gradient, BN buffers, eval logits (2 levels, odd channels, 8x12x4)."""
     g = golden("small_unet")
@@ -197,22 +204,22 @@ def test_small_unet_golden_fp32(golden):
     logits = m(x)
     loss = M.combined_loss(logits, y)
     loss.backward()
-    np.testing.assert_allclose(logits.detach().cpu().numpy(), g["logits"], rtol=1e-3, atol=2e-4)
-    np.testing.assert_allclose(loss.item(), g["loss"], rtol=1e-5)
+    np.testing.assert_allclose(logits.detach().cpu().numpy(), g["logits"], **SMALL_LOGITS_TOL)
+    np.testing.assert_allclose(loss.item(), g["loss"], rtol=SMALL_LOSS_RTOL)
     for k, p in m.named_parameters():
         ref = g["grad/" + k]
-        if np.abs(ref).max() < 1e-5:
-            assert p.grad.abs().max().item() < 1e-4, k
+        if np.abs(ref).max() < SMALL_GRAD_ZERO:
+            assert p.grad.abs().max().item() < SMALL_GRAD_ZERO_TOL, k
         else:
-            assert relerr(p.grad.cpu(), ref) < 2e-3, (k, relerr(p.grad.cpu(), ref))
+            assert relerr(p.grad.cpu(), ref) < SMALL_GRAD_TOL, (k, relerr(p.grad.cpu(), ref))
     sd = m.state_dict()
     for k, v in g.items():
         if k.startswith("sd1/"):
-            np.testing.assert_allclose(sd[k[4:]].cpu().numpy(), v, rtol=1e-4, atol=1e-5, err_msg=k)
+            np.testing.assert_allclose(sd[k[4:]].cpu().numpy(), v, err_msg=k, **SMALL_BN_TOL)
     m.eval()
     with torch.no_grad():
         le = m(x)
-    np.testing.assert_allclose(le.cpu().numpy(), g["logits_eval"], rtol=1e-3, atol=2e-4)
+    np.testing.assert_allclose(le.cpu().numpy(), g["logits_eval"], **SMALL_LOGITS_TOL)
 
 
 def _default_model(cls=UNet3D, seed=0):

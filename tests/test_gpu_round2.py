@@ -36,6 +36,11 @@ DEV = "cuda:0"
 # up to 4 M terms (norms 1e-5..1e-3 out of O(1) terms); two correct fp32 implementations with different summation orders
 # differ by up to ~0.6 % there (measured: 5.2e-3 on bottleneck BN beta at 128^3, 6.0e-3 on upconvs.0 at 96^3 DANN)
 FP32_GRAD_TOL = 1e-2
+# test_odd_sizes_default_net_vs_oracle's rule for "equals the float64 oracle" on the default net, by fp32 (True) / bf16 (False):
+# norm-relative logits, relative loss; gradients under FP32_GRAD_TOL on the fp32 path where the oracle's norm is above the floor
+ODD_LOGITS_TOL = {True: 2e-4, False: 3e-2}
+ODD_LOSS_RTOL = {True: 2e-5, False: 3e-3}
+ODD_GRAD_NORM_FLOOR = 1e-6
 
 
 def relerr(a, b):
@@ -884,12 +889,12 @@ def test_odd_sizes_default_net_vs_oracle(dtype):
     rl = torch_ref.seg_loss(ro, y, "combined")
     rl.backward()
     fp32 = dtype == torch.float32
-    assert relerr(lo.detach().cpu(), ro.detach()) < (2e-4 if fp32 else 3e-2)
-    np.testing.assert_allclose(l.item(), float(rl.detach()), rtol=2e-5 if fp32 else 3e-3)
+    assert relerr(lo.detach().cpu(), ro.detach()) < ODD_LOGITS_TOL[fp32]
+    np.testing.assert_allclose(l.item(), float(rl.detach()), rtol=ODD_LOSS_RTOL[fp32])
     if fp32:
         for k, p in m.named_parameters():
             ref = sd[k].grad
-            if float(ref.norm()) > 1e-6:
+            if float(ref.norm()) > ODD_GRAD_NORM_FLOOR:
                 assert relerr(p.grad.cpu(), ref) < FP32_GRAD_TOL, (k, relerr(p.grad.cpu(), ref))
     # native step on the same odd shape: graph replay == eager
     outs = []
@@ -899,7 +904,7 @@ def test_odd_sizes_default_net_vs_oracle(dtype):
         ts.load_batch(x.to(DEV), y.to(DEV))
         outs.append(torch.stack([ts.step_static().clone() for _ in range(2)]).cpu())
     assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
-    np.testing.assert_allclose(float(outs[0][0, 0]), float(rl.detach()), rtol=2e-5 if fp32 else 3e-3)
+    np.testing.assert_allclose(float(outs[0][0, 0]), float(rl.detach()), rtol=ODD_LOSS_RTOL[fp32])
 
 
 # ------------------------------------------------------------------------------------------------ input pipeline (F4)
